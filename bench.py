@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- regressor samples/s + TSQR TFLOP/s of the fused hot path on MI355X (contract: see the task statement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 starts N ranks ITSELF (re-executes under ``python -m torch.distributed.run --nproc-per-node N``; a launch that already
 runs under torchrun is used as is) and fails loudly when fewer than N devices / ranks come up.  One process per GPU,
@@ -67,9 +67,14 @@ def parse_args(argv=None):
     ap.add_argument("--engine", default=None,
                     help="module:factory returning an Engine-like object (tests inject a CPU stand-in to exercise the launch / "
                          "sharding / reduction logic without a GPU); default: flobaroid_amd._lib.Engine (HIP, fails without a device)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step (the all-reduced fp64 Gram) as "
+                         "DIR/<name>.npy, for comparing two builds output for output (the inputs are seeded: same arguments, same inputs)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="option of every model handle the bench creates (fbr_model_set_option, include/fbr.h); experiments only -- the line records them")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.opt:
         from flobaroid_amd import _lib
 
@@ -104,6 +109,24 @@ def maybe_spawn(args) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.exit(subprocess.call(cmd, env=env))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays) -> dict:
+    """``{name: tensor}`` -> ``path/<name>.npy`` (float64 kept, anything else as float32); returns ``{name: shape}``."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        host[name] = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -553,6 +576,7 @@ def run_rank(args) -> int:
     prof = eng.profile_get()
     eng.profile_enable(False)
     G_sharded = Gs[state.get("last", 0)].clone()
+    dumped = dump_outputs(args.dump_outputs, {"gram": G_sharded}) if args.dump_outputs and rank == 0 else None
 
     ms_per_step = dt / args.steps * 1e3
     value = S_total / (dt / args.steps)
@@ -650,6 +674,9 @@ def run_rank(args) -> int:
     }
     if check is not None:
         out["selfcheck_dist"] = check
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped,
+                                 "what": "gram: [Y|tau]^T[Y|tau] of the last timed step, all-reduced over the ranks, (P+1) x (P+1) fp64"}
     try:  # HBM traffic of the dominant kernel: committed rocprofv3 PMC passes, scaled to this run's samples per launch
         import glob
 

@@ -173,6 +173,28 @@ def test_bench_gpus_2_spawns_two_ranks_end_to_end():
     assert "weak_scaling" not in one and one["tsqr"]["rank_tree_levels"] == 0
 
 
+def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """``--dump-outputs DIR`` writes the Gram the timed path returned in its last step as DIR/gram.npy (fp64); the same arguments give
+    the same inputs, hence the same bits, run to run; ``--steps`` is the number of timed steps the line reports."""
+    import json
+
+    grams = []
+    for i, steps in enumerate((2, 3)):
+        d = tmp_path / f"run{i}"
+        r = _run_bench(["--gpus", "1", "--no-secondary", "--dump-outputs", str(d)] + (["--steps", str(steps)] if steps != 2 else []))
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["gram.npy"] and line["dumped_outputs"]["arrays"]["gram"] == list(np.load(d / "gram.npy").shape)
+        G = np.load(d / "gram.npy")
+        assert G.dtype == np.float64 and G.shape[0] == G.shape[1] and np.array_equal(G, G.T)
+        assert abs(np.trace(G) - line["gram_checksum"]["trace"]) <= 1e-12 * abs(np.trace(G))
+        grams.append(G)
+    assert np.array_equal(grams[0], grams[1])
+    r = _run_bench(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and b"--steps" in r.stderr
+
+
 def test_bench_refuses_a_mislabelled_world():
     """Launched by hand with fewer ranks than --gpus says, the bench fails instead of printing n_gpus: N for one rank."""
     r = _run_bench(["--gpus", "4"], {"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port())})

@@ -1,7 +1,7 @@
 """The floating-base estimator chain the way the reference's own ``Identification`` drives it, on the HIP engine.
 
 tests/golden/ref_identification_fb.npz holds what identifier.py (unchanged, run in the build container on the work-alike Model / Data with
-the CPU stand-in engine: tests/test_dropin_identifier.py, tools/make_fixtures.py) computes for
+the CPU stand-in engine: tools/make_fixtures.py) computes for
   * threeLinks, floating base, configs/threeLinks.yaml (data-driven pivoted QR, OLS, 2 000 samples), and
   * WALK-MAN with the configs/walkman_full.yaml option set: useBaseWrenchForBaseParams (identifier.py:888-892, :617-681),
     useTrajectoryWeighting over two measurement files of different noise, contact wrenches on both foot FT frames, post-identification

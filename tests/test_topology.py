@@ -9,7 +9,8 @@ import pytest
 
 from flobaroid_amd.topology import Topology, parse_urdf
 
-REF_MODEL = "/root/reference/model"
+# the reference's robot descriptions (model/<name>.urdf), stored as data fixtures
+URDF_DIR = os.path.join(GOLDEN, "urdf")
 
 _URDF = """<robot name="t">
   <link name="world_box"/>
@@ -93,9 +94,8 @@ def test_default_serialisation_reproduces_the_reference_held_joint_lists():
         assert all(t.parent[l] < l for l in range(t.num_links))
         d = [x for x in t.dof_index if x >= 0]
         assert d == sorted(d)
-        if os.path.isdir(REF_MODEL):
-            u = parse_urdf(os.path.join(REF_MODEL, name + ".urdf"))
-            assert u.link_names == t.link_names and u.dof_names == t.dof_names and u.parent == t.parent
+        u = parse_urdf(os.path.join(URDF_DIR, name + ".urdf"))
+        assert u.link_names == t.link_names and u.dof_names == t.dof_names and u.parent == t.parent
     w = load_topo("walkman_apriori")
     assert w.dof_names == g["walkman_static_yaml"]
     assert w.dof_order("document") != g["walkman_apriori"] and w.dof_order("document")[:3] == ["WaistLat", "WaistSag", "WaistYaw"]
@@ -131,9 +131,7 @@ def test_urdf_write_back_round_trip(tmp_path):
 
     from flobaroid_amd import topology as T
 
-    src = os.path.join(REF_MODEL, "kuka_lwr4.urdf") if os.path.isdir(REF_MODEL) else None
-    if src is None or not os.path.exists(src):
-        pytest.skip("reference URDFs not present (GPU box)")
+    src = os.path.join(URDF_DIR, "kuka_lwr4.urdf")
     topo = T.parse_urdf(src)
     L = topo.num_links
     rng = np.random.default_rng(3)
