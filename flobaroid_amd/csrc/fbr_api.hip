@@ -555,11 +555,16 @@ static void kinid_params(const fbr_model *m, DevKinId *kp)
     kp->steps = m->kinid_steps;
     kp->endflush = m->kinid_endflush;
 }
+// dynamic LDS of fbr_kinid_kernel: q, dq and ddq of a block of 64 samples
+static size_t kinid_lds(const fbr_model *m) { return (size_t)3 * 64 * (std::max(m->hm.n, 1) | 1) * sizeof(double); }
+// the fused kernel serves this model: a program exists (joint paths of at most FBR_KINID_MAXD) and the staged states fit a workgroup's
+// 160 KiB of LDS (up to 105 DOF); otherwise the two-kernel path (run_kin + fbr_id_kernel / fbr_contact_kernel)
+static bool kinid_fits(const fbr_model *m) { return m->opt.fused_id != 0 && m->kinid.nsteps > 0 && kinid_lds(m) <= (size_t)160 * 1024; }
 static int launch_kinid(fbr_model *m, const DevStates &d, long S, const double *dvs, const double *x, int mode, double *dst, int flink, const double *fp)
 {
     DevKinId kp;
     kinid_params(m, &kp);
-    const size_t lds = (size_t)3 * 64 * kp.ldn * sizeof(double);
+    const size_t lds = kinid_lds(m);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)(150 << 10) / std::max<size_t>(lds, 1)));
     const long nblk = (S + 63) / 64;
     const int blocks = (int)std::min<long>(nblk, (long)m->num_cus * per_cu);
@@ -639,12 +644,18 @@ static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, c
         if ((rc = m->out_tmp.ensure((size_t)S * hm.rows * sizeof(double)))) return rc;
         dst = m->out_tmp.as<double>();
     }
-    if (m->opt.fused_id != 0 && m->kinid.nsteps > 0) {
+    if (kinid_fits(m)) {
         if ((rc = launch_kinid(m, d, S, dvs, m->st_x.as<double>(), mode, dst, 0, nullptr))) return rc;
         return finish_output(m, dst, tau_out, (size_t)S * hm.rows, out_mem);
     }
-    const int waves = 4;
-    const size_t lds = (size_t)waves * (hm.rec_size() + 6 * hm.L) * sizeof(double);
+    // one wave per sample, each with its record and link forces in the LDS: up to four waves per workgroup, fewer for large trees
+    const size_t per_wave = (size_t)(hm.rec_size() + 6 * hm.L) * sizeof(double);
+    const int waves = (int)std::min<size_t>(4, (size_t)160 * 1024 / per_wave);
+    if (waves < 1) {
+        set_err("model too large: the inverse dynamics of one sample needs more than 160 KiB of LDS");
+        return FBR_E_UNSUPPORTED;
+    }
+    const size_t lds = (size_t)waves * per_wave;
     HIPCHK(hipFuncSetAttribute((const void *)fbr_id_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long ch = chunk_size(m, S);
     for (long s0 = 0; s0 < S; s0 += ch) {
@@ -715,7 +726,7 @@ extern "C" int fbr_contact_torques(fbr_model *m, const fbr_states *st, int32_t l
         if ((rc = m->out_tmp.ensure((size_t)S * hm.rows * sizeof(double)))) return rc;
         dst = m->out_tmp.as<double>();
     }
-    if (m->opt.fused_id != 0 && m->kinid.nsteps > 0) {  // the same fused kernel: only the frame's link carries a wrench (fbr_kinid.h, mode 2)
+    if (kinid_fits(m)) {  // the same fused kernel: only the frame's link carries a wrench (fbr_kinid.h, mode 2)
         if ((rc = launch_kinid(m, d, S, nullptr, dw, 2, dst, link, frame_p))) return rc;
         return finish_output(m, dst, out, (size_t)S * hm.rows, out_mem);
     }

@@ -233,6 +233,7 @@ extern "C" int fbr_gram_lane_info(const fbr_model *mc, int32_t k, int64_t num_sa
     if (int rc_enter = enter(m)) return rc_enter;
     if (const int wr = pick_gram_reduction(m, num_samples < 0 ? -1 : (long)num_samples); wr >= 0) m = m->rdm[wr].get();
     for (int i = 0; i < 12; i++) info[i] = 0;
+    if ((m->hm.rows + 3) / 4 * 4 > 60) return FBR_OK;  // (no tile program: the Gram comes from the TSQR factor, gram_via_tsqr)
     const bool moments = fbr_gram_rhs_moments(m->hm, k, m->opt.gram_rhs_tile != 0);
     GramHolder *h = nullptr;
     int rc = get_gram(m, k, &h, moments);
@@ -304,6 +305,11 @@ static int get_gram64(fbr_model *m, GramHolder *h)
     const size_t lds = (size_t)2 * g.maxact * 512 * sizeof(double) +
                        ((size_t)g.nlev * (g.NT + g.NF) + g.nlev + 1 + g.pieces.size() + g.wmeta.size() + g.stage_lev.size()) * sizeof(int);
     if (lds > 156 * 1024) return FBR_OK;
+    // the producer stages a block's states, row weights and rhs in the LDS (plds of gram64_pass, its largest form).  A defence only: the
+    // tile program's 60 rows bound it to (3 * 64 * 61 + 2 * 64 * 61) * 8 = 156 160 bytes today; it keeps a model the producer cannot
+    // launch on the per-sample-image pass should either bound move
+    const size_t plds_max = ((size_t)3 * 64 * (std::max(hm.n, 1) | 1) + (size_t)2 * 64 * (hm.rows | 1)) * sizeof(double);
+    if (plds_max > 160 * 1024) return FBR_OK;
     if (!fbr_gram64_build_producer(hm, h->prog, g, h->g64p)) return FBR_OK;
     std::vector<int> wgbegin{0, 0};  // (filled per launch: one part)
     int rc;
@@ -373,7 +379,9 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     const long nblocks = (S + 63) / 64;
     long chb = gram64_chunk_blocks(g);
     if (h2d_chunked) chb = std::min<long>(chb, 7L * m->num_cus);
-    if (m->opt.chunk_samples >= 1) chb = std::max<long>(1, ((long)m->opt.chunk_samples + 63) / 64);  // (tests: the multi-chunk paths at small sizes)
+    // (tests: the multi-chunk paths at small sizes.)  The cap holds whatever the option asks: the producer's image offsets are 32-bit
+    // (fbr_kinimg_kernel, vlane), so one chunk's image must stay below 4 GiB -- a larger chunk wrapped its stores inside the buffer
+    if (m->opt.chunk_samples >= 1) chb = std::min(gram64_chunk_blocks(g), std::max<long>(1, ((long)m->opt.chunk_samples + 63) / 64));
     chb = std::min(nblocks, chb);
     if (chb < nblocks && chb > m->num_cus) chb = chb / m->num_cus * m->num_cus;
     if ((rc = gram64_ensure_images(m, h, chb))) return rc;
@@ -573,7 +581,9 @@ static int gram64_grouped_pass(fbr_model *m, GramHolder *h, const DevStates &d, 
     const long S = d.S, Sg = S / ngroups, bpg = (Sg + 63) / 64;
     const int Pa = hm.cols, npw = g.npw;
     int rc;
-    const int gpc = (int)std::min<long>(ngroups, std::max<long>(1, gram64_chunk_blocks(g) / bpg));  // groups per chunk
+    // groups per chunk: what the image buffers hold, and at most 32768 -- a chunk's groups are gridDim.y of the launches below (limit
+    // 65535; the expand kernels of gram_via_red take the same 32768)
+    const int gpc = (int)std::min<long>(std::min(ngroups, 32768), std::max<long>(1, gram64_chunk_blocks(g) / bpg));
     if ((rc = gram64_ensure_images(m, h, (long)gpc * bpg))) return rc;
     const int wpg = (int)std::max<long>(1, std::min<long>(bpg, (long)m->num_cus / std::min(gpc, ngroups)));
     const int ldn = std::max(hm.n, 1) | 1, ldw = hm.rows | 1;

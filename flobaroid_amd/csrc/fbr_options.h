@@ -59,8 +59,8 @@ static inline const FbrOptionKey *fbr_option_keys(int *count)
         {"h2d_chunked", &FbrOptions::h2d_chunked, false},
         {"fused_id", &FbrOptions::fused_id, false},
         {"gram_lane", &FbrOptions::gram_lane, false},
-        {"gram_force_tiles", &FbrOptions::gram_force_tiles, false},
-        {"gram_lane_waves", &FbrOptions::gram_lane_waves, false},
+        {"gram_force_tiles", &FbrOptions::gram_force_tiles, true},   // (both shape the program of the sample-contiguous pass, get_gram64)
+        {"gram_lane_waves", &FbrOptions::gram_lane_waves, true},
         {"gram_shape", &FbrOptions::gram_shape, true},
         {"gram_rhs_tile", &FbrOptions::gram_rhs_tile, true},
         {"gram_orient", &FbrOptions::gram_orient, true},

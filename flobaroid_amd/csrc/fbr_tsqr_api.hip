@@ -244,6 +244,10 @@ static long tsqr_group_chunk_samples(const fbr_model *m, const TsqrGroupPlan &gp
     }
     long ch = std::max(1L, (long)(4.0 * 1024 * 1024 * 1024 / per));
     ch = std::min(ch, chunk_size(m, 1L << 40));  // (the memory-sized chunk; chunk_size caps at the call's own length otherwise)
+    // (an oversized chunk_samples costs memory only: the level-0 folds address a block's first row in 64 bits, r0 * n or r0 + c * cs,
+    // and the 32-bit products inside a block, row * ldb of fbr_tsqr.h, stay below MB * FBR_TSQR_MAXN whatever the chunk length; the lane
+    // writer's 32-bit lane offset, sample << 3 in fbr_kinwrite_kernel, wraps only at 2^29 samples per chunk, 4 GiB per regressor row and
+    // column of the chunk, which no allocation of the chunk holds)
     if (m->opt.chunk_samples >= 1) ch = (long)m->opt.chunk_samples;
     ch = std::max(lcm, ch - ch % lcm);
     if (lcm_out) *lcm_out = lcm;

@@ -282,7 +282,15 @@ int fbr_gram_program_info(const fbr_model *m, int32_t k, int64_t num_samples, in
    option is on (device-resident inputs, k <= 1), else every entry is 0; [1] tile rows of a 64-sample block image, [2] its bytes, [3] MFMA
    instructions per block, [4] row levels, [5] slabs of the widest stage, [6] LDS bytes of the Gram kernel, [7] column tiles, [8] force
    tiles (option "gram_force_tiles"), [9] sum over the levels of the busiest wave's active tile pairs, [10] the same for a perfect split
-   over the 8 waves, [11] stages (barriers) per half block.  The image is written once and read once per pass: 2 * info[2] / 64 bytes of HBM traffic per sample. */
+   over the 8 waves, [11] stages (barriers) per half block.  The image is written once and read once per pass: 2 * info[2] / 64 bytes of HBM traffic per sample.
+   Limits (info[0] = 0 beyond them, and the call takes the per-sample-image pass or the Gram from the TSQR factor): joint paths of at most
+   24 joints (the one-lane-per-sample kinematics), at most 60 regressor rows, and a producer whose staged states, row weights and rhs of a
+   64-sample block fit a workgroup's 160 KiB of LDS.  A pass cuts its samples into chunks whose images stay below 3 GB (also when the
+   option "chunk_samples" asks for more).
+   Size limits of the other entry points: fbr_predict / fbr_inverse_dynamics_batch / fbr_contact_torques run the one-kernel form for joint
+   paths of at most 24 joints and at most 105 DOF (the states of 64 samples in the LDS) and the two-kernel form beyond; the fused Gram of
+   fbr_gram_grouped / fbr_gram_submit takes at most 60 regressor rows; fbr_tsqr and the Gram from its factor (fbr_gram_accumulate beyond 60
+   rows) at most 768 columns including the rhs.  Beyond a limit a call fails with FBR_E_UNSUPPORTED and an error text that names it. */
 int fbr_gram_lane_info(const fbr_model *m, int32_t k, int64_t num_samples, int64_t info[12]);
 
 /*
