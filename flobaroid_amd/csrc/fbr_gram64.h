@@ -43,6 +43,8 @@ struct FbrGram64 {  // host program
     std::vector<int> lev_begin;  // [nlev + 1] into pieces
     std::vector<int> pieces;     // pairs: global offset (doubles, inside the block image, half 0), LDS offset (doubles, inside a stage buffer)
     std::vector<int> wmeta;      // [wpb waves][npw][3]: tile I (-1: empty slot), tile J, first level | (one past the last level) << 8
+    std::vector<int> runs;       // [wpb waves][nlev]: qa | qb << 8, the wave's slots active at the level are exactly qa .. qb-1 (empty table:
+                                 // some wave's pairs admit no such order, and the kernel walks every slot at every level)
     std::vector<int> slot_tiles; // [2][wpb * npw * 2] for the two reductions: main pairs, force pairs (the other kind's slots are -1), in the
                                  // partial-sum order fbr_gram_reduce_kernel walks: [wave & 7][wave >> 3][slot] (16 waves = 8 rows of twice the slots)
     std::vector<int> tilecol;    // [NT + NF][16] column of each tile slot, -1 = padding
@@ -285,15 +287,17 @@ static inline bool fbr_gram64_build(const FbrHostModel &hm, const FbrGramProgram
     }
     // slots of a wave: the A operand (tile I) of a slot is kept for the next one when it is the same tile, so the pairs of a wave are ordered
     // by the tile most of them contain (which of a pair's two tiles is "I" is free: the reduction writes the block and its mirror image)
-    g.wmeta.assign((size_t)W * g.npw * 3, -1);
-    g.slot_tiles.assign((size_t)2 * W * g.npw * 2, -1);
-    g.mfma_per_block = 0;
+    // Runs (the 8 x 18 shape): the kernel pipelines a level's active slots -- the operand reads of the next one in flight while the MFMAs of
+    // the current one run -- when they are consecutive slots.  The force pairs (levels 0 .. flev-1) first, then the others by end level,
+    // descending: the main pairs all start at flev, so the active ones of a level are a prefix of them.  Friction pairs start later and may
+    // break that; the run table stays empty then.  Ties keep the order above (same tile I next to each other: the A operand is kept).
+    // Neither the roles of a pair's tiles nor the order of its MFMAs change: only which slot holds it.
+    std::vector<std::vector<int>> slots(W);  // per wave: pairs, each with its tile I in front (T, J, lo, hi)
     for (int w = 0; w < W; w++) {
         std::vector<int> mine;
         for (int i = 0; i < NP; i++)
             if (wave_of[i] == w) mine.push_back(i);
         std::vector<char> done(NP, 0);
-        int q = 0;
         for (size_t left = mine.size(); left > 0;) {
             std::vector<int> freq(NTT, 0);
             for (int i : mine)
@@ -307,22 +311,69 @@ static inline bool fbr_gram64_build(const FbrHostModel &hm, const FbrGramProgram
             for (int i : mine) {
                 if (done[i] || (prs[i].a != T && prs[i].b != T)) continue;
                 const int J = prs[i].a == T ? prs[i].b : prs[i].a;
-                const size_t s = (size_t)w * g.npw + q;                                                  // wmeta: wave-major
-                const size_t sr = ((size_t)(w & 7) * (W / 8) + (size_t)(w >> 3)) * g.npw + q;             // the reduction's order
-                g.wmeta[3 * s] = T;
-                g.wmeta[3 * s + 1] = J;
-                g.wmeta[3 * s + 2] = prs[i].lo | (prs[i].hi << 8);
-                const int kind = T >= g.NT ? 1 : 0;
-                g.slot_tiles[((size_t)kind * W * g.npw + sr) * 2] = T;
-                g.slot_tiles[((size_t)kind * W * g.npw + sr) * 2 + 1] = J;
-                g.mfma_per_block += 16L * (prs[i].hi - prs[i].lo);  // 8 MFMAs per level and half
+                slots[w].insert(slots[w].end(), {T, J, prs[i].lo, prs[i].hi});
                 done[i] = 1;
-                q++;
                 left--;
             }
         }
     }
+    g.runs.clear();
+    if (W == 8 && g.npw > 10) {
+        std::vector<std::vector<int>> sorted(W);
+        std::vector<int> runs((size_t)W * g.nlev, 0);
+        bool ok = true;
+        for (int w = 0; w < W && ok; w++) {
+            const int n = (int)slots[w].size() / 4;
+            std::vector<int> ord(n);
+            for (int q = 0; q < n; q++) ord[q] = q;
+            const int *sw = slots[w].data();
+            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) {
+                const bool fx = sw[4 * x] >= g.NT, fy = sw[4 * y] >= g.NT;
+                return fx != fy ? fx : sw[4 * x + 3] > sw[4 * y + 3];
+            });
+            for (int q : ord) sorted[w].insert(sorted[w].end(), sw + 4 * q, sw + 4 * q + 4);
+            for (int lv = 0; lv < g.nlev && ok; lv++) {
+                int qa = -1, qb = -1;
+                for (int q = 0; q < n; q++) {
+                    const bool act = sorted[w][4 * q + 2] <= lv && lv < sorted[w][4 * q + 3];
+                    if (act && qa < 0) qa = q;
+                    if (act && qb >= 0) ok = false;  // (an active slot behind an inactive one)
+                    if (!act && qa >= 0 && qb < 0) qb = q;
+                }
+                if (qa < 0) qa = qb = 0;
+                else if (qb < 0) qb = n;
+                runs[(size_t)w * g.nlev + lv] = qa | (qb << 8);
+            }
+        }
+        if (ok) {
+            slots.swap(sorted);
+            g.runs.swap(runs);
+        }
+    }
+    g.wmeta.assign((size_t)W * g.npw * 3, -1);
+    g.slot_tiles.assign((size_t)2 * W * g.npw * 2, -1);
+    g.mfma_per_block = 0;
+    for (int w = 0; w < W; w++)
+        for (int q = 0; q < (int)slots[w].size() / 4; q++) {
+            const int T = slots[w][4 * q], J = slots[w][4 * q + 1], lo = slots[w][4 * q + 2], hi = slots[w][4 * q + 3];
+            const size_t s = (size_t)w * g.npw + q;                                       // wmeta: wave-major
+            const size_t sr = ((size_t)(w & 7) * (W / 8) + (size_t)(w >> 3)) * g.npw + q;  // the reduction's order
+            g.wmeta[3 * s] = T;
+            g.wmeta[3 * s + 1] = J;
+            g.wmeta[3 * s + 2] = lo | (hi << 8);
+            const int kind = T >= g.NT ? 1 : 0;
+            g.slot_tiles[((size_t)kind * W * g.npw + sr) * 2] = T;
+            g.slot_tiles[((size_t)kind * W * g.npw + sr) * 2 + 1] = J;
+            g.mfma_per_block += 16L * (hi - lo);  // 8 MFMAs per level and half
+        }
     return true;
+}
+
+// LDS of fbr_gram64_kernel: two stage buffers, then the tables
+static inline size_t fbr_gram64_lds_bytes(const FbrGram64 &g)
+{
+    return (size_t)2 * g.maxact * 512 * sizeof(double) +
+           ((size_t)g.nlev * (g.NT + g.NF) + g.nlev + 1 + g.pieces.size() + g.wmeta.size() + g.stage_lev.size() + g.runs.size()) * sizeof(int);
 }
 
 // Producer tables: the tree in parts for the waves of a workgroup (fbr_kinid.h) and, per (part, link), 14 destination words: one per
@@ -415,6 +466,7 @@ struct DevGram64 {
     int NT, nlev, maxact, npieces, nstage;  // NT: main + force tiles
     long blk_doubles;
     const int *slab, *lev_begin, *pieces, *wmeta, *stage_lev;
+    const int *runs;  // [WPB][nlev] (FbrGram64::runs) or null
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -697,7 +749,7 @@ __global__ __launch_bounds__(256) void fbr_gram64_mom_reduce_kernel(int P, int n
 // Consumer.  One workgroup (8 waves) per CU walks blocks blockIdx.x, + gridDim.x, ...; stage = (block, half, level).  partial:
 // [workgroup][wave][slot][4][64] (the layout fbr_gram_reduce_kernel sums); carry: start from it.
 // ------------------------------------------------------------------------------------------------
-template <int NPW, int WPB>
+template <int NPW, int WPB, bool RUNS = false>
 __global__ __launch_bounds__(WPB * 64, (NPW <= 10) ? 4 : 2) void fbr_gram64_kernel(DevGram64 g, long nblk, const double *__restrict__ img,
                                                                                   double *__restrict__ partial, int carry)
 {
@@ -710,13 +762,17 @@ __global__ __launch_bounds__(WPB * 64, (NPW <= 10) ? 4 : 2) void fbr_gram64_kern
     int *levb = slab + g.nlev * g.NT;          // [nlev + 1]
     int *pcs = levb + g.nlev + 1;              // [npieces][2]
     int *wm = pcs + 2 * g.npieces;             // [8][NPW][3]
-    int *stl = wm + WPB * MW;              // [nstage + 1]
+    int *rn = wm + WPB * MW;                   // [8][nlev] runs (when the table is there)
+    static_assert(!RUNS || NPW > 10, "the 128-register shapes walk every slot");
+    int *stl = rn + (RUNS ? WPB * g.nlev : 0);  // [nstage + 1]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int i = tid; i < g.nlev * g.NT; i += WPB * 64) slab[i] = g.slab[i];
+    for (int i = tid; i < g.nlev * g.NT; i += WPB * 64) slab[i] = g.slab[i] * 512;  // (in doubles)
     for (int i = tid; i <= g.nlev; i += WPB * 64) levb[i] = g.lev_begin[i];
     for (int i = tid; i < 2 * g.npieces; i += WPB * 64) pcs[i] = g.pieces[i];
     for (int i = tid; i < WPB * MW; i += WPB * 64) wm[i] = g.wmeta[i];
+    if (RUNS)
+        for (int i = tid; i < WPB * g.nlev; i += WPB * 64) rn[i] = g.runs[i];
     for (int i = tid; i <= g.nstage; i += WPB * 64) stl[i] = g.stage_lev[i];
     fbr_d4 acc[NPW];
     img += (long)blockIdx.y * nblk * g.blk_doubles;  // blockIdx.y: sample group (nblk blocks each, fbr_gram_grouped)
@@ -758,6 +814,103 @@ __global__ __launch_bounds__(WPB * 64, (NPW <= 10) ? 4 : 2) void fbr_gram64_kern
     const int idxv = (lane < MW && (lane % 3) != 2 && mv >= 0) ? mv : 0;  // the tile this lane looks up per level (lanes 3q, 3q + 1)
     // this lane's operand position inside a slab (doubles) at k-step ks: column li, sample (4 ks + kk) ^ sx = p0 ^ (4 ks)
     const int p0c = lofs | (sx ^ kk);
+    // runs: one LDS read per level gives the slab offsets of all slots (lanes 3q, 3q + 1) and, in lane 63, the level's run of active slots
+    static_assert(!RUNS || MW < 63, "lane 63 holds the run");
+    const int *lk = lane == 63 ? rn + wave * g.nlev : slab + idxv;
+    const int lks = lane == 63 ? 1 : g.NT;
+    // The levels of a stage with runs: the slots qa .. qb-1 of a level as one software pipeline.  Slot q's operands sit in set q & 1; the
+    // operand reads of slot q + 1 (B, then A -- or a copy of slot q's A when slot q + 1 has the same tile I) go out between slot q's MFMAs,
+    // so that slot q + 1 finds them landed.  The reads are inline asm (one statement per slot, its choice of B only / B + A / B + copy
+    // inside it; one more for the first slot's own reads): the compiler neither counts them nor sees a join behind which it would wait for every read, so a slot waits for its own
+    // reads only.  The slots outside the run are branched over.  Every accumulator receives the same MFMAs in the same order as in the walk
+    // below.
+    const unsigned rlm = [&] {  // bit q: slot q holds another tile I than slot q - 1 (its A operand is read, not copied)
+        unsigned m = 0;
+#pragma unroll
+        for (int q = 1; q < NPW; q++) m |= (unsigned)(__builtin_amdgcn_readlane(mv, 3 * q) != __builtin_amdgcn_readlane(mv, 3 * q - 3)) << q;
+        return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
+    }();
+    int ko[8];  // this lane's operand byte offsets inside a slab, k-steps 0 .. 7
+#pragma unroll
+    for (int ks = 0; ks < 8; ks++) ko[ks] = (p0c ^ (4 * ks)) * 8;
+    double X[2][8], Y[2][8];  // operand sets A, B of the even / odd slots
+#pragma unroll
+    for (int ks = 0; ks < 8; ks++) X[0][ks] = X[1][ks] = Y[0][ks] = Y[1][ks] = 0.0;
+    auto run_stage = [&](const double *buf, int lv0, int lv1) {
+        const unsigned bufb = (unsigned)(unsigned long)(fbr_lds_ptr)buf;
+        int offv = lk[lv0 * lks];
+        for (int lv = lv0; lv < lv1; lv++) {
+            const int cur = offv;
+            offv = lk[(lv + 1 < g.nlev ? lv + 1 : lv) * lks];  // the next level's offsets, in flight during this level
+            const int run = __builtin_amdgcn_readlane(cur, 63), qa = run & 0xff, qb = run >> 8;
+#define G64_RD(D, S, K, T) "v_add_u32 %[" T "], %[" S "], %[o" #K "]\n\tds_read_b64 %[" D #K "], %[" T "]\n\t"
+#define G64_MF(K) "v_mfma_f64_16x16x4_f64 %[acc], %[xa" #K "], %[xb" #K "], %[acc]\n\t"
+#define G64_MV(K) "v_mov_b64 %[ya" #K "], %[xa" #K "]\n\t"
+#pragma unroll
+            for (int q = 0; q < NPW; q++) {
+                if (q < qa || q >= qb) continue;
+                const int P = q & 1, N = P ^ 1;
+                int t0, t1;
+                if (q == qa) {  // the first slot of the run reads its own operands
+                    const unsigned sa = bufb + (__builtin_amdgcn_readlane(cur, 3 * q) << 3), sb = bufb + (__builtin_amdgcn_readlane(cur, 3 * q + 1) << 3);
+                    asm volatile(G64_RD("xa", "sa", 0, "t0") G64_RD("xa", "sa", 1, "t1") G64_RD("xa", "sa", 2, "t0") G64_RD("xa", "sa", 3, "t1")
+                                 G64_RD("xa", "sa", 4, "t0") G64_RD("xa", "sa", 5, "t1") G64_RD("xa", "sa", 6, "t0") G64_RD("xa", "sa", 7, "t1")
+                                 G64_RD("xb", "sb", 0, "t0") G64_RD("xb", "sb", 1, "t1") G64_RD("xb", "sb", 2, "t0") G64_RD("xb", "sb", 3, "t1")
+                                 G64_RD("xb", "sb", 4, "t0") G64_RD("xb", "sb", 5, "t1") G64_RD("xb", "sb", 6, "t0") G64_RD("xb", "sb", 7, "t1")
+                                 : [t0] "=&v"(t0), [t1] "=&v"(t1),
+                                   [xa0] "+v"(X[P][0]), [xa1] "+v"(X[P][1]), [xa2] "+v"(X[P][2]), [xa3] "+v"(X[P][3]),
+                                   [xa4] "+v"(X[P][4]), [xa5] "+v"(X[P][5]), [xa6] "+v"(X[P][6]), [xa7] "+v"(X[P][7]),
+                                   [xb0] "+v"(Y[P][0]), [xb1] "+v"(Y[P][1]), [xb2] "+v"(Y[P][2]), [xb3] "+v"(Y[P][3]),
+                                   [xb4] "+v"(Y[P][4]), [xb5] "+v"(Y[P][5]), [xb6] "+v"(Y[P][6]), [xb7] "+v"(Y[P][7])
+                                 : [sa] "s"(sa), [sb] "s"(sb),
+                                   [o0] "v"(ko[0]), [o1] "v"(ko[1]), [o2] "v"(ko[2]), [o3] "v"(ko[3]), [o4] "v"(ko[4]), [o5] "v"(ko[5]), [o6] "v"(ko[6]), [o7] "v"(ko[7])
+                                 : "memory");
+                }
+                // flags: 4 a next slot follows, 8 the next slot reads its A (else copies this one's)
+                const int f = __builtin_amdgcn_readfirstlane((q + 1 < qb ? 4 : 0) | ((rlm >> (q + 1)) & 1 ? 8 : 0));
+                const unsigned sna = q + 1 < NPW ? bufb + (__builtin_amdgcn_readlane(cur, 3 * q + 3) << 3) : 0u;
+                const unsigned snb = q + 1 < NPW ? bufb + (__builtin_amdgcn_readlane(cur, 3 * q + 4) << 3) : 0u;
+                asm volatile(
+                    "s_waitcnt lgkmcnt(0)\n\t"
+                    G64_MF(0)
+                    "s_bitcmp0_b32 %[f], 2\n\t"
+                    "s_cbranch_scc1 3f\n\t"
+                    G64_RD("yb", "snb", 0, "t0") G64_RD("yb", "snb", 1, "t1") G64_MF(1)
+                    G64_RD("yb", "snb", 2, "t0") G64_RD("yb", "snb", 3, "t1") G64_MF(2)
+                    G64_RD("yb", "snb", 4, "t0") G64_RD("yb", "snb", 5, "t1") G64_MF(3)
+                    G64_RD("yb", "snb", 6, "t0") G64_RD("yb", "snb", 7, "t1") G64_MF(4)
+                    "s_bitcmp0_b32 %[f], 3\n\t"
+                    "s_cbranch_scc1 2f\n\t"
+                    G64_RD("ya", "sna", 0, "t0") G64_RD("ya", "sna", 1, "t1") G64_RD("ya", "sna", 2, "t0") G64_RD("ya", "sna", 3, "t1") G64_MF(5)
+                    G64_RD("ya", "sna", 4, "t0") G64_RD("ya", "sna", 5, "t1") G64_RD("ya", "sna", 6, "t0") G64_RD("ya", "sna", 7, "t1") G64_MF(6)
+                    G64_MF(7)
+                    "s_branch 9f\n\t"
+                    "2:\n\t"
+                    G64_MV(0) G64_MV(1) G64_MV(2) G64_MV(3) G64_MF(5)
+                    G64_MV(4) G64_MV(5) G64_MV(6) G64_MV(7) G64_MF(6)
+                    G64_MF(7)
+                    "s_branch 9f\n\t"
+                    "3:\n\t"
+                    G64_MF(1) G64_MF(2) G64_MF(3) G64_MF(4) G64_MF(5) G64_MF(6) G64_MF(7)
+                    "9:"
+                    : [acc] "+v"(acc[q]), [t0] "=&v"(t0), [t1] "=&v"(t1),
+                      [xa0] "+v"(X[P][0]), [xa1] "+v"(X[P][1]), [xa2] "+v"(X[P][2]), [xa3] "+v"(X[P][3]),
+                      [xa4] "+v"(X[P][4]), [xa5] "+v"(X[P][5]), [xa6] "+v"(X[P][6]), [xa7] "+v"(X[P][7]),
+                      [xb0] "+v"(Y[P][0]), [xb1] "+v"(Y[P][1]), [xb2] "+v"(Y[P][2]), [xb3] "+v"(Y[P][3]),
+                      [xb4] "+v"(Y[P][4]), [xb5] "+v"(Y[P][5]), [xb6] "+v"(Y[P][6]), [xb7] "+v"(Y[P][7]),
+                      [ya0] "+v"(X[N][0]), [ya1] "+v"(X[N][1]), [ya2] "+v"(X[N][2]), [ya3] "+v"(X[N][3]),
+                      [ya4] "+v"(X[N][4]), [ya5] "+v"(X[N][5]), [ya6] "+v"(X[N][6]), [ya7] "+v"(X[N][7]),
+                      [yb0] "+v"(Y[N][0]), [yb1] "+v"(Y[N][1]), [yb2] "+v"(Y[N][2]), [yb3] "+v"(Y[N][3]),
+                      [yb4] "+v"(Y[N][4]), [yb5] "+v"(Y[N][5]), [yb6] "+v"(Y[N][6]), [yb7] "+v"(Y[N][7])
+                    : [f] "s"(f), [sna] "s"(sna), [snb] "s"(snb),
+                      [o0] "v"(ko[0]), [o1] "v"(ko[1]), [o2] "v"(ko[2]), [o3] "v"(ko[3]), [o4] "v"(ko[4]), [o5] "v"(ko[5]), [o6] "v"(ko[6]), [o7] "v"(ko[7])
+                    : "memory", "scc");
+            }
+#undef G64_RD
+#undef G64_MF
+#undef G64_MV
+        }
+    };
     int sg = 0;   // stage of step st
     long bh = 0;  // its block-half (of this workgroup's blocks)
     for (long st = 0; st < nst; st++) {
@@ -770,8 +923,12 @@ __global__ __launch_bounds__(WPB * 64, (NPW <= 10) ? 4 : 2) void fbr_gram64_kern
         const int lv0 = __builtin_amdgcn_readlane(svl, sg), lv1 = __builtin_amdgcn_readlane(svl, sg + 1);
         sg = sgn;
         bh = bhn;
+        if constexpr (RUNS) {
+            run_stage(buf, lv0, lv1);
+            continue;
+        }
         for (int lv = lv0; lv < lv1; lv++) {
-            const int offv = slab[lv * g.NT + idxv] * 512;  // the slab offsets of all slots of the wave at this level: one LDS read
+            const int offv = slab[lv * g.NT + idxv];  // the slab offsets of all slots of the wave at this level: one LDS read
             int curI = -1;  // the tile whose operand the registers a[] hold (of this level)
             double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -803,6 +960,7 @@ __global__ __launch_bounds__(WPB * 64, (NPW <= 10) ? 4 : 2) void fbr_gram64_kern
             }
         }
     }
+    if constexpr (RUNS) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");  // (the asm MFMAs' results, before the stores read them)
 #pragma unroll
     for (int q = 0; q < NPW; q++) {
         pp[q * 256 + 0 * 64 + lane] = acc[q][0];

@@ -248,8 +248,7 @@ extern "C" int fbr_gram_lane_info(const fbr_model *mc, int32_t k, int64_t num_sa
     info[3] = g.mfma_per_block;
     info[4] = g.nlev;
     info[5] = g.maxact;
-    info[6] = (int64_t)((size_t)2 * g.maxact * 512 * sizeof(double) +
-                        ((size_t)g.nlev * (g.NT + g.NF) + g.nlev + 1 + g.pieces.size() + g.wmeta.size() + g.stage_lev.size()) * sizeof(int));
+    info[6] = (int64_t)fbr_gram64_lds_bytes(g);
     info[7] = g.NT;
     info[8] = g.NF;
     info[9] = g.busiest;
@@ -302,9 +301,7 @@ static int get_gram64(fbr_model *m, GramHolder *h)
     const FbrHostModel &hm = m->hm;
     if (m->kinid.nsteps <= 0 || !fbr_gram64_build(hm, h->prog, h->g64, m->opt.gram_force_tiles != 0, m->opt.gram_lane_waves >= 16)) return FBR_OK;
     FbrGram64 &g = h->g64;
-    const size_t lds = (size_t)2 * g.maxact * 512 * sizeof(double) +
-                       ((size_t)g.nlev * (g.NT + g.NF) + g.nlev + 1 + g.pieces.size() + g.wmeta.size() + g.stage_lev.size()) * sizeof(int);
-    if (lds > 156 * 1024) return FBR_OK;
+    if (fbr_gram64_lds_bytes(g) > 156 * 1024) return FBR_OK;
     // the producer stages a block's states, row weights and rhs in the LDS (plds of gram64_pass, its largest form).  A defence only: the
     // tile program's 60 rows bound it to (3 * 64 * 61 + 2 * 64 * 61) * 8 = 156 160 bytes today; it keeps a model the producer cannot
     // launch on the per-sample-image pass should either bound move
@@ -317,7 +314,7 @@ static int get_gram64(fbr_model *m, GramHolder *h)
         (rc = upload(h->pool, g.wmeta, &h->d64_wmeta)) || (rc = upload(h->pool, h->g64p.lcol, &h->d64_lcol)) ||
         (rc = upload(h->pool, h->g64p.steps, &h->d64_steps)) ||
         (rc = upload(h->pool, g.slot_tiles, &h->d64_slot_tiles)) || (rc = upload(h->pool, g.tilecol, &h->d64_tilecol)) ||
-        (rc = upload(h->pool, g.stage_lev, &h->d64_stagelev)))
+        (rc = upload(h->pool, g.stage_lev, &h->d64_stagelev)) || (!g.runs.empty() && (rc = upload(h->pool, g.runs, &h->d64_runs))))
         return rc;
     h->g64_state = 1;
     return FBR_OK;
@@ -398,7 +395,7 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     }
     const int npw = g.npw;
     if ((rc = m->partial.ensure((size_t)m->num_cus * g.wpb * npw * 256 * sizeof(double)))) return rc;
-    const size_t glds = (size_t)2 * g.maxact * 512 * sizeof(double) + ((size_t)g.nlev * (g.NT + g.NF) + g.nlev + 1 + g.pieces.size() + g.wmeta.size() + g.stage_lev.size()) * sizeof(int);
+    const size_t glds = fbr_gram64_lds_bytes(g);
     DevKinId kp;
     kp.nsteps = 0;
     kp.maxlvl = m->kinid.maxlvl;
@@ -418,8 +415,11 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     dg.wmeta = h->d64_wmeta;
     dg.nstage = base_only ? g.base_stages : g.nstage;  // (base-wrench-only row masks: the joint levels' stages are not run)
     dg.stage_lev = h->d64_stagelev;
+    dg.runs = g.runs.empty() ? nullptr : h->d64_runs;
     typedef void (*g64_fn)(DevGram64, long, const double *, double *, int);
-    const g64_fn gk = g.wpb == 16 ? fbr_gram64_kernel<10, 16> : (g.npw == 10 ? fbr_gram64_kernel<10, 8> : fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8>);
+    const g64_fn gk = g.wpb == 16 ? fbr_gram64_kernel<10, 16>
+                      : g.npw == 10   ? fbr_gram64_kernel<10, 8>
+                      : g.runs.empty() ? fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8> : fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8, true>;
     const int vnpw = g.npw * (g.wpb / 8);  // accumulator slots per ROW of the partial sums (fbr_gram_reduce_kernel walks 8 rows per workgroup)
     HIPCHK(hipFuncSetAttribute((const void *)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
     int launches = 0, first_wgs = 0;
@@ -591,7 +591,7 @@ static int gram64_grouped_pass(fbr_model *m, GramHolder *h, const DevStates &d, 
     const int pgrid_max = (m->kinid.maxlvl <= 10 ? 2 : 1) * m->num_cus;
     if ((rc = h->scr64.ensure((size_t)pgrid_max * h->g64p.nparts * std::max(h->g64p.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double)))) return rc;
     if ((rc = m->partial.ensure((size_t)gpc * wpg * g.wpb * npw * 256 * sizeof(double)))) return rc;
-    const size_t glds = (size_t)2 * g.maxact * 512 * sizeof(double) + ((size_t)g.nlev * (g.NT + g.NF) + g.nlev + 1 + g.pieces.size() + g.wmeta.size() + g.stage_lev.size()) * sizeof(int);
+    const size_t glds = fbr_gram64_lds_bytes(g);
     DevKinId kp;
     kp.nsteps = 0;
     kp.maxlvl = m->kinid.maxlvl;
@@ -611,8 +611,11 @@ static int gram64_grouped_pass(fbr_model *m, GramHolder *h, const DevStates &d, 
     dg.wmeta = h->d64_wmeta;
     dg.nstage = g.nstage;
     dg.stage_lev = h->d64_stagelev;
+    dg.runs = g.runs.empty() ? nullptr : h->d64_runs;
     typedef void (*g64_fn)(DevGram64, long, const double *, double *, int);
-    const g64_fn gk = g.wpb == 16 ? fbr_gram64_kernel<10, 16> : (g.npw == 10 ? fbr_gram64_kernel<10, 8> : fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8>);
+    const g64_fn gk = g.wpb == 16 ? fbr_gram64_kernel<10, 16>
+                      : g.npw == 10   ? fbr_gram64_kernel<10, 8>
+                      : g.runs.empty() ? fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8> : fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8, true>;
     const int vnpw = g.npw * (g.wpb / 8);  // accumulator slots per ROW of the partial sums (fbr_gram_reduce_kernel walks 8 rows per workgroup)
     HIPCHK(hipFuncSetAttribute((const void *)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
     const int *wgb = nullptr;
