@@ -544,26 +544,16 @@ extern "C" int fbr_regressor_batch(fbr_model *m, const fbr_states *st, double *Y
     return FBR_OK;
 }
 
-// Fused kinematics + torques (csrc/fbr_kinid.h): one kernel, one lane per sample, the link records stay in registers, branch-point
-// records in a per-wave scratch.  mode 0 / 1: x = parameters (device); mode 2: x = [S][6] contact wrenches at frame (flink, fp).
-static void kinid_params(const fbr_model *m, DevKinId *kp)
-{
-    kp->nsteps = m->kinid.nsteps;
-    kp->maxlvl = m->kinid.maxlvl;
-    kp->nslots = m->kinid.nslots;
-    kp->ldn = std::max(m->hm.n, 1) | 1;
-    kp->steps = m->kinid_steps;
-    kp->endflush = m->kinid_endflush;
-}
 // dynamic LDS of fbr_kinid_kernel: q, dq and ddq of a block of 64 samples
 static size_t kinid_lds(const fbr_model *m) { return (size_t)3 * 64 * (std::max(m->hm.n, 1) | 1) * sizeof(double); }
 // the fused kernel serves this model: a program exists (joint paths of at most FBR_KINID_MAXD) and the staged states fit a workgroup's
 // 160 KiB of LDS (up to 105 DOF); otherwise the two-kernel path (run_kin + fbr_id_kernel / fbr_contact_kernel)
 static bool kinid_fits(const fbr_model *m) { return m->opt.fused_id != 0 && m->kinid.nsteps > 0 && kinid_lds(m) <= (size_t)160 * 1024; }
+// Fused kinematics + torques (csrc/fbr_kinid.h): one kernel, one lane per sample, the link records stay in registers, branch-point
+// records in a per-wave scratch.  mode 0 / 1: x = parameters (device); mode 2: x = [S][6] contact wrenches at frame (flink, fp).
 static int launch_kinid(fbr_model *m, const DevStates &d, long S, const double *dvs, const double *x, int mode, double *dst, int flink, const double *fp)
 {
-    DevKinId kp;
-    kinid_params(m, &kp);
+    const DevKinId kp = kinid_params(m);
     const size_t lds = kinid_lds(m);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)(150 << 10) / std::max<size_t>(lds, 1)));
     const long nblk = (S + 63) / 64;
@@ -571,23 +561,13 @@ static int launch_kinid(fbr_model *m, const DevStates &d, long S, const double *
     if (int rc = m->kinid_scratch.ensure((size_t)blocks * std::max(kp.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double))) return rc;
     const double f0 = fp ? fp[0] : 0.0, f1 = fp ? fp[1] : 0.0, f2 = fp ? fp[2] : 0.0;
     ProfScope ps(m, FBR_PROF_ID);
-#define FBR_KINID_LAUNCH(D)                                                                                                              \
-    do {                                                                                                                                 \
-        HIPCHK(hipFuncSetAttribute((const void *)fbr_kinid_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
-        hipLaunchKernelGGL(fbr_kinid_kernel<D>, dim3(blocks), dim3(64), lds, m->stream, m->dm, kp, S, d.q, d.dq, d.ddq, d.bv, d.ba, d.rpy, \
-                           d.sign, dvs, x, mode, dst, m->kinid_scratch.as<double>(), flink, f0, f1, f2);                                 \
-    } while (0)
-    if (kp.maxlvl <= 4)
-        FBR_KINID_LAUNCH(4);
-    else if (kp.maxlvl <= 8)
-        FBR_KINID_LAUNCH(8);
-    else if (kp.maxlvl <= 12)
-        FBR_KINID_LAUNCH(12);
-    else
-        FBR_KINID_LAUNCH(FBR_KINID_MAXD);
-#undef FBR_KINID_LAUNCH
-    HIPCHK(hipGetLastError());
-    return FBR_OK;
+    return fbr_by_depth<4, 8, 12, FBR_KINID_MAXD>(kp.maxlvl, [&](auto D) -> int {
+        HIPCHK(hipFuncSetAttribute((const void *)fbr_kinid_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(fbr_kinid_kernel<D>, dim3(blocks), dim3(64), lds, m->stream, m->dm, kp, S, d.q, d.dq, d.ddq, d.bv, d.ba, d.rpy, d.sign,
+                           dvs, x, mode, dst, m->kinid_scratch.as<double>(), flink, f0, f1, f2);
+        HIPCHK(hipGetLastError());
+        return FBR_OK;
+    });
 }
 
 static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, const double *vel_sign, int mode,
@@ -819,25 +799,16 @@ extern "C" int fbr_fd_scores(fbr_model *m, const fbr_states *st, const double *W
     }
     if (S > 0 && m->opt.fused_id != 0 && m->kinid.nsteps > 0 && !hm.masked) {
         // one lane per evaluation, nothing staged (fbr_kinfd_kernel, fbr_kinid.h)
-        DevKinId kp;
-        kinid_params(m, &kp);
+        const DevKinId kp = kinid_params(m);
         const long nblk = (S * nper + 63) / 64;
         const int blocks = (int)std::min<long>(nblk, (long)m->num_cus * 8);
         if ((rc = m->kinid_scratch.ensure((size_t)blocks * std::max(kp.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double)))) return rc;
         {
             ProfScope ps(m, FBR_PROF_REGRESSOR);
-#define FBR_KINFD_LAUNCH(D)                                                                                                               \
-    hipLaunchKernelGGL(fbr_kinfd_kernel<D>, dim3(blocks), dim3(64), 0, m->stream, m->dm, kp, S, nper, eps, d.q, d.dq, d.ddq, d.bv, d.ba, d.rpy, \
-                       d.sign, dW, dout, m->kinid_scratch.as<double>())
-            if (kp.maxlvl <= 4)
-                FBR_KINFD_LAUNCH(4);
-            else if (kp.maxlvl <= 8)
-                FBR_KINFD_LAUNCH(8);
-            else if (kp.maxlvl <= 12)
-                FBR_KINFD_LAUNCH(12);
-            else
-                FBR_KINFD_LAUNCH(FBR_KINID_MAXD);
-#undef FBR_KINFD_LAUNCH
+            fbr_by_depth<4, 8, 12, FBR_KINID_MAXD>(kp.maxlvl, [&](auto D) {
+                hipLaunchKernelGGL(fbr_kinfd_kernel<D>, dim3(blocks), dim3(64), 0, m->stream, m->dm, kp, S, nper, eps, d.q, d.dq, d.ddq, d.bv, d.ba,
+                                   d.rpy, d.sign, dW, dout, m->kinid_scratch.as<double>());
+            });
         }
         HIPCHK(hipGetLastError());
     } else if (S > 0) {

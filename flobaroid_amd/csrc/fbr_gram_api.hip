@@ -221,7 +221,7 @@ extern "C" int fbr_gram_program_info(const fbr_model *mc, int32_t k, int64_t num
     return FBR_OK;
 }
 
-static int get_gram64(fbr_model *m, GramHolder *h);
+static int gram64_serves(fbr_model *m, GramHolder *h, int k, bool *serves);
 
 extern "C" int fbr_gram_lane_info(const fbr_model *mc, int32_t k, int64_t num_samples, int64_t info[12])
 {
@@ -238,9 +238,8 @@ extern "C" int fbr_gram_lane_info(const fbr_model *mc, int32_t k, int64_t num_sa
     GramHolder *h = nullptr;
     int rc = get_gram(m, k, &h, moments);
     if (rc) return rc;
-    if (!m->opt.gram_lane || k > 1 || (k == 1 && !moments)) return FBR_OK;
-    if ((rc = get_gram64(m, h))) return rc;
-    if (h->g64_state != 1) return FBR_OK;
+    bool lane = false;
+    if ((rc = gram64_serves(m, h, k, &lane)) || !lane) return rc;
     const FbrGram64 &g = h->g64;
     info[0] = 1;
     info[1] = g.ntr;
@@ -320,6 +319,17 @@ static int get_gram64(fbr_model *m, GramHolder *h)
     return FBR_OK;
 }
 
+// the sample-contiguous pass can serve a call with k rhs columns on this model (its tables built on first use): the option is on, at most
+// one rhs column and that one's products from the producer's moments (h->moments).  What else a call needs is the caller's to check.
+static int gram64_serves(fbr_model *m, GramHolder *h, int k, bool *serves)
+{
+    *serves = false;
+    if (!m->opt.gram_lane || k > 1 || (k == 1 && !h->moments)) return FBR_OK;
+    if (int rc = get_gram64(m, h)) return rc;
+    *serves = h->g64_state == 1;
+    return FBR_OK;
+}
+
 // blocks a chunk of the sample-contiguous pass may hold (two image buffers of at most 3 GB)
 static long gram64_chunk_blocks(const FbrGram64 &g) { return std::max<long>(1, (long)((size_t)3 * 1024 * 1024 * 1024 / ((size_t)g.blk_doubles * 8))); }
 
@@ -357,6 +367,155 @@ static int gram64_ensure_images(fbr_model *m, GramHolder *h, long chb)
     return FBR_OK;
 }
 
+// fbr_kinimg_kernel's depth instances: f(std::integral_constant<int, D>()) with the one that serves the model's joint paths
+template <class F> static auto kinimg_by_depth(const fbr_model *m, F &&f) { return fbr_by_depth<4, 8, 10, 12, FBR_KINID_MAXD>(m->kinid.maxlvl, f); }
+
+// what both sample-contiguous passes launch with
+struct Gram64Launch {
+    DevKinId kp;    // the producer's: the parts' programs (DevKinWrite says which steps are whose)
+    int pgrid_max;  // producer workgroups at most
+    DevGram64 dg;
+    void (*gk)(DevGram64, long, const double *, double *, int);  // the fbr_gram64_kernel instance, its dynamic LDS set to glds
+    size_t glds;
+    int vnpw;  // accumulator slots per ROW of the partial sums (fbr_gram_reduce_kernel walks 8 rows per workgroup)
+};
+static int gram64_setup(fbr_model *m, GramHolder *h, bool base_only, Gram64Launch *L)
+{
+    const FbrGram64 &g = h->g64;
+    L->kp = kinid_params(m, 0, h->g64p.nslots, h->d64_steps);
+    // producer grid: two workgroups per CU where the kernel instance fits 256 registers (fbr_kinimg_kernel's launch bounds)
+    L->pgrid_max = kinimg_by_depth(m, [](auto D) { return D <= 10 ? 2 : 1; }) * m->num_cus;
+    if (int rc = h->scr64.ensure((size_t)L->pgrid_max * h->g64p.nparts * std::max(h->g64p.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double))) return rc;
+    DevGram64 &dg = L->dg;
+    dg.NT = g.NT + g.NF;
+    dg.nlev = g.nlev;
+    dg.maxact = g.maxact;
+    dg.npieces = (int)g.pieces.size() / 2;
+    dg.blk_doubles = g.blk_doubles;
+    dg.slab = h->d64_slab;
+    dg.lev_begin = h->d64_levb;
+    dg.pieces = h->d64_pieces;
+    dg.wmeta = h->d64_wmeta;
+    dg.nstage = base_only ? g.base_stages : g.nstage;  // (base-wrench-only row masks: the joint levels' stages are not run)
+    dg.stage_lev = h->d64_stagelev;
+    dg.runs = g.runs.empty() ? nullptr : h->d64_runs;
+    L->gk = g.wpb == 16 ? fbr_gram64_kernel<10, 16>
+            : g.npw == 10   ? fbr_gram64_kernel<10, 8>
+            : g.runs.empty() ? fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8> : fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8, true>;
+    L->glds = fbr_gram64_lds_bytes(g);
+    L->vnpw = g.npw * (g.wpb / 8);
+    HIPCHK(hipFuncSetAttribute((const void *)L->gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L->glds));
+    return FBR_OK;
+}
+
+// the producer's destinations and options for image buffer b
+static DevKinWrite gram64_kinwrite(const fbr_model *m, const GramHolder *h, int b, int k, bool has_w, bool base_only, long group_samples)
+{
+    DevKinWrite kw{};
+    kw.lcol10 = h->d64_lcol;
+    kw.dst = (const long *)h->dst64[b].p;
+    kw.ninert = m->hm.ninert;
+    kw.cols = m->hm.cols;
+    kw.k = k;
+    kw.has_w = has_w ? 1 : 0;
+    kw.flev = h->g64.flev;
+    kw.base_only = base_only ? 1 : 0;
+    kw.group_samples = group_samples;
+    kw.nparts = h->g64p.nparts;
+    for (int pq = 0; pq < FBR_KINWRITE_PARTS; pq++) {
+        kw.part_nsteps[pq] = h->g64p.nsteps[pq];
+        kw.part_step0[pq] = h->g64p.step0[pq];
+    }
+    return kw;
+}
+
+// the producer fbr_kinimg_kernel on the model's stream: cs samples from sample so of the arrays into the image kw writes (rhs, w, mom and
+// the sign of d may be null), pblocks workgroups with plds bytes of dynamic LDS
+static int gram64_produce(fbr_model *m, GramHolder *h, const Gram64Launch &L, const DevKinWrite &kw, int pblocks, size_t plds, long cs,
+                          const DevStates &d, long so, const double *rhs, int k, const double *w, double *mom)
+{
+    const FbrHostModel &hm = m->hm;
+    return kinimg_by_depth(m, [&](auto D) -> int {
+        const auto kernel = kw.has_w ? fbr_kinimg_kernel<D, true> : fbr_kinimg_kernel<D, false>;
+        HIPCHK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+        hipLaunchKernelGGL(kernel, dim3(pblocks), dim3(64 * h->g64p.nparts), plds, m->stream, m->dm, L.kp, kw, cs, h->g64.blk_doubles, d.q + so * hm.n,
+                           d.dq + so * hm.n, d.ddq + so * hm.n, d.bv ? d.bv + so * 6 : nullptr, d.ba ? d.ba + so * 6 : nullptr,
+                           d.rpy ? d.rpy + so * 3 : nullptr, rhs ? rhs + (size_t)so * hm.rows * k : nullptr, w ? w + (size_t)so * hm.rows : nullptr,
+                           h->scr64.as<double>(), mom, d.sign ? d.sign + so * hm.n : nullptr);
+        HIPCHK(hipGetLastError());
+        return FBR_OK;
+    });
+}
+
+// fbr_gram_reduce_kernel over the partial sums of ng groups of wpg workgroups each (wg_begin: gram64_wg_table) into the ng Grams at G:
+// the main tiles, then the force tiles
+static int gram64_reduce(fbr_model *m, GramHolder *h, const Gram64Launch &L, int wpg, const int *wg_begin, int ng, double *G)
+{
+    DevGram dr = h->dev;  // the reduction of fbr_gram_reduce_kernel: one part of wpg workgroups
+    dr.wpg = wpg;
+    dr.npw = L.vnpw;
+    dr.slot_tiles = h->d64_slot_tiles;
+    dr.wg_begin = wg_begin;
+    dr.tilecol = h->d64_tilecol;
+    hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(FBR_WPB * L.vnpw, ng), dim3(256), 0, m->stream, dr, m->partial.as<double>(), G);
+    HIPCHK(hipGetLastError());
+    if (h->g64.NF > 0) {  // the blocks of the force tiles: entries the main blocks have written too, hence a launch of their own
+        dr.slot_tiles = h->d64_slot_tiles + (size_t)FBR_WPB * L.vnpw * 2;
+        hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(FBR_WPB * L.vnpw, ng), dim3(256), 0, m->stream, dr, m->partial.as<double>(), G);
+        HIPCHK(hipGetLastError());
+    }
+    return FBR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pinned host inputs, staged chunk by chunk
+// ------------------------------------------------------------------------------------------------
+// the staging stream, created on first use: HIP maps streams to hardware queues in creation order, and the producer stream's queue must
+// stay what it is for device-resident inputs
+static int ensure_copy_stream(fbr_model *m)
+{
+    if (m->copy) return FBR_OK;
+    // a priority level of its own (main stream: normal, producer: lowest, copies: highest), so that the copy stream never lands on the
+    // hardware queue of the Gram stream whatever streams the process created before (seen in bench.py after the TSQR leg had created two
+    // more streams: copies and Gram launches serialised, 78.6 instead of 74.1 ms per step)
+    int least = 0, greatest = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHK(hipStreamCreateWithPriority(&m->copy, hipStreamNonBlocking, greatest));
+    return FBR_OK;
+}
+// staging buffers 0 .. nbuf - 1, each for a chunk of `samples` samples: per sample q dq ddq [bv ba rpy] [sign] [rhs] [w]
+static int ensure_stage_buffers(fbr_model *m, const DevStates &d, int k, const double *w, long samples, int nbuf)
+{
+    const FbrHostModel &hm = m->hm;
+    const size_t per = (size_t)3 * hm.n + (hm.floating ? 15 : 0) + (d.sign ? hm.n : 0) + (size_t)hm.rows * k + (w ? hm.rows : 0);
+    for (int b = 0; b < nbuf; b++)
+        if (int rc = m->st_chunk[b].ensure(std::max<size_t>(1, (size_t)samples * per) * sizeof(double))) return rc;
+    return FBR_OK;
+}
+// samples [s0, s0 + cs) of the pinned host arrays d / rhs / w copied into staging buffer b on stream cps; *dc, *crhs and *cw point at the
+// copies (sample 0 of the chunk).  What the copies wait for and what waits for them is the caller's.
+static int stage_chunk(fbr_model *m, const DevStates &d, const double *rhs, int k, const double *w, long s0, long cs, int b, hipStream_t cps,
+                       DevStates *dc, const double **crhs, const double **cw)
+{
+    const FbrHostModel &hm = m->hm;
+    double *p = m->st_chunk[b].as<double>();
+    auto put = [&](const double *src, size_t per, const double **dst) -> int {
+        *dst = nullptr;
+        if (!src || per == 0) return FBR_OK;
+        HIPCHK(hipMemcpyAsync(p, src + (size_t)s0 * per, (size_t)cs * per * sizeof(double), hipMemcpyHostToDevice, cps));
+        *dst = p;
+        p += (size_t)cs * per;
+        return FBR_OK;
+    };
+    *dc = d;
+    int rc;
+    if ((rc = put(d.q, hm.n, &dc->q)) || (rc = put(d.dq, hm.n, &dc->dq)) || (rc = put(d.ddq, hm.n, &dc->ddq)) || (rc = put(d.bv, 6, &dc->bv)) ||
+        (rc = put(d.ba, 6, &dc->ba)) || (rc = put(d.rpy, 3, &dc->rpy)) || (rc = put(d.sign, hm.n, &dc->sign)) ||
+        (rc = put(rhs, (size_t)hm.rows * k, crhs)) || (rc = put(w, hm.rows, cw)))
+        return rc;
+    return FBR_OK;
+}
+
 // One call of the fused pass through fbr_kinimg_kernel / fbr_gram64_kernel (device-resident inputs, one group, k <= 1); everything on the
 // model's stream.  G has been cleared / holds the running sum.
 // h2d_chunked: d / drhs / dw are PINNED HOST pointers: every chunk is copied into one of two staging buffers on the copy stream while the
@@ -365,9 +524,8 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
                        bool h2d_chunked)
 {
     const FbrHostModel &hm = m->hm;
-    FbrGram64 &g = h->g64;
+    const FbrGram64 &g = h->g64;
     const long S = d.S;
-    const int Pa = hm.cols + k;
     int rc;
     // blocks per chunk: what the image buffers hold (a call that fits is ONE chunk: a 125 k-sample shard ran 1792 + 162 blocks before);
     // several chunks: whole rounds of the chip (both kernels walk blocks workgroup by workgroup).  Pinned inputs: chunks of seven rounds
@@ -382,56 +540,20 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     chb = std::min(nblocks, chb);
     if (chb < nblocks && chb > m->num_cus) chb = chb / m->num_cus * m->num_cus;
     if ((rc = gram64_ensure_images(m, h, chb))) return rc;
-    const int ldn = std::max(hm.n, 1) | 1, ldw = hm.rows | 1;
-    const size_t plds = ((size_t)3 * 64 * ldn + (dw ? (size_t)64 * ldw : 0) + (k ? (size_t)64 * ldw : 0)) * sizeof(double);
-    // producer grid: two workgroups per CU where the kernel instance fits 256 registers (fbr_kinimg_kernel's launch bounds)
-    const int pgrid_max = (m->kinid.maxlvl <= 10 ? 2 : 1) * m->num_cus;
-    const int pblocks = (int)std::min<long>(chb, (long)pgrid_max);
+    Gram64Launch L;
+    if ((rc = gram64_setup(m, h, base_only, &L))) return rc;
+    const int ldw = hm.rows | 1;
+    const size_t plds = ((size_t)3 * 64 * L.kp.ldn + (dw ? (size_t)64 * ldw : 0) + (k ? (size_t)64 * ldw : 0)) * sizeof(double);
+    const int pblocks = (int)std::min<long>(chb, (long)L.pgrid_max);
     const int gwgs = (int)std::min<long>(chb, (long)m->num_cus);
-    if ((rc = h->scr64.ensure((size_t)pgrid_max * h->g64p.nparts * std::max(h->g64p.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double)))) return rc;
     if (k) {
-        if ((rc = h->mom64.ensure((size_t)pgrid_max * (hm.cols + 1) * 64 * sizeof(double)))) return rc;
+        if ((rc = h->mom64.ensure((size_t)L.pgrid_max * (hm.cols + 1) * 64 * sizeof(double)))) return rc;
         HIPCHK(hipMemsetAsync(h->mom64.p, 0, (size_t)pblocks * (hm.cols + 1) * 64 * sizeof(double), m->stream));  // (the producer grid of this call)
     }
-    const int npw = g.npw;
-    if ((rc = m->partial.ensure((size_t)m->num_cus * g.wpb * npw * 256 * sizeof(double)))) return rc;
-    const size_t glds = fbr_gram64_lds_bytes(g);
-    DevKinId kp;
-    kp.nsteps = 0;
-    kp.maxlvl = m->kinid.maxlvl;
-    kp.nslots = h->g64p.nslots;
-    kp.ldn = ldn;
-    kp.steps = h->d64_steps;
-    kp.endflush = m->kinid_endflush;
-    DevGram64 dg;
-    dg.NT = g.NT + g.NF;
-    dg.nlev = g.nlev;
-    dg.maxact = g.maxact;
-    dg.npieces = (int)g.pieces.size() / 2;
-    dg.blk_doubles = g.blk_doubles;
-    dg.slab = h->d64_slab;
-    dg.lev_begin = h->d64_levb;
-    dg.pieces = h->d64_pieces;
-    dg.wmeta = h->d64_wmeta;
-    dg.nstage = base_only ? g.base_stages : g.nstage;  // (base-wrench-only row masks: the joint levels' stages are not run)
-    dg.stage_lev = h->d64_stagelev;
-    dg.runs = g.runs.empty() ? nullptr : h->d64_runs;
-    typedef void (*g64_fn)(DevGram64, long, const double *, double *, int);
-    const g64_fn gk = g.wpb == 16 ? fbr_gram64_kernel<10, 16>
-                      : g.npw == 10   ? fbr_gram64_kernel<10, 8>
-                      : g.runs.empty() ? fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8> : fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8, true>;
-    const int vnpw = g.npw * (g.wpb / 8);  // accumulator slots per ROW of the partial sums (fbr_gram_reduce_kernel walks 8 rows per workgroup)
-    HIPCHK(hipFuncSetAttribute((const void *)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
+    if ((rc = m->partial.ensure((size_t)m->num_cus * g.wpb * g.npw * 256 * sizeof(double)))) return rc;
     int launches = 0, first_wgs = 0;
-    const size_t stage_per = (size_t)3 * hm.n + (hm.floating ? 15 : 0) + (d.sign ? hm.n : 0) + (size_t)hm.rows * k + (dw ? hm.rows : 0);  // doubles per staged sample
     if (h2d_chunked) {
-        for (int b = 0; b < 2; b++)
-            if ((rc = m->st_chunk[b].ensure(std::max<size_t>(1, (size_t)chb * 64 * stage_per) * sizeof(double)))) return rc;
-        if (!m->copy) {  // (a priority level of its own: see the per-sample-image pass below)
-            int least = 0, greatest = 0;
-            HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPCHK(hipStreamCreateWithPriority(&m->copy, hipStreamNonBlocking, greatest));
-        }
+        if ((rc = ensure_stage_buffers(m, d, k, dw, chb * 64, 2)) || (rc = ensure_copy_stream(m))) return rc;
         HIPCHK(hipEventRecord(m->ev_fork, m->stream));
     }
     // the states of chunk c in device memory: the caller's arrays, or staging buffer (c & 1) filled on the copy stream
@@ -443,28 +565,12 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     auto stage = [&](long c, Staged &out) -> int {
         const long s0 = c * chb * 64, cs = std::min(chb * 64, S - s0);
         const int b = (int)(c & 1);
-        out.dc = d;
-        out.o = s0;
-        out.rhs = drhs;
-        out.w = dw;
+        out = {d, s0, drhs, dw};
         if (!h2d_chunked) return FBR_OK;
         // the buffer's last reader is the producer launch of the chunk two before (or of an earlier call: the event is simply complete then)
         HIPCHK(hipStreamWaitEvent(m->copy, m->ev_pack_rec[b] ? m->ev_pack[b] : m->ev_fork, 0));
         ProfScope ps(m, FBR_PROF_H2D, m->copy);
-        double *p = m->st_chunk[b].as<double>();
-        auto put = [&](const double *src, size_t per, const double **dst) -> int {
-            *dst = nullptr;
-            if (!src || per == 0) return FBR_OK;
-            HIPCHK(hipMemcpyAsync(p, src + (size_t)s0 * per, (size_t)cs * per * sizeof(double), hipMemcpyHostToDevice, m->copy));
-            *dst = p;
-            p += (size_t)cs * per;
-            return FBR_OK;
-        };
-        int r3;
-        if ((r3 = put(d.q, hm.n, &out.dc.q)) || (r3 = put(d.dq, hm.n, &out.dc.dq)) || (r3 = put(d.ddq, hm.n, &out.dc.ddq)) ||
-            (r3 = put(d.bv, 6, &out.dc.bv)) || (r3 = put(d.ba, 6, &out.dc.ba)) || (r3 = put(d.rpy, 3, &out.dc.rpy)) ||
-            (r3 = put(d.sign, hm.n, &out.dc.sign)) || (r3 = put(drhs, (size_t)hm.rows * k, &out.rhs)) || (r3 = put(dw, hm.rows, &out.w)))
-            return r3;
+        if (int r3 = stage_chunk(m, d, drhs, k, dw, s0, cs, b, m->copy, &out.dc, &out.rhs, &out.w)) return r3;
         out.o = 0;
         HIPCHK(hipEventRecord(m->ev_h2d[b], m->copy));
         return FBR_OK;
@@ -477,58 +583,13 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
         cur = nxt;
         if ((b0 + chb) * 64 < S && (rc = stage(launches + 1, nxt))) return rc;  // the copy of the next chunk is enqueued before this chunk's kernels
         if (h2d_chunked) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_h2d[b], 0));
-        const DevStates &dc = cur.dc;
-        const long so = cur.o;
-        const double *crhs = cur.rhs, *cw = cur.w;
-        DevKinWrite kw;
-        kw.lcol10 = h->d64_lcol;
-        kw.colrec = nullptr;
-        kw.dst = (const long *)h->dst64[b].p;
-        kw.ninert = hm.ninert;
-        kw.cols = hm.cols;
-        kw.k = k;
-        kw.has_w = dw ? 1 : 0;
-        kw.flev = g.flev;
-        kw.base_only = base_only ? 1 : 0;
-        kw.group_samples = 0;
-        kw.nparts = h->g64p.nparts;
-        for (int pq = 0; pq < FBR_KINWRITE_PARTS; pq++) {
-            kw.part_nsteps[pq] = h->g64p.nsteps[pq];
-            kw.part_step0[pq] = h->g64p.step0[pq];
-        }
         if (cs & 63)  // the block the producer fills partly: what its idle lanes would have written (a buffer is reused from chunk to chunk)
             HIPCHK(hipMemsetAsync(h->img64[b].as<double>() + (nb - 1) * g.blk_doubles, 0, (size_t)g.blk_doubles * sizeof(double), m->stream));
         {
             ProfScope ps(m, FBR_PROF_PACK);
-#define FBR_KINIMG_LAUNCH2(D, W)                                                                                                                    \
-    do {                                                                                                                                         \
-        HIPCHK(hipFuncSetAttribute((const void *)fbr_kinimg_kernel<D, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));                 \
-        hipLaunchKernelGGL((fbr_kinimg_kernel<D, W>), dim3(pblocks), dim3(64 * h->g64p.nparts), plds, m->stream, m->dm, kp, kw, cs, g.blk_doubles,       \
-                           dc.q + so * hm.n, dc.dq + so * hm.n, dc.ddq + so * hm.n, dc.bv ? dc.bv + so * 6 : nullptr, dc.ba ? dc.ba + so * 6 : nullptr, \
-                           dc.rpy ? dc.rpy + so * 3 : nullptr, crhs ? crhs + (size_t)so * hm.rows * k : nullptr,                                   \
-                           cw ? cw + (size_t)so * hm.rows : nullptr, h->scr64.as<double>(), k ? h->mom64.as<double>() : nullptr,                   \
-                           dc.sign ? dc.sign + so * hm.n : nullptr);                                                                              \
-    } while (0)
-#define FBR_KINIMG_LAUNCH(D)            \
-    do {                                \
-        if (dw)                         \
-            FBR_KINIMG_LAUNCH2(D, true); \
-        else                            \
-            FBR_KINIMG_LAUNCH2(D, false); \
-    } while (0)
-            if (kp.maxlvl <= 4)
-                FBR_KINIMG_LAUNCH(4);
-            else if (kp.maxlvl <= 8)
-                FBR_KINIMG_LAUNCH(8);
-            else if (kp.maxlvl <= 10)
-                FBR_KINIMG_LAUNCH(10);
-            else if (kp.maxlvl <= 12)
-                FBR_KINIMG_LAUNCH(12);
-            else
-                FBR_KINIMG_LAUNCH(FBR_KINID_MAXD);
-#undef FBR_KINIMG_LAUNCH2
-#undef FBR_KINIMG_LAUNCH
-            HIPCHK(hipGetLastError());
+            if ((rc = gram64_produce(m, h, L, gram64_kinwrite(m, h, b, k, dw != nullptr, base_only, 0), pblocks, plds, cs, cur.dc, cur.o, cur.rhs, k,
+                                     cur.w, k ? h->mom64.as<double>() : nullptr)))
+                return rc;
             if (h2d_chunked) {  // (the staging buffer may be refilled once this launch is through)
                 HIPCHK(hipEventRecord(m->ev_pack[b], m->stream));
                 m->ev_pack_rec[b] = true;
@@ -543,31 +604,20 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
         }
         {
             ProfScope ps(m, FBR_PROF_GRAM);
-            hipLaunchKernelGGL(gk, dim3(first_wgs), dim3(g.wpb * 64), glds, m->stream, dg, nb, h->img64[b].as<double>(), m->partial.as<double>(), launches > 0 ? 1 : 0);
+            hipLaunchKernelGGL(L.gk, dim3(first_wgs), dim3(g.wpb * 64), L.glds, m->stream, L.dg, nb, h->img64[b].as<double>(), m->partial.as<double>(),
+                               launches > 0 ? 1 : 0);
             HIPCHK(hipGetLastError());
         }
     }
     if (launches > 0) {
         ProfScope ps(m, FBR_PROF_REDUCE);
-        DevGram dr = h->dev;  // the reduction of fbr_gram_reduce_kernel: one part of first_wgs workgroups
-        dr.wpg = first_wgs;
-        dr.npw = vnpw;
-        dr.slot_tiles = h->d64_slot_tiles;
-        if ((rc = gram64_wg_table(h, first_wgs, &dr.wg_begin))) return rc;
-        dr.tilecol = h->d64_tilecol;
-        hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(FBR_WPB * vnpw, 1), dim3(256), 0, m->stream, dr, m->partial.as<double>(), G);
-        HIPCHK(hipGetLastError());
-        if (g.NF > 0) {  // the blocks of the force tiles: entries the main blocks have written too, hence a launch of their own
-            dr.slot_tiles = h->d64_slot_tiles + (size_t)FBR_WPB * vnpw * 2;
-            hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(FBR_WPB * vnpw, 1), dim3(256), 0, m->stream, dr, m->partial.as<double>(), G);
-            HIPCHK(hipGetLastError());
-        }
+        const int *wgb = nullptr;
+        if ((rc = gram64_wg_table(h, first_wgs, &wgb)) || (rc = gram64_reduce(m, h, L, first_wgs, wgb, 1, G))) return rc;
         if (k) {
             hipLaunchKernelGGL(fbr_gram64_mom_reduce_kernel, dim3(hm.cols + 1), dim3(256), 0, m->stream, hm.cols, pblocks, h->mom64.as<double>(), G);
             HIPCHK(hipGetLastError());
         }
     }
-    (void)Pa;
     return FBR_OK;
 }
 
@@ -577,127 +627,265 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
 static int gram64_grouped_pass(fbr_model *m, GramHolder *h, const DevStates &d, const double *dw, double *G, int ngroups)
 {
     const FbrHostModel &hm = m->hm;
-    FbrGram64 &g = h->g64;
+    const FbrGram64 &g = h->g64;
     const long S = d.S, Sg = S / ngroups, bpg = (Sg + 63) / 64;
-    const int Pa = hm.cols, npw = g.npw;
+    const int Pa = hm.cols;
     int rc;
     // groups per chunk: what the image buffers hold, and at most 32768 -- a chunk's groups are gridDim.y of the launches below (limit
     // 65535; the expand kernels of gram_via_red take the same 32768)
     const int gpc = (int)std::min<long>(std::min(ngroups, 32768), std::max<long>(1, gram64_chunk_blocks(g) / bpg));
     if ((rc = gram64_ensure_images(m, h, (long)gpc * bpg))) return rc;
     const int wpg = (int)std::max<long>(1, std::min<long>(bpg, (long)m->num_cus / std::min(gpc, ngroups)));
-    const int ldn = std::max(hm.n, 1) | 1, ldw = hm.rows | 1;
-    const size_t plds = ((size_t)3 * 64 * ldn + (dw ? (size_t)64 * ldw : 0)) * sizeof(double);
-    const int pgrid_max = (m->kinid.maxlvl <= 10 ? 2 : 1) * m->num_cus;
-    if ((rc = h->scr64.ensure((size_t)pgrid_max * h->g64p.nparts * std::max(h->g64p.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double)))) return rc;
-    if ((rc = m->partial.ensure((size_t)gpc * wpg * g.wpb * npw * 256 * sizeof(double)))) return rc;
-    const size_t glds = fbr_gram64_lds_bytes(g);
-    DevKinId kp;
-    kp.nsteps = 0;
-    kp.maxlvl = m->kinid.maxlvl;
-    kp.nslots = h->g64p.nslots;
-    kp.ldn = ldn;
-    kp.steps = h->d64_steps;
-    kp.endflush = m->kinid_endflush;
-    DevGram64 dg;
-    dg.NT = g.NT + g.NF;
-    dg.nlev = g.nlev;
-    dg.maxact = g.maxact;
-    dg.npieces = (int)g.pieces.size() / 2;
-    dg.blk_doubles = g.blk_doubles;
-    dg.slab = h->d64_slab;
-    dg.lev_begin = h->d64_levb;
-    dg.pieces = h->d64_pieces;
-    dg.wmeta = h->d64_wmeta;
-    dg.nstage = g.nstage;
-    dg.stage_lev = h->d64_stagelev;
-    dg.runs = g.runs.empty() ? nullptr : h->d64_runs;
-    typedef void (*g64_fn)(DevGram64, long, const double *, double *, int);
-    const g64_fn gk = g.wpb == 16 ? fbr_gram64_kernel<10, 16>
-                      : g.npw == 10   ? fbr_gram64_kernel<10, 8>
-                      : g.runs.empty() ? fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8> : fbr_gram64_kernel<FBR_ONE_SEGW * FBR_ONE_NSEG, 8, true>;
-    const int vnpw = g.npw * (g.wpb / 8);  // accumulator slots per ROW of the partial sums (fbr_gram_reduce_kernel walks 8 rows per workgroup)
-    HIPCHK(hipFuncSetAttribute((const void *)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
+    Gram64Launch L;
+    if ((rc = gram64_setup(m, h, false, &L))) return rc;
+    const size_t plds = ((size_t)3 * 64 * L.kp.ldn + (dw ? (size_t)64 * (hm.rows | 1) : 0)) * sizeof(double);
+    if ((rc = m->partial.ensure((size_t)gpc * wpg * g.wpb * g.npw * 256 * sizeof(double)))) return rc;
     const int *wgb = nullptr;
     if ((rc = gram64_wg_table(h, wpg, &wgb))) return rc;
-    int launches = 0;
-    for (int g0 = 0; g0 < ngroups; g0 += gpc, launches++) {
+    for (int g0 = 0, launches = 0; g0 < ngroups; g0 += gpc, launches++) {
         const int ng = std::min(gpc, ngroups - g0), b = launches & 1;
         const long s0 = (long)g0 * Sg, cs = (long)ng * Sg, nb = (long)ng * bpg;
-        DevKinWrite kw;
-        kw.lcol10 = h->d64_lcol;
-        kw.colrec = nullptr;
-        kw.dst = (const long *)h->dst64[b].p;
-        kw.ninert = hm.ninert;
-        kw.cols = hm.cols;
-        kw.k = 0;
-        kw.has_w = dw ? 1 : 0;
-        kw.flev = g.flev;
-        kw.base_only = 0;
-        kw.group_samples = Sg;
-        kw.nparts = h->g64p.nparts;
-        for (int pq = 0; pq < FBR_KINWRITE_PARTS; pq++) {
-            kw.part_nsteps[pq] = h->g64p.nsteps[pq];
-            kw.part_step0[pq] = h->g64p.step0[pq];
-        }
-        const int pblocks = (int)std::min<long>(nb, (long)pgrid_max);
         if (Sg & 63) {  // every group ends in a block the producer fills partly: what its idle lanes would have written
             hipLaunchKernelGGL(fbr_gram64_tail_zero_kernel, dim3(16, ng), dim3(256), 0, m->stream, h->img64[b].as<double>(), g.blk_doubles, bpg, g.ntr, (int)(Sg & 63));
             HIPCHK(hipGetLastError());
         }
         {
             ProfScope ps(m, FBR_PROF_PACK);
-#define FBR_KINIMG_GLAUNCH2(D, W)                                                                                                                 \
-    do {                                                                                                                                         \
-        HIPCHK(hipFuncSetAttribute((const void *)fbr_kinimg_kernel<D, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));                 \
-        hipLaunchKernelGGL((fbr_kinimg_kernel<D, W>), dim3(pblocks), dim3(64 * h->g64p.nparts), plds, m->stream, m->dm, kp, kw, cs, g.blk_doubles, \
-                           d.q + s0 * hm.n, d.dq + s0 * hm.n, d.ddq + s0 * hm.n, d.bv ? d.bv + s0 * 6 : nullptr, d.ba ? d.ba + s0 * 6 : nullptr,    \
-                           d.rpy ? d.rpy + s0 * 3 : nullptr, (const double *)nullptr, dw ? dw + (size_t)s0 * hm.rows : nullptr,                    \
-                           h->scr64.as<double>(), (double *)nullptr, d.sign ? d.sign + s0 * hm.n : nullptr);                                      \
-    } while (0)
-#define FBR_KINIMG_GLAUNCH(D)             \
-    do {                                  \
-        if (dw)                           \
-            FBR_KINIMG_GLAUNCH2(D, true); \
-        else                              \
-            FBR_KINIMG_GLAUNCH2(D, false); \
-    } while (0)
-            if (kp.maxlvl <= 4)
-                FBR_KINIMG_GLAUNCH(4);
-            else if (kp.maxlvl <= 8)
-                FBR_KINIMG_GLAUNCH(8);
-            else if (kp.maxlvl <= 10)
-                FBR_KINIMG_GLAUNCH(10);
-            else if (kp.maxlvl <= 12)
-                FBR_KINIMG_GLAUNCH(12);
-            else
-                FBR_KINIMG_GLAUNCH(FBR_KINID_MAXD);
-#undef FBR_KINIMG_GLAUNCH2
-#undef FBR_KINIMG_GLAUNCH
-            HIPCHK(hipGetLastError());
+            if ((rc = gram64_produce(m, h, L, gram64_kinwrite(m, h, b, 0, dw != nullptr, false, Sg), (int)std::min<long>(nb, (long)L.pgrid_max), plds, cs,
+                                     d, s0, nullptr, 0, dw, nullptr)))
+                return rc;
         }
         {
             ProfScope ps(m, FBR_PROF_GRAM);
-            hipLaunchKernelGGL(gk, dim3(wpg, ng), dim3(g.wpb * 64), glds, m->stream, dg, bpg, h->img64[b].as<double>(), m->partial.as<double>(), 0);
+            hipLaunchKernelGGL(L.gk, dim3(wpg, ng), dim3(g.wpb * 64), L.glds, m->stream, L.dg, bpg, h->img64[b].as<double>(), m->partial.as<double>(), 0);
             HIPCHK(hipGetLastError());
         }
         {
             ProfScope ps(m, FBR_PROF_REDUCE);
-            DevGram dr = h->dev;
-            dr.wpg = wpg;
-            dr.npw = vnpw;
-            dr.slot_tiles = h->d64_slot_tiles;
-            dr.wg_begin = wgb;
-            dr.tilecol = h->d64_tilecol;
-            double *Gc = G + (size_t)g0 * Pa * Pa;
-            hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(FBR_WPB * vnpw, ng), dim3(256), 0, m->stream, dr, m->partial.as<double>(), Gc);
-            if (g.NF > 0) {
-                dr.slot_tiles = h->d64_slot_tiles + (size_t)FBR_WPB * vnpw * 2;
-                hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(FBR_WPB * vnpw, ng), dim3(256), 0, m->stream, dr, m->partial.as<double>(), Gc);
-            }
-            HIPCHK(hipGetLastError());
+            if ((rc = gram64_reduce(m, h, L, wpg, wgb, ng, G + (size_t)g0 * Pa * Pa))) return rc;
         }
     }
+    return FBR_OK;
+}
+
+// gram_timing (diagnostic): the per-part cycle counts fbr_gram_kernel<true> wrote into dbg for the NW workgroups of a launch, on stderr
+static int print_gram_timing(fbr_model *m, int T, const unsigned long long *dbg, int NW)
+{
+    std::vector<unsigned long long> hb((size_t)NW * FBR_WPB * 8);
+    HIPCHK(hipMemcpyAsync(hb.data(), dbg, hb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    static const char *names[3] = {"wait_dma+barrier", "dma_issue", "mfma"};
+    std::vector<double> sum((size_t)T * 3, 0.0), ns(T, 0.0), nw(T, 0.0), wv((size_t)T * FBR_WPB, 0.0);
+    for (size_t e = 0; e + 8 <= hb.size(); e += 8) {
+        const int part = (int)hb[e + 6];
+        if (part < 0 || part >= T) continue;
+        for (int i = 0; i < 3; i++) sum[(size_t)part * 3 + i] += (double)hb[e + i];
+        ns[part] += (double)hb[e + 7];
+        nw[part] += 1.0;
+        wv[(size_t)part * FBR_WPB + (e / 8) % FBR_WPB] += (double)hb[e + 2];
+    }
+    for (int part = 0; part < T; part++) {
+        fprintf(stderr, "[fbr gram timing] part %d (cycles per sample per wave):", part);
+        for (int i = 0; i < 3; i++) fprintf(stderr, " %s=%.0f", names[i], sum[(size_t)part * 3 + i] / std::max(ns[part], 1.0));
+        fprintf(stderr, " | workgroups=%.0f cycles per workgroup=%.0f | mfma phase per wave:", nw[part] / FBR_WPB,
+                (sum[(size_t)part * 3] + sum[(size_t)part * 3 + 1] + sum[(size_t)part * 3 + 2]) / std::max(nw[part], 1.0));
+        for (int w = 0; w < FBR_WPB; w++) fprintf(stderr, " %.0f", wv[(size_t)part * FBR_WPB + w] * FBR_WPB / std::max(ns[part], 1.0));
+        fprintf(stderr, "\n");
+    }
+    return FBR_OK;
+}
+
+// The pass over per-sample tile images (fbr_pack_kernel / fbr_gram_kernel), S > 0 samples in ngroups groups: the producer (kinematics +
+// packing of chunk i+1) on a second stream beside the Gram kernel of chunk i.  G has been cleared / holds the running sum.
+// h2d_chunked: d / drhs / dw are PINNED HOST pointers, staged chunk by chunk on the copy stream.  overlap_prev: a submission before this
+// one is still in flight.  async: nothing is waited for.
+static int gram_image_pass(fbr_model *m, GramHolder *h, const DevStates &d, const double *drhs, const double *dw, int k, double *G, int ngroups,
+                           bool base_only, bool h2d_chunked, bool overlap_prev, bool async)
+{
+    const FbrHostModel &hm = m->hm;
+    const long S = d.S;
+    const int Pa = h->prog.Pa, T = h->prog.T;
+    const bool moments = h->moments;
+    int rc;
+    const bool two_per_cu = h->prog.cfg == FBR_CFG_TWO_PER_CU;
+    const int blocks_per_cu = (two_per_cu && h->lds_bytes <= 79 * 1024) ? 2 : 1;
+    const int FBR_NPW = h->prog.cfg.npw();
+    const bool timing = m->opt.gram_timing != 0;
+    typedef void (*gram_fn)(DevGram, long, int, const double *, double *, unsigned long long *, int);
+    const gram_fn gram_kernel = two_per_cu ? (timing ? fbr_gram_kernel<true, 5, 2> : fbr_gram_kernel<false, 5, 2>)
+                                           : (timing ? fbr_gram_kernel<true, FBR_ONE_SEGW, FBR_ONE_NSEG> : fbr_gram_kernel<false, FBR_ONE_SEGW, FBR_ONE_NSEG>);
+    HIPCHK(hipFuncSetAttribute((const void *)gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    HIPCHK(hipFuncSetAttribute((const void *)fbr_pack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)h->pack_lds_bytes));
+    const size_t img_bytes = (size_t)h->prog.image_doubles * sizeof(double);
+    long ch = chunk_size(m, S);
+    ch = std::max(1L, std::min(ch, (long)((size_t)4 * 1024 * 1024 * 1024 / img_bytes)));
+    if (ngroups == 1 && m->opt.chunk_samples < 1) {
+        // a short batch (e.g. one rank's shard of a multi-GPU run) is still cut into several chunks, so that only a small first
+        // chunk's producer work runs before the first Gram launch instead of half the batch's
+        const long min_chunks = std::max(1L, (long)m->opt.min_chunks);  // measured: 125 k samples 2 / 4 / 8 / 16 chunks = 11.45 / 11.69 / 11.19 / 9.35 M samples/s
+        ch = std::max(std::min(ch, 8192L), std::min(ch, (S + min_chunks - 1) / min_chunks));
+    }
+    // work items: several whole groups per launch, or (groups larger than a chunk) pieces of one group
+    struct Item { long s0, cs; int g0, ng; };
+    std::vector<Item> items;
+    const long Sg = S / ngroups;
+    if (Sg <= ch) {
+        const int gpc = (int)std::min<long>(ngroups, std::max(1L, ch / Sg));
+        for (int g0 = 0; g0 < ngroups; g0 += gpc) {
+            const int ng = std::min(gpc, ngroups - g0);
+            items.push_back({g0 * Sg, ng * Sg, g0, ng});
+        }
+        ch = gpc * Sg;
+    } else {
+        // the producer work of the very first chunk is the only one that nothing hides: it is made smaller (a quarter of a chunk:
+        // measured on a 125 k-sample shard, tools/chunk_probe.py)
+        for (int g = 0; g < ngroups; g++)
+            for (long c0 = 0; c0 < Sg; c0 += ch) items.push_back({g * Sg + c0, std::min(ch, Sg - c0), g, 1});
+    }
+    const long nchunks = (long)items.size();
+    bool fresh_images = false;  // a tile-image buffer was (re)allocated and zeroed on the main stream in this call
+    // workgroups per group of a launch: every resident workgroup slot is used (see the launch below)
+    auto wpg_of = [&](long cs, int ng) {
+        const long spg_max = std::max(1L, cs / ng);
+        const int rounds = ng > 1 ? (T > 1 ? 4 : 2) : 1;
+        int wpg = std::max(T, (rounds * m->num_cus * blocks_per_cu) / ng);
+        if ((long)wpg > (long)T * spg_max) wpg = (int)((long)T * spg_max);
+        return std::min(wpg, 0xffff);
+    };
+    // One reduction per call: when every chunk of a single-group call has the same launch shape, a workgroup carries its partial
+    // sums from chunk to chunk (the accumulators start from the partial-sum buffer) and fbr_gram_reduce_kernel runs once, after
+    // the last chunk -- 15 of the 16 reductions of a 1 M-sample WALK-MAN pass (72 us each, between two Gram launches) go away.
+    bool carry_ok = ngroups == 1 && nchunks > 1 && !timing;
+    for (long ci = 1; ci < nchunks && carry_ok; ci++) carry_ok = wpg_of(items[ci].cs, 1) == wpg_of(items[0].cs, 1);
+    for (int b = 0; b < (nchunks > 1 ? 2 : 1); b++)
+        if ((size_t)ch * img_bytes > h->pimg[b].bytes) {
+            if ((rc = h->pimg[b].ensure((size_t)ch * img_bytes))) return rc;
+            HIPCHK(hipMemsetAsync(h->pimg[b].p, 0, h->pimg[b].bytes, m->stream));  // structural zeros are never rewritten
+            fresh_images = true;
+        }
+    // producer (kinematics + tile-image packing of chunk i+1) runs on a second stream and shares the CUs with the
+    // MFMA-bound Gram kernel of chunk i; the images are double buffered
+    HIPCHK(hipEventRecord(m->ev_fork, m->stream));
+    // FBR_GRAM_SERIAL (diagnostic): producer on the main stream, i.e. no overlap with the Gram kernel
+    hipStream_t side = m->opt.gram_serial ? m->stream : m->side;
+    // The producer normally starts after everything enqueued on the main stream so far.  A submission that follows another one
+    // (fbr_gram_submit) skips that: its inputs are device resident, and what its first producer launches must wait for is only
+    // the tile-image buffer they write (ev_gram below) -- kinematics and packing of its first chunk then run beside the last
+    // Gram launches of the submission before, the one piece of producer work nothing else hides.
+    const bool cross = overlap_prev && !fresh_images && side != m->stream;
+    if (!cross) HIPCHK(hipStreamWaitEvent(side, m->ev_fork, 0));
+    if (h2d_chunked && (rc = ensure_stage_buffers(m, d, k, dw, ch, nchunks > 1 ? 2 : 1))) return rc;
+    // pack workgroups per CU of a launch's grid (each walks its share of the chunk's samples).  More than are ever resident (7 per CU
+    // alone, 2 beside the Gram kernel): with 8 the workgroups of the last, partial round ran on a half-empty chip at the end of every
+    // launch (measured per 1 M-sample step, two runs each: 8 -> 24.1, 16 -> 23.5 ... 24.0, 24 -> 23.1 ... 23.4, 32 / 48 -> 23.4)
+    const int pack_wgs_per_cu = 24;
+    const int pack_blocks_max = m->num_cus * pack_wgs_per_cu;
+    auto produce = [&](long ci) -> int {
+        const long s0 = items[ci].s0, cs = items[ci].cs;
+        const int b = (int)(ci & 1);
+        // Gram of chunk ci-2 (or, across submissions, the last Gram launch that read this buffer) is done with it
+        if (ci >= 2 || (cross && m->ev_gram_rec[b])) HIPCHK(hipStreamWaitEvent(side, m->ev_gram[b], 0));
+        DevStates dc = d;     // what the kernels of this chunk read, and the sample offset into it
+        long o = s0;
+        const double *crhs = drhs, *cw = dw;
+        if (h2d_chunked) {
+            // copies run on their own stream so that the copy of this chunk overlaps the kinematics / packing of the one before:
+            // they wait for the pack kernel of chunk ci-2 (the last reader of this staging buffer), the producer waits for them
+            int r3;
+            if ((r3 = ensure_copy_stream(m))) return r3;
+            // the staging buffer's last reader is the pack kernel of the chunk two before (or, across submissions, the last
+            // pack launch that used this buffer)
+            if (ci >= 2 || (cross && m->ev_pack_rec[b]))
+                HIPCHK(hipStreamWaitEvent(m->copy, m->ev_pack[b], 0));
+            else
+                HIPCHK(hipStreamWaitEvent(m->copy, m->ev_fork, 0));
+            ProfScope ps(m, FBR_PROF_H2D, m->copy);
+            if ((r3 = stage_chunk(m, d, drhs, k, dw, s0, cs, b, m->copy, &dc, &crhs, &cw))) return r3;
+            o = 0;
+            HIPCHK(hipEventRecord(m->ev_h2d[b], m->copy));
+            HIPCHK(hipStreamWaitEvent(side, m->ev_h2d[b], 0));
+        }
+        int rc2 = run_kin(m, dc, o, cs, side, &m->rec2);
+        if (rc2) return rc2;
+        {
+            ProfScope ps(m, FBR_PROF_PACK, side);
+            const int blocks = (int)std::min<long>(cs, (long)pack_blocks_max);
+            hipLaunchKernelGGL(fbr_pack_kernel, dim3(blocks), dim3(256), h->pack_lds_bytes, side, h->dev, m->dm, cs, cs / items[ci].ng,
+                               m->rec2.as<double>(), dc.dq + o * hm.n, dc.sign ? dc.sign + o * hm.n : nullptr,
+                               crhs ? crhs + (size_t)o * hm.rows * k : nullptr, cw ? cw + (size_t)o * hm.rows : nullptr,
+                               h->pimg[b].as<double>(), base_only ? 1 : 0, moments ? h->mom[(int)(m->next_ticket & 1)].as<double>() : nullptr);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(m->ev_pack[b], side));
+        m->ev_pack_rec[b] = true;
+        return FBR_OK;
+    };
+    const int mpar = (int)(m->next_ticket & 1);
+    if (moments) {
+        const size_t mbytes = (size_t)pack_blocks_max * 256 * 4 * sizeof(double);
+        if (h->mom[mpar].bytes < mbytes) h->mom_clean[mpar] = false;
+        if ((rc = h->mom[mpar].ensure(mbytes))) return rc;
+        if (!h->mom_clean[mpar]) HIPCHK(hipMemsetAsync(h->mom[mpar].p, 0, mbytes, side));
+        h->mom_clean[mpar] = false;  // (until this call's reduction has been enqueued)
+    }
+    if ((rc = produce(0))) return rc;
+    for (long ci = 0; ci < nchunks; ci++) {
+        const long cs = items[ci].cs;
+        const int ng = items[ci].ng;
+        const int b = (int)(ci & 1);
+        if (ci + 1 < nchunks && (rc = produce(ci + 1))) return rc;
+        HIPCHK(hipStreamWaitEvent(m->stream, m->ev_pack[b], 0));
+        // every resident workgroup slot is used: the slots of a sample group are dealt to the parts by cost (fbr_gram_deal),
+        // a part's workgroups split the group's samples evenly.  Tiny batches: no more workgroups than samples per part.
+        // Grouped launches (many short candidates) are oversubscribed: with one round of resident workgroups a group gets too few
+        // of them to follow the parts' costs (WALK-MAN, 64 groups x 2000 samples: 5 per group, 15.4 ms; 4 rounds: 11.8 ms; KUKA
+        // 0.92 -> 0.90 ms with 2 rounds) and the hardware dispatcher evens out the rest.  Bulk launches lose 17 % when
+        // oversubscribed (late workgroups run beside the producer kernels of the next chunk): one round, dealt by cost.
+        const int wpg = wpg_of(cs, ng);
+        GramHolder::Deal deal;
+        if ((rc = get_deal(h, wpg, &deal, base_only))) return rc;
+        DevGram dg = h->dev;
+        dg.wpg = wpg;
+        dg.ks_limit = base_only ? hm.fbp / 4 : (1 << 20);
+        if (base_only && hm.fbp == 8) {  // (8 base positions x 16 columns = one full DMA piece per tile)
+            dg.pieces = dg.pieces_b;
+            dg.piece_begin = dg.piece_begin_b;
+        }
+        dg.wg_tab = deal.tab;
+        dg.wg_begin = deal.begin;
+        const int NW = wpg * ng;  // workgroups of this launch
+        const size_t pcount = (size_t)NW * FBR_WPB * FBR_NPW * 256;
+        if ((rc = m->partial.ensure(pcount * sizeof(double)))) return rc;
+        unsigned long long *dbg = nullptr;
+        if (timing) {
+            if ((rc = m->st_x.ensure((size_t)NW * FBR_WPB * 8 * sizeof(unsigned long long)))) return rc;
+            dbg = m->st_x.as<unsigned long long>();
+        }
+        {
+            ProfScope ps(m, FBR_PROF_GRAM);
+            hipLaunchKernelGGL(gram_kernel, dim3(NW), dim3(FBR_WPB * 64), h->lds_bytes, m->stream, dg, cs, ng,
+                               h->pimg[b].as<double>(), m->partial.as<double>(), dbg, (carry_ok && ci > 0) ? 1 : 0);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(m->ev_gram[b], m->stream));
+        m->ev_gram_rec[b] = true;
+        if (timing && (rc = print_gram_timing(m, T, dbg, NW))) return rc;
+        if (!carry_ok || ci + 1 == nchunks) {
+            ProfScope ps(m, FBR_PROF_REDUCE);
+            hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(T * FBR_WPB * FBR_NPW, ng), dim3(256), 0, m->stream, dg,
+                               m->partial.as<double>(), G + (size_t)items[ci].g0 * Pa * Pa);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    if (moments) {  // (the main stream has waited for the last pack launch before its last Gram launch)
+        ProfScope ps(m, FBR_PROF_REDUCE);
+        hipLaunchKernelGGL(fbr_gram_mom_reduce_kernel, dim3(256), dim3(256), 0, m->stream, hm.cols, k, pack_blocks_max, h->itemcol,
+                           h->mom[mpar].as<double>(), G);
+        HIPCHK(hipGetLastError());
+        h->mom_clean[mpar] = true;
+    }
+    if (!async) HIPCHK(hipStreamSynchronize(side));
     return FBR_OK;
 }
 
@@ -755,7 +943,7 @@ static int gram_impl_inner(fbr_model *m, const fbr_states *st, const double *rhs
     const long S = d.S;
     const double *drhs = nullptr, *dw = nullptr;
     if (h2d_chunked) {
-        drhs = rhs;  // host pointers: staged per chunk in produce()
+        drhs = rhs;  // host pointers: staged per chunk by the pass
         dw = w;
     } else {
         if ((rc = stage_one(m, m->st_aux, rhs, (size_t)S * hm.rows * k, st->mem, &drhs))) return rc;
@@ -789,262 +977,20 @@ static int gram_impl_inner(fbr_model *m, const fbr_states *st, const double *rhs
         if (accumulate) HIPCHK(hipMemcpyAsync(G, G_out, gcount * sizeof(double), hipMemcpyHostToDevice, m->stream));
     }
     if (!accumulate) HIPCHK(hipMemsetAsync(G, 0, gcount * sizeof(double), m->stream));
-    // the pass over sample-contiguous images (fbr_gram64.h) where the call allows it
-    bool lane_pass = false;
-    if (S > 0 && m->opt.gram_lane != 0 && ngroups == 1 && !m->opt.gram_timing && !m->opt.gram_serial &&
-        k <= 1 && (k == 0 || moments) && d.q) {
-        if ((rc = get_gram64(m, h))) return rc;
-        lane_pass = h->g64_state == 1;
-    }
-    bool lane_grouped = false;
-    if (!lane_pass && S > 0 && m->opt.gram_lane != 0 && ngroups > 1 && k == 0 && !h2d_chunked && !base_only && !m->opt.gram_timing &&
-        !m->opt.gram_serial && d.q) {
-        if ((rc = get_gram64(m, h))) return rc;
-        lane_grouped = h->g64_state == 1 && (S / ngroups + 63) / 64 <= gram64_chunk_blocks(h->g64);
-    }
-    if (lane_grouped) {
-        if ((rc = gram64_grouped_pass(m, h, d, dw, G, ngroups))) return rc;
-    } else if (lane_pass) {
-        if ((rc = gram64_pass(m, h, d, drhs, dw, k, G, base_only && h->g64.base_stages > 0, h2d_chunked))) return rc;
-        if (!async && h2d_chunked && m->copy) HIPCHK(hipStreamSynchronize(m->copy));
-    } else if (S > 0) {
-        const int T = h->prog.T;
-        const bool two_per_cu = h->prog.cfg == FBR_CFG_TWO_PER_CU;
-        const int blocks_per_cu = (two_per_cu && h->lds_bytes <= 79 * 1024) ? 2 : 1;
-        const int FBR_NPW = h->prog.cfg.npw();
-        const bool timing = m->opt.gram_timing != 0;
-        typedef void (*gram_fn)(DevGram, long, int, const double *, double *, unsigned long long *, int);
-        const gram_fn gram_kernel = two_per_cu ? (timing ? fbr_gram_kernel<true, 5, 2> : fbr_gram_kernel<false, 5, 2>)
-                                               : (timing ? fbr_gram_kernel<true, FBR_ONE_SEGW, FBR_ONE_NSEG> : fbr_gram_kernel<false, FBR_ONE_SEGW, FBR_ONE_NSEG>);
-        HIPCHK(hipFuncSetAttribute((const void *)gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        HIPCHK(hipFuncSetAttribute((const void *)fbr_pack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->pack_lds_bytes));
-        const size_t img_bytes = (size_t)h->prog.image_doubles * sizeof(double);
-        long ch = chunk_size(m, S);
-        ch = std::max(1L, std::min(ch, (long)((size_t)4 * 1024 * 1024 * 1024 / img_bytes)));
-        if (ngroups == 1 && m->opt.chunk_samples < 1) {
-            // a short batch (e.g. one rank's shard of a multi-GPU run) is still cut into several chunks, so that only a small first
-            // chunk's producer work runs before the first Gram launch instead of half the batch's
-            const long min_chunks = std::max(1L, (long)m->opt.min_chunks);  // measured: 125 k samples 2 / 4 / 8 / 16 chunks = 11.45 / 11.69 / 11.19 / 9.35 M samples/s
-            ch = std::max(std::min(ch, 8192L), std::min(ch, (S + min_chunks - 1) / min_chunks));
-        }
-        // work items: several whole groups per launch, or (groups larger than a chunk) pieces of one group
-        struct Item { long s0, cs; int g0, ng; };
-        std::vector<Item> items;
-        const long Sg = S / ngroups;
-        if (Sg <= ch) {
-            const int gpc = (int)std::min<long>(ngroups, std::max(1L, ch / Sg));
-            for (int g0 = 0; g0 < ngroups; g0 += gpc) {
-                const int ng = std::min(gpc, ngroups - g0);
-                items.push_back({g0 * Sg, ng * Sg, g0, ng});
-            }
-            ch = gpc * Sg;
-        } else {
-            // the producer work of the very first chunk is the only one that nothing hides: it is made smaller (a quarter of a chunk:
-            // measured on a 125 k-sample shard, tools/chunk_probe.py)
-            for (int g = 0; g < ngroups; g++)
-                for (long c0 = 0; c0 < Sg; c0 += ch) items.push_back({g * Sg + c0, std::min(ch, Sg - c0), g, 1});
-        }
-        const long nchunks = (long)items.size();
-        bool fresh_images = false;  // a tile-image buffer was (re)allocated and zeroed on the main stream in this call
-        // workgroups per group of a launch: every resident workgroup slot is used (see the launch below)
-        auto wpg_of = [&](long cs, int ng) {
-            const long spg_max = std::max(1L, cs / ng);
-            const int rounds = ng > 1 ? (T > 1 ? 4 : 2) : 1;
-            int wpg = std::max(T, (rounds * m->num_cus * blocks_per_cu) / ng);
-            if ((long)wpg > (long)T * spg_max) wpg = (int)((long)T * spg_max);
-            return std::min(wpg, 0xffff);
-        };
-        // One reduction per call: when every chunk of a single-group call has the same launch shape, a workgroup carries its partial
-        // sums from chunk to chunk (the accumulators start from the partial-sum buffer) and fbr_gram_reduce_kernel runs once, after
-        // the last chunk -- 15 of the 16 reductions of a 1 M-sample WALK-MAN pass (72 us each, between two Gram launches) go away.
-        bool carry_ok = ngroups == 1 && nchunks > 1 && !timing;
-        for (long ci = 1; ci < nchunks && carry_ok; ci++) carry_ok = wpg_of(items[ci].cs, 1) == wpg_of(items[0].cs, 1);
-        for (int b = 0; b < (nchunks > 1 ? 2 : 1); b++)
-            if ((size_t)ch * img_bytes > h->pimg[b].bytes) {
-                if ((rc = h->pimg[b].ensure((size_t)ch * img_bytes))) return rc;
-                HIPCHK(hipMemsetAsync(h->pimg[b].p, 0, h->pimg[b].bytes, m->stream));  // structural zeros are never rewritten
-                fresh_images = true;
-            }
-        // producer (kinematics + tile-image packing of chunk i+1) runs on a second stream and shares the CUs with the
-        // MFMA-bound Gram kernel of chunk i; the images are double buffered
-        HIPCHK(hipEventRecord(m->ev_fork, m->stream));
-        // FBR_GRAM_SERIAL (diagnostic): producer on the main stream, i.e. no overlap with the Gram kernel
-        hipStream_t side = m->opt.gram_serial ? m->stream : m->side;
-        // The producer normally starts after everything enqueued on the main stream so far.  A submission that follows another one
-        // (fbr_gram_submit) skips that: its inputs are device resident, and what its first producer launches must wait for is only
-        // the tile-image buffer they write (ev_gram below) -- kinematics and packing of its first chunk then run beside the last
-        // Gram launches of the submission before, the one piece of producer work nothing else hides.
-        const bool cross = overlap_prev && !fresh_images && side != m->stream;
-        if (!cross) HIPCHK(hipStreamWaitEvent(side, m->ev_fork, 0));
-        // per-sample doubles of one staged chunk (pinned host inputs): q dq ddq [bv ba rpy] [sign] [rhs] [w]
-        const size_t stage_per = (size_t)3 * hm.n + (hm.floating ? 15 : 0) + (d.sign ? hm.n : 0) + (size_t)hm.rows * k + (dw ? hm.rows : 0);
-        if (h2d_chunked)
-            for (int b = 0; b < (nchunks > 1 ? 2 : 1); b++)
-                if ((rc = m->st_chunk[b].ensure(std::max<size_t>(1, (size_t)ch * stage_per) * sizeof(double)))) return rc;
-        // pack workgroups per CU of a launch's grid (each walks its share of the chunk's samples).  More than are ever resident (7 per CU
-        // alone, 2 beside the Gram kernel): with 8 the workgroups of the last, partial round ran on a half-empty chip at the end of every
-        // launch (measured per 1 M-sample step, two runs each: 8 -> 24.1, 16 -> 23.5 ... 24.0, 24 -> 23.1 ... 23.4, 32 / 48 -> 23.4)
-        const int pack_wgs_per_cu = 24;
-        const int pack_blocks_max = m->num_cus * pack_wgs_per_cu;
-        auto produce = [&](long ci) -> int {
-            const long s0 = items[ci].s0, cs = items[ci].cs;
-            const int b = (int)(ci & 1);
-            // Gram of chunk ci-2 (or, across submissions, the last Gram launch that read this buffer) is done with it
-            if (ci >= 2 || (cross && m->ev_gram_rec[b])) HIPCHK(hipStreamWaitEvent(side, m->ev_gram[b], 0));
-            DevStates dc = d;     // what the kernels of this chunk read, and the sample offset into it
-            long o = s0;
-            const double *crhs = drhs, *cw = dw;
-            if (h2d_chunked) {
-                // copies run on their own stream so that the copy of this chunk overlaps the kinematics / packing of the one before:
-                // they wait for the pack kernel of chunk ci-2 (the last reader of this staging buffer), the producer waits for them
-                // (created on first use: HIP maps streams to hardware queues in creation order, and the producer stream's queue must
-                // stay what it is for device-resident inputs)
-                if (!m->copy) {
-                    // a priority level of its own (main stream: normal, producer: lowest, copies: highest), so that the copy stream
-                    // never lands on the hardware queue of the Gram stream whatever streams the process created before (seen in
-                    // bench.py after the TSQR leg had created two more streams: copies and Gram launches serialised, 78.6 instead
-                    // of 74.1 ms per step)
-                    int least = 0, greatest = 0;
-                    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-                    HIPCHK(hipStreamCreateWithPriority(&m->copy, hipStreamNonBlocking, greatest));
-                }
-                hipStream_t cps = m->copy ? m->copy : side;
-                if (cps != side) {
-                    // the staging buffer's last reader is the pack kernel of the chunk two before (or, across submissions, the last
-                    // pack launch that used this buffer)
-                    if (ci >= 2 || (cross && m->ev_pack_rec[b]))
-                        HIPCHK(hipStreamWaitEvent(cps, m->ev_pack[b], 0));
-                    else
-                        HIPCHK(hipStreamWaitEvent(cps, m->ev_fork, 0));
-                }
-                ProfScope ps(m, FBR_PROF_H2D, cps);
-                double *p = m->st_chunk[b].as<double>();
-                auto put = [&](const double *src, size_t per, const double **dst) -> int {
-                    *dst = nullptr;
-                    if (!src || per == 0) return FBR_OK;
-                    HIPCHK(hipMemcpyAsync(p, src + (size_t)s0 * per, (size_t)cs * per * sizeof(double), hipMemcpyHostToDevice, cps));
-                    *dst = p;
-                    p += (size_t)cs * per;
-                    return FBR_OK;
-                };
-                int r3;
-                if ((r3 = put(d.q, hm.n, &dc.q)) || (r3 = put(d.dq, hm.n, &dc.dq)) || (r3 = put(d.ddq, hm.n, &dc.ddq)) ||
-                    (r3 = put(d.bv, 6, &dc.bv)) || (r3 = put(d.ba, 6, &dc.ba)) || (r3 = put(d.rpy, 3, &dc.rpy)) ||
-                    (r3 = put(d.sign, hm.n, &dc.sign)) || (r3 = put(drhs, (size_t)hm.rows * k, &crhs)) || (r3 = put(dw, hm.rows, &cw)))
-                    return r3;
-                o = 0;
-                if (cps != side) {
-                    HIPCHK(hipEventRecord(m->ev_h2d[b], cps));
-                    HIPCHK(hipStreamWaitEvent(side, m->ev_h2d[b], 0));
-                }
-            }
-            int rc2 = run_kin(m, dc, o, cs, side, &m->rec2);
-            if (rc2) return rc2;
-            {
-                ProfScope ps(m, FBR_PROF_PACK, side);
-                const int blocks = (int)std::min<long>(cs, (long)pack_blocks_max);
-                hipLaunchKernelGGL(fbr_pack_kernel, dim3(blocks), dim3(256), h->pack_lds_bytes, side, h->dev, m->dm, cs, cs / items[ci].ng,
-                                   m->rec2.as<double>(), dc.dq + o * hm.n, dc.sign ? dc.sign + o * hm.n : nullptr,
-                                   crhs ? crhs + (size_t)o * hm.rows * k : nullptr, cw ? cw + (size_t)o * hm.rows : nullptr,
-                                   h->pimg[b].as<double>(), base_only ? 1 : 0, moments ? h->mom[(int)(m->next_ticket & 1)].as<double>() : nullptr);
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(m->ev_pack[b], side));
-            m->ev_pack_rec[b] = true;
-            return FBR_OK;
-        };
-        const int mpar = (int)(m->next_ticket & 1);
-        if (moments) {
-            const size_t mbytes = (size_t)pack_blocks_max * 256 * 4 * sizeof(double);
-            if (h->mom[mpar].bytes < mbytes) h->mom_clean[mpar] = false;
-            if ((rc = h->mom[mpar].ensure(mbytes))) return rc;
-            if (!h->mom_clean[mpar]) HIPCHK(hipMemsetAsync(h->mom[mpar].p, 0, mbytes, side));
-            h->mom_clean[mpar] = false;  // (until this call's reduction has been enqueued)
-        }
-        if ((rc = produce(0))) return rc;
-        for (long ci = 0; ci < nchunks; ci++) {
-            const long cs = items[ci].cs;
-            const int ng = items[ci].ng;
-            const int b = (int)(ci & 1);
-            if (ci + 1 < nchunks && (rc = produce(ci + 1))) return rc;
-            HIPCHK(hipStreamWaitEvent(m->stream, m->ev_pack[b], 0));
-            // every resident workgroup slot is used: the slots of a sample group are dealt to the parts by cost (fbr_gram_deal),
-            // a part's workgroups split the group's samples evenly.  Tiny batches: no more workgroups than samples per part.
-            // Grouped launches (many short candidates) are oversubscribed: with one round of resident workgroups a group gets too few
-            // of them to follow the parts' costs (WALK-MAN, 64 groups x 2000 samples: 5 per group, 15.4 ms; 4 rounds: 11.8 ms; KUKA
-            // 0.92 -> 0.90 ms with 2 rounds) and the hardware dispatcher evens out the rest.  Bulk launches lose 17 % when
-            // oversubscribed (late workgroups run beside the producer kernels of the next chunk): one round, dealt by cost.
-            const int wpg = wpg_of(cs, ng);
-            GramHolder::Deal deal;
-            if ((rc = get_deal(h, wpg, &deal, base_only))) return rc;
-            DevGram dg = h->dev;
-            dg.wpg = wpg;
-            dg.ks_limit = base_only ? hm.fbp / 4 : (1 << 20);
-            if (base_only && hm.fbp == 8) {  // (8 base positions x 16 columns = one full DMA piece per tile)
-                dg.pieces = dg.pieces_b;
-                dg.piece_begin = dg.piece_begin_b;
-            }
-            dg.wg_tab = deal.tab;
-            dg.wg_begin = deal.begin;
-            const int NW = wpg * ng;  // workgroups of this launch
-            const size_t pcount = (size_t)NW * FBR_WPB * FBR_NPW * 256;
-            if ((rc = m->partial.ensure(pcount * sizeof(double)))) return rc;
-            unsigned long long *dbg = nullptr;
-            if (timing) {
-                if ((rc = m->st_x.ensure((size_t)NW * FBR_WPB * 8 * sizeof(unsigned long long)))) return rc;
-                dbg = m->st_x.as<unsigned long long>();
-            }
-            {
-                ProfScope ps(m, FBR_PROF_GRAM);
-                hipLaunchKernelGGL(gram_kernel, dim3(NW), dim3(FBR_WPB * 64), h->lds_bytes, m->stream, dg, cs, ng,
-                                   h->pimg[b].as<double>(), m->partial.as<double>(), dbg, (carry_ok && ci > 0) ? 1 : 0);
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(m->ev_gram[b], m->stream));
-            m->ev_gram_rec[b] = true;
-            if (timing) {
-                std::vector<unsigned long long> hb((size_t)NW * FBR_WPB * 8);
-                HIPCHK(hipMemcpyAsync(hb.data(), dbg, hb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
-                HIPCHK(hipStreamSynchronize(m->stream));
-                static const char *names[3] = {"wait_dma+barrier", "dma_issue", "mfma"};
-                std::vector<double> sum((size_t)T * 3, 0.0), ns(T, 0.0), nw(T, 0.0), wv((size_t)T * FBR_WPB, 0.0);
-                for (size_t e = 0; e + 8 <= hb.size(); e += 8) {
-                    const int part = (int)hb[e + 6];
-                    if (part < 0 || part >= T) continue;
-                    for (int i = 0; i < 3; i++) sum[(size_t)part * 3 + i] += (double)hb[e + i];
-                    ns[part] += (double)hb[e + 7];
-                    nw[part] += 1.0;
-                    wv[(size_t)part * FBR_WPB + (e / 8) % FBR_WPB] += (double)hb[e + 2];
-                }
-                for (int part = 0; part < T; part++) {
-                    fprintf(stderr, "[fbr gram timing] part %d (cycles per sample per wave):", part);
-                    for (int i = 0; i < 3; i++) fprintf(stderr, " %s=%.0f", names[i], sum[(size_t)part * 3 + i] / std::max(ns[part], 1.0));
-                    fprintf(stderr, " | workgroups=%.0f cycles per workgroup=%.0f | mfma phase per wave:", nw[part] / FBR_WPB,
-                            (sum[(size_t)part * 3] + sum[(size_t)part * 3 + 1] + sum[(size_t)part * 3 + 2]) / std::max(nw[part], 1.0));
-                    for (int w = 0; w < FBR_WPB; w++) fprintf(stderr, " %.0f", wv[(size_t)part * FBR_WPB + w] * FBR_WPB / std::max(ns[part], 1.0));
-                    fprintf(stderr, "\n");
-                }
-            }
-            if (!carry_ok || ci + 1 == nchunks) {
-                ProfScope ps(m, FBR_PROF_REDUCE);
-                hipLaunchKernelGGL(fbr_gram_reduce_kernel, dim3(T * FBR_WPB * FBR_NPW, ng), dim3(256), 0, m->stream, dg,
-                                   m->partial.as<double>(), G + (size_t)items[ci].g0 * Pa * Pa);
-            }
-            HIPCHK(hipGetLastError());
-        }
-        if (moments) {  // (the main stream has waited for the last pack launch before its last Gram launch)
-            ProfScope ps(m, FBR_PROF_REDUCE);
-            hipLaunchKernelGGL(fbr_gram_mom_reduce_kernel, dim3(256), dim3(256), 0, m->stream, hm.cols, k, pack_blocks_max, h->itemcol,
-                               h->mom[mpar].as<double>(), G);
-            HIPCHK(hipGetLastError());
-            h->mom_clean[mpar] = true;
-        }
-        if (!async) {
-            HIPCHK(hipStreamSynchronize(side));
-            if (h2d_chunked && m->copy) HIPCHK(hipStreamSynchronize(m->copy));
-        }
-    }
+    // the pass over sample-contiguous images (fbr_gram64.h) where the call allows it.  Its grouped form takes no rhs, no pinned inputs, no
+    // base-wrench-only masks, and groups of at most one chunk
+    bool lane = false;
+    if (S > 0 && d.q && !m->opt.gram_timing && !m->opt.gram_serial && (ngroups == 1 || (k == 0 && !h2d_chunked && !base_only)) &&
+        (rc = gram64_serves(m, h, k, &lane)))
+        return rc;
+    if (lane && ngroups > 1 && (S / ngroups + 63) / 64 <= gram64_chunk_blocks(h->g64))
+        rc = gram64_grouped_pass(m, h, d, dw, G, ngroups);
+    else if (lane && ngroups == 1)
+        rc = gram64_pass(m, h, d, drhs, dw, k, G, base_only && h->g64.base_stages > 0, h2d_chunked);
+    else if (S > 0)
+        rc = gram_image_pass(m, h, d, drhs, dw, k, G, ngroups, base_only, h2d_chunked, overlap_prev, async);
+    if (rc) return rc;
+    if (S > 0 && !async && h2d_chunked && m->copy) HIPCHK(hipStreamSynchronize(m->copy));
     if (async) {
         const int64_t t = m->next_ticket++;
         m->ticket_kind[t & 1] = 0;

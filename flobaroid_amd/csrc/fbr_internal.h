@@ -297,6 +297,21 @@ int run_kin(fbr_model *m, const DevStates &d, long s0, long cs, hipStream_t st =
 int finish_output(fbr_model *m, double *dev_src, double *user_dst, size_t count, int out_mem);
 int active_rows(fbr_model *m, const double *dw, long S, std::vector<char> *act);
 int pick_gram_reduction(const fbr_model *m, long S = -1);
+// the program a lane kernel walks: a step table of nsteps steps needing nslots branch-point slots (the lane writers, fbr_kinimg_kernel and
+// fbr_kinwrite_kernel, walk their parts' programs: DevKinWrite says where each part's steps are)
+static inline DevKinId kinid_params(const fbr_model *m, int nsteps, int nslots, const int *steps)
+{
+    DevKinId kp;
+    kp.nsteps = nsteps;
+    kp.maxlvl = m->kinid.maxlvl;
+    kp.nslots = nslots;
+    kp.ldn = std::max(m->hm.n, 1) | 1;
+    kp.steps = steps;
+    kp.endflush = m->kinid_endflush;
+    return kp;
+}
+// the model's own program (fbr_kinid_kernel, fbr_kinfd_kernel)
+static inline DevKinId kinid_params(const fbr_model *m) { return kinid_params(m, m->kinid.nsteps, m->kinid.nslots, m->kinid_steps); }
 // the materialising regressor kernel of samples [s0, s0 + cs) into dst (leading dimension ldy, row strides rs_s / rs_r, optional link
 // positions / skipped leading zeros of the TSQR chunk layout): fbr_regressor_batch and the single-factorisation TSQR path
 int launch_regressor(fbr_model *m, const DevStates &d, long s0, long cs, double *dst, int ldy, long rs_s, long rs_r, const int *linkpos, const int *skipfc);

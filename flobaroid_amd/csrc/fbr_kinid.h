@@ -20,6 +20,7 @@
 // The program (steps, flush lists, slots) is built on the host by fbr_kinid_build -- HIP-free, so that tests/emul runs the same
 // program and the same lane body (fbr_kinid_lane) on the CPU (checked there against the CPU restatement of the reference).
 #pragma once
+#include <type_traits>
 #include <vector>
 
 #include "fbr_math.h"
@@ -29,6 +30,15 @@
 #define FBR_KINID_MAXD 24 // deepest joint path the register-stack instances cover (deeper trees keep the two-kernel path)
 
 #define FBR_KINWRITE_PARTS 4  // waves of a lane-WRITER workgroup = parts the tree is cut into (fbr_kinid_build_parts)
+
+// (host) the register-stack instance of a lane kernel for a program of depth maxlvl: f(std::integral_constant<int, D>()) with the first
+// of the instance depths D... that is >= maxlvl, or the last one
+template <int D, int... Ds, class F> inline auto fbr_by_depth(int maxlvl, F &&f)
+{
+    if constexpr (sizeof...(Ds) > 0)
+        if (maxlvl > D) return fbr_by_depth<Ds...>(maxlvl, f);
+    return f(std::integral_constant<int, D>());
+}
 
 #if defined(__HIPCC__)
 // tables every lane of a wave reads at the same index: through the constant address space they are scalar loads

@@ -634,14 +634,8 @@ static int tsqr_groups_impl(fbr_model *m, const DevStates &d, const TsqrGroupPla
                 set_err("internal: chunk stride of the lane writer does not match its row tables");
                 return FBR_E_INVALID;
             }
-            DevKinId kp;
-            kp.nsteps = m->kinid.nsteps;
-            kp.maxlvl = m->kinid.maxlvl;
-            kp.nslots = lane_slots;
-            kp.ldn = std::max(hm.n, 1) | 1;
-            kp.steps = t + o_lsteps;
-            kp.endflush = m->kinid_endflush;
-            DevKinWrite kw;
+            const DevKinId kp = kinid_params(m, m->kinid.nsteps, lane_slots, t + o_lsteps);
+            DevKinWrite kw{};
             kw.nparts = lane_parts;
             for (int pq = 0; pq < FBR_KINWRITE_PARTS; pq++) {
                 kw.part_nsteps[pq] = lane_nsteps[pq];
@@ -658,25 +652,16 @@ static int tsqr_groups_impl(fbr_model *m, const DevStates &d, const TsqrGroupPla
             const int blocks = (int)std::min<long>((cs + 63) / 64, (long)m->num_cus * per_cu);
             if ((rc = m->kinid_scratch.ensure((size_t)blocks * lane_parts * std::max(kp.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double)))) return rc;
             ProfScope ps(m, FBR_PROF_REGRESSOR, cst);
-#define FBR_KINWRITE_LAUNCH(D)                                                                                                                  \
-    do {                                                                                                                                        \
-        HIPCHK(hipFuncSetAttribute((const void *)fbr_kinwrite_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lane_lds));          \
-        hipLaunchKernelGGL(fbr_kinwrite_kernel<D>, dim3(blocks), dim3(64 * lane_parts), lane_lds, cst, m->dm, kp, kw, cs, d.q + s0 * hm.n, d.dq + s0 * hm.n,  \
-                           d.ddq + s0 * hm.n, d.bv ? d.bv + s0 * 6 : nullptr, d.ba ? d.ba + s0 * 6 : nullptr, d.rpy ? d.rpy + s0 * 3 : nullptr, \
-                           d.sign ? d.sign + s0 * hm.n : nullptr, drhs ? drhs + (size_t)s0 * hm.rows * k : nullptr,                            \
-                           dw ? dw + (size_t)s0 * hm.rows : nullptr, m->kinid_scratch.as<double>());                                            \
-    } while (0)
-            if (kp.maxlvl <= 4)
-                FBR_KINWRITE_LAUNCH(4);
-            else if (kp.maxlvl <= 8)
-                FBR_KINWRITE_LAUNCH(8);
-            else if (kp.maxlvl <= 10)
-                FBR_KINWRITE_LAUNCH(10);
-            else if (kp.maxlvl <= 12)
-                FBR_KINWRITE_LAUNCH(12);
-            else
-                FBR_KINWRITE_LAUNCH(FBR_KINID_MAXD);
-#undef FBR_KINWRITE_LAUNCH
+            if ((rc = fbr_by_depth<4, 8, 10, 12, FBR_KINID_MAXD>(kp.maxlvl, [&](auto D) -> int {
+                     HIPCHK(hipFuncSetAttribute((const void *)fbr_kinwrite_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lane_lds));
+                     hipLaunchKernelGGL(fbr_kinwrite_kernel<D>, dim3(blocks), dim3(64 * lane_parts), lane_lds, cst, m->dm, kp, kw, cs, d.q + s0 * hm.n,
+                                        d.dq + s0 * hm.n, d.ddq + s0 * hm.n, d.bv ? d.bv + s0 * 6 : nullptr, d.ba ? d.ba + s0 * 6 : nullptr,
+                                        d.rpy ? d.rpy + s0 * 3 : nullptr, d.sign ? d.sign + s0 * hm.n : nullptr,
+                                        drhs ? drhs + (size_t)s0 * hm.rows * k : nullptr, dw ? dw + (size_t)s0 * hm.rows : nullptr,
+                                        m->kinid_scratch.as<double>());
+                     return FBR_OK;
+                 })))
+                return rc;
         } else {
         if (s0 == k0 && (rc = run_kin(m, d, k0, std::min(kin_span, S - k0), cst))) return rc;
         const double *recs = m->rec.as<double>() + (size_t)(s0 - k0) * hm.rec_size();
