@@ -18,7 +18,8 @@
 //   * consumer fbr_gram64_kernel: one workgroup of 8 waves per CU, the accumulators of the tile pairs in registers for the whole pass;
 //     a stage = (a few consecutive row levels, 32 samples): the slabs of the tiles that have the levels arrive by LDS-DMA into one of two
 //     buffers while the MFMAs of the stage before run; a pair takes part in the levels of its range; 8 MFMAs per pair, level and half block;
-//   * the force rows of the base wrench (levels 0 .. 2) run on tiles of their own that hold the columns with a force only (fbr_gram64_build).
+//   * the force rows of the base wrench (levels 0 .. 2) run on tiles of their own that hold the columns with a force only (fbr_gram64_build);
+//   * the main tiles are the pass's own (fbr_gram64_fill_tiles): a column sits in any tile whose joint path contains its own.
 // Conditions (else the first pass runs): k <= 1 rhs column (or none), a tile program in one part; sample groups (fbr_gram_grouped) for k = 0.
 // Friction columns are tiles whose levels are the rows of their own joints.
 // Inputs resident in HBM or pinned host memory (staged chunk by chunk); row weights; a base-wrench-only row mask runs the base stages only.
@@ -31,8 +32,15 @@
 
 #include "fbr_kinid.h"
 
+struct FbrGram64Tile {     // a main tile of the pass
+    int col[FBR_TILE];     // column of each slot, -1 = padding
+    std::vector<int> path; // joints of its rows: the path of each of its columns is a prefix of it
+    int friction = 0;      // friction columns: the rows of their own joints only
+    int lo = 0, hi = 0;    // its levels [lo, hi) (fbr_gram64_build)
+};
+
 struct FbrGram64 {  // host program
-    int NT = 0;      // column tiles of the tile program ("main" tiles)
+    int NT = 0;      // main tiles (tiles below)
     int NF = 0;      // force tiles (below); tiles are numbered main 0 .. NT-1, force NT .. NT+NF-1
     int nlev = 0, fb = 0, flev = 0, ntr = 0, maxact = 0, npw = 0, wpb = 8;  // npw accumulators per wave, wpb waves per workgroup (8 or 16)
     long blk_doubles = 0;
@@ -50,11 +58,84 @@ struct FbrGram64 {  // host program
     std::vector<int> tilecol;    // [NT + NF][16] column of each tile slot, -1 = padding
     std::vector<int> fcol_tile, fcol_slot;  // per column: its force tile / slot there, or -1
     std::vector<int> tile_lo;    // [NT] first level of every main / friction tile
+    std::vector<FbrGram64Tile> tiles;  // [NT] the main tiles (fbr_gram64_build)
+    int tiling = 0;                    // which tiling they are: 0 the tile program's, 1 the bottom-up fill (fbr_gram64_build)
     long mfma_per_block = 0;
     long busiest = 0, balanced = 0;  // sum over the stages of the busiest wave's pair-levels / of ceil(all pair-levels / 8)
 };
 
-// Tiles / pairs of a one-part tile program built WITHOUT rhs tiles (moments); false: the model is outside this pass.
+// Levels [lo, hi) of a main tile before the force levels are known: a main tile has the base-wrench rows and the joints of its path; a
+// FRICTION tile (its columns are non-zero on the row of their own joint only) just the levels of its own columns' joints -- a contiguous
+// stretch of its path.  false: a friction tile without such a joint.
+static inline bool fbr_gram64_tile_levels(const FbrHostModel &hm, FbrGram64Tile &t)
+{
+    t.lo = 0;
+    t.hi = hm.fb + (int)t.path.size();
+    if (!t.friction) return true;
+    int jmin = (int)t.path.size(), jmax = -1;
+    for (int sl = 0; sl < FBR_TILE; sl++) {
+        if (t.col[sl] < 0) continue;
+        const int jnt = hm.coldesc[t.col[sl]].joint;
+        for (int j = 0; j < (int)t.path.size(); j++)
+            if (t.path[j] == jnt) jmin = std::min(jmin, j), jmax = std::max(jmax, j);
+    }
+    if (jmax < 0) return false;
+    t.lo = hm.fb + jmin;
+    t.hi = hm.fb + jmax + 1;
+    return true;
+}
+
+// ---- Tilings of the pass.  A pair of main tiles costs 16 MFMAs per block for every level it runs (moment levels + common prefix of the
+// two paths), so the tiles that suit this pass are not the tile program's (built for the per-sample-image pass: tiles closed where a
+// depth-first walk stops nesting, fewest tiles).  Any column can sit in a tile whose path contains its own: the base link, the waist and
+// the upper links of a chain can fill up the tiles of deeper links, where a tile of their own would run levels against every other tile.
+// The program's tiles as they are.  false: a tile outside this pass (dense).
+static inline bool fbr_gram64_program_tiles(const FbrHostModel &hm, const FbrGramProgram &gp, std::vector<FbrGram64Tile> &tiles)
+{
+    tiles.assign(gp.NT, FbrGram64Tile());
+    for (int t = 0; t < gp.NT; t++) {
+        const FbrTile &tl = gp.tiles[t];
+        if (tl.type != 0) return false;
+        std::copy(tl.col, tl.col + FBR_TILE, tiles[t].col);
+        tiles[t].path = tl.tpath;
+        tiles[t].friction = tl.friction;
+        if (!fbr_gram64_tile_levels(hm, tiles[t])) return false;
+    }
+    return true;
+}
+
+// Bottom-up fill of the inertial columns of `from` (friction tiles kept as they are, behind): the deepest unplaced column opens a tile on
+// its path, which takes the unplaced columns nested in that path, deepest first (ties: column order), until it is full; repeat.
+static inline void fbr_gram64_fill_tiles(const FbrHostModel &hm, const std::vector<FbrGram64Tile> &from, std::vector<FbrGram64Tile> &tiles)
+{
+    std::vector<int> cols;
+    for (const FbrGram64Tile &t : from)
+        if (!t.friction)
+            for (int c : t.col)
+                if (c >= 0) cols.push_back(c);
+    auto depth = [&](int c) { return (int)hm.path[hm.coldesc[c].link].size(); };
+    std::stable_sort(cols.begin(), cols.end(), [&](int x, int y) { return depth(x) != depth(y) ? depth(x) > depth(y) : x < y; });
+    std::vector<char> placed(cols.size(), 0);
+    tiles.clear();
+    for (size_t i = 0; i < cols.size(); i++) {
+        if (placed[i]) continue;
+        FbrGram64Tile t;
+        std::fill(t.col, t.col + FBR_TILE, -1);
+        t.path = hm.path[hm.coldesc[cols[i]].link];
+        for (size_t j = i, fill = 0; j < cols.size() && fill < FBR_TILE; j++)
+            if (!placed[j] && FbrGramProgram::nested(t.path, hm.path[hm.coldesc[cols[j]].link])) {
+                t.col[fill++] = cols[j];
+                placed[j] = 1;
+            }
+        fbr_gram64_tile_levels(hm, t);
+        tiles.push_back(t);
+    }
+    for (const FbrGram64Tile &t : from)
+        if (t.friction) tiles.push_back(t);
+}
+
+// Tiles / pairs of the pass for the given main tiles; pairs: (I, J) of every main pair in slot order, or empty: every I <= J that runs
+// at least one level.
 //
 // FORCE TILES (floating base).  The first three regressor rows are the force rows of the base wrench, and only the mass and the first
 // moments of a link produce a force: in the column tiles of the program most entries of those rows are structural zeros (6 of 10 columns
@@ -65,54 +146,44 @@ struct FbrGram64 {  // host program
 // wide16 (option gram_lane_waves = 16): models of the one-workgroup-per-CU shape (18 accumulators per wave of an 8-wave workgroup) run 16
 // waves of 10 accumulators instead -- four waves per SIMD at 128 registers.  Measured: the Gram kernel 9.70 instead of 9.32 ms per 1 M
 // WALK-MAN samples (operand reads in half groups, more A reloads, less reuse per wave): not the default.
-static inline bool fbr_gram64_build(const FbrHostModel &hm, const FbrGramProgram &gp, FbrGram64 &g, bool force_tiles = true, bool wide16 = false)
+static inline bool fbr_gram64_build_tiles(const FbrHostModel &hm, const FbrGramConfig &cfg, const std::vector<FbrGram64Tile> &tiles,
+                                          const std::vector<int> &pairs, FbrGram64 &g, bool force_tiles, bool wide16)
 {
-    if (gp.T != 1 || (gp.k > 0 && gp.rhs_tiles)) return false;
-    g.npw = gp.cfg.segw * gp.cfg.nseg;
+    g.npw = cfg.segw * cfg.nseg;
     g.wpb = FBR_WPB;
     if (wide16 && g.npw > 10) {
         g.wpb = 2 * FBR_WPB;
         g.npw = 10;
     }
     const int W = g.wpb;
-    g.NT = gp.NT;
+    g.tiles = tiles;
+    g.NT = (int)tiles.size();
     g.fb = hm.fb;
     g.nlev = 0;
-    // levels of a tile: a main tile has the base-wrench rows and the joints of its path; a FRICTION tile (its columns are non-zero on the row
-    // of their own joint only) just the levels of its own columns' joints -- a contiguous stretch of its path
-    std::vector<int> tlo(gp.NT, 0), thi(gp.NT, 0);
-    for (int t = 0; t < gp.NT; t++) {
-        const FbrTile &tl = gp.tiles[t];
-        if (tl.type != 0) return false;
-        thi[t] = hm.fb + (int)tl.tpath.size();
-        if (tl.friction) {
-            int jmin = (int)tl.tpath.size(), jmax = -1;
-            for (int sl = 0; sl < FBR_TILE; sl++) {
-                if (tl.col[sl] < 0) continue;
-                const int jnt = hm.coldesc[tl.col[sl]].joint;
-                for (int j = 0; j < (int)tl.tpath.size(); j++)
-                    if (tl.tpath[j] == jnt) jmin = std::min(jmin, j), jmax = std::max(jmax, j);
-            }
-            if (jmax < 0) return false;
-            tlo[t] = hm.fb + jmin;
-            thi[t] = hm.fb + jmax + 1;
-        }
+    std::vector<int> tlo(g.NT, 0), thi(g.NT, 0);
+    for (int t = 0; t < g.NT; t++) {
+        tlo[t] = tiles[t].lo;
+        thi[t] = tiles[t].hi;
+        if (thi[t] <= tlo[t]) return false;  // (a tile without rows: the columns of the base link of a fixed base)
         g.nlev = std::max(g.nlev, thi[t]);
     }
     if (g.nlev == 0 || g.nlev > 255) return false;
-    // the tile pairs of the program: unordered, with their common depth cp = fb + joints both tiles' columns have rows on
+    // the tile pairs: unordered, with their common depth cp = fb + joints both tiles' columns have rows on
     struct Pr {
         int a, b, lo, hi;
     };
     std::vector<Pr> prs;
-    for (size_t s = 0; s < gp.slots.size(); s++) {
-        const int pi = gp.slots[s].pair;
-        if (pi < 0) continue;
-        const FbrPair &p = gp.pairs[pi];
-        if (p.mode != 0) return false;
-        const int cp = hm.fb + FbrGramProgram::common_prefix(gp.tiles[p.I].tpath, gp.tiles[p.J].tpath);
-        prs.push_back({p.I, p.J, std::max(tlo[p.I], tlo[p.J]), std::min(cp, std::min(thi[p.I], thi[p.J]))});
-    }
+    auto add = [&](int I, int J) {
+        const int cp = hm.fb + FbrGramProgram::common_prefix(tiles[I].path, tiles[J].path);
+        prs.push_back({I, J, std::max(tlo[I], tlo[J]), std::min(cp, std::min(thi[I], thi[J]))});
+    };
+    for (size_t i = 0; i + 1 < pairs.size(); i += 2) add(pairs[i], pairs[i + 1]);
+    if (pairs.empty())
+        for (int I = 0; I < g.NT; I++)
+            for (int J = I; J < g.NT; J++) {
+                add(I, J);
+                if (prs.back().lo >= prs.back().hi) prs.pop_back();
+            }
     // force columns and their tiles
     g.fcol_tile.assign(hm.cols, -1);
     g.fcol_slot.assign(hm.cols, -1);
@@ -120,8 +191,9 @@ static inline bool fbr_gram64_build(const FbrHostModel &hm, const FbrGramProgram
     std::vector<char> has_tile(hm.cols, 0);
     for (int t = 0; t < g.NT; t++)
         for (int sl = 0; sl < FBR_TILE; sl++) {
-            const int c = gp.tiles[t].col[sl];
+            const int c = tiles[t].col[sl];
             if (c >= 0 && c < hm.cols) {
+                if (has_tile[c]) return false;
                 g.tilecol[(size_t)t * FBR_TILE + sl] = c;
                 has_tile[c] = 1;
             }
@@ -150,7 +222,7 @@ static inline bool fbr_gram64_build(const FbrHostModel &hm, const FbrGramProgram
     for (int c = 0; c < hm.cols; c++)
         if (g.fcol_tile[c] >= 0) g.tilecol[(size_t)g.fcol_tile[c] * FBR_TILE + g.fcol_slot[c]] = c;
     for (int t = 0; t < g.NT; t++)
-        if (!gp.tiles[t].friction) tlo[t] = g.flev;  // (the main tiles start behind the force levels)
+        if (!tiles[t].friction) g.tiles[t].lo = tlo[t] = g.flev;  // (the main tiles start behind the force levels)
     for (Pr &p : prs) p.lo = std::max(p.lo, std::max(tlo[p.a], tlo[p.b]));
     prs.erase(std::remove_if(prs.begin(), prs.end(), [](const Pr &p) { return p.lo >= p.hi; }), prs.end());
     for (int f = 0; f < g.NF; f++)
@@ -370,10 +442,42 @@ static inline bool fbr_gram64_build(const FbrHostModel &hm, const FbrGramProgram
 }
 
 // LDS of fbr_gram64_kernel: two stage buffers, then the tables
+#define FBR_G64_LDS_MAX (156 * 1024)
 static inline size_t fbr_gram64_lds_bytes(const FbrGram64 &g)
 {
     return (size_t)2 * g.maxact * 512 * sizeof(double) +
            ((size_t)g.nlev * (g.NT + g.NF) + g.nlev + 1 + g.pieces.size() + g.wmeta.size() + g.stage_lev.size() + g.runs.size()) * sizeof(int);
+}
+
+// The program of the pass for a one-part tile program built WITHOUT rhs tiles (moments); false: the model is outside this pass.
+// tiling (option gram_lane_tiling) 0: the tile program's tiles and pairs.  1: the cheaper of those and the bottom-up fill -- by MFMAs per
+// block (sum of pair-levels), then tile rows -- if the fill's program fits the kernel (pairs in the accumulator slots, stages, LDS): never
+// more MFMAs than 0, and the pass serves the same models.
+static inline bool fbr_gram64_build(const FbrHostModel &hm, const FbrGramProgram &gp, FbrGram64 &g, bool force_tiles = true, bool wide16 = false,
+                                    int tiling = 1)
+{
+    if (gp.T != 1 || (gp.k > 0 && gp.rhs_tiles)) return false;
+    std::vector<FbrGram64Tile> prog;
+    if (!fbr_gram64_program_tiles(hm, gp, prog)) return false;
+    std::vector<int> pairs;
+    for (size_t s = 0; s < gp.slots.size(); s++) {
+        const int pi = gp.slots[s].pair;
+        if (pi < 0) continue;
+        if (gp.pairs[pi].mode != 0) return false;
+        pairs.insert(pairs.end(), {gp.pairs[pi].I, gp.pairs[pi].J});
+    }
+    bool ok = fbr_gram64_build_tiles(hm, gp.cfg, prog, pairs, g, force_tiles, wide16) && fbr_gram64_lds_bytes(g) <= FBR_G64_LDS_MAX;
+    g.tiling = 0;
+    if (!ok || !tiling) return ok;
+    std::vector<FbrGram64Tile> fill;
+    fbr_gram64_fill_tiles(hm, prog, fill);
+    FbrGram64 c;
+    if (fbr_gram64_build_tiles(hm, gp.cfg, fill, {}, c, force_tiles, wide16) && fbr_gram64_lds_bytes(c) <= FBR_G64_LDS_MAX &&
+        (c.mfma_per_block < g.mfma_per_block || (c.mfma_per_block == g.mfma_per_block && c.ntr < g.ntr))) {
+        g = std::move(c);
+        g.tiling = 1;
+    }
+    return true;
 }
 
 // Producer tables: the tree in parts for the waves of a workgroup (fbr_kinid.h) and, per (part, link), 14 destination words: one per
@@ -390,14 +494,14 @@ struct FbrGram64Producer {
     std::vector<int> steps;      // the parts' step programs, one after the other
 };
 
-static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGramProgram &gp, const FbrGram64 &g, FbrGram64Producer &pr)
+static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGram64 &g, FbrGram64Producer &pr)
 {
     std::vector<int> tile_of(hm.cols, -1), slot_of(hm.cols, -1);
     for (int t = 0; t < g.NT; t++)
         for (int sl = 0; sl < FBR_TILE; sl++)
-            if (gp.tiles[t].col[sl] >= 0 && gp.tiles[t].col[sl] < hm.cols) {
-                tile_of[gp.tiles[t].col[sl]] = t;
-                slot_of[gp.tiles[t].col[sl]] = sl;
+            if (g.tiles[t].col[sl] >= 0 && g.tiles[t].col[sl] < hm.cols) {
+                tile_of[g.tiles[t].col[sl]] = t;
+                slot_of[g.tiles[t].col[sl]] = sl;
             }
     std::vector<double> lcost(hm.L, 30.0);
     for (int c = 0; c < hm.ninert; c++)
@@ -418,7 +522,7 @@ static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGr
     for (int c = 0; c < hm.ninert; c++) {
         const int t = tile_of[c], sl = slot_of[c], l = hm.coldesc[c].link, pidx = hm.coldesc[c].pidx;
         if (t < 0) continue;  // (a column without a tile: structurally zero, e.g. the base link of a fixed base)
-        if (hm.path[l].size() > gp.tiles[t].tpath.size()) return false;  // (cannot happen: the tile's path contains the link's)
+        if (!FbrGramProgram::nested(g.tiles[t].path, hm.path[l]) || hm.path[l].size() > g.tiles[t].path.size()) return false;  // (cannot happen: the tile's path contains the link's)
         const long long tr0 = (long long)g.trow[(size_t)t * g.nlev + g.tile_lo[t]] - g.tile_lo[t];
         if (tr0 < 0) return false;  // (cannot happen: the force tiles' rows come first)
         for (int pq = 0; pq < pr.nparts; pq++)
@@ -459,6 +563,12 @@ static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGr
         pr.steps.insert(pr.steps.end(), progs[pq].steps.begin(), progs[pq].steps.begin() + (size_t)progs[pq].nsteps * FBR_KINID_STEP);
     }
     return true;
+}
+
+// (the form that takes the tile program too: the pass's tiles are its own, g.tiles)
+static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGramProgram &, const FbrGram64 &g, FbrGram64Producer &pr)
+{
+    return fbr_gram64_build_producer(hm, g, pr);
 }
 
 #if defined(__HIPCC__) && defined(FBR_KERNELS_GRAM)

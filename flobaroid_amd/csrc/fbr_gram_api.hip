@@ -298,15 +298,17 @@ static int get_gram64(fbr_model *m, GramHolder *h)
     if (h->g64_state) return FBR_OK;
     h->g64_state = -1;
     const FbrHostModel &hm = m->hm;
-    if (m->kinid.nsteps <= 0 || !fbr_gram64_build(hm, h->prog, h->g64, m->opt.gram_force_tiles != 0, m->opt.gram_lane_waves >= 16)) return FBR_OK;
+    if (m->kinid.nsteps <= 0 || !fbr_gram64_build(hm, h->prog, h->g64, m->opt.gram_force_tiles != 0, m->opt.gram_lane_waves >= 16,
+                                                         (int)m->opt.gram_lane_tiling))
+        return FBR_OK;
     FbrGram64 &g = h->g64;
-    if (fbr_gram64_lds_bytes(g) > 156 * 1024) return FBR_OK;
+    if (fbr_gram64_lds_bytes(g) > FBR_G64_LDS_MAX) return FBR_OK;
     // the producer stages a block's states, row weights and rhs in the LDS (plds of gram64_pass, its largest form).  A defence only: the
     // tile program's 60 rows bound it to (3 * 64 * 61 + 2 * 64 * 61) * 8 = 156 160 bytes today; it keeps a model the producer cannot
     // launch on the per-sample-image pass should either bound move
     const size_t plds_max = ((size_t)3 * 64 * (std::max(hm.n, 1) | 1) + (size_t)2 * 64 * (hm.rows | 1)) * sizeof(double);
     if (plds_max > 160 * 1024) return FBR_OK;
-    if (!fbr_gram64_build_producer(hm, h->prog, g, h->g64p)) return FBR_OK;
+    if (!fbr_gram64_build_producer(hm, g, h->g64p)) return FBR_OK;
     std::vector<int> wgbegin{0, 0};  // (filled per launch: one part)
     int rc;
     if ((rc = upload(h->pool, g.slab, &h->d64_slab)) || (rc = upload(h->pool, g.lev_begin, &h->d64_levb)) || (rc = upload(h->pool, g.pieces, &h->d64_pieces)) ||

@@ -20,6 +20,7 @@ struct FbrOptions {
     double gram_lane_waves = 8;             // gram_lane, models of the one-workgroup-per-CU shape: 8 waves of 18 accumulators (16: 16 waves of 10; measured slower)
     double gram_force_tiles = 1;            // gram_lane: the force rows of the base wrench run on tiles of the columns that have a force (fbr_gram64.h)
     double gram_lane = 1;                   // fused Gram over sample-contiguous images with the one-lane-per-sample producer where the model allows (fbr_gram64.h)
+    double gram_lane_tiling = 1;            // gram_lane: column tiles built for the pass's cost (fbr_gram64_build); 0: the tile program's
     double gram_shape = 0;                  // 0: by model, 1: one workgroup per CU (18 accumulators), 2: two per CU (10)
     double gram_rhs_tile = 0;               // 1: dense rhs tiles even for k <= 2 (default: tau's products come from the pack kernel)
     double gram_orient = 1;                 // pairs turned so that the row segments fill up
@@ -59,8 +60,9 @@ static inline const FbrOptionKey *fbr_option_keys(int *count)
         {"h2d_chunked", &FbrOptions::h2d_chunked, false},
         {"fused_id", &FbrOptions::fused_id, false},
         {"gram_lane", &FbrOptions::gram_lane, false},
-        {"gram_force_tiles", &FbrOptions::gram_force_tiles, true},   // (both shape the program of the sample-contiguous pass, get_gram64)
+        {"gram_force_tiles", &FbrOptions::gram_force_tiles, true},   // (these three shape the program of the sample-contiguous pass, get_gram64)
         {"gram_lane_waves", &FbrOptions::gram_lane_waves, true},
+        {"gram_lane_tiling", &FbrOptions::gram_lane_tiling, true},
         {"gram_shape", &FbrOptions::gram_shape, true},
         {"gram_rhs_tile", &FbrOptions::gram_rhs_tile, true},
         {"gram_orient", &FbrOptions::gram_orient, true},

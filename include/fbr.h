@@ -328,7 +328,10 @@ int fbr_model_link_merge_info(const fbr_model *m, int64_t num_samples, int32_t *
  *   "gram_force_tiles"           1     gram_lane: the three force rows of the base wrench run on tiles of their own that hold only the columns
  *                                      with a force (mass, first moments), when the extra tile pairs fit the accumulators (0: every tile pair
  *                                      pays the three levels)
- *   "gram_shape"                 0     fused Gram kernel shape: 0 by model, 1 one workgroup per CU, 2 two per CU
+ *   "gram_lane_tiling"           1     gram_lane: column tiles of its own for the pass (a bottom-up fill: a column may sit in any tile whose
+ *                                      joint path contains its own), kept when they need fewer MFMAs than the tile program's (0: the tile
+ *                                      program's tiles and pairs)
+ *   "gram_shape"                0     fused Gram kernel shape: 0 by model, 1 one workgroup per CU, 2 two per CU
  *   "gram_rhs_tile"              0     1: dense tiles for the rhs columns even for k <= 2 (default: their products come from the packer)
  *   "gram_orient"                1     tile pairs turned so that the row segments fill up
  *   "tsqr_groups"                1     rows grouped along the kinematic tree ...
