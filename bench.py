@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- regressor samples/s + TSQR TFLOP/s of the fused hot path on MI355X (contract: see the task statement).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 starts N ranks ITSELF (re-executes under ``python -m torch.distributed.run --nproc-per-node N``; a launch that already
 runs under torchrun is used as is) and fails loudly when fewer than N devices / ranks come up.  One process per GPU,
@@ -10,10 +10,12 @@ RCCL (backend "nccl") over xGMI.
 A step = one pass of the hot path over BASELINE.json configs[3] -- WALK-MAN floating base, 1 M synthetic samples SHARDED
 over the N ranks (125 k per GPU at 8), inputs resident in HBM: link kinematics + fused regressor -> [Y|tau]^T[Y|tau] Gram
 (fp64 MFMA), reduced deterministically on the device, then ONE RCCL all-reduce of the (P+1)^2 fp64 Gram.  ``value`` =
-1 M / (max-over-ranks seconds per step): strong scaling, identical to the one-GPU workload at N = 1.  The same JSON line
-carries the weak-scaling figure (1 M samples PER GPU), the Householder-TSQR legs (per-rank ``fbr_tsqr`` + binary tree of
-``fbr_tsqr_merge`` over the ranks, checked against the all-reduced Gram inside the bench), and at N = 1 the other
-BASELINE configs, the PCIe-inclusive rate, the roofline of the dominant kernel and the CPU baselines.
+1 M / (max-over-ranks seconds per step): strong scaling, identical to the one-GPU workload at N = 1.  A plain run sets up,
+warms up, times the steps, writes ``--dump-outputs`` and prints the line (with the roofline of the dominant kernel, taken
+from the timed steps' own launches).  ``--full`` then runs the secondary legs and adds them to the same line: the
+weak-scaling figure (1 M samples PER GPU), the Householder-TSQR legs (per-rank ``fbr_tsqr`` + binary tree of
+``fbr_tsqr_merge`` over the ranks, checked against the all-reduced Gram inside the bench), and at N = 1 the shard legs,
+the other BASELINE configs, the PCIe-inclusive rate and the CPU baselines.
 
 The global data set is made of 8 seeded blocks (seeds 42..49), so every world size sees the same 1 M samples and
 ``gram_checksum`` must agree across the N = 1, 2, 4, 8 lines.
@@ -56,9 +58,12 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--samples", type=int, default=1_000_000, help="samples of the whole job per step (sharded over the ranks)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="only the timed steps (profiling runs)")
-    ap.add_argument("--sustain-seconds", type=float, default=10.0, help="N = 1: length of the sustained leg after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run the secondary legs (TSQR, weak scaling, shards, H2D, other configs, CPU baselines, parity) "
+                         "and add their figures to the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="only the timed steps even with --full (what a run without --full does)")
+    ap.add_argument("--sustain-seconds", type=float, default=10.0, help="--full, N = 1: length of the sustained leg after the timed steps")
     ap.add_argument("--selfcheck-dist", action="store_true",
                     help="N > 1: only the self-check of the exchange steps (it also runs at the start of every --gpus N > 1 run)")
     ap.add_argument("--dist-timeout", type=float, default=180.0, help="seconds a distributed step may take before the watchdog ends the rank with a message")
@@ -578,6 +583,7 @@ def run_rank(args) -> int:
     G_sharded = Gs[state.get("last", 0)].clone()
     dumped = dump_outputs(args.dump_outputs, {"gram": G_sharded}) if args.dump_outputs and rank == 0 else None
 
+    full = args.full and not args.no_secondary
     ms_per_step = dt / args.steps * 1e3
     value = S_total / (dt / args.steps)
     info = eng.gram_program_info(1, S) if on_gpu else eng.gram_program_info(1)  # (the program a pass over S samples executes)
@@ -604,6 +610,7 @@ def run_rank(args) -> int:
         "scaling": "strong",
         "vs_baseline": None,
         "dtype": "f64",
+        "full": full,
         "data": "synthetic",
         "config": {
             "workload": f"BASELINE configs[3]: walkman_apriori floating base (29 DOF, 48 links, {rows}x{P} regressor block), "
@@ -627,13 +634,13 @@ def run_rank(args) -> int:
         },
         # `value` is the rate with the inputs resident in HBM when the timed region starts -- the bench contract of this build's task
         # statement ("if the boundary hands over host buffers, note the PCIe-inclusive rate ... it is never `value`"); ms_per_step is that
-        # region.  SURVEY 8(d) words the metric "incl. H2D of states": that rate is `value_incl_h2d` below (N = 1), measured in the same
+        # region.  SURVEY 8(d) words the metric "incl. H2D of states": that rate is `value_incl_h2d` below (N = 1, --full), measured in the same
         # run on the same workload with pinned host inputs staged chunk by chunk on a copy stream (the two differ by run-to-run noise: the
         # 1.1 GB per step cross PCIe behind the kernels).
         "value_resident": value,
         "engine_options": dict(getattr(__import__("flobaroid_amd._lib", fromlist=["DEFAULT_OPTIONS"]), "DEFAULT_OPTIONS", {})),
         "value_definition": "samples per second of the whole job with states and tau resident in HBM (bench contract); value_incl_h2d = the same "
-                            "pass fed from pinned host memory (SURVEY 8(d) wording), reported beside it",
+                            "pass fed from pinned host memory (SURVEY 8(d) wording), reported beside it by --full",
         # all world sizes reduce the same 1 M samples: these must agree (to rounding) between the N = 1, 2, 4, 8 lines
         "gram_checksum": {"trace": float(torch.trace(G_sharded).item()), "fro": float(torch.linalg.norm(G_sharded).item())},
         "roofline": {
@@ -701,7 +708,7 @@ def run_rank(args) -> int:
         out["roofline"]["traffic"] = lane["block_image_bytes"] / 64.0 * samples_per_launch
         out["roofline"]["traffic_source"] = "fbr_gram_lane_info: bytes of the block images one launch reads (no committed PMC pass of this kernel found)"
 
-    if not args.no_secondary:
+    if full:
         secondary(args, out, eng, topo, st, rhs, G_sharded, dev, world, rank, use_dist, on_gpu, timed, barrier, sync, max_over_ranks)
     if rank == 0:
         print(json.dumps(out))
@@ -711,7 +718,7 @@ def run_rank(args) -> int:
 
 
 def secondary(args, out, eng, topo, st, rhs, G_sharded, dev, world, rank, use_dist, on_gpu, timed, barrier, sync, max_over_ranks):
-    """Everything outside the contract's timed region (all ranks take part in the distributed legs)."""
+    """Everything outside the contract's timed region, run by --full (all ranks take part in the distributed legs)."""
     import torch
     import torch.distributed as dist
 

@@ -154,7 +154,7 @@ def test_bench_gpus_2_spawns_two_ranks_end_to_end():
 
     lines = {}
     for n in (1, 2):
-        r = _run_bench(["--gpus", str(n)])
+        r = _run_bench(["--gpus", str(n), "--full"])
         assert r.returncode == 0, r.stderr.decode()[-3000:]
         js = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
         assert len(js) == 1, r.stdout.decode()
@@ -171,6 +171,21 @@ def test_bench_gpus_2_spawns_two_ranks_end_to_end():
     r = _run_bench(["--gpus", "2", "--selfcheck-dist"])   # the self-check alone
     assert r.returncode == 0 and b'"selfcheck_dist": "ok"' in r.stdout, r.stderr.decode()[-2000:]
     assert "weak_scaling" not in one and one["tsqr"]["rank_tree_levels"] == 0
+
+
+def test_bench_without_full_runs_only_the_timed_steps():
+    """A plain run is what its headline figure needs: the self-check and the timed steps, no secondary leg; ``--full`` adds them
+    (test_bench_gpus_2_spawns_two_ranks_end_to_end)."""
+    import json
+
+    r = _run_bench(["--gpus", "2"])
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    js = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(js) == 1, r.stdout.decode()
+    line = json.loads(js[0])
+    assert line["full"] is False and line["n_gpus"] == 2 and line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["selfcheck_dist"]["world"] == 2 and len(line["per_rank_ms_per_step"]) == 2
+    assert not {"tsqr", "weak_scaling", "cpu_baseline"} & set(line)
 
 
 def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
@@ -210,7 +225,7 @@ def test_bench_gpus_8_dry_run_over_gloo():
     against the all-reduced Gram, and the weak-scaling leg.  Same checksums as the one-rank run of the same 512 samples."""
     import json
 
-    r8 = _run_bench(["--gpus", "8", "--samples", "512", "--dist-timeout", "240"], timeout=900)
+    r8 = _run_bench(["--gpus", "8", "--samples", "512", "--dist-timeout", "240", "--full"], timeout=900)
     assert r8.returncode == 0, r8.stderr.decode()[-3000:]
     js = [l for l in r8.stdout.decode().splitlines() if l.startswith("{")]
     assert len(js) == 1

@@ -114,7 +114,7 @@ def test_bench_two_gpus_over_rccl(tmp_path):
     lines = {}
     for n in (1, 2):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--samples", "200000",
-                              "--no-cpu-baseline", "--sustain-seconds", "0"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                              "--full", "--no-cpu-baseline", "--sustain-seconds", "0"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-2000:]
         lines[n] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     two = lines[2]

@@ -10,10 +10,10 @@ export TMPDIR=/tmp
 REPO=$(pwd)
 cd /tmp
 B="python $REPO/bench.py"
-# 1. the default bench command (all legs but the CPU baselines and the 10 s sustained loop) under the kernel trace
-rocprofv3 --kernel-trace --stats --output-format csv -d "$REPO/$OUT" -o bench -- $B --no-cpu-baseline --sustain-seconds 0 > "$REPO/$OUT/bench_rocprof_stdout.txt" 2>&1
+# 1. the full bench command (all legs but the CPU baselines and the 10 s sustained loop) under the kernel trace
+rocprofv3 --kernel-trace --stats --output-format csv -d "$REPO/$OUT" -o bench -- $B --full --no-cpu-baseline --sustain-seconds 0 > "$REPO/$OUT/bench_rocprof_stdout.txt" 2>&1
 # 2. the same command without the profiler, CPU baselines included (the bench line the summary quotes)
-$B > "$REPO/$OUT/bench_default.json" 2> "$REPO/$OUT/bench_default.err"
+$B --full > "$REPO/$OUT/bench_default.json" 2> "$REPO/$OUT/bench_default.err"
 # 3. HBM traffic counters of the fused pass, one pass each, on a shorter run of the same workload
 S="--samples 200000 --steps 1 --warmup 0 --no-secondary"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$REPO/$OUT" -o pmc_fetch -- $B $S > /dev/null 2>&1

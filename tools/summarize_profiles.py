@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Summarise gpurun_out/prof_<tag>/ (written by tools/profile_round.sh) into the small files committed under profiles/:
 
-  profiles/<tag>_bench_default.json        the bench line of the unprofiled default run
-  profiles/<tag>_bench_kernel_stats.csv    rocprofv3 --kernel-trace --stats summary of `python bench.py`
+  profiles/<tag>_bench_default.json        the bench line of the unprofiled `python bench.py --full` run
+  profiles/<tag>_bench_kernel_stats.csv    rocprofv3 --kernel-trace --stats summary of `python bench.py --full`
   profiles/<tag>_pmc.json                  per-kernel PMC sums per launch (FETCH_SIZE, WRITE_SIZE, MFMA, SQ)
   profiles/<tag>_gram_pmc_traffic.json     HBM bytes per sample of the Gram kernel (FETCH_SIZE x2: MI355X_MICROARCH.md, HBM)
 """
@@ -152,11 +152,11 @@ lines = [
     "# profiles/", "",
     f"Generated by `tools/summarize_profiles.py {tag}` from `gpurun_out/prof_{tag}/` (`tools/profile_round.sh {tag}`, one MI355X, the final code of the round). "
     f"`{tag}_*` is the current evidence; older tags are the earlier rounds, kept for the history in DESIGN §11.", "",
-    f"* `{tag}_bench_default.json` – the line printed by `python bench.py` (unprofiled run, CPU baselines included): "
+    f"* `{tag}_bench_default.json` – the line printed by `python bench.py --full` (unprofiled run, CPU baselines included): "
     f"{bench['value'] / 1e6:.2f} M samples/s, {bench['ms_per_step']:.2f} ms/step, Gram kernel {bench['roofline']['frac']:.3f} of the fp64 MFMA peak (executed); "
     f"TSQR {bench['tsqr']['seconds'] * 1e3:.1f} ms per 1 M samples = {bench['tsqr']['executed_frac_of_fp64_mfma_peak']:.3f} executed"
     + (f"; 125 k-sample shard {bench['tsqr_shard']['seconds'] * 1e3:.1f} ms = {bench['tsqr_shard']['ratio_to_one_eighth']:.2f} x one eighth of the 1 M call" if "tsqr_shard" in bench else ""),
-    f"* `{tag}_bench_kernel_stats.csv` – `rocprofv3 --kernel-trace --stats` summary of `python bench.py --no-cpu-baseline --sustain-seconds 0` "
+    f"* `{tag}_bench_kernel_stats.csv` – `rocprofv3 --kernel-trace --stats` summary of `python bench.py --full --no-cpu-baseline --sustain-seconds 0` "
     f"(timed steps + TSQR / shard / H2D / assembly / other-config legs). {gram_line}",
     f"* `{tag}_pmc.json` – per-kernel PMC sums per launch of the fused pass (FETCH_SIZE, WRITE_SIZE, MFMA, SQ counters; separate passes, "
     "`bench.py --samples 200000 --steps 1 --warmup 0 --no-secondary`)"
