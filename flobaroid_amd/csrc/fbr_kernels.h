@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256) void fbr_row_active_kernel(const double *__res
 #endif  // FBR_KERNELS_CORE
 #ifdef FBR_KERNELS_GROUPS  // row-group writers of the tree-structured TSQR (fbr_tsqr_api.hip)
 // ------------------------------------------------------------------------------------------------
-// K2c: the regressor written as the ROW GROUPS of the tree-structured TSQR (fbr_api.hip: tsqr_group_plan).  A regressor row
+// K2c: the regressor written as the ROW GROUPS of the tree-structured TSQR (fbr_tsqr_plan.h: tsqr_group_plan).  A regressor row
 // belongs to one group; a group g owns a packed chunk A_g [slot][sample][ld_g] that holds only the columns its rows can touch,
 // followed by the rhs columns at psel_g.  One workgroup per sample (grid-stride), one thread per model column / rhs column.  What a
 // column thread writes is a host-built entry list (ent[ebeg[c] .. ebeg[c+1])): regressor row | kind << 8 | position in the row's

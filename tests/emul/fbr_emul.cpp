@@ -13,6 +13,7 @@
 #include "../../flobaroid_amd/csrc/fbr_reduce.h"
 #include "../../flobaroid_amd/csrc/fbr_kinid.h"
 #include "../../flobaroid_amd/csrc/fbr_gram64.h"
+#include "../../flobaroid_amd/csrc/fbr_tsqr_plan.h"
 
 extern "C" {
 
@@ -68,6 +69,23 @@ int emul_reduction(const EmulTopo *t, int which, int32_t *parent, int32_t *dof, 
     for (int j = 0; j < hm.cols; j++)
         for (int e = beg[j]; e < beg[j + 1]; e++) E[(long)row[e] * hm.cols + j] = val[e];
     return rr.Lr;
+}
+
+// The row groups of the tree-structured TSQR (csrc/fbr_tsqr_plan.h tsqr_group_plan) over every column, k = 1, every row active:
+// rowgroup [rows] the group of every regressor row (-1: none), *main the dense group, colmask [cap][cols] per group whether it factorises
+// the column.  Returns the number of groups (at most cap are written).
+int emul_tsqr_group_plan(const EmulTopo *t, int force_group, int32_t *rowgroup, int32_t *main, int32_t *colmask, int cap)
+{
+    FbrHostModel hm;
+    make(t, hm);
+    const TsqrGroupPlan gp = tsqr_group_plan(hm, nullptr, 0, 1, nullptr, force_group != 0);
+    for (int r = 0; r < hm.rows; r++) rowgroup[r] = gp.rowgroup[r];
+    *main = gp.main;
+    for (int g = 0; g < (int)gp.groups.size() && g < cap; g++) {
+        for (int c = 0; c < hm.cols; c++) colmask[(long)g * hm.cols + c] = 0;
+        for (int j : gp.groups[g].sel) colmask[(long)g * hm.cols + j] = 1;
+    }
+    return (int)gp.groups.size();
 }
 
 // mirrors fbr_kin_kernel: one "lane" per sample, links in traversal order, AoS record

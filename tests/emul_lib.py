@@ -26,7 +26,8 @@ class EmulTopo(ctypes.Structure):
 def lib():
     global _lib
     if _lib is None:
-        deps = [_SRC, os.path.join(_CSRC, "fbr_math.h"), os.path.join(_CSRC, "fbr_program.h"), os.path.join(_CSRC, "fbr_reduce.h"), os.path.join(_CSRC, "fbr_kinid.h"), os.path.join(_CSRC, "fbr_gram64.h")]
+        deps = [_SRC, os.path.join(_CSRC, "fbr_math.h"), os.path.join(_CSRC, "fbr_program.h"), os.path.join(_CSRC, "fbr_reduce.h"), os.path.join(_CSRC, "fbr_kinid.h"), os.path.join(_CSRC, "fbr_gram64.h"),
+                os.path.join(_CSRC, "fbr_tsqr_plan.h")]
         if not os.path.exists(_OUT) or any(os.path.getmtime(d) > os.path.getmtime(_OUT) for d in deps):
             os.makedirs(os.path.dirname(_OUT), exist_ok=True)
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _OUT, _SRC])
@@ -154,6 +155,17 @@ class Emul:
         if rc != 0:
             raise RuntimeError(f"emul_kinfd: rc {rc}")
         return out
+
+    def tsqr_group_plan(self, force_group):
+        """(rowgroup [rows], main, colmask [groups][cols]) of the library's row groups of the TSQR (csrc/fbr_tsqr_plan.h tsqr_group_plan,
+        every column, k = 1): the group of every regressor row (-1: none), the dense group, and the columns every group factorises"""
+        rowgroup = np.zeros(self.rows, np.int32)
+        main = ctypes.c_int32()
+        mask = np.zeros((self.rows, self.cols), np.int32)
+        G = lib().emul_tsqr_group_plan(ctypes.byref(self.t), int(force_group), rowgroup.ctypes.data_as(_ip), ctypes.byref(main),
+                                       mask.ctypes.data_as(_ip), self.rows)
+        assert 0 <= G <= self.rows
+        return rowgroup, main.value, mask[:G].astype(bool)
 
     def program_info(self, k):
         NT, npairs, T, img, items = (ctypes.c_int() for _ in range(5))

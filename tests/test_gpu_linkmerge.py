@@ -193,7 +193,7 @@ def test_column_subset_factor_through_the_regrouped_model():
     import scipy.linalg as sla
     import torch
     from common import load_topo
-    from flobaroid_amd._lib import Engine
+    from flobaroid_amd._lib import Engine, FbrError
     from oracle.oracle import OracleModel
 
     t = load_topo("walkman_apriori")
@@ -240,6 +240,12 @@ def test_column_subset_factor_through_the_regrouped_model():
         assert eng.tsqr_work_info(S, k=1, cols=sub) != (eng.set_option("link_merge", 0), eng.tsqr_work_info(S, k=1, cols=sub), eng.set_option("link_merge", 1))[1]
         Rn = eng.tsqr(st, rhs=rhs, cols=sub)
         assert np.all(np.tril(Rn, -1) == 0) and _rel(Rn.T @ Rn, A.T @ A) <= 1e-11, len(sub)
+    # a list with a repeated column: refused by the factorisation and by its work count alike
+    rep = ic.copy()
+    rep[1] = rep[0]
+    for call in (lambda: eng.tsqr(st, rhs=rhs, cols=rep), lambda: eng.tsqr_work_info(S, k=1, cols=rep)):
+        with pytest.raises(FbrError, match="code -1"):
+            call()
     # narrow subset / masked joint rows: the direct path (same answers)
     few = ic[:60]
     A = np.hstack([Y[:, few], rhs])

@@ -1,12 +1,12 @@
-"""The algebra behind the tree-structured TSQR (csrc/fbr_api.hip: tsqr_group_plan), checked on the CPU with the
+"""The algebra behind the tree-structured TSQR (csrc/fbr_tsqr_plan.h: tsqr_group_plan), checked on the CPU with the
 oracle's regressor: the rows grouped along the kinematic tree -- base-wrench rows, one group per unbranched chain of joints --
 touch only the columns of their own sub-tree; factorising every group over those columns and folding the embedded group factors
 gives the R of the whole matrix; and the dense tile-update count drops as DESIGN states.  `group_plan` below restates the
-grouping rule of the library in Python (the library's own plan is exercised by tests/test_gpu_parity.py on the GPU)."""
+grouping rule of the library in Python, and the library's own plan (built on the CPU through tests/emul) is checked against it."""
 import numpy as np
 import pytest
 
-from common import load_topo, random_states
+from common import load_topo, random_states, random_topology
 from oracle.oracle import OracleModel
 
 
@@ -94,3 +94,41 @@ def test_group_factors_assemble_the_full_factor(name, floating, ngroups):
         # 6 x 481, 3 x 311, 2 x (6 x 71), 2 x (7 x 91): 0.23 of the dense row x column^2 work before the in-group first-column skipping
         assert dense_updates / om.rows < 0.24
         assert sorted(len(r) for r, _ in plan) == [3, 6, 6, 6, 7, 7]
+
+
+PLAN_CASES = [(name, fl) for name in ("walkman_apriori", "walkman_left_arm", "kuka_lwr4", "threeLinks") for fl in (0, 1)] + \
+             [(f"random{seed}", fl) for seed in range(4) for fl in (0, 1)]
+
+
+@pytest.mark.parametrize("name,floating", PLAN_CASES, ids=[f"{n}-{'fb' if f else 'fixed'}" for n, f in PLAN_CASES])
+def test_the_library_plan_is_the_rule(name, floating):
+    """The library's tsqr_group_plan over every column: with tsqr_force_group = 0 the row and column sets of `group_plan` (a group's
+    links x 10 parameters); with it on a floating base, rows 0 .. 2 in a group of their own over exactly the mass and first-moment
+    columns, and the other groups unchanged."""
+    from emul_lib import Emul
+
+    if name.startswith("random"):
+        seed = int(name[len("random"):])
+        t = random_topology(np.random.default_rng(40 + seed), 6 + 4 * seed, p_fixed=0.25, branchiness=0.5)
+    else:
+        t = load_topo(name)
+    em = Emul(t, floating=bool(floating))
+    L = t.num_links
+    assert em.cols == 10 * L
+
+    def lib_groups(force_group):
+        rowgroup, main, mask = em.tsqr_group_plan(force_group)
+        assert (rowgroup >= 0).all()  # every row is in a group
+        return {tuple(np.flatnonzero(rowgroup == g)): tuple(np.flatnonzero(mask[g])) for g in range(len(mask))}, main, rowgroup
+
+    rule = {tuple(sorted(rows)): tuple(10 * l + p for l in sorted(links) for p in range(10)) for rows, links in group_plan(t, floating)}
+    groups, main, rowgroup = lib_groups(0)
+    assert groups == rule
+    if floating:
+        if tuple(range(6)) in rule:  # base-wrench rows alone: dense in every column, the final factor's group
+            assert main == rowgroup[0]
+        split, _, _ = lib_groups(1)
+        assert split.pop((0, 1, 2)) == tuple(10 * l + p for l in range(L) for p in range(4))
+        base = next(rows for rows in rule if 0 in rows)  # the moment rows keep the base group and its columns
+        rule[tuple(r for r in base if r >= 3)] = rule.pop(base)
+        assert split == rule
