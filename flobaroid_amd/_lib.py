@@ -75,6 +75,11 @@ _SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_candidate_extrema": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -145,7 +150,7 @@ _SIGNATURES = {
 # Options every new Engine starts with (``fbr_model_set_option``, include/fbr.h lists the keys), on top of the library's defaults and below
 # the ``options`` argument of the constructor.  A plain Python dict: the library itself never reads the process environment.  The test
 # suite uses it to run whole modules with the column reductions forced / switched off (tests/conftest.py: reduction_mode).
-FBR_VERSION = 102  # include/fbr.h FBR_VERSION: the C-ABI these ctypes signatures describe
+FBR_VERSION = 103  # include/fbr.h FBR_VERSION: the C-ABI these ctypes signatures describe
 DEFAULT_OPTIONS: dict = {}
 
 
@@ -269,6 +274,7 @@ class Engine:
         self.L = topo.num_links
         self.floating = bool(floating)
         self.friction = bool(friction)
+        self.stribeck = float(stribeck_velocity) if friction else 0.0  # > 0: the torques need vel_sign
         self.device = int(device)
         for key, val in {**DEFAULT_OPTIONS, **(options or {})}.items():
             self.set_option(key, val)
@@ -391,6 +397,40 @@ class Engine:
             "fbr_inverse_dynamics_batch",
         )
         return ret
+
+    EXTREMA = ("q_min", "q_max", "dq_absmax", "tau_absmax")
+
+    def candidate_extrema(self, st: dict, ncand: int, x_std, vel_sign=None, device_out: bool | None = None) -> dict:
+        """Per-candidate extrema of ``ncand`` equal candidates stacked along the sample axis (``fbr_candidate_extrema``): a dict of (C, n)
+        arrays -- values ``q_min``, ``q_max``, ``dq_absmax``, ``tau_absmax`` (joint rows of the torques ``inverse_dynamics`` returns, NaN
+        counted as 0, inf as DBL_MAX) and their int64 sample indices inside the candidate, ``<name>_idx``.  Torch tensors when the states
+        are on the device, NumPy arrays otherwise (``device_out`` overrides)."""
+        s, keep, S, mem = self._states(st)
+        x = np.ascontiguousarray(x_std, dtype=np.float64)
+        vs = _Ref(vel_sign, (S, self.n), "vel_sign") if vel_sign is not None else _Ref(None)
+        if vs.mem is not None and vs.mem != mem:
+            raise ValueError("vel_sign must live in the same memory space as the states")
+        C = int(ncand)
+        shape = (max(C, 1), 4, self.n)  # (ncand < 1 is refused by the library)
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        if out_mem == FBR_DEVICE:
+            import torch
+
+            val = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
+            idx = torch.empty(shape, dtype=torch.int64, device=f"cuda:{self.device}")
+            pv, pi = val.data_ptr(), idx.data_ptr()
+        else:
+            val, idx = np.empty(shape), np.empty(shape, dtype=np.int64)
+            pv, pi = val.ctypes.data, idx.ctypes.data
+        _check(
+            self._lib.fbr_candidate_extrema(self._h, ctypes.byref(s), C, x.ctypes.data_as(_dp), int(x.size), vs.ptr, pv, pi, out_mem),
+            "fbr_candidate_extrema",
+        )
+        out = {}
+        for k, name in enumerate(self.EXTREMA):
+            out[name] = val[:, k]
+            out[name + "_idx"] = idx[:, k]
+        return out
 
     def predict(self, st: dict, x, out=None):
         s, keep, S, mem = self._states(st)

@@ -9,7 +9,7 @@ thread_local std::string g_fbr_err;
 
 // ------------------------------------------------------------------------------------------------
 // 101 (round 6): fbr_topology.joint_type, the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info (both added in
-// round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group".
+// round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema.
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
 
@@ -551,27 +551,75 @@ static size_t kinid_lds(const fbr_model *m) { return (size_t)3 * 64 * (std::max(
 static bool kinid_fits(const fbr_model *m) { return m->opt.fused_id != 0 && m->kinid.nsteps > 0 && kinid_lds(m) <= (size_t)160 * 1024; }
 // Fused kinematics + torques (csrc/fbr_kinid.h): one kernel, one lane per sample, the link records stay in registers, branch-point
 // records in a per-wave scratch.  mode 0 / 1: x = parameters (device); mode 2: x = [S][6] contact wrenches at frame (flink, fp).
-static int launch_kinid(fbr_model *m, const DevStates &d, long S, const double *dvs, const double *x, int mode, double *dst, int flink, const double *fp)
+// ex (mode 0 only): the candidate-extrema instance, which writes the partials of ex instead of dst.
+static int launch_kinid(fbr_model *m, const DevStates &d, long S, const double *dvs, const double *x, int mode, double *dst, int flink, const double *fp,
+                        const DevKinExt *ex = nullptr)
 {
     const DevKinId kp = kinid_params(m);
     const size_t lds = kinid_lds(m);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)(150 << 10) / std::max<size_t>(lds, 1)));
-    const long nblk = (S + 63) / 64;
+    const long nblk = ex ? ex->nblk : (S + 63) / 64;
     const int blocks = (int)std::min<long>(nblk, (long)m->num_cus * per_cu);
     if (int rc = m->kinid_scratch.ensure((size_t)blocks * std::max(kp.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double))) return rc;
     const double f0 = fp ? fp[0] : 0.0, f1 = fp ? fp[1] : 0.0, f2 = fp ? fp[2] : 0.0;
+    const DevKinExt ex0 = ex ? *ex : DevKinExt{0, 0, 0, nullptr, nullptr};
     ProfScope ps(m, FBR_PROF_ID);
     return fbr_by_depth<4, 8, 12, FBR_KINID_MAXD>(kp.maxlvl, [&](auto D) -> int {
-        HIPCHK(hipFuncSetAttribute((const void *)fbr_kinid_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(fbr_kinid_kernel<D>, dim3(blocks), dim3(64), lds, m->stream, m->dm, kp, S, d.q, d.dq, d.ddq, d.bv, d.ba, d.rpy, d.sign,
-                           dvs, x, mode, dst, m->kinid_scratch.as<double>(), flink, f0, f1, f2);
+        const auto kern = ex ? fbr_kinid_kernel<D, true> : fbr_kinid_kernel<D, false>;
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, m->stream, m->dm, kp, S, d.q, d.dq, d.ddq, d.bv, d.ba, d.rpy, d.sign,
+                           dvs, x, mode, dst, m->kinid_scratch.as<double>(), flink, f0, f1, f2, ex0);
         HIPCHK(hipGetLastError());
         return FBR_OK;
     });
 }
 
+// fbr_candidate_extrema's request to run_id: the torques are reduced to per-candidate extrema instead of returned
+struct ExtremaReq {
+    long ncand;
+    double *val_out;
+    int64_t *idx_out;
+};
+
+// the tiles of ncand candidates of S / ncand samples each, their partials in m->ext_part
+static int extrema_tiles(fbr_model *m, long S, long ncand, DevKinExt *ex)
+{
+    const long T = S / ncand, tiles = (T + 63) / 64;
+    const size_t cnt = (size_t)ncand * tiles * 4 * std::max(m->hm.n, 1);
+    if (int rc = m->ext_part.ensure(cnt * (sizeof(double) + sizeof(long)))) return rc;
+    *ex = DevKinExt{T, tiles, ncand * tiles, m->ext_part.as<double>(), (long *)(m->ext_part.as<double>() + cnt)};
+    return FBR_OK;
+}
+
+// the candidates' partials reduced in tile order into [ncand][4][n] values and indices (the caller's memory space)
+static int finish_extrema(fbr_model *m, const DevKinExt &ex, const ExtremaReq &rq, int32_t out_mem)
+{
+    const int n = m->hm.n;
+    const size_t cnt = (size_t)rq.ncand * 4 * n;
+    double *val = rq.val_out;
+    long *idx = (long *)rq.idx_out;
+    if (out_mem == FBR_HOST) {
+        if (int rc = m->ext_out.ensure(cnt * (sizeof(double) + sizeof(long)))) return rc;
+        val = m->ext_out.as<double>();
+        idx = (long *)(val + cnt);
+    }
+    {
+        ProfScope ps(m, FBR_PROF_ID);
+        hipLaunchKernelGGL(fbr_extrema_finish_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, m->stream, ex, n, rq.ncand, val, idx);
+        HIPCHK(hipGetLastError());
+    }
+    if (out_mem == FBR_HOST) {
+        HIPCHK(hipMemcpyAsync(rq.val_out, val, cnt * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(rq.idx_out, idx, cnt * sizeof(long), hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    prof_collect(m);
+    return FBR_OK;
+}
+
+// ext: the candidate extrema of the torques (fbr_candidate_extrema) instead of the torques -- the same route, the same kernels' arithmetic
 static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, const double *vel_sign, int mode,
-                  double *tau_out, int32_t out_mem)
+                  double *tau_out, int32_t out_mem, const ExtremaReq *ext = nullptr)
 {
     // Y x = Y_red (E x): torques are linear in the parameters, and the parameters of a link welded to a moving body are parameters of that
     // body (build_reduction, merged model rdm[0]: every moving link keeps its ten columns).  The kinematics and the per-link wrench loop
@@ -591,14 +639,14 @@ static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, c
             if (int rc = enter_blocking(m)) return rc;
             r->stream = m->stream;
             r->prof = m->prof;
-            return run_id(r, st, xr.data(), rin + (nx - ninert), vel_sign, mode, tau_out, out_mem);
+            return run_id(r, st, xr.data(), rin + (nx - ninert), vel_sign, mode, tau_out, out_mem, ext);
         }
     }
     DevStates d;
     int rc = stage_states(m, st, &d);
     if (rc) return rc;
     const FbrHostModel &hm = m->hm;
-    if (!x || !tau_out) {
+    if (!x || (!tau_out && !ext)) {
         set_err("null x / tau_out");
         return FBR_E_INVALID;
     }
@@ -619,14 +667,16 @@ static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, c
         }
         if ((rc = stage_one(m, m->st_aux, vel_sign, (size_t)S * hm.n, st->mem, &dvs))) return rc;
     }
+    DevKinExt ex;
+    if (ext && (rc = extrema_tiles(m, S, ext->ncand, &ex))) return rc;
     double *dst = tau_out;
-    if (out_mem == FBR_HOST) {
+    if (ext ? !kinid_fits(m) : out_mem == FBR_HOST) {  // (extrema on the two-kernel route: the torques in a device temporary)
         if ((rc = m->out_tmp.ensure((size_t)S * hm.rows * sizeof(double)))) return rc;
         dst = m->out_tmp.as<double>();
     }
     if (kinid_fits(m)) {
-        if ((rc = launch_kinid(m, d, S, dvs, m->st_x.as<double>(), mode, dst, 0, nullptr))) return rc;
-        return finish_output(m, dst, tau_out, (size_t)S * hm.rows, out_mem);
+        if ((rc = launch_kinid(m, d, S, dvs, m->st_x.as<double>(), mode, ext ? nullptr : dst, 0, nullptr, ext ? &ex : nullptr))) return rc;
+        return ext ? finish_extrema(m, ex, *ext, out_mem) : finish_output(m, dst, tau_out, (size_t)S * hm.rows, out_mem);
     }
     // one wave per sample, each with its record and link forces in the LDS: up to four waves per workgroup, fewer for large trees
     const size_t per_wave = (size_t)(hm.rec_size() + 6 * hm.L) * sizeof(double);
@@ -648,6 +698,15 @@ static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, c
                            m->st_x.as<double>(), mode, dst + (size_t)s0 * hm.rows);
         HIPCHK(hipGetLastError());
     }
+    if (ext) {
+        {
+            ProfScope ps(m, FBR_PROF_ID);
+            hipLaunchKernelGGL(fbr_extrema_tiles_kernel, dim3((unsigned)std::min<long>(ex.nblk, (long)m->num_cus * 8)), dim3(256), 0, m->stream, ex, hm.n,
+                               hm.fb, hm.rows, d.q, d.dq, (const double *)dst);
+            HIPCHK(hipGetLastError());
+        }
+        return finish_extrema(m, ex, *ext, out_mem);
+    }
     return finish_output(m, dst, tau_out, (size_t)S * hm.rows, out_mem);
 }
 
@@ -655,6 +714,25 @@ extern "C" int fbr_inverse_dynamics_batch(fbr_model *m, const fbr_states *st, co
                                           const double *vel_sign, double *tau_out, int32_t out_mem)
 {
     return run_id(m, st, x_std, num_x, vel_sign, 0, tau_out, out_mem);
+}
+
+extern "C" int fbr_candidate_extrema(fbr_model *m, const fbr_states *st, int32_t ncand, const double *x_std, int32_t num_x, const double *vel_sign,
+                                     double *val_out, int64_t *idx_out, int32_t out_mem)
+{
+    if (!m || !st || !val_out || !idx_out) {
+        set_err("null model / states / val_out / idx_out");
+        return FBR_E_INVALID;
+    }
+    if (ncand < 1) {
+        set_err("ncand must be at least 1");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
+        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
+        return FBR_E_INVALID;
+    }
+    const ExtremaReq rq{ncand, val_out, idx_out};
+    return run_id(m, st, x_std, num_x, vel_sign, 0, nullptr, out_mem, &rq);
 }
 
 extern "C" int fbr_predict(fbr_model *m, const fbr_states *st, const double *x, double *tau_out, int32_t out_mem)

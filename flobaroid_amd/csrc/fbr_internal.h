@@ -147,6 +147,7 @@ struct fbr_model {
     FbrKinIdProgram kinid;    // program of the fused kinematics + torque kernel (fbr_kinid.h); nsteps == 0: not available for this tree
     const int *kinid_steps = nullptr, *kinid_endflush = nullptr;
     DevBuf kinid_scratch;     // branch-point records of the waves in flight
+    DevBuf ext_part, ext_out; // candidate extrema: per-tile (value, index) partials; the final values and indices of a host-memory call
     DevBuf fd_tab, fd_part;   // sub-tree column lists of every joint [n + 1 | entries] (built on first use), baseline partial sums [S][n]
     int fd_tab_entries = -1;
     FbrTsqrWork tsqr;

@@ -264,6 +264,29 @@ struct DevKinId {
     int nsteps, maxlvl, nslots, ldn;  // ldn: row stride (doubles, odd) of the staged joint states of one sample
     const int *steps, *endflush;
 };
+// candidate extrema (fbr_candidate_extrema): C candidates of T consecutive samples each, cut into tiles of 64 samples that never span two
+// candidates (tiles = ceil(T / 64) per candidate, tile b = candidate b / tiles).  Every tile writes [4][n] (value, index) partials --
+// 0 min q, 1 max q, 2 max |dq|, 3 max |nan_to_num(tau)| over the joint rows -- the index counted inside the candidate; the finishing kernel
+// reduces a candidate's tiles in tile order (no atomics: deterministic).
+struct DevKinExt {
+    long T, tiles, nblk;  // samples per candidate, tiles per candidate, tiles in all
+    double *val;          // [nblk][4][n]
+    long *idx;            // [nblk][4][n]
+};
+// value of quantity k that the extrema compare: q as is, |dq|, |nan_to_num(tau)| (NaN -> 0, +-inf -> DBL_MAX: what np.nan_to_num hands on)
+FBR_HD double fbr_ext_value(int k, double v)
+{
+    if (k == 2) return fabs(v);
+    if (k == 3) return v != v ? 0.0 : fmin(fabs(v), 1.7976931348623157e308);
+    return v;
+}
+// does a LATER sample's value a replace the running extremum b (k == 0: minimum, else maximum)?  NumPy's rules: the first NaN wins and
+// stays, ties keep the earlier index
+FBR_HD bool fbr_ext_take(int k, double a, double b)
+{
+    if (b != b) return false;
+    return a != a || (k == 0 ? a < b : a > b);
+}
 // tables of the lane WRITERS (fbr_kinwrite_kernel below, fbr_kinimg_kernel in fbr_gram64.h)
 // destinations arrive as integers: a pointer made from one is GENERIC (flat_store: counted by lgkmcnt as well, so that every wait for a scalar load
 // or an LDS read would also wait for the stores in flight) unless it is given the global address space explicitly
@@ -287,22 +310,35 @@ struct DevKinWrite {
 // (link `flink`, point fpx/y/z in its axes), every other link contributes nothing, no friction.
 // grid-stride over blocks of 64 samples; dynamic LDS: 3 x [64][ldn] doubles (q, dq, ddq of the wave's samples).
 // scratch: [gridDim.x][nslots][FBR_LINK_REC][64] doubles.
-template <int MAXD>
+// EXT (fbr_candidate_extrema, mode 0): blocks of 64 samples of ONE candidate (DevKinExt); `emit` puts a sample's joint torques into the
+// LDS (over its staged ddq, read by then) instead of HBM, and the block's extrema of q, |dq| and |tau| are scanned from the LDS after the
+// lane body -- nothing per sample leaves the CU.  The lane body and `emit`'s arithmetic are the plain instance's: the torques compared are
+// the ones fbr_inverse_dynamics_batch returns, bit for bit.
+template <int MAXD, bool EXT = false>
 __global__ __launch_bounds__(64) void fbr_kinid_kernel(DevModel m, DevKinId p, long S, const double *__restrict__ q, const double *__restrict__ dq,
                                                        const double *__restrict__ ddq, const double *__restrict__ bv,
                                                        const double *__restrict__ ba, const double *__restrict__ rpy,
                                                        const double *__restrict__ sign, const double *__restrict__ vel_sign,
                                                        const double *__restrict__ x, int mode, double *__restrict__ tau, double *__restrict__ scratch, int flink, double fpx,
-                                                       double fpy, double fpz)
+                                                       double fpy, double fpz, DevKinExt ex)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int lane = threadIdx.x, n = m.n, ldn = p.ldn;
     double *sq = smem, *sdq = sq + 64 * ldn, *sddq = sdq + 64 * ldn;
     double *scr = scratch + (long)blockIdx.x * p.nslots * FBR_LINK_REC * 64 + lane;
-    const long nblk = (S + 63) >> 6;
+    const long nblk = EXT ? ex.nblk : (S + 63) >> 6;
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-        const long base = blk << 6;
-        const int valid = (int)min(64L, S - base);
+        long base, i0 = 0;  // i0 (EXT): index of the block's first sample inside its candidate
+        int valid;
+        if constexpr (EXT) {
+            const long c = blk / ex.tiles;
+            i0 = (blk - c * ex.tiles) << 6;
+            base = c * ex.T + i0;
+            valid = (int)min(64L, ex.T - i0);
+        } else {
+            base = blk << 6;
+            valid = (int)min(64L, S - base);
+        }
         __syncthreads();  // (the block before has read its states)
         {
             // coalesced copy of the block's q / dq / ddq rows into [sample][ldn]
@@ -400,10 +436,98 @@ __global__ __launch_bounds__(64) void fbr_kinid_kernel(DevModel m, DevKinId p, l
                     }
                 }
             }
-            if (live) ts[r] = v;
+            if constexpr (EXT) {
+                // the joint row goes into the lane's own staged ddq entry of that joint: the joint's link has read it (a joint's torque is
+                // complete only after every link below it has been walked), nothing reads it again
+                if (r >= m.fb && live) sddq[lane * ldn + r - m.fb] = v;
+            } else if (live) {
+                ts[r] = v;
+            }
         };
         fbr_kinid_lane<MAXD, true>(p.nsteps, p.maxlvl, p.steps, p.endflush, m.floating, m.g, m.fb, state, basest, save, load, link, emit, consts);
+        if constexpr (EXT) {
+            // one lane per joint scans the block's rows in sample order (ties keep the first): q and dq as staged, the torques where emit
+            // left them
+            __syncthreads();
+            double *pv = ex.val + blk * 4 * n;
+            long *pi = ex.idx + blk * 4 * n;
+            for (int d = lane; d < n; d += 64) {
+                // plain comparisons (a NaN compares false: it is never taken), the NaN rules of fbr_ext_take only for a column that has
+                // one past its first row; a NaN torque counts as 0, which the running maximum (>= 0 from the first row on) never takes
+                double b[4] = {sq[d], sq[d], fbr_ext_value(2, sdq[d]), fbr_ext_value(3, sddq[d])};
+                int ib[4] = {0, 0, 0, 0};
+                bool nan = false;
+                for (int r = 1; r < valid; r++) {
+                    const double aq = sq[r * ldn + d], ad = fabs(sdq[r * ldn + d]), at = sddq[r * ldn + d];
+                    const double ct = fmin(fabs(at), 1.7976931348623157e308);
+                    nan |= __builtin_isunordered(aq, ad);
+                    if (aq < b[0]) b[0] = aq, ib[0] = r;
+                    if (aq > b[1]) b[1] = aq, ib[1] = r;
+                    if (ad > b[2]) b[2] = ad, ib[2] = r;
+                    if (ct > b[3] && at == at) b[3] = ct, ib[3] = r;
+                }
+                if (nan) {
+                    b[0] = b[1] = sq[d];
+                    b[2] = fbr_ext_value(2, sdq[d]);
+                    ib[0] = ib[1] = ib[2] = 0;
+                    for (int r = 1; r < valid; r++) {
+                        const double aq = sq[r * ldn + d], ad = fbr_ext_value(2, sdq[r * ldn + d]);
+                        if (fbr_ext_take(0, aq, b[0])) b[0] = aq, ib[0] = r;
+                        if (fbr_ext_take(1, aq, b[1])) b[1] = aq, ib[1] = r;
+                        if (fbr_ext_take(2, ad, b[2])) b[2] = ad, ib[2] = r;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    pv[k * n + d] = b[k];
+                    pi[k * n + d] = i0 + ib[k];
+                }
+            }
+        }
     }
+}
+// Candidate extrema from MATERIALISED states and torques (the two-kernel route of fbr_candidate_extrema: fused_id = 0, joint paths beyond
+// FBR_KINID_MAXD, more than 105 DOF): the tiles and partials of the EXT instance above.  A workgroup per tile, a thread per (quantity,
+// joint) scans the tile's samples in order; tau [S][rows], the joint rows from fb on.
+__global__ __launch_bounds__(256) void fbr_extrema_tiles_kernel(DevKinExt ex, int n, int fb, int rows, const double *__restrict__ q,
+                                                                const double *__restrict__ dq, const double *__restrict__ tau)
+{
+    for (long blk = blockIdx.x; blk < ex.nblk; blk += gridDim.x) {
+        const long c = blk / ex.tiles, i0 = (blk - c * ex.tiles) << 6, base = c * ex.T + i0;
+        const int valid = (int)min(64L, ex.T - i0);
+        for (int kd = threadIdx.x; kd < 4 * n; kd += blockDim.x) {
+            const int k = kd / n, d = kd - k * n;
+            const double *src = k < 2 ? q + base * n + d : k == 2 ? dq + base * n + d : tau + base * rows + fb + d;
+            const long ld = k < 3 ? n : rows;
+            double b = fbr_ext_value(k, src[0]);
+            int ib = 0;
+            for (int r = 1; r < valid; r++) {
+                const double a = fbr_ext_value(k, src[r * ld]);
+                if (fbr_ext_take(k, a, b)) b = a, ib = r;
+            }
+            ex.val[blk * 4 * n + kd] = b;
+            ex.idx[blk * 4 * n + kd] = i0 + ib;
+        }
+    }
+}
+// the partials of a candidate's tiles reduced in tile order: out [C][4][n], one thread per entry
+__global__ __launch_bounds__(256) void fbr_extrema_finish_kernel(DevKinExt ex, int n, long C, double *__restrict__ val, long *__restrict__ idx)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= C * 4 * n) return;
+    const long c = t / (4 * n);
+    const int kd = (int)(t - c * 4 * n), k = kd / n;
+    const double *v = ex.val + c * ex.tiles * 4 * n + kd;
+    const long *ix = ex.idx + c * ex.tiles * 4 * n + kd;
+    double b = v[0];
+    long ib = ix[0];
+#pragma unroll 8
+    for (long j = 1; j < ex.tiles; j++) {
+        const double a = v[j * 4 * n];
+        if (fbr_ext_take(k, a, b)) b = a, ib = ix[j * 4 * n];
+    }
+    val[t] = b;
+    idx[t] = ib;
 }
 // Finite-difference sweep (analyticalGradient.py:92-185): one lane per EVALUATION e = s (1 + 3 n) + j -- j = 0 the state of
 // sample s itself, 1 + kind n + d the state with +eps on q_d / dq_d / ddq_d -- score[e] = sum_{r,c} W_s[r][c] Y_e[r][c], the regressor

@@ -291,11 +291,20 @@ def d_optimality_batch(G_groups: np.ndarray, independent_cols, dopt_regularizati
     """``d_optimality`` of every candidate trajectory of a batch: ``G_groups`` (ngroups, Pa, Pa) from
     ``Engine.gram_grouped`` (one pass over all candidates; the optimiser's inner loop, trajectoryOptimizer.py:248-272).
     delta is taken per candidate from that candidate's own largest eigenvalue, as the reference does per trajectory."""
+    return d_optimality_batch_terms(G_groups, independent_cols, dopt_regularization, YtY_prior)[0]
+
+
+def d_optimality_batch_terms(G_groups: np.ndarray, independent_cols, dopt_regularization: float = 1e-4,
+                             YtY_prior: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``d_optimality_batch`` with the other numbers the reference takes from the same eigenvalues: per candidate
+    ``(neg_log_det, lambda_max, n_observable)``, n_observable = #(eig > delta) (trajectoryOptimizer.py:266-275)."""
     ic = np.asarray(independent_cols, dtype=np.int64)
     YtY = G_groups[:, ic[:, None], ic[None, :]]
     if YtY_prior is not None:
         YtY = YtY + np.asarray(YtY_prior, dtype=np.float64)[None]
-    return _regularized_neg_log_det(la.eigvalsh(YtY), dopt_regularization)
+    ev = la.eigvalsh(YtY)
+    delta = float(dopt_regularization) * np.maximum(ev[..., -1:], 1e-30)
+    return _regularized_neg_log_det(ev, dopt_regularization), ev[..., -1].copy(), np.sum(ev > delta, axis=-1).astype(np.int64)
 
 
 def n_observable_base_params(G_aug: np.ndarray, independent_cols, dopt_regularization: float = 1e-4) -> int:

@@ -5,7 +5,9 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 (excitation/analyticalGradient.py:92-185).  Here both are single device passes:
 
 * ``candidate_dopt``      -- D-optimality of many candidate trajectories from ``Engine.gram_grouped``;
-* ``dopt_sensitivities``  -- the worker's ``sens_q, sens_dq, sens_ddq`` from ``Engine.fd_scores``.
+* ``dopt_sensitivities``  -- the worker's ``sens_q, sens_dq, sens_ddq`` from ``Engine.fd_scores``;
+* ``candidate_objectives`` -- the whole ``objectiveFunc`` (f, g, soft costs; no collision constraints) of many candidates from
+  ``Engine.gram_grouped`` + ``Engine.candidate_extrema``: only per-candidate numbers reach the host.
 """
 from __future__ import annotations
 
@@ -125,3 +127,130 @@ def candidate_dopt_from_coefficients(engine, candidates: list, T: int, freq: flo
 
         st["sign"] = torch.tanh(st["dq"] / float(friction_sign_threshold))
     return candidate_dopt(engine, st, len(candidates), independent_cols, dopt_regularization, YtY_prior=YtY_prior)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The optimiser's objective per candidate (trajectoryOptimizer.py objectiveFunc, lines 259-475 without the collision block): everything it
+# needs of the samples is the per-joint extrema of q, |dq| and |tau| (Engine.candidate_extrema), the rest is per-candidate host arithmetic.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def constraint_layout(n: int, min_velocity_constraint: bool) -> dict:
+    """Offsets of the blocks of ``g`` (each n long): lower position, upper position, peak velocity, peak torque, [minimum velocity,]
+    minimum torque utilisation -- the reference's order without its collision block; ``len`` = 5 n, or 6 n with the minimum velocity."""
+    names = ["pos_lower", "pos_upper", "vel", "torque"] + (["min_vel"] if min_velocity_constraint else []) + ["min_torque_util"]
+    lay = {k: i * n for i, k in enumerate(names)}
+    lay["len"] = len(names) * n
+    return lay
+
+
+def _check_config(config: dict) -> None:
+    if config.get("floatingBaseAttachment") == "suspended":
+        raise ValueError("floatingBaseAttachment 'suspended' simulates the base motion with a sequential ODE (suspendedDynamics.py): "
+                         "not supported by the batched objective")
+    if config.get("identifyGravityParamsOnly"):
+        raise ValueError("identifyGravityParamsOnly: the batched objective needs the full torques, which the gravity-only model does not give")
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, joint_names, config: dict, dopt_scale=None) -> dict:
+    """``objectiveFunc``'s f, g and soft costs of C candidates from their D-optimality terms and the extrema of ``Engine.candidate_extrema``
+    (values and indices, (C, n) each) -- pure host arithmetic.
+
+    ``limits[name]``: ``lower``, ``upper``, ``velocity``, ``torque`` of joint ``name`` (the reference's ``self.limits``); ``joint_names``:
+    the n joints in dof order.  ``config`` keys read: ``minVelocityConstraint`` (+ ``minVelocityPercentage``), ``ovrPosLimit`` ({joint:
+    [lower_deg, upper_deg]}), ``minTorqueUtilization`` (0.02), ``trajectoryTargetTorqueUtil`` (0.25), ``trajectoryTargetVelocity`` (0).
+    ``dopt_scale``: the reference's ``_dopt_scale``; None: 10 / max(|neg_log_det[0]|, 1), what its first call sets.
+
+    Returns, per candidate: ``f`` (C,), ``g`` (C, len) with NaN entries set to 10 (layout: ``constraint_layout``), ``dopt`` (neg_log_det *
+    dopt_scale), ``f1`` (torque balance), ``f2`` (position range, already x10 as in the reference), ``f3`` (torque magnitude), ``f4``
+    (velocity magnitude), ``n_observable``, ``failed`` (non-finite D-optimality: f starts from 100), ``dopt_scale`` and ``ag_cache`` -- the
+    per-candidate entries of the reference's ``_ag_cache`` (``torque_absmax_idx``, ``pos_min_idx``, ``pos_max_idx``, ``vel_absmax_idx``,
+    ``vel_absmax``, ``utilization``, ``util_mean``, ``util_std``, ``f1``, ``f3``, ``pos_range_available``)."""
+    _check_config(config)
+    nld = np.asarray(neg_log_det, dtype=np.float64).reshape(-1)
+    C = nld.shape[0]
+    e = {k: _host(v) for k, v in ext.items()}
+    pos_min, pos_max, vel_absmax, torque_absmax = (e[k].astype(np.float64).reshape(C, -1) for k in ("q_min", "q_max", "dq_absmax", "tau_absmax"))
+    n = pos_min.shape[1]
+    jn = list(joint_names)
+    if len(jn) != n:
+        raise ValueError(f"{len(jn)} joint names for {n} joints")
+    if dopt_scale is None:
+        dopt_scale = 10.0 / max(abs(float(nld[0])), 1.0)
+    dopt_scale = float(dopt_scale)
+
+    lower = np.array([limits[j]["lower"] for j in jn], dtype=np.float64)
+    upper = np.array([limits[j]["upper"] for j in jn], dtype=np.float64)
+    vlim = np.array([limits[j]["velocity"] for j in jn], dtype=np.float64)
+    tlim = np.array([limits[j]["torque"] for j in jn], dtype=np.float64)
+    lo_c, hi_c = lower.copy(), upper.copy()  # position constraints: ovrPosLimit (degrees) overrides the URDF limits
+    ovr = config.get("ovrPosLimit", {})
+    for i, j in enumerate(jn):
+        pair = ovr.get(j) if isinstance(ovr, dict) else None
+        if pair:
+            lo_c[i], hi_c[i] = np.deg2rad(pair[0]), np.deg2rad(pair[1])
+
+    minvel = bool(config.get("minVelocityConstraint", False))
+    lay = constraint_layout(n, minvel)
+    g = np.empty((C, lay["len"]))
+    g[:, lay["pos_lower"]:lay["pos_lower"] + n] = lo_c - pos_min
+    g[:, lay["pos_upper"]:lay["pos_upper"] + n] = pos_max - hi_c
+    g[:, lay["vel"]:lay["vel"] + n] = vel_absmax - vlim
+    g[:, lay["torque"]:lay["torque"] + n] = torque_absmax - tlim
+    if minvel:
+        g[:, lay["min_vel"]:lay["min_vel"] + n] = vlim * config["minVelocityPercentage"] - vel_absmax
+    g[:, lay["min_torque_util"]:lay["min_torque_util"] + n] = tlim * config.get("minTorqueUtilization", 0.02) - torque_absmax
+    g[np.isnan(g)] = 10.0
+
+    dopt = nld * dopt_scale
+    failed = ~np.isfinite(dopt)
+    f = np.where(failed, 100.0, dopt)
+    utilization = torque_absmax / tlim
+    util_mean = utilization.mean(axis=1)
+    util_std = utilization.std(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f1 = np.where(util_mean > 0, util_std / util_mean, 1.0)
+    target = config.get("trajectoryTargetTorqueUtil", 0.25)
+    f3 = np.maximum(0.0, 1.0 - util_mean / target)
+    pos_range_available = upper - lower
+    f2 = (1.0 - ((pos_max - pos_min) / pos_range_available).mean(axis=1)) * 10.0
+    vel_target = float(config.get("trajectoryTargetVelocity", 0.0))
+    f4 = np.maximum(0.0, 1.0 - vel_absmax / vel_target).mean(axis=1) if vel_target > 0 else np.zeros(C)
+    f = f + f1 * 10.0 + f3 * 10.0 + f2 + f4 * 10.0
+    ag = {"torque_absmax_idx": e["tau_absmax_idx"], "pos_min_idx": e["q_min_idx"], "pos_max_idx": e["q_max_idx"], "vel_absmax_idx": e["dq_absmax_idx"],
+          "vel_absmax": vel_absmax, "utilization": utilization, "util_mean": util_mean, "util_std": util_std, "f1": f1, "f3": f3,
+          "pos_range_available": pos_range_available}
+    return {"f": f, "g": g, "dopt": dopt, "f1": f1, "f2": f2, "f3": f3, "f4": f4, "n_observable": np.asarray(n_observable).reshape(-1),
+            "failed": failed, "dopt_scale": dopt_scale, "ag_cache": ag}
+
+
+def candidate_objectives(engine, states: dict, ncand: int, independent_cols, x_std, limits: dict, joint_names, config: dict, dopt_scale=None,
+                         YtY_prior=None, vel_sign=None) -> dict:
+    """``objectives_from_extrema`` of ``ncand`` equal candidates stacked in ``states``: one ``gram_grouped`` (D-optimality, lambda_max,
+    n_observable per candidate with ``doptRegularization``, default 1e-4) and one ``candidate_extrema`` (the a-priori torques of ``x_std``
+    reduced on the device) over the same states.  ``vel_sign``: Stribeck friction, as for ``Engine.inverse_dynamics``."""
+    _check_config(config)
+    G = _host(engine.gram_grouped(states, int(ncand)))
+    nld, _, nobs = est.d_optimality_batch_terms(G, independent_cols, config.get("doptRegularization", 1e-4), YtY_prior)
+    ext = engine.candidate_extrema(states, int(ncand), x_std, vel_sign=vel_sign)
+    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale)
+
+
+def candidate_objectives_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict,
+                                           joint_names, config: dict, dopt_scale=None, YtY_prior=None) -> dict:
+    """``candidate_objectives`` from Fourier coefficients (``fourier_coefficients`` dicts): states generated on the device
+    (``candidate_states``), the Coulomb column tanh(dq / ``frictionSignThreshold``) as ``candidate_dopt_from_coefficients`` sets it and
+    ``vel_sign`` = dq under Stribeck friction -- only per-candidate arrays come back to the host.  ``model_or_x_std``: the a-priori standard
+    parameters, or an object with ``xStdModel`` (``Model``)."""
+    _check_config(config)
+    x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
+    st = candidate_states(engine, candidates, T, freq, device=True)
+    if engine.friction:
+        import torch
+
+        st["sign"] = torch.tanh(st["dq"] / float(config.get("frictionSignThreshold", 0.02)))
+    vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
+    return candidate_objectives(engine, st, len(candidates), independent_cols, x_std, limits, joint_names, config, dopt_scale=dopt_scale,
+                                YtY_prior=YtY_prior, vel_sign=vel_sign)

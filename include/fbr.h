@@ -85,7 +85,7 @@ typedef struct {
  * call (flobaroid_amd/_lib.py load_library refuses a mismatch), because the C-ABI has grown in place -- 101: fbr_topology.joint_type,
  * the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info, option "fused_id"; 102: fbr_gram_lane_info, options
  * "gram_lane" / "gram_force_tiles". */
-#define FBR_VERSION 102
+#define FBR_VERSION 103
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
 const char *fbr_last_error(void);  /* thread-local message of the last failing call */
@@ -116,6 +116,19 @@ int fbr_regressor_batch(fbr_model *m, const fbr_states *st, double *Y_out, int32
  */
 int fbr_inverse_dynamics_batch(fbr_model *m, const fbr_states *st, const double *x_std, int32_t num_x,
                                const double *vel_sign, double *tau_out, int32_t out_mem);
+
+/*
+ * Per-candidate extrema of the trajectory optimiser's constraints (excitation/trajectoryOptimizer.py objectiveFunc: g and the soft costs,
+ * and the sample indices its analytical gradient caches) without the torques leaving the device.  The states are ncand equal candidates
+ * of T = num_samples / ncand consecutive samples (the layout of fbr_gram_grouped / fbr_fourier_states); x_std, vel_sign and the sign
+ * series as for fbr_inverse_dynamics_batch, whose torques -- bit for bit, on the same route -- are the ones reduced.
+ *   val_out [ncand][4][n], idx_out [ncand][4][n] (out_mem): quantity 0 min q, 1 max q, 2 max |dq|, 3 max |nan_to_num(tau)| over the
+ *   joint rows (fb .. fb+n-1: the base wrench is skipped); the index is the sample inside its candidate (0 .. T-1).  NumPy's rules:
+ *   ties go to the first sample, a NaN in q / dq is the value and its first occurrence the index; in tau NaN counts as 0, +-inf as DBL_MAX.
+ * FBR_E_INVALID: ncand < 1, num_samples 0 or not a multiple of ncand, x_std too short, Stribeck without vel_sign.
+ */
+int fbr_candidate_extrema(fbr_model *m, const fbr_states *st, int32_t ncand, const double *x_std, int32_t num_x,
+                          const double *vel_sign, double *val_out, int64_t *idx_out, int32_t out_mem);
 
 /*
  * tau_out [S][rows] = Y_s . x for an identified-parameter vector x (host, length cols) WITHOUT
