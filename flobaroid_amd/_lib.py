@@ -80,6 +80,12 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_int32],
     ),
+    "fbr_model_set_capsules": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip]),
+    "fbr_candidate_capsule_distances": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -150,7 +156,7 @@ _SIGNATURES = {
 # Options every new Engine starts with (``fbr_model_set_option``, include/fbr.h lists the keys), on top of the library's defaults and below
 # the ``options`` argument of the constructor.  A plain Python dict: the library itself never reads the process environment.  The test
 # suite uses it to run whole modules with the column reductions forced / switched off (tests/conftest.py: reduction_mode).
-FBR_VERSION = 103  # include/fbr.h FBR_VERSION: the C-ABI these ctypes signatures describe
+FBR_VERSION = 104  # include/fbr.h FBR_VERSION: the C-ABI these ctypes signatures describe
 DEFAULT_OPTIONS: dict = {}
 
 
@@ -431,6 +437,61 @@ class Engine:
             out[name] = val[:, k]
             out[name + "_idx"] = idx[:, k]
         return out
+
+    def set_capsules(self, capsules, pairs) -> None:
+        """Capsule collision set of the handle (``fbr_model_set_capsules``).  ``capsules``: a sequence of ``(link, p0, p1, radius)`` -- link
+        an index into the topology's links or a link name, p0 / p1 in that link's frame -- or of objects with ``link`` / ``link_name``,
+        ``p0_local``, ``p1_local``, ``radius`` (``flobaroid_amd.collision.Capsule``); ``pairs``: (P, 2) indices into that sequence.  Replaces
+        the set in place; an empty ``capsules`` clears it."""
+        names = list(self.topo.link_names)
+        link, seg, rad = [], [], []
+        for c in capsules:
+            if hasattr(c, "radius"):
+                l, p0, p1, r = (c.link if getattr(c, "link", None) is not None else c.link_name), c.p0_local, c.p1_local, c.radius
+            else:
+                l, p0, p1, r = c
+            link.append(names.index(l) if isinstance(l, str) else int(l))
+            seg.append(np.concatenate([np.asarray(p0, dtype=np.float64).reshape(3), np.asarray(p1, dtype=np.float64).reshape(3)]))
+            rad.append(float(r))
+        link = np.ascontiguousarray(link, dtype=np.int32)
+        seg = np.ascontiguousarray(np.array(seg, dtype=np.float64).reshape(-1, 6))
+        rad = np.ascontiguousarray(rad, dtype=np.float64)
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        _check(self._lib.fbr_model_set_capsules(self._h, int(link.size), link.ctypes.data_as(_ip), seg.ctypes.data_as(_dp), rad.ctypes.data_as(_dp),
+                                                int(pr.shape[0]), pr.ctypes.data_as(_ip)), "fbr_model_set_capsules")
+        self.num_capsules, self.num_capsule_pairs = int(link.size), int(pr.shape[0])
+
+    def candidate_capsule_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:
+        """Per candidate and capsule pair, the smallest capsule distance over every ``step``-th sample of the candidate and the sample index
+        (inside the candidate) where it is reached (``fbr_candidate_capsule_distances``): ``{"dist": (C, P), "idx": (C, P) int64}``; 1e10 / -1
+        for a pair no sample won (NaN poses).  ``st`` needs ``q`` and, with a floating base, ``rpy`` only; ``base_pos`` (S, 3) places the
+        base (None: the origin).  Torch tensors when the states are on the device, NumPy arrays otherwise (``device_out`` overrides)."""
+        q = _Ref(st["q"], None, "q")
+        if len(q.obj.shape) != 2 or q.obj.shape[1] != self.n:
+            raise ValueError(f"q: expected (S, {self.n}), got {tuple(q.obj.shape)}")
+        S = int(q.obj.shape[0])
+        rpy = _Ref(st.get("rpy", st.get("base_rpy")), (S, 3), "base_rpy") if self.floating else _Ref(None)
+        bp = _Ref(base_pos, (S, 3), "base_pos") if self.floating else _Ref(None)
+        mem = _same_space([q, rpy, bp])
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        s = fbr_states()
+        s.num_samples, s.mem, s.q, s.base_rpy = S, mem, q.ptr, rpy.ptr
+        C, P = int(ncand), int(getattr(self, "num_capsule_pairs", 0))
+        shape = (max(C, 1), P)
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        if out_mem == FBR_DEVICE:
+            import torch
+
+            val = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
+            idx = torch.empty(shape, dtype=torch.int64, device=f"cuda:{self.device}")
+            pv, pi = val.data_ptr(), idx.data_ptr()
+        else:
+            val, idx = np.empty(shape), np.empty(shape, dtype=np.int64)
+            pv, pi = val.ctypes.data, idx.ctypes.data
+        _check(self._lib.fbr_candidate_capsule_distances(self._h, ctypes.byref(s), bp.ptr, C, int(step), pv, pi, out_mem),
+               "fbr_candidate_capsule_distances")
+        return {"dist": val, "idx": idx}
 
     def predict(self, st: dict, x, out=None):
         s, keep, S, mem = self._states(st)

@@ -9,7 +9,8 @@ thread_local std::string g_fbr_err;
 
 // ------------------------------------------------------------------------------------------------
 // 101 (round 6): fbr_topology.joint_type, the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info (both added in
-// round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema.
+// round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
+// 104: fbr_model_set_capsules, fbr_candidate_capsule_distances.
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
 
@@ -733,6 +734,191 @@ extern "C" int fbr_candidate_extrema(fbr_model *m, const fbr_states *st, int32_t
     }
     const ExtremaReq rq{ncand, val_out, idx_out};
     return run_id(m, st, x_std, num_x, vel_sign, 0, nullptr, out_mem, &rq);
+}
+
+// ---- capsule collision distances (csrc/fbr_capsule.h) --------------------------------------------------------------------------------
+extern "C" int fbr_model_set_capsules(fbr_model *m, int32_t ncaps, const int32_t *link, const double *seg, const double *radius, int32_t npairs,
+                                      const int32_t *pairs)
+{
+    if (!m) {
+        set_err("null model");
+        return FBR_E_INVALID;
+    }
+    if (ncaps < 0 || npairs < 0 || ncaps > FBR_MAX_CAPSULES || npairs > FBR_MAX_CAPSULE_PAIRS) {
+        set_err("capsule set: at most " + std::to_string(FBR_MAX_CAPSULES) + " capsules and " + std::to_string(FBR_MAX_CAPSULE_PAIRS) + " pairs");
+        return FBR_E_INVALID;
+    }
+    if ((ncaps > 0 && (!link || !seg || !radius)) || (npairs > 0 && !pairs)) {
+        set_err("capsule set: null array");
+        return FBR_E_INVALID;
+    }
+    const FbrHostModel &hm = m->hm;
+    for (int c = 0; c < ncaps; c++) {
+        if (link[c] < 0 || link[c] >= hm.L) {
+            set_err("capsule " + std::to_string(c) + ": link index out of range");
+            return FBR_E_INVALID;
+        }
+        if (!(radius[c] >= 0.0) || !std::isfinite(radius[c])) {
+            set_err("capsule " + std::to_string(c) + ": the radius must be finite and not negative");
+            return FBR_E_INVALID;
+        }
+        for (int i = 0; i < 6; i++)
+            if (!std::isfinite(seg[6 * c + i])) {
+                set_err("capsule " + std::to_string(c) + ": non-finite endpoint");
+                return FBR_E_INVALID;
+            }
+    }
+    for (int k = 0; k < npairs; k++) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a < 0 || a >= ncaps || b < 0 || b >= ncaps || a == b) {
+            set_err("capsule pair " + std::to_string(k) + ": capsule index out of range, or a capsule paired with itself");
+            return FBR_E_INVALID;
+        }
+    }
+    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->caps = DevCapsules{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (ncaps == 0) return FBR_OK;
+    FbrKinIdProgram prog;
+    try {
+        fbr_kinid_build(hm, prog);
+    } catch (const std::exception &e) {
+        set_err(e.what());
+        return FBR_E_INVALID;
+    }
+    // capsules sorted by the step of their link (stable: the caller's order within a link)
+    std::vector<int> stepof(hm.L, 0), capbeg(prog.nsteps + 1, 0), capid(ncaps);
+    for (int k = 0; k < prog.nsteps; k++) stepof[prog.steps[(size_t)k * FBR_KINID_STEP]] = k;
+    for (int c = 0; c < ncaps; c++) capbeg[stepof[link[c]] + 1]++;
+    for (int k = 0; k < prog.nsteps; k++) capbeg[k + 1] += capbeg[k];
+    std::vector<int> fill(capbeg.begin(), capbeg.end() - 1);
+    std::vector<double> sseg((size_t)ncaps * 6);
+    for (int c = 0; c < ncaps; c++) {
+        const int slot = fill[stepof[link[c]]]++;
+        capid[slot] = c;
+        for (int i = 0; i < 6; i++) sseg[(size_t)slot * 6 + i] = seg[6 * c + i];
+    }
+    // one allocation: seg | radius | steps | capbeg | capid | pairs  (doubles first: every table keeps its alignment)
+    const size_t nd = (size_t)ncaps * 7, ni = prog.steps.size() + capbeg.size() + (size_t)ncaps + 1 + 2 * (size_t)std::max(npairs, 1);  // (+ 1: the padding in front of the pairs)
+    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int));
+    double *hd = (double *)host.data();
+    std::copy(sseg.begin(), sseg.end(), hd);
+    std::copy(radius, radius + ncaps, hd + (size_t)ncaps * 6);
+    int *hi = (int *)(hd + nd), *hsteps = hi, *hcapbeg = hsteps + prog.steps.size(), *hcapid = hcapbeg + capbeg.size();
+    int *hpairs = hcapid + ncaps + ((prog.steps.size() + capbeg.size() + (size_t)ncaps) & 1);  // (int2: 8-byte aligned)
+    std::copy(prog.steps.begin(), prog.steps.end(), hsteps);
+    std::copy(capbeg.begin(), capbeg.end(), hcapbeg);
+    std::copy(capid.begin(), capid.end(), hcapid);
+    std::copy(pairs, pairs + 2 * (size_t)npairs, hpairs);
+    if (int rc = m->cap_tab.ensure(host.size() + 8)) return rc;
+    HIPCHK(hipMemcpy(m->cap_tab.p, host.data(), host.size(), hipMemcpyHostToDevice));
+    const char *base = (const char *)m->cap_tab.p;
+    DevCapsules dc;
+    dc.nsteps = prog.nsteps;
+    dc.nslots = prog.nslots;
+    dc.ncaps = ncaps;
+    dc.npairs = npairs;
+    dc.seg = (const double *)base;
+    dc.radius = dc.seg + (size_t)ncaps * 6;
+    dc.steps = (const int *)(base + ((const char *)hsteps - host.data()));
+    dc.capbeg = (const int *)(base + ((const char *)hcapbeg - host.data()));
+    dc.capid = (const int *)(base + ((const char *)hcapid - host.data()));
+    dc.pairs = (const int2 *)(base + ((const char *)hpairs - host.data()));
+    m->caps = dc;
+    return FBR_OK;
+}
+
+extern "C" int fbr_candidate_capsule_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step,
+                                               double *dist_out, int64_t *idx_out, int32_t out_mem)
+{
+    if (!m || !st || !dist_out || !idx_out) {
+        set_err("null model / states / dist_out / idx_out");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q) {
+        set_err("bad fbr_states header, or q is NULL");
+        return FBR_E_INVALID;
+    }
+    if (m->caps.ncaps == 0 || m->caps.npairs == 0) {
+        set_err("no capsule set with at least one pair (fbr_model_set_capsules)");
+        return FBR_E_INVALID;
+    }
+    if (ncand < 1 || step < 1) {
+        set_err("ncand and step must be at least 1");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
+        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;
+    const FbrHostModel &hm = m->hm;
+    const DevCapsules &cp = m->caps;
+    const long S = st->num_samples, C = ncand, P = cp.npairs;
+    const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr;
+    int rc;
+    if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
+    if (hm.floating && st->base_rpy) {
+        if ((rc = stage_one(m, m->st_rpy, st->base_rpy, (size_t)S * 3, st->mem, &drpy))) return rc;
+        if ((rc = stage_one(m, m->st_bpos, base_pos, (size_t)S * 3, st->mem, &dbp))) return rc;
+    }
+    DevCapTiles tl;
+    tl.T = S / C;
+    tl.step = step;
+    tl.Tc = (tl.T + step - 1) / step;
+    tl.tiles = (tl.Tc + 63) / 64;
+    tl.nblk = C * tl.tiles;
+    // blocks per launch: the endpoints of the blocks in flight stay below 256 MB, their partials below 64 MB
+    const size_t ep_blk = (size_t)cp.ncaps * 6 * 64 * sizeof(double), part_blk = (size_t)P * (sizeof(double) + sizeof(long));
+    long ch = (long)std::min((size_t)(256u << 20) / ep_blk, (size_t)(64u << 20) / part_blk);
+    if (m->opt.chunk_samples >= 1) ch = (long)m->opt.chunk_samples / 64;  // (tests: the multi-launch path at small sizes)
+    ch = std::max(1L, std::min(ch, tl.nblk));
+    if ((rc = m->cap_ep.ensure((size_t)ch * ep_blk))) return rc;
+    if ((rc = m->cap_part.ensure((size_t)ch * part_blk))) return rc;
+    double *pval = m->cap_part.as<double>();
+    long *pidx = (long *)(pval + (size_t)ch * P);
+    const size_t cnt = (size_t)C * P;
+    double *val = dist_out;
+    long *idx = (long *)idx_out;
+    if (out_mem == FBR_HOST) {
+        if ((rc = m->cap_out.ensure(cnt * (sizeof(double) + sizeof(long))))) return rc;
+        val = m->cap_out.as<double>();
+        idx = (long *)(val + cnt);
+    }
+    const int ldn = std::max(hm.n, 1) | 1;
+    const size_t lds_want = (size_t)64 * ldn * sizeof(double);
+    const int stage = lds_want <= (size_t)64 * 1024;  // up to 127 DOF; beyond, the lanes read their rows from memory
+    const size_t lds = stage ? lds_want : 0;
+    const int pgrid = (int)std::min<long>(ch, (long)m->num_cus * 8);
+    if ((rc = m->cap_scratch.ensure((size_t)pgrid * std::max(cp.nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
+    const long nbatch = (P + FBR_CAPSULE_BATCH - 1) / FBR_CAPSULE_BATCH;
+    if (lds) HIPCHK(hipFuncSetAttribute((const void *)fbr_capsule_points_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (long b0 = 0; b0 < tl.nblk; b0 += ch) {
+        const long nb = std::min(ch, tl.nblk - b0);
+        {
+            ProfScope ps(m, FBR_PROF_KIN);
+            hipLaunchKernelGGL(fbr_capsule_points_kernel, dim3((unsigned)std::min<long>(nb, pgrid)), dim3(64), lds, m->stream, m->dm, cp, tl, b0, nb, stage,
+                               ldn, dq, drpy, dbp, m->cap_ep.as<double>(), m->cap_scratch.as<double>());
+            HIPCHK(hipGetLastError());
+        }
+        {
+            ProfScope ps(m, FBR_PROF_REDUCE);
+            hipLaunchKernelGGL(fbr_capsule_pairs_kernel, dim3((unsigned)std::min<long>(nb * nbatch, (long)m->num_cus * 16)), dim3(64), 0, m->stream, cp, tl,
+                               b0, nb, (const double *)m->cap_ep.as<double>(), pval, pidx);
+            HIPCHK(hipGetLastError());
+            const long cands = (b0 + nb - 1) / tl.tiles - b0 / tl.tiles + 1;
+            hipLaunchKernelGGL(fbr_capsule_finish_kernel, dim3((unsigned)((cands * P + 255) / 256)), dim3(256), 0, m->stream, tl, (int)P, b0, nb,
+                               (const double *)pval, (const long *)pidx, val, idx);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (out_mem == FBR_HOST) {
+        HIPCHK(hipMemcpyAsync(dist_out, val, cnt * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(idx_out, idx, cnt * sizeof(long), hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    prof_collect(m);
+    return FBR_OK;
 }
 
 extern "C" int fbr_predict(fbr_model *m, const fbr_states *st, const double *x, double *tau_out, int32_t out_mem)

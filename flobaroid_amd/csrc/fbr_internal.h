@@ -19,6 +19,7 @@
 #include "fbr_options.h"
 #include "fbr_kernels.h"
 #include "fbr_kinid.h"
+#include "fbr_capsule.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 
@@ -148,6 +149,10 @@ struct fbr_model {
     const int *kinid_steps = nullptr, *kinid_endflush = nullptr;
     DevBuf kinid_scratch;     // branch-point records of the waves in flight
     DevBuf ext_part, ext_out; // candidate extrema: per-tile (value, index) partials; the final values and indices of a host-memory call
+    // capsule collision set (fbr_model_set_capsules; csrc/fbr_capsule.h): its tables in one allocation, the world endpoints and the per-block
+    // partials of the blocks in flight, the branch-point poses of the waves in flight, the results of a host-memory call
+    DevCapsules caps = {0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf cap_tab, cap_ep, cap_part, cap_scratch, cap_out, st_bpos;
     DevBuf fd_tab, fd_part;   // sub-tree column lists of every joint [n + 1 | entries] (built on first use), baseline partial sums [S][n]
     int fd_tab_entries = -1;
     FbrTsqrWork tsqr;

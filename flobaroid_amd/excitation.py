@@ -6,8 +6,10 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 
 * ``candidate_dopt``      -- D-optimality of many candidate trajectories from ``Engine.gram_grouped``;
 * ``dopt_sensitivities``  -- the worker's ``sens_q, sens_dq, sens_ddq`` from ``Engine.fd_scores``;
-* ``candidate_objectives`` -- the whole ``objectiveFunc`` (f, g, soft costs; no collision constraints) of many candidates from
-  ``Engine.gram_grouped`` + ``Engine.candidate_extrema``: only per-candidate numbers reach the host.
+* ``candidate_objectives`` -- the whole ``objectiveFunc`` (f, g, soft costs) of many candidates from ``Engine.gram_grouped`` +
+  ``Engine.candidate_extrema``: only per-candidate numbers reach the host;
+* ``candidate_collision_constraints`` -- its collision block in capsule mode (``collisionMode: "capsule"``, robot links) from
+  ``Engine.candidate_capsule_distances``; ``candidate_objectives(..., collision=...)`` appends it to ``g``.
 """
 from __future__ import annotations
 
@@ -130,15 +132,20 @@ def candidate_dopt_from_coefficients(engine, candidates: list, T: int, freq: flo
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-# The optimiser's objective per candidate (trajectoryOptimizer.py objectiveFunc, lines 259-475 without the collision block): everything it
-# needs of the samples is the per-joint extrema of q, |dq| and |tau| (Engine.candidate_extrema), the rest is per-candidate host arithmetic.
+# The optimiser's objective per candidate (trajectoryOptimizer.py objectiveFunc, lines 259-475): everything it needs of the samples is the
+# per-joint extrema of q, |dq| and |tau| (Engine.candidate_extrema) and, for the collision block in capsule mode, the per-pair minima of the
+# capsule distances (Engine.candidate_capsule_distances); the rest is per-candidate host arithmetic.
 # ------------------------------------------------------------------------------------------------------------------------------------
-def constraint_layout(n: int, min_velocity_constraint: bool) -> dict:
+def constraint_layout(n: int, min_velocity_constraint: bool, num_collision_pairs: int | None = None) -> dict:
     """Offsets of the blocks of ``g`` (each n long): lower position, upper position, peak velocity, peak torque, [minimum velocity,]
-    minimum torque utilisation -- the reference's order without its collision block; ``len`` = 5 n, or 6 n with the minimum velocity."""
+    minimum torque utilisation -- the reference's order; ``len`` = 5 n, or 6 n with the minimum velocity.  With ``num_collision_pairs``
+    the collision block (one entry per pair: the smallest distance, positive = free) follows as ``collision`` and ``len`` grows by it."""
     names = ["pos_lower", "pos_upper", "vel", "torque"] + (["min_vel"] if min_velocity_constraint else []) + ["min_torque_util"]
     lay = {k: i * n for i, k in enumerate(names)}
     lay["len"] = len(names) * n
+    if num_collision_pairs is not None:
+        lay["collision"] = lay["len"]
+        lay["len"] += int(num_collision_pairs)
     return lay
 
 
@@ -154,7 +161,7 @@ def _host(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
 
 
-def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, joint_names, config: dict, dopt_scale=None) -> dict:
+def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, joint_names, config: dict, dopt_scale=None, collision=None) -> dict:
     """``objectiveFunc``'s f, g and soft costs of C candidates from their D-optimality terms and the extrema of ``Engine.candidate_extrema``
     (values and indices, (C, n) each) -- pure host arithmetic.
 
@@ -167,7 +174,11 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
     dopt_scale), ``f1`` (torque balance), ``f2`` (position range, already x10 as in the reference), ``f3`` (torque magnitude), ``f4``
     (velocity magnitude), ``n_observable``, ``failed`` (non-finite D-optimality: f starts from 100), ``dopt_scale`` and ``ag_cache`` -- the
     per-candidate entries of the reference's ``_ag_cache`` (``torque_absmax_idx``, ``pos_min_idx``, ``pos_max_idx``, ``vel_absmax_idx``,
-    ``vel_absmax``, ``utilization``, ``util_mean``, ``util_std``, ``f1``, ``f3``, ``pos_range_available``)."""
+    ``vel_absmax``, ``utilization``, ``util_mean``, ``util_std``, ``f1``, ``f3``, ``pos_range_available``).
+
+    ``collision``: the dict ``candidate_collision_constraints`` returns.  Its ``g`` (C, P) is appended after ``min_torque_util`` (layout key
+    ``collision``), and ``ag_cache`` gains ``collision_argmin_idx`` (C, P): per pair the main-trajectory sample of its smallest distance
+    (-1: none), what the reference's ``_ag_collision_cache`` holds.  None: everything is what it is without the argument."""
     _check_config(config)
     nld = np.asarray(neg_log_det, dtype=np.float64).reshape(-1)
     C = nld.shape[0]
@@ -193,7 +204,8 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
             lo_c[i], hi_c[i] = np.deg2rad(pair[0]), np.deg2rad(pair[1])
 
     minvel = bool(config.get("minVelocityConstraint", False))
-    lay = constraint_layout(n, minvel)
+    coll_g = None if collision is None else np.asarray(collision["g"], dtype=np.float64).reshape(C, -1)
+    lay = constraint_layout(n, minvel, None if coll_g is None else coll_g.shape[1])
     g = np.empty((C, lay["len"]))
     g[:, lay["pos_lower"]:lay["pos_lower"] + n] = lo_c - pos_min
     g[:, lay["pos_upper"]:lay["pos_upper"] + n] = pos_max - hi_c
@@ -202,6 +214,8 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
     if minvel:
         g[:, lay["min_vel"]:lay["min_vel"] + n] = vlim * config["minVelocityPercentage"] - vel_absmax
     g[:, lay["min_torque_util"]:lay["min_torque_util"] + n] = tlim * config.get("minTorqueUtilization", 0.02) - torque_absmax
+    if coll_g is not None:
+        g[:, lay["collision"]:] = coll_g
     g[np.isnan(g)] = 10.0
 
     dopt = nld * dopt_scale
@@ -222,24 +236,114 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
     ag = {"torque_absmax_idx": e["tau_absmax_idx"], "pos_min_idx": e["q_min_idx"], "pos_max_idx": e["q_max_idx"], "vel_absmax_idx": e["dq_absmax_idx"],
           "vel_absmax": vel_absmax, "utilization": utilization, "util_mean": util_mean, "util_std": util_std, "f1": f1, "f3": f3,
           "pos_range_available": pos_range_available}
+    if collision is not None:
+        ag["collision_argmin_idx"] = np.asarray(collision["argmin"], dtype=np.int64).reshape(C, -1)
     return {"f": f, "g": g, "dopt": dopt, "f1": f1, "f2": f2, "f3": f3, "f4": f4, "n_observable": np.asarray(n_observable).reshape(-1),
             "failed": failed, "dopt_scale": dopt_scale, "ag_cache": ag}
 
 
+def candidate_collision_constraints(engine, states: dict, ncand: int, config: dict, margins=None) -> dict:
+    """The collision block of ``objectiveFunc`` in capsule mode for ``ncand`` equal candidates stacked in ``states``, for the capsule set of
+    the engine (``Engine.set_capsules``; pairs of robot links): per candidate and pair the smallest ``distance - margin`` over
+
+    * every ``collisionCheckStep``-th (3) sample of the main trajectory -- one ``Engine.candidate_capsule_distances`` over ``states``
+      (``q``, with a floating base ``rpy`` and optionally ``base_position`` (S, 3)), and
+    * with ``transitionDuration`` (3.0) > 0, the minimum-jerk ramps between the zero position and the candidate's first and last sample:
+      ``transitionCollisionSamples`` (10) configurations ``s(tau) q`` each, every one at the base poses of six evenly spaced samples and of
+      the sample with the largest |rpy| sum -- a second, small device call on states built from the 2 C boundary rows.
+
+    Merged in the reference's order (trajectory first, strict <): a transition configuration wins only when strictly closer.  Returns ``g``
+    (C, P) (1e10 where no configuration won), ``idx`` (C, P): the winning sample, or the reference's negative count -1, -2, ... of a
+    transition configuration (-1 also stands for "none won": then g is 1e10), ``argmin`` (C, P): the winning main-trajectory sample (-1:
+    none), ``dist`` (C, P): the raw main-trajectory minima.  ``margins`` (P,): per-pair clearance subtracted from the distances
+    (``_collision_pair_margins``; None: 0).  Not covered: the mesh modes, world links, the distance gradient."""
+    _check_config(config)
+    C = int(ncand)
+    q = states["q"]
+    S, n = int(q.shape[0]), int(q.shape[1])
+    T = S // max(C, 1)
+    rpy = states.get("rpy", states.get("base_rpy")) if engine.floating else None
+    bpos = states.get("base_position") if engine.floating else None
+    main = engine.candidate_capsule_distances(states, C, int(config.get("collisionCheckStep", 3)), base_pos=bpos)
+    dist, idx = _host(main["dist"]), _host(main["idx"]).astype(np.int64)
+    P = dist.shape[1]
+    m = np.zeros(P) if margins is None else np.asarray(margins, dtype=np.float64).reshape(P)
+    g = np.where(idx >= 0, dist - m, 1e10)
+    out_idx = idx.copy()
+    ns = int(config.get("transitionCollisionSamples", 10))
+    if config.get("transitionDuration", 3.0) > 0 and ns > 0 and S == C * T and T > 0:
+        torch_in = hasattr(q, "cpu")
+        if torch_in:
+            import torch
+
+            dev = lambda a, dt=None: torch.as_tensor(a, dtype=dt, device=q.device)  # noqa: E731
+            expand = lambda a, shape: a.expand(*shape).reshape(-1, shape[-1]).contiguous()  # noqa: E731
+        else:
+            dev = lambda a, dt=None: np.asarray(a)  # noqa: E731
+            expand = lambda a, shape: np.ascontiguousarray(np.broadcast_to(a, shape).reshape(-1, shape[-1]))  # noqa: E731
+        # base poses of the transition configurations: six evenly spaced samples and the extreme swing, in sample order.  The reference
+        # drops repeated samples; here all seven are evaluated (equal candidates) and a repeated pose, whose distances are the same,
+        # never wins against its first occurrence: `rank` is a pose's position among the distinct ones.
+        lin = np.linspace(0, T - 1, 6).astype(int)
+        if rpy is not None:
+            r3 = rpy.reshape(C, T, 3)
+            ext = _host(abs(r3).sum(-1).argmax(1)).astype(int)
+            poses = np.sort(np.concatenate([np.tile(lin, (C, 1)), ext[:, None]], axis=1), axis=1)
+        else:
+            poses = np.sort(np.concatenate([lin, [0]]))[None].repeat(C, axis=0)
+        rank = np.cumsum(np.concatenate([np.zeros((C, 1), dtype=int), (poses[:, 1:] != poses[:, :-1]).astype(int)], axis=1), axis=1)
+        nuniq = rank[:, -1] + 1
+        npose = poses.shape[1] if rpy is not None else 1  # (fixed base: every pose gives the same distances, one is evaluated)
+        tau = (np.arange(ns) + 1) / (ns + 1)
+        sv = 10.0 * tau**3 - 15.0 * tau**4 + 6.0 * tau**5
+        qb = q.reshape(C, T, n)[:, [0, T - 1]]  # (C, 2, n)
+        qt = qb[:, :, None, None, :] * dev(sv, qb.dtype if torch_in else None)[None, None, :, None, None]
+        shape = (C, 2, ns, npose)
+        st_tr = {"q": expand(qt, shape + (n,))}
+        bp_tr = None
+        if rpy is not None:
+            ci, pi = dev(np.arange(C)[:, None]), dev(poses)
+            st_tr["rpy"] = expand(r3[ci, pi][:, None, None], shape + (3,))
+            if bpos is not None:
+                bp_tr = expand(bpos.reshape(C, T, 3)[ci, pi][:, None, None], shape + (3,))
+        tr = engine.candidate_capsule_distances(st_tr, C, 1, base_pos=bp_tr)
+        dt, it = _host(tr["dist"]), _host(tr["idx"]).astype(np.int64)
+        kk = np.maximum(it, 0)
+        ref_idx = -((kk // npose) * nuniq[:, None] + np.take_along_axis(rank, kk % npose, axis=1) + 1)
+        gt = dt - m
+        take = (it >= 0) & (gt < g)
+        g = np.where(take, gt, g)
+        out_idx = np.where(take, ref_idx, out_idx)
+    return {"g": g, "idx": out_idx, "argmin": idx, "dist": dist}
+
+
+def _collision_block(engine, states, ncand, config, collision):
+    """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins`` (``flobaroid_amd.collision.collision_set``)"""
+    if collision is None:
+        return None
+    if config.get("collisionMode", "capsule") != "capsule":
+        raise ValueError("collision constraints on the device cover collisionMode 'capsule' only (no mesh code: DESIGN 9)")
+    engine.set_capsules(collision["capsules"], collision["pairs"])
+    return candidate_collision_constraints(engine, states, ncand, config, margins=collision.get("margins"))
+
+
 def candidate_objectives(engine, states: dict, ncand: int, independent_cols, x_std, limits: dict, joint_names, config: dict, dopt_scale=None,
-                         YtY_prior=None, vel_sign=None) -> dict:
+                         YtY_prior=None, vel_sign=None, collision=None) -> dict:
     """``objectives_from_extrema`` of ``ncand`` equal candidates stacked in ``states``: one ``gram_grouped`` (D-optimality, lambda_max,
     n_observable per candidate with ``doptRegularization``, default 1e-4) and one ``candidate_extrema`` (the a-priori torques of ``x_std``
-    reduced on the device) over the same states.  ``vel_sign``: Stribeck friction, as for ``Engine.inverse_dynamics``."""
+    reduced on the device) over the same states.  ``vel_sign``: Stribeck friction, as for ``Engine.inverse_dynamics``.  ``collision``
+    (``flobaroid_amd.collision.collision_set``: capsules, pairs, margins): the collision block of capsule mode is appended to ``g``
+    (``candidate_collision_constraints``); None: no collision block, every array as without the argument."""
     _check_config(config)
     G = _host(engine.gram_grouped(states, int(ncand)))
     nld, _, nobs = est.d_optimality_batch_terms(G, independent_cols, config.get("doptRegularization", 1e-4), YtY_prior)
     ext = engine.candidate_extrema(states, int(ncand), x_std, vel_sign=vel_sign)
-    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale)
+    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale,
+                                   collision=_collision_block(engine, states, ncand, config, collision))
 
 
 def candidate_objectives_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict,
-                                           joint_names, config: dict, dopt_scale=None, YtY_prior=None) -> dict:
+                                           joint_names, config: dict, dopt_scale=None, YtY_prior=None, collision=None) -> dict:
     """``candidate_objectives`` from Fourier coefficients (``fourier_coefficients`` dicts): states generated on the device
     (``candidate_states``), the Coulomb column tanh(dq / ``frictionSignThreshold``) as ``candidate_dopt_from_coefficients`` sets it and
     ``vel_sign`` = dq under Stribeck friction -- only per-candidate arrays come back to the host.  ``model_or_x_std``: the a-priori standard
@@ -253,4 +357,4 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
         st["sign"] = torch.tanh(st["dq"] / float(config.get("frictionSignThreshold", 0.02)))
     vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
     return candidate_objectives(engine, st, len(candidates), independent_cols, x_std, limits, joint_names, config, dopt_scale=dopt_scale,
-                                YtY_prior=YtY_prior, vel_sign=vel_sign)
+                                YtY_prior=YtY_prior, vel_sign=vel_sign, collision=collision)

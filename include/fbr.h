@@ -84,8 +84,8 @@ typedef struct {
 /* Version of THIS header.  fbr_version() returns the value the loaded library was built with: a caller compares the two before its first
  * call (flobaroid_amd/_lib.py load_library refuses a mismatch), because the C-ABI has grown in place -- 101: fbr_topology.joint_type,
  * the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info, option "fused_id"; 102: fbr_gram_lane_info, options
- * "gram_lane" / "gram_force_tiles". */
-#define FBR_VERSION 103
+ * "gram_lane" / "gram_force_tiles"; 103: fbr_candidate_extrema; 104: fbr_model_set_capsules, fbr_candidate_capsule_distances. */
+#define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
 const char *fbr_last_error(void);  /* thread-local message of the last failing call */
@@ -129,6 +129,43 @@ int fbr_inverse_dynamics_batch(fbr_model *m, const fbr_states *st, const double 
  */
 int fbr_candidate_extrema(fbr_model *m, const fbr_states *st, int32_t ncand, const double *x_std, int32_t num_x,
                           const double *vel_sign, double *val_out, int64_t *idx_out, int32_t out_mem);
+
+/*
+ * Capsule collision geometry of the robot, for fbr_candidate_capsule_distances: the reference's collisionMode "capsule"
+ * (excitation/capsule.py: a capsule is a segment in a link's frame plus a radius; optimizer.py self._capsules, trajectoryOptimizer.py
+ * self._collision_pairs).  Host arrays, copied:
+ *   link [ncaps]      index of the capsule's link in the topology as the caller serialised it -- the UNMERGED links: a link attached by a
+ *                     fixed joint keeps its own capsule (the column reductions of "link_merge" play no part in this path)
+ *   seg [ncaps][6]    p0 | p1 in that link's frame (p0 == p1: a sphere)
+ *   radius [ncaps]
+ *   pairs [npairs][2] indices into the CAPSULE list (not link indices); the pairs kernel keeps a pair's first capsule in registers while it
+ *                     does not change, so a list sorted by its first entry (the reference's order) is the cheapest
+ * A second call replaces the set; ncaps = 0 clears it.  At most FBR_MAX_CAPSULES capsules and FBR_MAX_CAPSULE_PAIRS pairs (WALK-MAN: 48
+ * links, 1 128 link pairs).  FBR_E_INVALID: more than that, a link or a pair index out of range, a capsule paired with itself, a negative
+ * or non-finite radius, a non-finite endpoint; the set in place before a refused call stays.
+ */
+#define FBR_MAX_CAPSULES 4096
+#define FBR_MAX_CAPSULE_PAIRS 262144
+int fbr_model_set_capsules(fbr_model *m, int32_t ncaps, const int32_t *link, const double *seg, const double *radius, int32_t npairs,
+                           const int32_t *pairs);
+
+/*
+ * Per candidate and capsule pair, the smallest capsule distance over the candidate's checked samples -- the collision block of
+ * objectiveFunc in capsule mode (excitation/trajectoryOptimizer.py "check collision constraints": setCollisionRobotState per checked
+ * sample, capsule_distance per pair, `if d < g[...]`) for the main-trajectory samples, without a pose leaving the device.
+ * The states are ncand equal candidates of T = num_samples / ncand consecutive samples (the layout of fbr_candidate_extrema); only q and,
+ * on a floating-base model, base_rpy are read (dq, ddq and the twists may be NULL).  base_pos [S][3] (st->mem space) or NULL (zero): the
+ * base sits at world_T_base = Transform(RPY(base_rpy).inverse(), base_pos), the reference's setCollisionRobotState; fixed base, or
+ * base_rpy NULL: identity.  The samples t = 0, step, 2 step, ... < T of every candidate are checked (collisionCheckStep).
+ *   dist_out [ncand][npairs]  min over t of |closest_a - closest_b| - r_a - r_b (negative: the capsules overlap)
+ *   idx_out [ncand][npairs]   the sample index inside the candidate where it is reached
+ * The reference's rules: the comparison is a strict < walking t upwards from 1e10, so the first sample wins a tie, a NaN distance never
+ * wins, and a pair for which no sample wins returns 1e10 and index -1.  Margins (a constant per pair) are the caller's.  No atomics: the
+ * same bits on every run.
+ * FBR_E_INVALID: no capsule set or one without pairs, ncand < 1, step < 1, num_samples 0 or not a multiple of ncand.
+ */
+int fbr_candidate_capsule_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step,
+                                    double *dist_out, int64_t *idx_out, int32_t out_mem);
 
 /*
  * tau_out [S][rows] = Y_s . x for an identified-parameter vector x (host, length cols) WITHOUT

@@ -889,7 +889,183 @@ def reference_trajectories(golden):
     np.savez_compressed(os.path.join(golden, "ref_trajectories.npz"), **out)
     print("ref_trajectories.npz:", len(out), "arrays")
 
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Capsule collision mode: the reference's excitation/capsule.py (NumPy only) and the pair list of _buildCollisionPairs
+# ------------------------------------------------------------------------------------------------------------------------------------
+def reference_capsules(golden):
+    """tests/golden/ref_capsules.npz: (i) the capsules the reference's fit_capsules_from_urdf fits to the bundled URDFs that carry primitive
+    collision geometry (mesh paths resolve to None: its own "mesh file not found" path, the trimesh module an empty stand-in); (ii) for a
+    seeded set of capsule pairs and link transforms the outputs (dist, s, t) of its capsule_distance, built so that every branch of
+    segment_segment_distance is taken (asserted below); (iii) the pair lists of its _buildCollisionPairs, run unmodified on an object that
+    carries what the method reads, the neighbours from its URDFHelpers.getNeighbors on a stand-in for the iDynTree model."""
+    import types
+    import xml.etree.ElementTree as ET
+
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    sys.modules.setdefault("trimesh", types.ModuleType("trimesh"))
+    import importlib
+
+    cap = importlib.import_module("excitation.capsule")
+    from flobaroid_amd.topology import Topology
+
+    class Helpers:
+        def parseURDF(self, f):
+            return ET.parse(f)
+
+        def getCollisionMeshPath(self, *a):
+            return None
+
+        def getMeshPath(self, *a):
+            return None
+
+    out = {}
+    urdf_dir = os.path.join(golden, "urdf")
+    for name in ("kuka_lwr4", "threeLinks"):
+        urdf = os.path.join(urdf_dir, name + ".urdf")
+        names = [l.attrib["name"] for l in ET.parse(urdf).findall("link")]
+        for scale, tag in ((1.0, ""), (0.8, "_s08")):
+            caps = cap.fit_capsules_from_urdf(urdf, names, Helpers(), radius_scale=scale)
+            out[f"fit_{name}{tag}_links"] = np.array(list(caps))
+            out[f"fit_{name}{tag}_p0"] = np.array([c.p0_local for c in caps.values()])
+            out[f"fit_{name}{tag}_p1"] = np.array([c.p1_local for c in caps.values()])
+            out[f"fit_{name}{tag}_radius"] = np.array([c.radius for c in caps.values()])
+        print("  fitted", name, len(caps), "capsules")
+
+    # ---- capsule_distance on seeded cases of every branch
+    from scipy.spatial.transform import Rotation
+
+    rng = np.random.default_rng(20261016)
+    kinds = ["both_points", "a_point", "b_point", "parallel", "general"]
+    rec = {k: [] for k in ("p0a", "p1a", "ra", "p0b", "p1b", "rb", "Ra", "pa", "Rb", "pb", "dist", "s", "t", "world")}
+    seen = set()
+    for i in range(400):
+        kind = kinds[i % len(kinds)]
+        Ra, Rb = Rotation.random(2, random_state=int(rng.integers(1 << 30))).as_matrix()
+        pa, pb = rng.standard_normal(3) * 0.4, rng.standard_normal(3) * 0.4
+        p0a, p0b = rng.standard_normal(3) * 0.1, rng.standard_normal(3) * 0.1
+        la, lb = rng.uniform(0.02, 0.5), rng.uniform(0.02, 0.5)
+        ua, ub = rng.standard_normal(3), rng.standard_normal(3)
+        ua, ub = ua / np.linalg.norm(ua), ub / np.linalg.norm(ub)
+        if kind == "parallel":
+            Rb = Ra.copy()
+            ub = ua.copy() if i % 2 else -ua
+        p1a = p0a.copy() if kind in ("both_points", "a_point") else p0a + la * ua
+        p1b = p0b.copy() if kind in ("both_points", "b_point") else p0b + lb * ub
+        if i % 7 == 3:  # near and overlapping pairs as well
+            pb = pa + rng.standard_normal(3) * 0.02
+        ca = cap.Capsule("a", p0a, p1a, float(rng.uniform(0.0, 0.08)))
+        cb = cap.Capsule("b", p0b, p1b, float(rng.uniform(0.0, 0.08)))
+        d, sv, tv, a0, a1, b0, b1 = cap.capsule_distance(ca, cb, Ra, pa, Rb, pb)
+        # which branch this was, from the world end points the reference returned
+        d1, d2, r = a1 - a0, b1 - b0, a0 - b0
+        a, e = float(d1 @ d1), float(d2 @ d2)
+        if a <= 1e-10 and e <= 1e-10:
+            br = "both_points"
+        elif a <= 1e-10:
+            br = "a_point"
+        elif e <= 1e-10:
+            br = "b_point"
+        else:
+            b, f, c = float(d1 @ d2), float(d2 @ r), float(d1 @ r)
+            den = a * e - b * b
+            s0 = float(np.clip((b * f - c * e) / den, 0.0, 1.0)) if den > 1e-10 else 0.0
+            t0 = (b * s0 + f) / e
+            br = ("general" if den > 1e-10 else "parallel") + ("_t_below" if t0 < 0 else "_t_above" if t0 > 1 else "_t_inside")
+        seen.add(br)
+        for k, v in (("p0a", p0a), ("p1a", p1a), ("ra", ca.radius), ("p0b", p0b), ("p1b", p1b), ("rb", cb.radius), ("Ra", Ra), ("pa", pa),
+                     ("Rb", Rb), ("pb", pb), ("dist", d), ("s", sv), ("t", tv), ("world", np.concatenate([a0, a1, b0, b1]))):
+            rec[k].append(v)
+    want = {"both_points", "a_point", "b_point"} | {g + t for g in ("general", "parallel") for t in ("_t_below", "_t_above", "_t_inside")}
+    assert seen == want, sorted(want - seen)
+    assert min(rec["dist"]) < 0 < max(rec["dist"])
+    out.update({"cd_" + k: np.array(v) for k, v in rec.items()})
+    print("  capsule_distance:", len(rec["dist"]), "cases, branches", sorted(seen))
+
+    # ---- _buildCollisionPairs, unmodified, on the bundled topologies
+    to = _import_reference("excitation.trajectoryOptimizer")
+    hp = _import_reference("identification.helpers")
+
+    class FakeJoint:
+        def __init__(self, a, b, fixed):
+            self.a, self.b, self.fixed = a, b, fixed
+
+        def isFixedJoint(self):
+            return self.fixed
+
+        def getFirstAttachedLink(self):
+            return self.a
+
+        def getSecondAttachedLink(self):
+            return self.b
+
+    class FakeModel:  # the calls getNeighbors makes on an iDynTree model, answered from a Topology
+        def __init__(self, t):
+            self.t = t
+            self.joints = [(l, t.parent[l]) for l in range(t.num_links) if t.parent[l] >= 0]  # joint j connects child, parent
+            self.nb = [[] for _ in range(t.num_links)]
+            for j, (c, p) in enumerate(self.joints):
+                self.nb[c].append(types.SimpleNamespace(neighborLink=p, neighborJoint=j))
+                self.nb[p].append(types.SimpleNamespace(neighborLink=c, neighborJoint=j))
+
+        def getNrOfLinks(self):
+            return self.t.num_links
+
+        def getLinkName(self, l):
+            return self.t.link_names[l]
+
+        def getLinkIndex(self, name):
+            return self.t.link_names.index(name)
+
+        def getNrOfNeighbors(self, l):
+            return len(self.nb[l])
+
+        def getNeighbor(self, l, i):
+            return self.nb[l][i]
+
+        def getJointName(self, j):
+            return "joint%d" % j
+
+        def getJointIndex(self, name):
+            return int(name[5:])
+
+        def getJoint(self, j):
+            c, p = self.joints[j]
+            return FakeJoint(p, c, self.t.joint_type[c] == 0)
+
+    import json as _json
+
+    cases = {
+        "kuka_all": ("kuka_lwr4", {}),
+        "kuka_ignore": ("kuka_lwr4", {"ignoreLinksForCollision": ["lwr_3_link"], "ignoreLinkPairsForCollision": [["lwr_base_link", "lwr_6_link"]],
+                                      "collisionMaxKinematicDistance": 4}),
+        "walkman_dist5": ("walkman_apriori", {"collisionMaxKinematicDistance": 5, "ignoreLinksForCollision": ["Waist"],
+                                              "ignoreCollisionBetweenGroups": [[["LFoot", "LLowLeg"], ["RFoot", "RLowLeg", "RHipMot"]]]}),
+        "walkman_all": ("walkman_apriori", {}),
+    }
+    for tag, (robot, cfg) in cases.items():
+        t = Topology.load(os.path.join(REPO, "flobaroid_amd", "robots", robot + ".topology.json"))
+        for key in ("ignoreLinksForCollision", "ignoreLinkPairsForCollision"):
+            cfg.setdefault(key, [])
+        cfg.setdefault("verbose", 0)
+        me = types.SimpleNamespace(model=types.SimpleNamespace(linkNames=list(t.link_names), num_links=t.num_links), world_links=[], config=cfg,
+                                   no_geometry_links=set(), neighbors=hp.URDFHelpers.getNeighbors(FakeModel(t)))
+        to.TrajectoryOptimizer._buildCollisionPairs(me)
+        for a, b in me._collision_pairs:
+            assert a in t.link_names and b in t.link_names
+        out["pairs_" + tag] = np.array(me._collision_pairs).reshape(-1, 2)
+        out["pairs_" + tag + "_config"] = np.array(_json.dumps(cfg))
+        out["pairs_" + tag + "_robot"] = np.array(robot)
+        print("  pairs", tag, len(me._collision_pairs))
+    np.savez_compressed(os.path.join(golden, "ref_capsules.npz"), **out)
+    print("ref_capsules.npz:", len(out), "arrays")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "capsules":
+        reference_capsules(os.path.join(REPO, "tests", "golden"))
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "blocks_wls":
         reference_blocks_and_wls(os.path.join(REPO, "tests", "golden"))
         sys.exit(0)
@@ -906,3 +1082,4 @@ if __name__ == "__main__":
     reference_blocks_and_wls(os.path.join(REPO, "tests", "golden"))
     reference_identification_fb(os.path.join(REPO, "tests", "golden"))
     reference_trajectories(os.path.join(REPO, "tests", "golden"))
+    reference_capsules(os.path.join(REPO, "tests", "golden"))
