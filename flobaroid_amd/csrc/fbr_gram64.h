@@ -12,15 +12,15 @@
 //     round 6's first layout, columns c and c + 8 collided: SQ_LDS_BANK_CONFLICT 42 % of the LDS cycles of the kernel), with the LDS layout
 //     EQUAL to the global one (one contiguous 4 KB DMA per slab);
 //   * producer fbr_kinimg_kernel: one lane per sample, kinematics fused in, the tree cut into parts for the waves of a workgroup
-//     (fbr_kinid.h); every value of a (column, row) goes out as two 256-byte runs per wave;  tau's products with the columns (k <= 1) are
-//     accumulated on the way: one six-term dot product per column against the link's t_base + sum_j S_j t_j, added to the lane's own running
+//     (fbr_kinid.h); every value of a (column, row) goes out as two 256-byte runs per wave;  the rhs columns' products with the columns (k <= 2) are
+//     accumulated on the way: one six-term dot product per (column, rhs column) against the link's t_base + sum_j S_j t_j, added to the lane's own running
 //     sum in HBM (no-return atomics, one adder per address: deterministic);
 //   * consumer fbr_gram64_kernel: one workgroup of 8 waves per CU, the accumulators of the tile pairs in registers for the whole pass;
 //     a stage = (a few consecutive row levels, 32 samples): the slabs of the tiles that have the levels arrive by LDS-DMA into one of two
 //     buffers while the MFMAs of the stage before run; a pair takes part in the levels of its range; 8 MFMAs per pair, level and half block;
 //   * the force rows of the base wrench (levels 0 .. 2) run on tiles of their own that hold the columns with a force only (fbr_gram64_build);
 //   * the main tiles are the pass's own (fbr_gram64_fill_tiles): a column sits in any tile whose joint path contains its own.
-// Conditions (else the first pass runs): k <= 1 rhs column (or none), a tile program in one part; sample groups (fbr_gram_grouped) for k = 0.
+// Conditions (else the first pass runs): k <= 2 rhs columns (or none), a tile program in one part; sample groups (fbr_gram_grouped) for k = 0.
 // Friction columns are tiles whose levels are the rows of their own joints.
 // Inputs resident in HBM or pinned host memory (staged chunk by chunk); row weights; a base-wrench-only row mask runs the base stages only.
 #pragma once
@@ -571,6 +571,24 @@ static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGr
     return fbr_gram64_build_producer(hm, g, pr);
 }
 
+// The producer's rhs moments for k rhs columns (k <= FBR_G64_MAXK): per producer workgroup and lane, running sum r * cols + c =
+// (w Y_c)^T (w rhs_r), then the upper triangle of (w rhs_i)^T (w rhs_j) row by row (k = 2: 00, 01, 11).  k = 1: [cols + 1].
+#define FBR_G64_MAXK 2
+FBR_HD int fbr_gram64_mom_count(int cols, int k) { return k * cols + k * (k + 1) / 2; }
+// the entry (row, col), row <= col, of the (cols + k)^2 Gram that running sum idx belongs to (its mirror image too when row != col)
+FBR_HD void fbr_gram64_mom_target(int cols, int k, int idx, int *row, int *col)
+{
+    if (idx < k * cols) {
+        *row = idx % cols;
+        *col = cols + idx / cols;
+        return;
+    }
+    int e = idx - k * cols, i = 0;
+    while (e >= k - i) e -= k - i, i++;
+    *row = cols + i;
+    *col = cols + i + e;
+}
+
 #if defined(__HIPCC__) && defined(FBR_KERNELS_GRAM)
 struct DevGram64 {
     int NT, nlev, maxact, npieces, nstage;  // NT: main + force tiles
@@ -583,9 +601,10 @@ struct DevGram64 {
 // Producer: the lane writer of fbr_kinid.h with the image addressing of this pass.  Destination word of a (column, row): address of the
 // slab position of column slot c, sample 0 (256-byte aligned) | the slot's swizzle in its low byte; sample slot s of block b goes to
 // + b * blk_doubles + (s >> 5) * 512 + ((s & 31) ^ x).  The positions of the lanes behind the last sample of the last block are cleared by the host before the launch (the Gram
-// kernel runs whole blocks).  mom (k == 1): [workgroup][cols + 1][64] per-lane running sums of (w Y)^T (w tau) per column and (w tau)^T (w tau), added in block order.
+// kernel runs whole blocks).  mom (k >= 1; KR = max(k, 1) rhs columns, row-major [S rows][k]): [workgroup][fbr_gram64_mom_count][64] per-lane running sums of
+// (w Y)^T (w rhs_r) per column and of (w rhs_i)^T (w rhs_j), added in block order.  The KR = 1 instances serve k = 0 and k = 1.
 // ------------------------------------------------------------------------------------------------
-template <int MAXD, bool HASW>
+template <int MAXD, bool HASW, int KR = 1>
 __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void fbr_kinimg_kernel(DevModel m, DevKinId p, DevKinWrite wr, long S, long blk_doubles,
                                                                               const double *__restrict__ q, const double *__restrict__ dq,
                                                                               const double *__restrict__ ddq, const double *__restrict__ bv,
@@ -598,9 +617,9 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
     const int lane = threadIdx.x & 63, part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nth = blockDim.x, tid = threadIdx.x;
     const int n = m.n, ldn = p.ldn, ldw = m.rows | 1, rows = m.rows;
     double *sq = smem, *sdq = sq + 64 * ldn, *sddq = sdq + 64 * ldn, *sw = sddq + 64 * ldn;  // sw [64][ldw] row weights (has_w)
-    double *st = sw + (HASW ? 64 * ldw : 0);                                             // st [64][ldw] w^2 tau (k == 1)
+    double *st = sw + (HASW ? 64 * ldw : 0);                                             // st [KR][64][ldw] w^2 rhs_r (k >= 1)
     double *scr = scratch + ((long)blockIdx.x * wr.nparts + part) * p.nslots * FBR_LINK_REC * 64 + lane;
-    double *mo = mom ? mom + (long)blockIdx.x * (wr.cols + 1) * 64 : nullptr;  // [cols + 1][64 lanes]
+    double *mo = mom ? mom + (long)blockIdx.x * (KR * wr.cols + KR * (KR + 1) / 2) * 64 : nullptr;  // [fbr_gram64_mom_count(cols, KR)][64 lanes]
     // sample groups (fbr_gram_grouped): every group starts a block -- block b = (group b / bpg, block b % bpg of the group)
     const long Sg = wr.group_samples > 0 ? wr.group_samples : S, bpg = (Sg + 63) >> 6;
     const long nblk = (S / Sg) * bpg;
@@ -635,7 +654,12 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
                 for (int i = tid; i < cw; i += nth) {
                     const double wv = HASW ? wts[base * rows + i] : 1.0;
                     if (HASW) sw[wr_ * ldw + wc] = wv;
-                    if (wr.k) st[wr_ * ldw + wc] = wv * wv * rhs[base * rows + i];
+                    if constexpr (KR == 1) {
+                        if (wr.k) st[wr_ * ldw + wc] = wv * wv * rhs[base * rows + i];
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < KR; r++) st[r * 64 * ldw + wr_ * ldw + wc] = wv * wv * rhs[(base * rows + i) * KR + r];
+                    }
                     wr_ += es;
                     wc += ed;
                     if (wc >= rows) {
@@ -689,20 +713,45 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
             for (int pp = 0; pp < 10; pp++) d10[pp] = cdst[((long)part * m.L + l) * FBR_G64_WORDS + pp];
 #pragma unroll
             for (int pp = 0; pp < 4; pp++) dF[pp] = cdst[((long)part * m.L + l) * FBR_G64_WORDS + 10 + pp];  // force-tile words (rows 0 .. flev-1)
-            // tau's side of the moments: sum_r v_r t_r over the rows of one column = w6 . (t_base + sum_j S_j t_j), t = w^2 tau
-            double Ft[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            if (wr.k) {
+            // the rhs side of the moments: sum_r v_r t_r over the rows of one column = w6 . (t_base + sum_j S_j t_j), t = w^2 rhs_r: one
+            // six-vector per rhs column.  F = w^2 rhs_r's, from this lane's staged row at LDS offset ro
+            auto ft_of = [&](int ro, double *F) {
 #pragma unroll
                 for (int i = 0; i < 6; i++)
-                    if (i < m.fb) Ft[i] = myt[i];
+                    if (i < m.fb) F[i] = myt[ro + i];
 #pragma unroll
                 for (int j = 0; j < MAXD; j++)
                     if (j < depth) {
-                        const double tj = myt[m.fb + lvd[j]];
+                        const double tj = myt[ro + m.fb + lvd[j]];
 #pragma unroll
-                        for (int i = 0; i < 6; i++) Ft[i] += Sst[j][i] * tj;
+                        for (int i = 0; i < 6; i++) F[i] += Sst[j][i] * tj;
                     }
+            };
+            double Ft[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if constexpr (KR == 1) {
+                if (wr.k) {
+#pragma unroll
+                    for (int i = 0; i < 6; i++)
+                        if (i < m.fb) Ft[i] = myt[i];
+#pragma unroll
+                    for (int j = 0; j < MAXD; j++)
+                        if (j < depth) {
+                            const double tj = myt[m.fb + lvd[j]];
+#pragma unroll
+                            for (int i = 0; i < 6; i++) Ft[i] += Sst[j][i] * tj;
+                        }
+                }
             }
+            // KR > 1: the instances sit at their register bound with ONE such vector live (two waves per SIMD at 256 registers up to depth
+            // 10), so every column group rebuilds the vector of each rhs column in front of its products instead of keeping KR of them for
+            // the whole link.  The offset is made opaque: the compiler would otherwise hoist the KR vectors out of the groups again.
+            auto ft_group = [&](int r, double *F) {
+                int ro = r * 64 * ldw;
+                asm volatile("" : "+v"(ro));
+#pragma unroll
+                for (int i = 0; i < 6; i++) F[i] = 0.0;
+                ft_of(ro, F);
+            };
             // One value to (column q of the group, level lv).  Scalar base (the column's word, 8192 bytes per level) + this lane's 32-bit
             // offset with the column's swizzle; a column the part does not write (word 0) skips the store only -- the products of a level
             // are computed for the whole group first, branch-free, so that their dependent chains overlap.
@@ -733,10 +782,21 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) store(d10[Q0 + qq], m.fb + j, HASW ? v[qq] * wj : v[qq]);
                     }
-                if (wr.k) {
+                if constexpr (KR == 1) {
+                    if (wr.k) {
 #pragma unroll
-                    for (int qq = 0; qq < NQ; qq++)
-                        if (d10[Q0 + qq]) unsafeAtomicAdd(mo + (long)ccol[10 * l + Q0 + qq] * 64 + lane, fbr_dot6(Ft, wA[qq]));  // this lane's own running sum
+                        for (int qq = 0; qq < NQ; qq++)
+                            if (d10[Q0 + qq]) unsafeAtomicAdd(mo + (long)ccol[10 * l + Q0 + qq] * 64 + lane, fbr_dot6(Ft, wA[qq]));  // this lane's own running sum
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < KR; r++) {
+                        double F[6];
+                        ft_group(r, F);
+#pragma unroll
+                        for (int qq = 0; qq < NQ; qq++)
+                            if (d10[Q0 + qq]) unsafeAtomicAdd(mo + ((long)r * wr.cols + ccol[10 * l + Q0 + qq]) * 64 + lane, fbr_dot6(F, wA[qq]));
+                    }
                 }
             };
             // inertia entries: pure moments -- the force rows of the base wrench are structural zeros of the image (never written), the joint
@@ -762,11 +822,24 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) store(d10[4 + Q0 + qq], m.fb + j, HASW ? v[qq] * wj : v[qq]);
                     }
-                if (wr.k) {
+                if constexpr (KR == 1) {
+                    if (wr.k) {
 #pragma unroll
-                    for (int qq = 0; qq < NQ; qq++)
-                        if (d10[4 + Q0 + qq])
-                            unsafeAtomicAdd(mo + (long)ccol[10 * l + 4 + Q0 + qq] * 64 + lane, Ft[3] * nB[qq][0] + Ft[4] * nB[qq][1] + Ft[5] * nB[qq][2]);
+                        for (int qq = 0; qq < NQ; qq++)
+                            if (d10[4 + Q0 + qq])
+                                unsafeAtomicAdd(mo + (long)ccol[10 * l + 4 + Q0 + qq] * 64 + lane, Ft[3] * nB[qq][0] + Ft[4] * nB[qq][1] + Ft[5] * nB[qq][2]);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < KR; r++) {
+                        double F[6];
+                        ft_group(r, F);
+#pragma unroll
+                        for (int qq = 0; qq < NQ; qq++)
+                            if (d10[4 + Q0 + qq])
+                                unsafeAtomicAdd(mo + ((long)r * wr.cols + ccol[10 * l + 4 + Q0 + qq]) * 64 + lane,
+                                                F[3] * nB[qq][0] + F[4] * nB[qq][1] + F[5] * nB[qq][2]);
+                    }
                 }
             };
             using std::integral_constant;
@@ -792,7 +865,12 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
                         const int c = cfr[pf];
                         const double fv = fbr_friction_value(m.coldesc[c].z, mysdq[dj], sign ? sign[s * n + dj] : 0.0, m.stribeck);
                         store(dfw, m.fb + depth - 1, HASW ? fv * myw[m.fb + dj] : fv);
-                        if (wr.k) unsafeAtomicAdd(mo + (long)c * 64 + lane, fv * myt[m.fb + dj]);
+                        if constexpr (KR == 1) {
+                            if (wr.k) unsafeAtomicAdd(mo + (long)c * 64 + lane, fv * myt[m.fb + dj]);
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < KR; r++) unsafeAtomicAdd(mo + ((long)r * wr.cols + c) * 64 + lane, fv * myt[r * 64 * ldw + m.fb + dj]);
+                        }
                     }
             }
         };
@@ -801,13 +879,31 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
         if (live) {
             fbr_kinid_lane<MAXD, false>(wr.part_nsteps[part], p.maxlvl, p.steps + wr.part_step0[part] * FBR_KINID_STEP, p.endflush, m.floating, m.g, m.fb,
                                         state, basest, save, load, link, emit, consts);
-            if (wr.k && part == wr.nparts - 1) {  // (w tau)^T (w tau)
-                double tt = 0.0;
-                for (int r = 0; r < rows; r++) {
-                    const double wv = HASW ? myw[r] : 1.0, tv = rhs[s * rows + r] * wv;
-                    tt += tv * tv;
+            if constexpr (KR == 1) {
+                if (wr.k && part == wr.nparts - 1) {  // (w tau)^T (w tau)
+                    double tt = 0.0;
+                    for (int r = 0; r < rows; r++) {
+                        const double wv = HASW ? myw[r] : 1.0, tv = rhs[s * rows + r] * wv;
+                        tt += tv * tv;
+                    }
+                    unsafeAtomicAdd(mo + (long)wr.cols * 64 + lane, tt);
                 }
-                unsafeAtomicAdd(mo + (long)wr.cols * 64 + lane, tt);
+            } else if (part == wr.nparts - 1) {  // (w rhs_i)^T (w rhs_j), i <= j, row by row
+                double tt[KR * (KR + 1) / 2];
+#pragma unroll
+                for (int e = 0; e < KR * (KR + 1) / 2; e++) tt[e] = 0.0;
+                for (int r = 0; r < rows; r++) {
+                    const double wv = HASW ? myw[r] : 1.0;
+                    double tv[KR];
+#pragma unroll
+                    for (int i = 0; i < KR; i++) tv[i] = rhs[(s * rows + r) * KR + i] * wv;
+#pragma unroll
+                    for (int i = 0, e = 0; i < KR; i++)
+#pragma unroll
+                        for (int j = i; j < KR; j++, e++) tt[e] += tv[i] * tv[j];
+                }
+#pragma unroll
+                for (int e = 0; e < KR * (KR + 1) / 2; e++) unsafeAtomicAdd(mo + ((long)KR * wr.cols + e) * 64 + lane, tt[e]);
             }
         }
     }
@@ -825,20 +921,21 @@ __global__ __launch_bounds__(256) void fbr_gram64_tail_zero_kernel(double *__res
     }
 }
 
-// rhs moments of a call -> G (k == 1): one workgroup per column sums the per-lane running sums of the producer's workgroups in a fixed order
-__global__ __launch_bounds__(256) void fbr_gram64_mom_reduce_kernel(int P, int nwg, const double *__restrict__ mom, double *__restrict__ G)
+// rhs moments of a call -> G (k rhs columns): one workgroup per running sum (fbr_gram64_mom_count of them) adds up that sum's per-lane
+// copies of the producer's workgroups in a fixed order; where it goes in G: fbr_gram64_mom_target
+__global__ __launch_bounds__(256) void fbr_gram64_mom_reduce_kernel(int P, int k, int nwg, const double *__restrict__ mom, double *__restrict__ G)
 {
     __shared__ double part[256];
-    const int c = blockIdx.x, t = threadIdx.x;
+    const int c = blockIdx.x, t = threadIdx.x, nm = fbr_gram64_mom_count(P, k);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;  // (independent running sums: the loads are far apart)
     int i = t;
     for (; i + 768 < nwg * 64; i += 1024) {
-        s0 += mom[((long)(i >> 6) * (P + 1) + c) * 64 + (i & 63)];
-        s1 += mom[((long)((i + 256) >> 6) * (P + 1) + c) * 64 + ((i + 256) & 63)];
-        s2 += mom[((long)((i + 512) >> 6) * (P + 1) + c) * 64 + ((i + 512) & 63)];
-        s3 += mom[((long)((i + 768) >> 6) * (P + 1) + c) * 64 + ((i + 768) & 63)];
+        s0 += mom[((long)(i >> 6) * nm + c) * 64 + (i & 63)];
+        s1 += mom[((long)((i + 256) >> 6) * nm + c) * 64 + ((i + 256) & 63)];
+        s2 += mom[((long)((i + 512) >> 6) * nm + c) * 64 + ((i + 512) & 63)];
+        s3 += mom[((long)((i + 768) >> 6) * nm + c) * 64 + ((i + 768) & 63)];
     }
-    for (; i < nwg * 64; i += 256) s0 += mom[((long)(i >> 6) * (P + 1) + c) * 64 + (i & 63)];
+    for (; i < nwg * 64; i += 256) s0 += mom[((long)(i >> 6) * nm + c) * 64 + (i & 63)];
     part[t] = (s0 + s1) + (s2 + s3);
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -846,13 +943,11 @@ __global__ __launch_bounds__(256) void fbr_gram64_mom_reduce_kernel(int P, int n
         __syncthreads();
     }
     if (t) return;
-    const int Pa = P + 1;
-    if (c == P) {
-        G[(long)P * Pa + P] += part[0];
-    } else {
-        G[(long)c * Pa + P] += part[0];
-        G[(long)P * Pa + c] += part[0];
-    }
+    const int Pa = P + k;
+    int row, col;
+    fbr_gram64_mom_target(P, k, c, &row, &col);
+    G[(long)row * Pa + col] += part[0];
+    if (row != col) G[(long)col * Pa + row] += part[0];
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -293,6 +293,12 @@ static int gram_via_tsqr(fbr_model *m, const fbr_states *st, const double *rhs, 
 // ------------------------------------------------------------------------------------------------
 // The pass over sample-contiguous images (fbr_gram64.h): tables of a holder, built on first use
 // ------------------------------------------------------------------------------------------------
+// dynamic LDS of fbr_kinimg_kernel: q, dq, ddq [64][n | 1] (kinid_params' ldn), the row weights and k rhs columns [64][rows | 1] each
+static size_t gram64_plds(const FbrHostModel &hm, int k, bool has_w)
+{
+    return ((size_t)3 * 64 * (std::max(hm.n, 1) | 1) + (size_t)((has_w ? 1 : 0) + k) * 64 * (hm.rows | 1)) * sizeof(double);
+}
+
 static int get_gram64(fbr_model *m, GramHolder *h)
 {
     if (h->g64_state) return FBR_OK;
@@ -303,11 +309,10 @@ static int get_gram64(fbr_model *m, GramHolder *h)
         return FBR_OK;
     FbrGram64 &g = h->g64;
     if (fbr_gram64_lds_bytes(g) > FBR_G64_LDS_MAX) return FBR_OK;
-    // the producer stages a block's states, row weights and rhs in the LDS (plds of gram64_pass, its largest form).  A defence only: the
-    // tile program's 60 rows bound it to (3 * 64 * 61 + 2 * 64 * 61) * 8 = 156 160 bytes today; it keeps a model the producer cannot
-    // launch on the per-sample-image pass should either bound move
-    const size_t plds_max = ((size_t)3 * 64 * (std::max(hm.n, 1) | 1) + (size_t)2 * 64 * (hm.rows | 1)) * sizeof(double);
-    if (plds_max > 160 * 1024) return FBR_OK;
+    // the producer stages a block's states, row weights and the holder's rhs columns in the LDS (gram64_plds, with weights).  A model whose
+    // producer could not launch (a CU has 160 KB) stays on the per-sample-image pass: with two rhs columns that is 3 n' + 3 rows' > 320,
+    // e.g. 54 joints on a floating base; with at most one column the tile program's 60 rows bound it to 156 160 bytes
+    if (gram64_plds(hm, h->prog.k, true) > 160 * 1024) return FBR_OK;
     if (!fbr_gram64_build_producer(hm, g, h->g64p)) return FBR_OK;
     std::vector<int> wgbegin{0, 0};  // (filled per launch: one part)
     int rc;
@@ -322,11 +327,11 @@ static int get_gram64(fbr_model *m, GramHolder *h)
 }
 
 // the sample-contiguous pass can serve a call with k rhs columns on this model (its tables built on first use): the option is on, at most
-// one rhs column and that one's products from the producer's moments (h->moments).  What else a call needs is the caller's to check.
+// two rhs columns and their products from the producer's moments (h->moments).  What else a call needs is the caller's to check.
 static int gram64_serves(fbr_model *m, GramHolder *h, int k, bool *serves)
 {
     *serves = false;
-    if (!m->opt.gram_lane || k > 1 || (k == 1 && !h->moments)) return FBR_OK;
+    if (!m->opt.gram_lane || k > FBR_G64_MAXK || (k > 0 && !h->moments)) return FBR_OK;
     if (int rc = get_gram64(m, h)) return rc;
     *serves = h->g64_state == 1;
     return FBR_OK;
@@ -438,7 +443,8 @@ static int gram64_produce(fbr_model *m, GramHolder *h, const Gram64Launch &L, co
 {
     const FbrHostModel &hm = m->hm;
     return kinimg_by_depth(m, [&](auto D) -> int {
-        const auto kernel = kw.has_w ? fbr_kinimg_kernel<D, true> : fbr_kinimg_kernel<D, false>;
+        const auto kernel = k == 2 ? (kw.has_w ? fbr_kinimg_kernel<D, true, 2> : fbr_kinimg_kernel<D, false, 2>)
+                                   : (kw.has_w ? fbr_kinimg_kernel<D, true> : fbr_kinimg_kernel<D, false>);
         HIPCHK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
         hipLaunchKernelGGL(kernel, dim3(pblocks), dim3(64 * h->g64p.nparts), plds, m->stream, m->dm, L.kp, kw, cs, h->g64.blk_doubles, d.q + so * hm.n,
                            d.dq + so * hm.n, d.ddq + so * hm.n, d.bv ? d.bv + so * 6 : nullptr, d.ba ? d.ba + so * 6 : nullptr,
@@ -518,7 +524,7 @@ static int stage_chunk(fbr_model *m, const DevStates &d, const double *rhs, int 
     return FBR_OK;
 }
 
-// One call of the fused pass through fbr_kinimg_kernel / fbr_gram64_kernel (device-resident inputs, one group, k <= 1); everything on the
+// One call of the fused pass through fbr_kinimg_kernel / fbr_gram64_kernel (device-resident inputs, one group, k <= 2); everything on the
 // model's stream.  G has been cleared / holds the running sum.
 // h2d_chunked: d / drhs / dw are PINNED HOST pointers: every chunk is copied into one of two staging buffers on the copy stream while the
 // kernels of the chunk before run (the rate including the transfer of the states).
@@ -541,21 +547,24 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     if (m->opt.chunk_samples >= 1) chb = std::min(gram64_chunk_blocks(g), std::max<long>(1, ((long)m->opt.chunk_samples + 63) / 64));
     chb = std::min(nblocks, chb);
     if (chb < nblocks && chb > m->num_cus) chb = chb / m->num_cus * m->num_cus;
+    // samples per chunk: whole blocks -- or what the option asks for, as the per-sample-image pass chunks it (one staging copy group and
+    // one producer launch per chunk_samples samples whichever pass serves the call); such a chunk ends in a partly filled block
+    long chs = chb * 64;
+    if (m->opt.chunk_samples >= 1) chs = std::min(chs, (long)m->opt.chunk_samples);
     if ((rc = gram64_ensure_images(m, h, chb))) return rc;
     Gram64Launch L;
     if ((rc = gram64_setup(m, h, base_only, &L))) return rc;
-    const int ldw = hm.rows | 1;
-    const size_t plds = ((size_t)3 * 64 * L.kp.ldn + (dw ? (size_t)64 * ldw : 0) + (k ? (size_t)64 * ldw : 0)) * sizeof(double);
+    const size_t plds = gram64_plds(hm, k, dw != nullptr);
     const int pblocks = (int)std::min<long>(chb, (long)L.pgrid_max);
     const int gwgs = (int)std::min<long>(chb, (long)m->num_cus);
     if (k) {
-        if ((rc = h->mom64.ensure((size_t)L.pgrid_max * (hm.cols + 1) * 64 * sizeof(double)))) return rc;
-        HIPCHK(hipMemsetAsync(h->mom64.p, 0, (size_t)pblocks * (hm.cols + 1) * 64 * sizeof(double), m->stream));  // (the producer grid of this call)
+        if ((rc = h->mom64.ensure((size_t)L.pgrid_max * fbr_gram64_mom_count(hm.cols, k) * 64 * sizeof(double)))) return rc;
+        HIPCHK(hipMemsetAsync(h->mom64.p, 0, (size_t)pblocks * fbr_gram64_mom_count(hm.cols, k) * 64 * sizeof(double), m->stream));  // (the producer grid of this call)
     }
     if ((rc = m->partial.ensure((size_t)m->num_cus * g.wpb * g.npw * 256 * sizeof(double)))) return rc;
     int launches = 0, first_wgs = 0;
     if (h2d_chunked) {
-        if ((rc = ensure_stage_buffers(m, d, k, dw, chb * 64, 2)) || (rc = ensure_copy_stream(m))) return rc;
+        if ((rc = ensure_stage_buffers(m, d, k, dw, chs, 2)) || (rc = ensure_copy_stream(m))) return rc;
         HIPCHK(hipEventRecord(m->ev_fork, m->stream));
     }
     // the states of chunk c in device memory: the caller's arrays, or staging buffer (c & 1) filled on the copy stream
@@ -565,7 +574,7 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
         const double *rhs, *w;
     };
     auto stage = [&](long c, Staged &out) -> int {
-        const long s0 = c * chb * 64, cs = std::min(chb * 64, S - s0);
+        const long s0 = c * chs, cs = std::min(chs, S - s0);
         const int b = (int)(c & 1);
         out = {d, s0, drhs, dw};
         if (!h2d_chunked) return FBR_OK;
@@ -579,11 +588,11 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     };
     Staged cur, nxt;
     if (S > 0 && (rc = stage(0, nxt))) return rc;
-    for (long b0 = 0; b0 * 64 < S; b0 += chb, launches++) {
-        const long s0 = b0 * 64, cs = std::min(chb * 64, S - s0), nb = (cs + 63) / 64;
+    for (long s0 = 0; s0 < S; s0 += chs, launches++) {
+        const long cs = std::min(chs, S - s0), nb = (cs + 63) / 64;
         const int b = launches & 1;
         cur = nxt;
-        if ((b0 + chb) * 64 < S && (rc = stage(launches + 1, nxt))) return rc;  // the copy of the next chunk is enqueued before this chunk's kernels
+        if (s0 + chs < S && (rc = stage(launches + 1, nxt))) return rc;  // the copy of the next chunk is enqueued before this chunk's kernels
         if (h2d_chunked) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_h2d[b], 0));
         if (cs & 63)  // the block the producer fills partly: what its idle lanes would have written (a buffer is reused from chunk to chunk)
             HIPCHK(hipMemsetAsync(h->img64[b].as<double>() + (nb - 1) * g.blk_doubles, 0, (size_t)g.blk_doubles * sizeof(double), m->stream));
@@ -616,7 +625,8 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
         const int *wgb = nullptr;
         if ((rc = gram64_wg_table(h, first_wgs, &wgb)) || (rc = gram64_reduce(m, h, L, first_wgs, wgb, 1, G))) return rc;
         if (k) {
-            hipLaunchKernelGGL(fbr_gram64_mom_reduce_kernel, dim3(hm.cols + 1), dim3(256), 0, m->stream, hm.cols, pblocks, h->mom64.as<double>(), G);
+            hipLaunchKernelGGL(fbr_gram64_mom_reduce_kernel, dim3(fbr_gram64_mom_count(hm.cols, k)), dim3(256), 0, m->stream, hm.cols, k, pblocks,
+                               h->mom64.as<double>(), G);
             HIPCHK(hipGetLastError());
         }
     }
@@ -640,7 +650,7 @@ static int gram64_grouped_pass(fbr_model *m, GramHolder *h, const DevStates &d, 
     const int wpg = (int)std::max<long>(1, std::min<long>(bpg, (long)m->num_cus / std::min(gpc, ngroups)));
     Gram64Launch L;
     if ((rc = gram64_setup(m, h, false, &L))) return rc;
-    const size_t plds = ((size_t)3 * 64 * L.kp.ldn + (dw ? (size_t)64 * (hm.rows | 1) : 0)) * sizeof(double);
+    const size_t plds = gram64_plds(hm, 0, dw != nullptr);
     if ((rc = m->partial.ensure((size_t)gpc * wpg * g.wpb * g.npw * 256 * sizeof(double)))) return rc;
     const int *wgb = nullptr;
     if ((rc = gram64_wg_table(h, wpg, &wgb))) return rc;

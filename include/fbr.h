@@ -329,7 +329,7 @@ int fbr_gram_program_info(const fbr_model *m, int32_t k, int64_t num_samples, in
                           int64_t *mfma_per_sample, int32_t *num_parts);
 
 /* The sample-contiguous Gram pass (option "gram_lane", csrc/fbr_gram64.h) for the same batch: info[0] = 1 when the model qualifies and the
-   option is on (device-resident inputs, k <= 1), else every entry is 0; [1] tile rows of a 64-sample block image, [2] its bytes, [3] MFMA
+   option is on (device-resident inputs, k <= 2), else every entry is 0; [1] tile rows of a 64-sample block image, [2] its bytes, [3] MFMA
    instructions per block, [4] row levels, [5] slabs of the widest stage, [6] LDS bytes of the Gram kernel, [7] column tiles, [8] force
    tiles (option "gram_force_tiles"), [9] sum over the levels of the busiest wave's active tile pairs, [10] the same for a perfect split
    over the 8 waves, [11] stages (barriers) per half block.  The image is written once and read once per pass: 2 * info[2] / 64 bytes of HBM traffic per sample.
@@ -369,7 +369,7 @@ int fbr_model_link_merge_info(const fbr_model *m, int64_t num_samples, int32_t *
  *   "fused_id"                   1     fbr_predict / fbr_inverse_dynamics_batch run kinematics and torques in ONE kernel, the link records
  *                                      stay in registers (0: kinematics kernel + torque kernel with the records staged through HBM)
  *   "gram_lane"                  1     fused Gram over SAMPLE-contiguous images (MFMA k-steps over four samples of one regressor row) with a
- *                                      one-lane-per-sample producer, where the call allows: at most one rhs column, a tile program in one part
+ *                                      one-lane-per-sample producer, where the call allows: at most two rhs columns, a tile program in one part
  *                                      (friction columns included); inputs resident in HBM, pageable or pinned (staged chunk by chunk);
  *                                      fbr_gram_grouped without rhs columns (0: always the per-sample images of the kinematics + packer kernels)
  *   "gram_lane_waves"            8     gram_lane, models whose tile pairs need the one-workgroup-per-CU shape: workgroups of 8 waves with 18

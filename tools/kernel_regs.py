@@ -3,12 +3,20 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "flobaroid_amd", "libfbr.so")
 llvm = "/opt/rocm/lib/llvm/bin"
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+notes = ""
 with tempfile.TemporaryDirectory() as td:
-    # the fat binary sits in the .hip_fatbin section of the shared object
+    # the fat binaries sit in the .hip_fatbin section of the shared object, one bundle per translation unit
     subprocess.check_call([os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={td}/fat", lib])
-    subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={td}/fat",
-                           f"--output={td}/co", "--unbundle"])
-    notes = subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", f"{td}/co"], text=True)
+    with open(f"{td}/fat", "rb") as fh:
+        fat = fh.read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), fat)]
+    for i, a in enumerate(starts):
+        with open(f"{td}/fat{i}", "wb") as fh:
+            fh.write(fat[a : starts[i + 1] if i + 1 < len(starts) else len(fat)])
+        subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                               f"--input={td}/fat{i}", f"--output={td}/co{i}", "--unbundle"])
+        notes += subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", f"{td}/co{i}"], text=True)
 pat = re.compile(r"\.agpr_count:\s+(\d+).*?\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.sgpr_spill_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", re.S)
 frag = sys.argv[1] if len(sys.argv) > 1 else ""
 for m in pat.finditer(notes):
