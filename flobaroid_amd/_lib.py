@@ -116,6 +116,15 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, _dp, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_regressor_weights": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, _ip, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
+    "fbr_fourier_gradient": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_tsqr": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
@@ -178,6 +187,10 @@ def load_library():
     except Exception:
         pass
     lib = ctypes.CDLL(LIB_PATH)
+    missing = [name for name in _SIGNATURES if not hasattr(lib, name)]
+    if missing:  # (entry points have been added without a new FBR_VERSION: an older library of the same number lacks them)
+        raise FbrError(f"{LIB_PATH} does not export {', '.join(missing)}: it was built from older sources -- rebuild it with "
+                       "`python -c 'import __graft_entry__ as g; g.build()'`")
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -650,6 +663,55 @@ class Engine:
                                             qo.ctypes.data_as(_dp), None if qr is None else qr.ctypes.data_as(_dp), refs[0].ptr, refs[1].ptr, refs[2].ptr,
                                             refs[0].mem), "fbr_fourier_states")
         return {"q": outs[0], "dq": outs[1], "ddq": outs[2]}
+
+    def regressor_weights(self, st: dict, ngroups: int, C, cols=None, out=None):
+        """Weight rows of the D-optimality gradient (``fbr_regressor_weights``): (S * rows, cols_of_the_model) with
+        ``W[s][:, cols] = Y_s[:, cols] @ C[g]`` for the sample's group g (``ngroups`` equal groups of consecutive samples) and exact zeros in
+        every other column -- the ``W`` that ``fd_scores`` takes.  ``C`` (ngroups, ncols, ncols), general; ``cols=None``: every column.
+        ``C`` may be a NumPy array or a tensor: it is brought to the memory space of the states."""
+        s, keep, S, mem = self._states(st)
+        ca = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        nc = self.cols if ca is None else int(ca.size)
+        G = int(ngroups)
+        if _is_torch(C):
+            C = C.reshape(max(G, 1), nc, nc)
+            if mem == FBR_HOST:
+                C = C.cpu()
+            elif C.device.type != "cuda":
+                C = C.to(f"cuda:{self.device}")
+        else:
+            C = np.ascontiguousarray(C, dtype=np.float64).reshape(max(G, 1), nc, nc)
+            if mem == FBR_DEVICE:
+                import torch
+
+                C = torch.from_numpy(C).to(f"cuda:{self.device}")
+        Cr = _Ref(C, (max(G, 1), nc, nc), "C")
+        r, ret = self._out(out, (S * self.rows, self.cols), mem)
+        _check(self._lib.fbr_regressor_weights(self._h, ctypes.byref(s), G, None if ca is None else ca.ctypes.data_as(_ip), nc, Cr.ptr, r.ptr, r.mem),
+               "fbr_regressor_weights")
+        return ret
+
+    def fourier_gradient(self, wf, a, b, sens_q, sens_dq, sens_ddq, T: int, freq: float, q_range=None, tstride: int = 1, device_out: bool | None = None):
+        """Chain of sensitivities (C * T, n) with the Jacobian of the series of ``fourier_states`` (``fbr_fourier_gradient``): a (C, 1 + 2 n +
+        2 n nharm) array ``[wf | q_offset (n) | q_range (n) | a (n, nharm) | b (n, nharm)]``; sample i of a candidate sits at time
+        ``i * tstride / freq``.  A CUDA tensor when the sensitivities are (``device_out`` overrides), else NumPy."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        C, n, nh = a.shape
+        if n != self.n or b.shape != a.shape:
+            raise ValueError(f"a / b: expected (C, {self.n}, nharm)")
+        wf = np.ascontiguousarray(np.broadcast_to(np.asarray(wf, dtype=np.float64), (C,)))
+        qr = None if q_range is None else np.ascontiguousarray(q_range, dtype=np.float64).reshape(C, n)
+        refs = [_Ref(x, (C * int(T), n), nm) for x, nm in ((sens_q, "sens_q"), (sens_dq, "sens_dq"), (sens_ddq, "sens_ddq"))]
+        mem = _same_space(refs)
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        r, ret = self._out(None, (C, 1 + 2 * n + 2 * n * nh), out_mem)
+        _check(self._lib.fbr_fourier_gradient(self._h, C, int(T), int(tstride), nh, float(freq), wf.ctypes.data_as(_dp), a.ctypes.data_as(_dp),
+                                              b.ctypes.data_as(_dp), None if qr is None else qr.ctypes.data_as(_dp), refs[0].ptr, refs[1].ptr,
+                                              refs[2].ptr, mem, r.ptr, r.mem), "fbr_fourier_gradient")
+        return ret
 
     def tsqr(self, st: dict, rhs=None, w=None, R_in=None, out=None, cols=None):
         """Upper-triangular R with R^T R = [Y[:, cols]|rhs]^T [Y[:, cols]|rhs] (blocked Householder TSQR);

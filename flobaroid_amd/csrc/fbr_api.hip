@@ -10,7 +10,7 @@ thread_local std::string g_fbr_err;
 // ------------------------------------------------------------------------------------------------
 // 101 (round 6): fbr_topology.joint_type, the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info (both added in
 // round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
-// 104: fbr_model_set_capsules, fbr_candidate_capsule_distances.
+// 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
 
@@ -1179,6 +1179,151 @@ extern "C" int fbr_fourier_states(fbr_model *m, int32_t ncand, int64_t T, int32_
     }
     HIPCHK(hipStreamSynchronize(m->stream));
     return FBR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// D-optimality weight rows W = Y[:, cols] . C_g of the analytical trajectory gradient (fbr.h; kernel and tiling: fbr_weights.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int fbr_regressor_weights(fbr_model *m, const fbr_states *st, int32_t ngroups, const int32_t *cols, int32_t ncols, const double *C,
+                                     double *W, int32_t mem)
+{
+    DevStates d;
+    int rc = stage_states(m, st, &d);
+    if (rc) return rc;
+    const FbrHostModel &hm = m->hm;
+    const int P = hm.cols;
+    if (!cols) ncols = P;
+    if (!W || !C || ngroups < 1 || ncols < 1 || ncols > P || (mem != FBR_HOST && mem != FBR_DEVICE)) {
+        set_err("fbr_regressor_weights: W / C is NULL, ngroups < 1, ncols outside 1 .. cols or a bad memory space");
+        return FBR_E_INVALID;
+    }
+    const long S = d.S;
+    if (S % ngroups) {
+        set_err("fbr_regressor_weights: num_samples must be a multiple of ngroups");
+        return FBR_E_INVALID;
+    }
+    // device tables [cols (ncols) | columns not selected (P - ncols)]
+    std::vector<int> tab;
+    if (cols) {
+        std::vector<char> seen(P, 0);
+        for (int i = 0; i < ncols; i++) {
+            if (cols[i] < 0 || cols[i] >= P || seen[cols[i]]) {
+                set_err("fbr_regressor_weights: cols holds an index out of range or twice");
+                return FBR_E_INVALID;
+            }
+            seen[cols[i]] = 1;
+            tab.push_back(cols[i]);
+        }
+        for (int c = 0; c < P; c++)
+            if (!seen[c]) tab.push_back(c);
+    }
+    const int mt = fbr_weights_mt(ncols);
+    if (!mt) {
+        set_err("fbr_regressor_weights: a 16-row tile of the selected columns exceeds the LDS (at most 1196 columns)");
+        return FBR_E_UNSUPPORTED;
+    }
+    if (S == 0) return FBR_OK;
+    DevWeights wp;
+    wp.Rg = (S / ngroups) * hm.rows;
+    wp.P = P;
+    wp.ncols = ncols;
+    wp.ldk = fbr_weights_ldk(ncols);
+    wp.nunsel = cols ? P - ncols : 0;
+    wp.cols = wp.unsel = nullptr;
+    if (cols) {
+        if ((rc = m->wt_tab.ensure(tab.size() * sizeof(int)))) return rc;
+        HIPCHK(hipMemcpyAsync(m->wt_tab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));  // (tab is a local)
+        wp.cols = m->wt_tab.as<int>();
+        wp.unsel = wp.cols + ncols;
+    }
+    if ((rc = stage_one(m, m->st_aux, C, (size_t)ngroups * ncols * ncols, st->mem, &wp.C))) return rc;
+    const size_t per = (size_t)hm.rows * P, lds = (size_t)16 * mt * wp.ldk * sizeof(double);
+    long ch = chunk_size(m, S);
+    if (mem == FBR_HOST) {  // as fbr_regressor_batch: the device copy of a chunk of the output stays within ~1 GiB
+        ch = std::max(1L, std::min(ch, (long)((size_t)(1u << 30) / (per * sizeof(double)))));
+        if ((rc = m->out_tmp.ensure((size_t)ch * per * sizeof(double)))) return rc;
+    }
+    void (*kern)(DevWeights, double *) = mt == 4 ? fbr_weights_kernel<4> : mt == 2 ? fbr_weights_kernel<2> : fbr_weights_kernel<1>;
+    HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (long s0 = 0; s0 < S; s0 += ch) {
+        const long cs = std::min(ch, S - s0);
+        if ((rc = run_kin(m, d, s0, cs))) return rc;
+        double *dst = (mem == FBR_HOST) ? m->out_tmp.as<double>() : W + (size_t)s0 * per;
+        if ((rc = launch_regressor(m, d, s0, cs, dst, P, (long)hm.rows, 1L, nullptr, nullptr))) return rc;
+        wp.R0 = s0 * hm.rows;
+        wp.R1 = (s0 + cs) * hm.rows;
+        const long tiles = fbr_weights_tiles(&wp, mt);
+        {
+            ProfScope ps(m, FBR_PROF_GRAM);
+            hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, m->stream, wp, dst);
+        }
+        HIPCHK(hipGetLastError());
+        if (mem == FBR_HOST) {
+            HIPCHK(hipMemcpyAsync(W + (size_t)s0 * per, dst, (size_t)cs * per * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+            HIPCHK(hipStreamSynchronize(m->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    prof_collect(m);
+    return FBR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Chain of the sensitivities with the Jacobian of the Fourier series (fbr.h; kernels beside fbr_fourier_kernel, fbr_kernels.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int fbr_fourier_gradient(fbr_model *m, int32_t ncand, int64_t T, int32_t tstride, int32_t nharm, double freq, const double *wf,
+                                    const double *a, const double *b, const double *q_range, const double *sens_q, const double *sens_dq,
+                                    const double *sens_ddq, int32_t sens_mem, double *out, int32_t out_mem)
+{
+    if (!m || ncand < 1 || T < 1 || tstride < 1 || nharm < 1 || !(freq > 0) || !wf || !a || !b || !sens_q || !sens_dq || !sens_ddq || !out ||
+        (sens_mem != FBR_HOST && sens_mem != FBR_DEVICE) || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
+        set_err("fbr_fourier_gradient: bad arguments");
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;
+    const int n = m->hm.n, K = 3 + 2 * nharm;
+    const size_t nc = (size_t)ncand * n, ncoef = nc * nharm, count = (size_t)ncand * (size_t)T * n, nout = (size_t)ncand * (1 + 2 * n + 2 * (size_t)n * nharm);
+    std::vector<double> h;  // [wf (C) | a | b | q_range]
+    h.insert(h.end(), wf, wf + ncand);
+    h.insert(h.end(), a, a + ncoef);
+    h.insert(h.end(), b, b + ncoef);
+    if (q_range) h.insert(h.end(), q_range, q_range + nc);
+    int rc;
+    if ((rc = m->st_x.ensure(h.size() * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(m->st_x.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));  // (h is a local)
+    const double *dc = m->st_x.as<double>();
+    const double *dwf = dc, *da = dc + ncand, *db = da + ncoef, *drng = q_range ? db + ncoef : nullptr;
+    const double *dsq, *dsdq, *dsddq;
+    if ((rc = stage_one(m, m->st_q, sens_q, count, sens_mem, &dsq))) return rc;
+    if ((rc = stage_one(m, m->st_dq, sens_dq, count, sens_mem, &dsdq))) return rc;
+    if ((rc = stage_one(m, m->st_ddq, sens_ddq, count, sens_mem, &dsddq))) return rc;
+    // samples per block: 64, halved until the five staged factors of a block fit 64 KiB of LDS
+    int TB = 64;
+    while (TB > 1 && (size_t)5 * TB * n * sizeof(double) > (size_t)64 * 1024) TB >>= 1;
+    const size_t lds = (size_t)5 * TB * n * sizeof(double);
+    if (lds > (size_t)160 * 1024) {
+        set_err("fbr_fourier_gradient: more than 4096 joints");
+        return FBR_E_UNSUPPORTED;
+    }
+    const long ntb = (long)((T + TB - 1) / TB), nblk = (long)ncand * ntb;
+    if ((rc = m->fgrad_part.ensure((size_t)nblk * n * K * sizeof(double)))) return rc;
+    double *dout = out;
+    if (out_mem == FBR_HOST) {
+        if ((rc = m->g_tmp.ensure(nout * sizeof(double)))) return rc;
+        dout = m->g_tmp.as<double>();
+    }
+    {
+        ProfScope ps(m, FBR_PROF_REDUCE);
+        HIPCHK(hipFuncSetAttribute((const void *)fbr_fourier_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(fbr_fourier_grad_kernel, dim3((unsigned)std::min<long>(nblk, (long)m->num_cus * 16)), dim3(256), lds, m->stream, (int)ncand, (long)T,
+                           (int)tstride, n, (int)nharm, TB, ntb, freq, dwf, da, db, drng, dsq, dsdq, dsddq, m->fgrad_part.as<double>());
+        hipLaunchKernelGGL(fbr_fourier_grad_finish_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, m->stream, (int)ncand, n, (int)nharm, ntb,
+                           m->fgrad_part.as<double>(), dout);
+    }
+    HIPCHK(hipGetLastError());
+    return finish_output(m, dout, out, nout, out_mem);
 }
 
 // A submission that fails after work was enqueued has no ticket its caller could wait on: everything in flight is drained before the

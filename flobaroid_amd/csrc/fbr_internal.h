@@ -22,6 +22,7 @@
 #include "fbr_capsule.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
+#include "fbr_weights.h"
 
 extern thread_local std::string g_fbr_err;
 static inline void set_err(const std::string &s) { g_fbr_err = s; }
@@ -155,6 +156,8 @@ struct fbr_model {
     DevBuf cap_tab, cap_ep, cap_part, cap_scratch, cap_out, st_bpos;
     DevBuf fd_tab, fd_part;   // sub-tree column lists of every joint [n + 1 | entries] (built on first use), baseline partial sums [S][n]
     int fd_tab_entries = -1;
+    DevBuf wt_tab;            // fbr_regressor_weights: [selected columns | the others] of the call
+    DevBuf fgrad_part;        // fbr_fourier_gradient: per-block partial sums [C][blocks][n][3 + 2 nharm]
     FbrTsqrWork tsqr;
     std::vector<FbrTsqrWork> tsqr_groups;  // one factorisation per row group of the tree-structured TSQR (tsqr_group_plan)
     hipStream_t tsqr_streams[4] = {nullptr, nullptr, nullptr, nullptr};  // the groups' merge trees run beside the final factor's (created on first use)

@@ -903,6 +903,151 @@ __global__ __launch_bounds__(256) void fbr_fourier_kernel(int C, long T, int n, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// K6b: chain of per-sample sensitivities with the Jacobian of the series K6 evaluates -- Phase B of the reference's analytical gradient
+// (excitation/analyticalGradient.py:664-762, Python loops over joints and harmonics; its wf column by central differences of the whole
+// trajectory, _compute_wf_derivatives) for C candidates at once.  For every parameter p of candidate c
+//   grad_p = sum_t sum_j  sq[t][j] dq_j/dp + sdq[t][j] d(dq_j)/dp + sddq[t][j] d(ddq_j)/dp,          t = i tstride / freq, i = 0 .. T - 1.
+// Every derivative of a joint's (q, dq, ddq) is linear in the derivatives (r0, r1, r2) of three per-sample sums that are plain trigonometric
+// terms in each parameter: classic (r0, r1, r2) = d(q, dq, ddq)/dp itself; bounded, with raw / rd / rdd the argument of the tanh and its two
+// time derivatives, th = tanh(raw), s2 = 1 - th^2:
+//   dq/dp = qr s2 r0,   d(dq)/dp = qr s2 (r1 - 2 th rd r0),   d(ddq)/dp = qr s2 (r2 - 4 th rd r1 + (-2 th rdd - 2 s2 rd^2 + 4 th^2 rd^2) r0)
+// so that grad_p = sum_t E0 r0 + E1 r1 + E2 r2 with three factors per (t, j) that do not depend on p.  A workgroup takes TB consecutive
+// samples of one candidate: phase A stages E0, E1, E2 and the q_offset / q_range terms of every (t, j) in the LDS [5][TB][n], phase B gives
+// one thread each (joint, parameter) pair, which walks the TB samples in ascending order and writes one partial
+//   part [C][ntb][n][K],  K = 3 + 2 nh:  wf share of joint j | q_offset | q_range | a_1 .. a_nh | b_1 .. b_nh.
+// fbr_fourier_grad_finish_kernel adds the partials of the blocks (and, for wf, of the joints) in ascending order: no atomics, the same bits
+// on every run.  Harmonics beyond a joint's own nf (coefficient 0) are differentiated like the others; the caller drops them.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fbr_fourier_grad_kernel(int C, long T, int tstride, int n, int nh, int TB, long ntb, double freq,
+                                                               const double *__restrict__ wf, const double *__restrict__ a,
+                                                               const double *__restrict__ b, const double *__restrict__ qrange,
+                                                               const double *__restrict__ sq, const double *__restrict__ sdq,
+                                                               const double *__restrict__ sddq, double *__restrict__ part)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x, K = 3 + 2 * nh, pl = TB * n;
+    double *E0 = smem, *E1 = E0 + pl, *E2 = E1 + pl, *EQ = E2 + pl, *ER = EQ + pl;
+    for (long blk = blockIdx.x; blk < (long)C * ntb; blk += gridDim.x) {
+        const int c = (int)(blk / ntb);
+        const long tb = blk - (long)c * ntb, t0 = tb * TB;
+        const int nt = (int)min((long)TB, T - t0);
+        const double w = wf[c];
+        __syncthreads();  // (the block before has read its factors)
+        for (int i = tid; i < nt * n; i += 256) {
+            const int tt = i / n, j = i - tt * n;
+            const long s = ((long)c * T + t0 + tt) * n + j;
+            const double s0 = sq[s], s1 = sdq[s], s2 = sddq[s];
+            if (!qrange) {
+                E0[i] = s0;
+                E1[i] = s1;
+                E2[i] = s2;
+                EQ[i] = s0;
+                ER[i] = 0.0;
+            } else {
+                const double ts = (double)((t0 + tt) * tstride) / freq;
+                const double *aa = a + ((long)c * n + j) * nh, *bb = b + ((long)c * n + j) * nh;
+                double raw = 0.0, rd = 0.0, rdd = 0.0;
+                for (int l = 1; l <= nh; l++) {
+                    const double x = w * (ts * (double)l), wl = w * (double)l;
+                    double sn, cs;
+                    sincos(x, &sn, &cs);
+                    const double al = aa[l - 1], bl = bb[l - 1];
+                    raw += bl * cs + al * sn;
+                    rd += (al * wl) * cs - (bl * wl) * sn;
+                    rdd += -(al * wl * wl) * sn - (bl * wl * wl) * cs;
+                }
+                const double th = tanh(raw), sech2 = 1.0 - th * th, qr = qrange[(long)c * n + j], f = qr * sech2;
+                E0[i] = f * (s0 - 2.0 * th * rd * s1 + (-2.0 * th * rdd - 2.0 * sech2 * rd * rd + 4.0 * th * th * rd * rd) * s2);
+                E1[i] = f * (s1 - 4.0 * th * rd * s2);
+                E2[i] = f * s2;
+                EQ[i] = s0;
+                ER[i] = s0 * th + s1 * (sech2 * rd) + s2 * (sech2 * rdd - 2.0 * th * sech2 * rd * rd);
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < n * K; i += 256) {
+            const int j = i / K, k = i - j * K;
+            const double *aa = a + ((long)c * n + j) * nh, *bb = b + ((long)c * n + j) * nh;
+            double acc = 0.0;
+            if (k == 1 || k == 2) {
+                const double *e = k == 1 ? EQ : ER;
+                for (int tt = 0; tt < nt; tt++) acc += e[tt * n + j];
+            } else if (k == 0) {  // wf: every harmonic's phase l t wf moves
+                for (int tt = 0; tt < nt; tt++) {
+                    const double ts = (double)((t0 + tt) * tstride) / freq;
+                    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+                    for (int l = 1; l <= nh; l++) {
+                        const double dl = (double)l, x = w * (ts * dl), wl = w * dl, lt = dl * ts;
+                        double sn, cs;
+                        sincos(x, &sn, &cs);
+                        const double al = aa[l - 1], bl = bb[l - 1];
+                        if (!qrange) {
+                            r0 += al * (ts * cs / w - sn / (w * wl)) + bl * (ts * sn / w + cs / (w * wl));
+                            r1 += (bl * cs - al * sn) * lt;
+                            r2 += -al * (dl * sn + wl * lt * cs) + bl * (dl * cs - wl * lt * sn);
+                        } else {
+                            r0 += (al * cs - bl * sn) * lt;
+                            r1 += al * (dl * cs - wl * lt * sn) - bl * (dl * sn + wl * lt * cs);
+                            r2 += -al * (2.0 * wl * dl * sn + wl * wl * lt * cs) - bl * (2.0 * wl * dl * cs - wl * wl * lt * sn);
+                        }
+                    }
+                    acc += E0[tt * n + j] * r0 + E1[tt * n + j] * r1 + E2[tt * n + j] * r2;
+                }
+            } else {
+                const bool isb = k >= 3 + nh;
+                const int l = k - 2 - (isb ? nh : 0);
+                const double dl = (double)l, wl = w * dl;
+                for (int tt = 0; tt < nt; tt++) {
+                    const double ts = (double)((t0 + tt) * tstride) / freq, x = w * (ts * dl);
+                    double sn, cs, r0, r1, r2;
+                    sincos(x, &sn, &cs);
+                    if (!qrange) {
+                        r0 = isb ? -cs / wl : sn / wl;
+                        r1 = isb ? sn : cs;
+                        r2 = isb ? wl * cs : -wl * sn;
+                    } else {
+                        r0 = isb ? cs : sn;
+                        r1 = isb ? -wl * sn : wl * cs;
+                        r2 = isb ? -(wl * wl) * cs : -(wl * wl) * sn;
+                    }
+                    acc += E0[tt * n + j] * r0 + E1[tt * n + j] * r1 + E2[tt * n + j] * r2;
+                }
+            }
+            part[(blk * n + j) * K + k] = acc;
+        }
+    }
+}
+
+// out [C][1 + 2 n + 2 n nh] = [wf | q_offset (n) | q_range (n) | a (n, nh) | b (n, nh)]: one thread per entry, partials in ascending block
+// (and, for wf, joint) order
+__global__ __launch_bounds__(256) void fbr_fourier_grad_finish_kernel(int C, int n, int nh, long ntb, const double *__restrict__ part,
+                                                                      double *__restrict__ out)
+{
+    const int K = 3 + 2 * nh, E = 1 + 2 * n + 2 * n * nh;
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long)C * E) return;
+    const int c = (int)(e / E), i = (int)(e - (long)c * E);
+    const double *pc = part + (long)c * ntb * n * K;
+    double acc = 0.0;
+    if (i == 0) {
+        for (long tb = 0; tb < ntb; tb++)
+            for (int j = 0; j < n; j++) acc += pc[(tb * n + j) * K];
+    } else {
+        int j, k;
+        if (i < 1 + 2 * n) {
+            j = (i - 1) % n;
+            k = 1 + (i - 1) / n;
+        } else {
+            const int r = i - 1 - 2 * n, isb = r >= n * nh, rr = r - isb * n * nh;
+            j = rr / nh;
+            k = 3 + isb * nh + (rr - j * nh);
+        }
+        for (long tb = 0; tb < ntb; tb++) acc += pc[(tb * n + j) * K + k];
+    }
+    out[e] = acc;
+}
+
 #endif  // FBR_KERNELS_CORE
 #ifdef FBR_KERNELS_GRAM  // tile-image packer and fused Gram (fbr_gram_api.hip)
 // ------------------------------------------------------------------------------------------------

@@ -9,7 +9,9 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``candidate_objectives`` -- the whole ``objectiveFunc`` (f, g, soft costs) of many candidates from ``Engine.gram_grouped`` +
   ``Engine.candidate_extrema``: only per-candidate numbers reach the host;
 * ``candidate_collision_constraints`` -- its collision block in capsule mode (``collisionMode: "capsule"``, robot links) from
-  ``Engine.candidate_capsule_distances``; ``candidate_objectives(..., collision=...)`` appends it to ``g``.
+  ``Engine.candidate_capsule_distances``; ``candidate_objectives(..., collision=...)`` appends it to ``g``;
+* ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
+  candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``.
 """
 from __future__ import annotations
 
@@ -358,3 +360,134 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
     vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
     return candidate_objectives(engine, st, len(candidates), independent_cols, x_std, limits, joint_names, config, dopt_scale=dopt_scale,
                                 YtY_prior=YtY_prior, vel_sign=vel_sign, collision=collision)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The D-optimality term of the optimiser's gradient per candidate (analyticalGradient.py compute_analytical_gradient, Phases 1, A and B,
+# lines 538-762): weight rows on the device (Engine.regressor_weights), the finite-difference sweep (Engine.fd_scores) and the chain with
+# the Jacobian of the Fourier series (Engine.fourier_gradient).  Not covered: the soft-cost / constraint gradients of Phase C, the
+# collision gradient, the suspended base.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4, dopt_scale=1.0, YtY_prior=None, B=None):
+    """The constant matrices of ``Engine.regressor_weights`` for C candidates from their Grams ``G`` (C, Pa, Pa) (``Engine.gram_grouped``):
+    returns ``(Cmat, cols)``, ``Cmat`` (C, ncols, ncols), such that ``W_c = Y_c[:, cols] @ Cmat[c]`` are the reference's weight rows
+    ``W_std = R_dopt Pb^T`` (analyticalGradient.py:538-565) restricted to ``cols``:
+
+        Cmat[c] = -2 scale Pb (Pb^T G_c Pb [+ YtY_prior] + delta_c I)^-1 Pb^T,      delta_c = dopt_regularization * lambda_max,
+
+    lambda_max the largest eigenvalue of ``Pb^T G_c Pb [+ YtY_prior]`` (floored at 1e-30) -- the delta of ``estimation.d_optimality_batch``.
+    Without ``B`` the base regressor is ``Y[:, independent_cols]`` (Pb selects columns): ``cols = independent_cols`` and Cmat[c] is the
+    regularised inverse itself.  With ``B`` (P, nb) (``useBasisProjection``: YBase = Y B) ``cols`` is every column and
+    ``Cmat[c] = -2 scale B (B^T G_c B [+ prior] + delta_c I)^-1 B^T``.  ``dopt_scale``: a number or one per candidate.
+
+    delta is HELD FIXED in the derivative, as the reference does: the weights are the gradient of -scale logdet(M + delta_0 I) at
+    delta_0 = delta(theta_0), not of the objective with delta following lambda_max(theta)."""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim == 2:
+        G = G[None]
+    nC = G.shape[0]
+    scale = np.broadcast_to(np.asarray(dopt_scale, dtype=np.float64), (nC,))
+    if B is None:
+        cols = np.asarray(independent_cols, dtype=np.int64)
+        M = G[:, cols[:, None], cols[None, :]]
+    else:
+        B = np.asarray(B, dtype=np.float64)
+        P = B.shape[0]
+        cols = np.arange(P, dtype=np.int64)
+        M = B.T[None] @ G[:, :P, :P] @ B[None]
+    if YtY_prior is not None:
+        M = M + np.asarray(YtY_prior, dtype=np.float64)[None]
+    ev = np.linalg.eigvalsh(M)
+    delta = float(dopt_regularization) * np.maximum(ev[:, -1], 1e-30)
+    Minv = np.linalg.inv(M + delta[:, None, None] * np.eye(M.shape[1])[None])
+    Cm = Minv if B is None else B[None] @ Minv @ B.T[None]
+    return np.ascontiguousarray(-2.0 * scale[:, None, None] * Cm), cols.astype(np.int32)
+
+
+def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, independent_cols, dopt_regularization: float = 1e-4,
+                                              dopt_scale=None, YtY_prior=None, epsilon: float = 1e-7, subsample: int = 1,
+                                              friction_sign_threshold: float = 0.02, max_weight_bytes: int = 2**31):
+    """D-optimality term and its gradient for every candidate (``fourier_coefficients`` dicts) without a sample leaving the device:
+    coefficients -> states (``fbr_fourier_states``) -> one Gram per candidate (``fbr_gram_grouped``) -> ``dopt_weight_matrices`` on the host
+    -> for chunks of whole candidates whose weight rows fit ``max_weight_bytes``: ``regressor_weights`` -> ``fd_scores`` -> forward
+    differences on the device -> ``fourier_gradient``.  Only per-candidate numbers and the matrices C cross PCIe.
+
+    Returns ``(f, grad)``: ``f`` (C,) = ``dopt_scale`` * the value of ``candidate_dopt_from_coefficients`` (``dopt_scale`` None: 1) and a
+    dict of arrays ``wf`` (C,), ``q_offset`` (C, n), ``q_range`` (C, n) (zeros for classic candidates), ``a`` / ``b`` (C, n, nh), the
+    derivatives of f with respect to the entries of the ``fourier_coefficients`` dicts, delta held fixed (``dopt_weight_matrices``);
+    columns that only pad ``a`` / ``b`` to a common width are removed (nh = the widest candidate's).
+
+    ``subsample`` = k sweeps the samples 0, k, 2 k, ... only and scales the result by k (``analyticalGradientSubsample``); the Gram, f and
+    C always use every sample.  Friction engines: the viscous column is linear in dq and sits in W, so the sweep carries its derivative
+    (the reference adds it analytically, ``W_visc``); the Coulomb sign tanh(dq / threshold) is held at its baseline value, as there."""
+    import torch
+
+    C = len(candidates)
+    n = engine.n
+    T, k = int(T), max(int(subsample), 1)
+    st = candidate_states(engine, candidates, T, freq, device=True)
+    if engine.friction:
+        st["sign"] = torch.tanh(st["dq"] / float(friction_sign_threshold))
+    G = _host(engine.gram_grouped(st, C))
+    nld = est.d_optimality_batch(G, independent_cols, dopt_regularization, YtY_prior)
+    scale = 1.0 if dopt_scale is None else float(dopt_scale)
+    Cm, cols = dopt_weight_matrices(G, independent_cols, dopt_regularization, scale, YtY_prior)
+    Ts = (T + k - 1) // k
+    if k > 1:
+        st = {key: v.reshape(C, T, -1)[:, ::k].reshape(C * Ts, -1).contiguous() for key, v in st.items()}
+    per_cand = Ts * engine.rows * engine.cols * 8
+    cc = max(1, min(C, int(max_weight_bytes) // max(per_cand, 1)))
+    sens = torch.empty((3, C * Ts, n), dtype=torch.float64, device=st["q"].device)
+    W = torch.empty((cc * Ts * engine.rows, engine.cols), dtype=torch.float64, device=st["q"].device)
+    for c0 in range(0, C, cc):
+        c1 = min(C, c0 + cc)
+        sub = {key: v[c0 * Ts:c1 * Ts] for key, v in st.items()}
+        Wc = W[: (c1 - c0) * Ts * engine.rows]
+        engine.regressor_weights(sub, c1 - c0, Cm[c0:c1], cols=cols, out=Wc)
+        sc = engine.fd_scores(sub, Wc, float(epsilon))
+        d = (sc[:, 1:] - sc[:, :1]) * (k / float(epsilon))
+        sens[:, c0 * Ts:c1 * Ts] = d.reshape(-1, 3, n).permute(1, 0, 2)
+    nh = max(c["a"].shape[1] for c in candidates)
+    A, B = np.zeros((C, n, nh)), np.zeros((C, n, nh))
+    for i, c in enumerate(candidates):
+        A[i, :, : c["a"].shape[1]] = c["a"]
+        B[i, :, : c["b"].shape[1]] = c["b"]
+    bounded = all(c["q_range"] is not None for c in candidates)
+    g = _host(engine.fourier_gradient([c["wf"] for c in candidates], A, B, sens[0], sens[1], sens[2], Ts, float(freq),
+                                      q_range=np.stack([c["q_range"] for c in candidates]) if bounded else None, tstride=k))
+    grad = {"wf": g[:, 0].copy(), "q_offset": g[:, 1:1 + n].copy(), "q_range": g[:, 1 + n:1 + 2 * n].copy(),
+            "a": g[:, 1 + 2 * n:1 + 2 * n + n * nh].reshape(C, n, nh).copy(), "b": g[:, 1 + 2 * n + n * nh:].reshape(C, n, nh).copy()}
+    return nld * scale, grad
+
+
+def gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
+                                    joint_limits=None, q0=None) -> np.ndarray:
+    """One candidate's gradient (the entries ``wf`` (), ``q_offset`` (n,), ``q_range`` (n,), ``a`` / ``b`` (n, nh) of
+    ``candidate_dopt_gradient_from_coefficients``, i.e. ``{k: v[c] for k, v in grad.items()}``) on the reference's variable vector
+    ``[wf | q0 (n) | a_0[:nf_0] .. a_{n-1}[:nf_{n-1}] | b_0[:nf_0] ..]`` (trajectoryOptimizer.py; analyticalGradient.py:675-762), with the
+    reference's own conventions for q0: classic ``q_offset = nf * q0`` enters as ``nf_d * deg_factor`` (deg_factor = pi / 180 with
+    ``use_deg``); bounded through ``q_center`` only, ``deg_factor``.
+
+    ``exact`` (bounded): adds what the reference leaves out -- ``q_center = clip(mid + q0, lo, hi)`` has derivative 0 where it clips and
+    ``q_range = 0.95 min(q_center - lo, hi - q_center)`` moves with q0 by +-0.95.  Needs ``joint_limits`` [(lo, hi)] and ``q0`` (the
+    variable's value, in degrees with ``use_deg``)."""
+    nf = [int(x) for x in nf]
+    n = len(nf)
+    if bounded is None:  # the candidate's own form
+        bounded = candidate.get("q_range") is not None
+    deg = np.pi / 180.0 if use_deg else 1.0
+    gq = np.asarray(grad["q_offset"], dtype=np.float64).reshape(n)
+    if not bounded:
+        dq0 = gq * np.asarray(nf, dtype=np.float64) * deg
+    else:
+        dq0 = gq * deg
+        if exact:
+            lo = np.array([l[0] for l in joint_limits], dtype=np.float64)
+            hi = np.array([l[1] for l in joint_limits], dtype=np.float64)
+            raw = 0.5 * (lo + hi) + np.asarray(q0, dtype=np.float64) * deg
+            inside = ((raw > lo) & (raw < hi)).astype(np.float64)
+            qc = np.clip(raw, lo, hi)
+            dqr = 0.95 * np.where(qc - lo <= hi - qc, 1.0, -1.0)
+            dq0 = (gq + np.asarray(grad["q_range"], dtype=np.float64).reshape(n) * dqr) * inside * deg
+    ga, gb = np.asarray(grad["a"], dtype=np.float64), np.asarray(grad["b"], dtype=np.float64)
+    return np.concatenate([[float(np.asarray(grad["wf"]))], dq0] + [ga[j, :nf[j]] for j in range(n)] + [gb[j, :nf[j]] for j in range(n)])

@@ -84,7 +84,9 @@ typedef struct {
 /* Version of THIS header.  fbr_version() returns the value the loaded library was built with: a caller compares the two before its first
  * call (flobaroid_amd/_lib.py load_library refuses a mismatch), because the C-ABI has grown in place -- 101: fbr_topology.joint_type,
  * the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info, option "fused_id"; 102: fbr_gram_lane_info, options
- * "gram_lane" / "gram_force_tiles"; 103: fbr_candidate_extrema; 104: fbr_model_set_capsules, fbr_candidate_capsule_distances. */
+ * "gram_lane" / "gram_force_tiles"; 103: fbr_candidate_extrema; 104: fbr_model_set_capsules, fbr_candidate_capsule_distances, and -- added under the same number, which
+ * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
+ * fbr_fourier_gradient. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -228,6 +230,23 @@ int fbr_gram_grouped(fbr_model *m, const fbr_states *st, int32_t ngroups, const 
 int fbr_fd_scores(fbr_model *m, const fbr_states *st, const double *W, double eps, double *out, int32_t out_mem);
 
 /*
+ * Weight rows of the D-optimality gradient, formed on the device: W [S][rows][P] (P = every column of the model, friction columns
+ * included: the layout fbr_fd_scores reads) with
+ *   W[s][:, cols] = Y_s[:, cols] . C[g(s)],   g(s) = s / (S / ngroups),   every column not in cols = exact 0.0 (whatever W held before).
+ * The reference builds them on the host for ONE trajectory -- R_dopt = -2 scale YBase (YBase^T YBase + delta I)^-1 by SVD or solve and
+ * W_std = R_dopt Pb^T over the stacked regressor (excitation/analyticalGradient.py:538-565, W_iner / W_visc 578-596); with YBase =
+ * Y[:, cols] Pb that is Y[:, cols] times a constant ncols x ncols matrix per candidate, C = -2 scale Pb (Pb^T G Pb + delta I)^-1 Pb^T.
+ *   cols [ncols] (host; no repeats, any order) or NULL: every column (ncols is then ignored);  C [ngroups][ncols][ncols] row-major,
+ *   general (no symmetry assumed), in st->mem space like the states;  W in `mem` space.  The regressor kernel of fbr_regressor_batch writes
+ *   Y into W and an fp64 MFMA kernel transforms it in place, row tile by row tile (csrc/fbr_weights.h); no atomics, the same bits on every
+ *   run and for every chunking.
+ * num_samples == 0 is a no-op.  FBR_E_INVALID: num_samples not a multiple of ngroups, ngroups < 1, a bad column list;
+ * FBR_E_UNSUPPORTED: more than 1196 selected columns (a 16-row tile has to fit the LDS).
+ */
+int fbr_regressor_weights(fbr_model *m, const fbr_states *st, int32_t ngroups, const int32_t *cols, int32_t ncols, const double *C, double *W,
+                          int32_t mem);
+
+/*
  * Joint states of ncand candidate trajectories, T samples each, generated ON THE DEVICE from their Fourier coefficients -- the
  * parametrisation the trajectory optimiser searches over (excitation/trajectoryGenerator.py: OscillationGenerator 411-460,
  * BoundedOscillationGenerator 462-560; evaluated per candidate by computeTrajectoryDynamics 83-128 before every objective call,
@@ -240,6 +259,21 @@ int fbr_fd_scores(fbr_model *m, const fbr_states *st, const double *W, double ep
  */
 int fbr_fourier_states(fbr_model *m, int32_t ncand, int64_t T, int32_t nharm, double freq, const double *wf, const double *a, const double *b,
                        const double *q_offset, const double *q_range, double *q, double *dq, double *ddq, int32_t out_mem);
+
+/*
+ * Chain of per-sample sensitivities with the Jacobian of the series fbr_fourier_states evaluates -- Phase B of the reference's analytical
+ * gradient (excitation/analyticalGradient.py:664-762: Python loops over joints and harmonics; its wf column, line 672, from central
+ * differences of the whole trajectory, _compute_wf_derivatives) for ncand candidates in one call.  sens_q / sens_dq / sens_ddq
+ * [ncand * T][n] (sens_mem space): the sensitivities of sample i = 0 .. T - 1 of every candidate, taken at time i * tstride / freq
+ * (tstride > 1: the sub-sampled sweep of analyticalGradientSubsample).  wf, a, b, q_range: host arrays as for fbr_fourier_states.
+ *   out [ncand][1 + 2 n + 2 n nharm] (out_mem) = [d/dwf | d/dq_offset (n) | d/dq_range (n; zeros when q_range == NULL) | d/da (n, nharm) |
+ *   d/db (n, nharm)],  each entry = sum_t sum_j sens_q dq/dp + sens_dq d(dq)/dp + sens_ddq d(ddq)/dp, every derivative analytic (wf too).
+ * Harmonics beyond a joint's own nf (coefficient 0) are differentiated like the others: the caller drops them.  Fixed summation order
+ * (per-block partials, then a finishing pass): the same bits on every run.
+ */
+int fbr_fourier_gradient(fbr_model *m, int32_t ncand, int64_t T, int32_t tstride, int32_t nharm, double freq, const double *wf, const double *a,
+                         const double *b, const double *q_range, const double *sens_q, const double *sens_dq, const double *sens_ddq,
+                         int32_t sens_mem, double *out, int32_t out_mem);
 
 /*
  * R_out [(cols+k)][(cols+k)] upper triangular with R^T R = [Y|rhs]^T [Y|rhs], by blocked Householder
@@ -296,8 +330,8 @@ int fbr_central_diff(fbr_model *m, const double *A, const double *T, double *D, 
 /* ---- profiling ---------------------------------------------------------------------------------- */
 #define FBR_PROF_KIN 0       /* link kinematics kernel */
 #define FBR_PROF_REGRESSOR 1 /* materialising regressor kernel */
-#define FBR_PROF_GRAM 2      /* fused regressor->Gram MFMA kernel */
-#define FBR_PROF_REDUCE 3    /* slice reduction / scatter of the Gram partials */
+#define FBR_PROF_GRAM 2      /* fused regressor->Gram MFMA kernel; the in-place weight GEMM of fbr_regressor_weights (its writer: REGRESSOR) */
+#define FBR_PROF_REDUCE 3    /* slice reduction / scatter of the Gram partials; chain kernel + finishing pass of fbr_fourier_gradient */
 #define FBR_PROF_ID 4        /* inverse dynamics / predict kernel */
 #define FBR_PROF_TSQR 5      /* TSQR fold kernels (level 0 per chunk, merge tree) */
 #define FBR_PROF_PACK 6      /* tile-image packing kernel of the fused Gram pass (producer stream) */
