@@ -86,6 +86,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_int32],
     ),
+    "fbr_capsule_distance_gradients": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -124,6 +129,11 @@ _SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32],
+    ),
+    "fbr_fourier_position_chain": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32],
     ),
     "fbr_tsqr": (
         ctypes.c_int,
@@ -505,6 +515,90 @@ class Engine:
         _check(self._lib.fbr_candidate_capsule_distances(self._h, ctypes.byref(s), bp.ptr, C, int(step), pv, pi, out_mem),
                "fbr_candidate_capsule_distances")
         return {"dist": val, "idx": idx}
+
+    def _index_array(self, x, shape, mem, name):
+        """an int64 index array in the memory space ``mem``: (keep-alive object, pointer)"""
+        if mem == FBR_DEVICE:
+            import torch
+
+            t = torch.as_tensor(x, device=f"cuda:{self.device}").to(torch.int64).contiguous()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+            return t, t.data_ptr()
+        a = np.ascontiguousarray(x.cpu().numpy() if _is_torch(x) else x, dtype=np.int64)
+        if a.shape != tuple(shape):
+            raise ValueError(f"{name}: expected shape {shape}, got {a.shape}")
+        return a, a.ctypes.data
+
+    def _to_space(self, x, mem):
+        """a float64 array brought to the memory space ``mem`` (None stays None)"""
+        if x is None:
+            return None
+        if mem == FBR_DEVICE:
+            import torch
+
+            return torch.as_tensor(x, dtype=torch.float64, device=f"cuda:{self.device}")
+        return x.cpu().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float64)
+
+    def capsule_distance_gradients(self, st: dict, ncand: int, sample, scale=None, pose_sample=None, base_pos=None,
+                                   device_out: bool | None = None) -> dict:
+        """Capsule distance and its derivative with respect to the joint positions at one chosen configuration per candidate and pair
+        (``fbr_capsule_distance_gradients``): ``{"dist": (C, P), "grad_q": (C, P, n)}``.  ``sample`` (C, P) int: the sample inside the
+        candidate whose row of ``q`` is evaluated (-1: none -- 1e10 and a zero row); ``scale`` (C, P) or None: the configuration is
+        ``scale * q[sample]``; ``pose_sample`` (C, P) or None: the sample whose base pose is used (floating base).  ``grad_q`` is the
+        derivative with respect to the EVALUATED configuration; joints off the tree path between a pair's links are exact zeros.  ``st``,
+        ``base_pos`` and the result's memory space as for ``candidate_capsule_distances``; the index and scale arrays are brought to the
+        memory space of the states."""
+        q = _Ref(st["q"], None, "q")
+        if len(q.obj.shape) != 2 or q.obj.shape[1] != self.n:
+            raise ValueError(f"q: expected (S, {self.n}), got {tuple(q.obj.shape)}")
+        S = int(q.obj.shape[0])
+        rpy = _Ref(st.get("rpy", st.get("base_rpy")), (S, 3), "base_rpy") if self.floating else _Ref(None)
+        bp = _Ref(base_pos, (S, 3), "base_pos") if self.floating else _Ref(None)
+        mem = _same_space([q, rpy, bp])
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        s = fbr_states()
+        s.num_samples, s.mem, s.q, s.base_rpy = S, mem, q.ptr, rpy.ptr
+        C, P = int(ncand), int(getattr(self, "num_capsule_pairs", 0))
+        shape = (max(C, 1), P)
+        smp, psmp = self._index_array(sample, shape, mem, "sample")
+        pose, ppose = (None, None) if pose_sample is None else self._index_array(pose_sample, shape, mem, "pose_sample")
+        sc = _Ref(self._to_space(scale, mem), shape, "scale")
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        rd, dist = self._out(None, shape, out_mem)
+        rg, grad = self._out(None, shape + (self.n,), out_mem)
+        _check(self._lib.fbr_capsule_distance_gradients(self._h, ctypes.byref(s), bp.ptr, C, psmp, sc.ptr, ppose, rd.ptr, rg.ptr, out_mem),
+               "fbr_capsule_distance_gradients")
+        return {"dist": dist, "grad_q": grad}
+
+    def fourier_position_chain(self, wf, a, b, sample, grad_q, freq: float, scale=None, q_range=None, device_out: bool | None = None):
+        """Rows of position sensitivities ``grad_q`` (C, R, n), row r of candidate c taken at time ``sample[c, r] / freq``, chained with the
+        position Jacobian of the series of ``fourier_states`` (``fbr_fourier_position_chain``): a (C, R, 1 + 2 n + 2 n nharm) array in the
+        column layout of ``fourier_gradient``, entry = ``scale[c, r] * sum_d grad_q[c, r, d] * dq_d/dp``; rows with ``sample`` < 0 are
+        zero.  A CUDA tensor when ``grad_q`` is (``device_out`` overrides), else NumPy; ``sample`` and ``scale`` are brought to its space."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        C, n, nh = a.shape
+        if n != self.n or b.shape != a.shape:
+            raise ValueError(f"a / b: expected (C, {self.n}, nharm)")
+        wf = np.ascontiguousarray(np.broadcast_to(np.asarray(wf, dtype=np.float64), (C,)))
+        qr = None if q_range is None else np.ascontiguousarray(q_range, dtype=np.float64).reshape(C, n)
+        g = _Ref(grad_q, None, "grad_q")
+        if len(g.obj.shape) != 3 or g.obj.shape[0] != C or g.obj.shape[2] != n:
+            raise ValueError(f"grad_q: expected ({C}, R, {n}), got {tuple(g.obj.shape)}")
+        R = int(g.obj.shape[1])
+        mem = g.mem
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        smp, psmp = self._index_array(sample, (C, R), mem, "sample")
+        sc = _Ref(self._to_space(scale, mem), (C, R), "scale")
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        r, ret = self._out(None, (C, R, 1 + 2 * n + 2 * n * nh), out_mem)
+        _check(self._lib.fbr_fourier_position_chain(self._h, C, R, nh, float(freq), wf.ctypes.data_as(_dp), a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
+                                                    None if qr is None else qr.ctypes.data_as(_dp), psmp, sc.ptr, g.ptr, mem, r.ptr, r.mem),
+               "fbr_fourier_position_chain")
+        return ret
 
     def predict(self, st: dict, x, out=None):
         s, keep, S, mem = self._states(st)

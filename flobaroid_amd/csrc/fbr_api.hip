@@ -10,7 +10,8 @@ thread_local std::string g_fbr_err;
 // ------------------------------------------------------------------------------------------------
 // 101 (round 6): fbr_topology.joint_type, the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info (both added in
 // round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
-// 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient).
+// 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
+// fbr_capsule_distance_gradients, fbr_fourier_position_chain).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
 
@@ -824,6 +825,24 @@ extern "C" int fbr_model_set_capsules(fbr_model *m, int32_t ncaps, const int32_t
     dc.capbeg = (const int *)(base + ((const char *)hcapbeg - host.data()));
     dc.capid = (const int *)(base + ((const char *)hcapid - host.data()));
     dc.pairs = (const int2 *)(base + ((const char *)hpairs - host.data()));
+    // tables of fbr_capsule_distance_gradients: per pair the steps of the two links and the slots of the two capsules | ancestor masks
+    std::vector<int> stepof2, anc, slotof(ncaps);
+    fbr_capgrad_ancestors(hm, prog, stepof2, anc);
+    for (int sl = 0; sl < ncaps; sl++) slotof[capid[sl]] = sl;
+    std::vector<int> gt((size_t)4 * std::max(npairs, 1) + anc.size(), 0);
+    for (int k = 0; k < npairs; k++) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        gt[4 * (size_t)k] = stepof[link[a]];
+        gt[4 * (size_t)k + 1] = stepof[link[b]];
+        gt[4 * (size_t)k + 2] = slotof[a];
+        gt[4 * (size_t)k + 3] = slotof[b];
+    }
+    std::copy(anc.begin(), anc.end(), gt.begin() + (size_t)4 * std::max(npairs, 1));
+    if (int rc = m->capg_tab.ensure(gt.size() * sizeof(int))) return rc;
+    HIPCHK(hipMemcpy(m->capg_tab.p, gt.data(), gt.size() * sizeof(int), hipMemcpyHostToDevice));
+    m->capg.W = fbr_capgrad_words(prog.nsteps);
+    m->capg.pair = (const int4 *)m->capg_tab.p;
+    m->capg.anc = m->capg_tab.as<int>() + (size_t)4 * std::max(npairs, 1);
     m->caps = dc;
     return FBR_OK;
 }
@@ -918,6 +937,79 @@ extern "C" int fbr_candidate_capsule_distances(fbr_model *m, const fbr_states *s
     }
     HIPCHK(hipStreamSynchronize(m->stream));
     prof_collect(m);
+    return FBR_OK;
+}
+
+// ---- capsule distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h) ---------------------------------
+extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                              const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem)
+{
+    if (!m || !st || !sample || !dist_out || !grad_q_out) {
+        set_err("null model / states / sample / dist_out / grad_q_out");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
+        set_err("bad fbr_states header or memory space, or q is NULL");
+        return FBR_E_INVALID;
+    }
+    if (m->caps.ncaps == 0 || m->caps.npairs == 0) {
+        set_err("no capsule set with at least one pair (fbr_model_set_capsules)");
+        return FBR_E_INVALID;
+    }
+    if (ncand < 1) {
+        set_err("ncand must be at least 1");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
+        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;
+    const FbrHostModel &hm = m->hm;
+    const DevCapsules &cp = m->caps;
+    const long S = st->num_samples, C = ncand, P = cp.npairs, T = S / C;
+    const size_t items = (size_t)C * P;
+    const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr, *dsmp = nullptr, *dscale = nullptr, *dpose = nullptr;
+    int rc;
+    if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
+    if (hm.floating && st->base_rpy) {
+        if ((rc = stage_one(m, m->st_rpy, st->base_rpy, (size_t)S * 3, st->mem, &drpy))) return rc;
+        if ((rc = stage_one(m, m->st_bpos, base_pos, (size_t)S * 3, st->mem, &dbp))) return rc;
+    }
+    // (the index arrays are 8 bytes an entry, like the doubles the staging helper copies)
+    if ((rc = stage_one(m, m->st_dq, (const double *)sample, items, st->mem, &dsmp))) return rc;
+    if ((rc = stage_one(m, m->st_ddq, (const double *)pose_sample, items, st->mem, &dpose))) return rc;
+    if ((rc = stage_one(m, m->st_aux, scale, items, st->mem, &dscale))) return rc;
+    double *ddist = dist_out, *dgrad = grad_q_out;
+    if (out_mem == FBR_HOST) {
+        if ((rc = m->cap_out.ensure(items * (1 + (size_t)hm.n) * sizeof(double)))) return rc;
+        ddist = m->cap_out.as<double>();
+        dgrad = ddist + items;
+    }
+    const long tiles = (C + 63) / 64;
+    const int grid = (int)std::min<long>(P * tiles, (long)m->num_cus * 8);
+    if ((rc = m->cap_scratch.ensure((size_t)grid * std::max(cp.nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
+    if ((rc = m->capg_flag.ensure(sizeof(int)))) return rc;
+    int flag = 0;
+    HIPCHK(hipMemsetAsync(m->capg_flag.p, 0, sizeof(int), m->stream));
+    HIPCHK(hipMemsetAsync(dgrad, 0, items * hm.n * sizeof(double), m->stream));  // (joints off a pair's path: exact zeros, never touched by the kernel)
+    {
+        ProfScope ps(m, FBR_PROF_KIN);
+        hipLaunchKernelGGL(fbr_capsule_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, cp, m->capg, C, T, dq, drpy, dbp, (const long *)dsmp,
+                           dscale, (const long *)dpose, ddist, dgrad, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(&flag, m->capg_flag.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (out_mem == FBR_HOST) {
+        HIPCHK(hipMemcpyAsync(dist_out, ddist, items * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(grad_q_out, dgrad, items * hm.n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    prof_collect(m);
+    if (flag) {
+        set_err("fbr_capsule_distance_gradients: a sample or pose_sample index lies outside -1 .. T - 1");
+        return FBR_E_INVALID;
+    }
     return FBR_OK;
 }
 
@@ -1321,6 +1413,51 @@ extern "C" int fbr_fourier_gradient(fbr_model *m, int32_t ncand, int64_t T, int3
                            (int)tstride, n, (int)nharm, TB, ntb, freq, dwf, da, db, drng, dsq, dsdq, dsddq, m->fgrad_part.as<double>());
         hipLaunchKernelGGL(fbr_fourier_grad_finish_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, m->stream, (int)ncand, n, (int)nharm, ntb,
                            m->fgrad_part.as<double>(), dout);
+    }
+    HIPCHK(hipGetLastError());
+    return finish_output(m, dout, out, nout, out_mem);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Chain of position sensitivities at single times with the position Jacobian of the Fourier series (fbr.h; fbr_fourier_poschain_kernel)
+// ------------------------------------------------------------------------------------------------
+extern "C" int fbr_fourier_position_chain(fbr_model *m, int32_t ncand, int64_t nrows, int32_t nharm, double freq, const double *wf, const double *a,
+                                          const double *b, const double *q_range, const int64_t *sample, const double *scale, const double *grad_q,
+                                          int32_t mem, double *out, int32_t out_mem)
+{
+    if (!m || ncand < 1 || nrows < 1 || nharm < 1 || !(freq > 0) || !wf || !a || !b || !sample || !grad_q || !out ||
+        (mem != FBR_HOST && mem != FBR_DEVICE) || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
+        set_err("fbr_fourier_position_chain: bad arguments");
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;
+    const int n = m->hm.n;
+    const size_t nc = (size_t)ncand * n, ncoef = nc * nharm, rows = (size_t)ncand * (size_t)nrows, E = 1 + 2 * (size_t)n + 2 * (size_t)n * nharm,
+                 nout = rows * E;
+    std::vector<double> h;  // [wf (C) | a | b | q_range]
+    h.insert(h.end(), wf, wf + ncand);
+    h.insert(h.end(), a, a + ncoef);
+    h.insert(h.end(), b, b + ncoef);
+    if (q_range) h.insert(h.end(), q_range, q_range + nc);
+    int rc;
+    if ((rc = m->st_x.ensure(h.size() * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(m->st_x.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));  // (h is a local)
+    const double *dc = m->st_x.as<double>();
+    const double *dwf = dc, *da = dc + ncand, *db = da + ncoef, *drng = q_range ? db + ncoef : nullptr;
+    const double *dsmp, *dscale, *dg;
+    if ((rc = stage_one(m, m->st_dq, (const double *)sample, rows, mem, &dsmp))) return rc;  // (8 bytes an entry, like a double)
+    if ((rc = stage_one(m, m->st_aux, scale, rows, mem, &dscale))) return rc;
+    if ((rc = stage_one(m, m->st_q, grad_q, rows * n, mem, &dg))) return rc;
+    double *dout = out;
+    if (out_mem == FBR_HOST) {
+        if ((rc = m->g_tmp.ensure(nout * sizeof(double)))) return rc;
+        dout = m->g_tmp.as<double>();
+    }
+    {
+        ProfScope ps(m, FBR_PROF_REDUCE);
+        hipLaunchKernelGGL(fbr_fourier_poschain_kernel, dim3((unsigned)std::min<size_t>((nout + 255) / 256, (size_t)m->num_cus * 32)), dim3(256), 0, m->stream,
+                           (int)ncand, (long)nrows, n, (int)nharm, freq, dwf, da, db, drng, (const long *)dsmp, dscale, dg, dout);
     }
     HIPCHK(hipGetLastError());
     return finish_output(m, dout, out, nout, out_mem);

@@ -20,6 +20,7 @@
 #include "fbr_kernels.h"
 #include "fbr_kinid.h"
 #include "fbr_capsule.h"
+#include "fbr_capsule_grad.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -154,6 +155,8 @@ struct fbr_model {
     // partials of the blocks in flight, the branch-point poses of the waves in flight, the results of a host-memory call
     DevCapsules caps = {0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     DevBuf cap_tab, cap_ep, cap_part, cap_scratch, cap_out, st_bpos;
+    DevCapGrad capg = {0, nullptr, nullptr};  // fbr_capsule_distance_gradients: ancestor masks and per-pair steps / slots of the set above
+    DevBuf capg_tab, capg_flag;
     DevBuf fd_tab, fd_part;   // sub-tree column lists of every joint [n + 1 | entries] (built on first use), baseline partial sums [S][n]
     int fd_tab_entries = -1;
     DevBuf wt_tab;            // fbr_regressor_weights: [selected columns | the others] of the call

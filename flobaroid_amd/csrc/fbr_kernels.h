@@ -919,6 +919,53 @@ __global__ __launch_bounds__(256) void fbr_fourier_kernel(int C, long T, int n, 
 // fbr_fourier_grad_finish_kernel adds the partials of the blocks (and, for wf, of the joints) in ascending order: no atomics, the same bits
 // on every run.  Harmonics beyond a joint's own nf (coefficient 0) are differentiated like the others; the caller drops them.
 // ------------------------------------------------------------------------------------------------
+// The three per-sample sums behind a joint's (q, dq, ddq) and their derivatives with respect to the parameters -- ONE definition, shared by
+// the chain kernels below (fbr_fourier_grad_kernel: all three; fbr_fourier_poschain_kernel: the position only).
+// raw / rd / rdd: the argument of the bounded form's tanh and its two time derivatives at time ts
+__device__ __forceinline__ void fbr_fourier_raw(int nh, double w, double ts, const double *aa, const double *bb, double &raw,
+                                                double &rd, double &rdd)
+{
+    raw = rd = rdd = 0.0;
+    for (int l = 1; l <= nh; l++) {
+        const double x = w * (ts * (double)l), wl = w * (double)l;
+        double sn, cs;
+        sincos(x, &sn, &cs);
+        const double al = aa[l - 1], bl = bb[l - 1];
+        raw += bl * cs + al * sn;
+        rd += (al * wl) * cs - (bl * wl) * sn;
+        rdd += -(al * wl * wl) * sn - (bl * wl * wl) * cs;
+    }
+}
+// (r0, r1, r2) for a_l (isb false) or b_l, wl = wf l, (sn, cs) = sincos(wf l t): classic, the derivatives of (q, dq, ddq) themselves;
+// bounded, those of (raw, rd, rdd)
+__device__ __forceinline__ void fbr_fourier_dcoef(bool bounded, bool isb, double wl, double sn, double cs, double &r0, double &r1, double &r2)
+{
+    if (!bounded) {
+        r0 = isb ? -cs / wl : sn / wl;
+        r1 = isb ? sn : cs;
+        r2 = isb ? wl * cs : -wl * sn;
+    } else {
+        r0 = isb ? cs : sn;
+        r1 = isb ? -wl * sn : wl * cs;
+        r2 = isb ? -(wl * wl) * cs : -(wl * wl) * sn;
+    }
+}
+// harmonic l's share of (r0, r1, r2) for wf, added: every harmonic's phase l t wf moves (classic: its amplitude 1 / (wf l) too)
+__device__ __forceinline__ void fbr_fourier_dwf_add(bool bounded, double w, double ts, double dl, double al, double bl, double sn, double cs, double &r0,
+                                                    double &r1, double &r2)
+{
+    const double wl = w * dl, lt = dl * ts;
+    if (!bounded) {
+        r0 += al * (ts * cs / w - sn / (w * wl)) + bl * (ts * sn / w + cs / (w * wl));
+        r1 += (bl * cs - al * sn) * lt;
+        r2 += -al * (dl * sn + wl * lt * cs) + bl * (dl * cs - wl * lt * sn);
+    } else {
+        r0 += (al * cs - bl * sn) * lt;
+        r1 += al * (dl * cs - wl * lt * sn) - bl * (dl * sn + wl * lt * cs);
+        r2 += -al * (2.0 * wl * dl * sn + wl * wl * lt * cs) - bl * (2.0 * wl * dl * cs - wl * wl * lt * sn);
+    }
+}
+
 __global__ __launch_bounds__(256) void fbr_fourier_grad_kernel(int C, long T, int tstride, int n, int nh, int TB, long ntb, double freq,
                                                                const double *__restrict__ wf, const double *__restrict__ a,
                                                                const double *__restrict__ b, const double *__restrict__ qrange,
@@ -947,16 +994,8 @@ __global__ __launch_bounds__(256) void fbr_fourier_grad_kernel(int C, long T, in
             } else {
                 const double ts = (double)((t0 + tt) * tstride) / freq;
                 const double *aa = a + ((long)c * n + j) * nh, *bb = b + ((long)c * n + j) * nh;
-                double raw = 0.0, rd = 0.0, rdd = 0.0;
-                for (int l = 1; l <= nh; l++) {
-                    const double x = w * (ts * (double)l), wl = w * (double)l;
-                    double sn, cs;
-                    sincos(x, &sn, &cs);
-                    const double al = aa[l - 1], bl = bb[l - 1];
-                    raw += bl * cs + al * sn;
-                    rd += (al * wl) * cs - (bl * wl) * sn;
-                    rdd += -(al * wl * wl) * sn - (bl * wl * wl) * cs;
-                }
+                double raw, rd, rdd;
+                fbr_fourier_raw(nh, w, ts, aa, bb, raw, rd, rdd);
                 const double th = tanh(raw), sech2 = 1.0 - th * th, qr = qrange[(long)c * n + j], f = qr * sech2;
                 E0[i] = f * (s0 - 2.0 * th * rd * s1 + (-2.0 * th * rdd - 2.0 * sech2 * rd * rd + 4.0 * th * th * rd * rd) * s2);
                 E1[i] = f * (s1 - 4.0 * th * rd * s2);
@@ -978,19 +1017,10 @@ __global__ __launch_bounds__(256) void fbr_fourier_grad_kernel(int C, long T, in
                     const double ts = (double)((t0 + tt) * tstride) / freq;
                     double r0 = 0.0, r1 = 0.0, r2 = 0.0;
                     for (int l = 1; l <= nh; l++) {
-                        const double dl = (double)l, x = w * (ts * dl), wl = w * dl, lt = dl * ts;
+                        const double dl = (double)l, x = w * (ts * dl);
                         double sn, cs;
                         sincos(x, &sn, &cs);
-                        const double al = aa[l - 1], bl = bb[l - 1];
-                        if (!qrange) {
-                            r0 += al * (ts * cs / w - sn / (w * wl)) + bl * (ts * sn / w + cs / (w * wl));
-                            r1 += (bl * cs - al * sn) * lt;
-                            r2 += -al * (dl * sn + wl * lt * cs) + bl * (dl * cs - wl * lt * sn);
-                        } else {
-                            r0 += (al * cs - bl * sn) * lt;
-                            r1 += al * (dl * cs - wl * lt * sn) - bl * (dl * sn + wl * lt * cs);
-                            r2 += -al * (2.0 * wl * dl * sn + wl * wl * lt * cs) - bl * (2.0 * wl * dl * cs - wl * wl * lt * sn);
-                        }
+                        fbr_fourier_dwf_add(qrange != nullptr, w, ts, dl, aa[l - 1], bb[l - 1], sn, cs, r0, r1, r2);
                     }
                     acc += E0[tt * n + j] * r0 + E1[tt * n + j] * r1 + E2[tt * n + j] * r2;
                 }
@@ -1002,15 +1032,7 @@ __global__ __launch_bounds__(256) void fbr_fourier_grad_kernel(int C, long T, in
                     const double ts = (double)((t0 + tt) * tstride) / freq, x = w * (ts * dl);
                     double sn, cs, r0, r1, r2;
                     sincos(x, &sn, &cs);
-                    if (!qrange) {
-                        r0 = isb ? -cs / wl : sn / wl;
-                        r1 = isb ? sn : cs;
-                        r2 = isb ? wl * cs : -wl * sn;
-                    } else {
-                        r0 = isb ? cs : sn;
-                        r1 = isb ? -wl * sn : wl * cs;
-                        r2 = isb ? -(wl * wl) * cs : -(wl * wl) * sn;
-                    }
+                    fbr_fourier_dcoef(qrange != nullptr, isb, wl, sn, cs, r0, r1, r2);
                     acc += E0[tt * n + j] * r0 + E1[tt * n + j] * r1 + E2[tt * n + j] * r2;
                 }
             }
@@ -1046,6 +1068,79 @@ __global__ __launch_bounds__(256) void fbr_fourier_grad_finish_kernel(int C, int
         for (long tb = 0; tb < ntb; tb++) acc += pc[(tb * n + j) * K + k];
     }
     out[e] = acc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K6c: chain of rows of position sensitivities, each at ONE time, with the position Jacobian of the series (fbr_fourier_position_chain):
+// row r of candidate c carries grad_q [n] = d(something) / d(q at t = sample / freq) and
+//   out [c][r][p] = scale sum_d grad_q[d] dq_d(t) / dp,        p over [wf | q_offset (n) | q_range (n) | a (n, nh) | b (n, nh)]
+// (the layout and conventions of K6b's output).  One thread per entry; a joint whose grad_q entry is an exact 0 (most: a collision pair
+// moves with the joints between its two links only) costs nothing.  The wf entry adds its joints in ascending order: no atomics.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double fbr_fourier_dq_dp(int kind, int l, bool bounded, int nh, double w, double ts, const double *aa, const double *bb,
+                                                    double qr)
+{  // kind 0 wf, 1 q_offset, 2 q_range, 3 a_l, 4 b_l
+    if (kind == 1) return 1.0;
+    double f = 1.0, th = 0.0;
+    if (bounded) {
+        double raw, rd, rdd;
+        fbr_fourier_raw(nh, w, ts, aa, bb, raw, rd, rdd);
+        th = tanh(raw);
+        f = qr * (1.0 - th * th);
+    }
+    if (kind == 2) return bounded ? th : 0.0;
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0, sn, cs;
+    if (kind == 0) {
+        for (int h = 1; h <= nh; h++) {
+            const double dl = (double)h;
+            sincos(w * (ts * dl), &sn, &cs);
+            fbr_fourier_dwf_add(bounded, w, ts, dl, aa[h - 1], bb[h - 1], sn, cs, r0, r1, r2);
+        }
+    } else {
+        const double dl = (double)l;
+        sincos(w * (ts * dl), &sn, &cs);
+        fbr_fourier_dcoef(bounded, kind == 4, w * dl, sn, cs, r0, r1, r2);
+    }
+    return bounded ? f * r0 : r0;
+}
+
+__global__ __launch_bounds__(256) void fbr_fourier_poschain_kernel(int C, long R, int n, int nh, double freq, const double *__restrict__ wf,
+                                                                   const double *__restrict__ a, const double *__restrict__ b,
+                                                                   const double *__restrict__ qrange, const long *__restrict__ sample,
+                                                                   const double *__restrict__ scale, const double *__restrict__ gq,
+                                                                   double *__restrict__ out)
+{
+    const int E = 1 + 2 * n + 2 * n * nh;
+    const long total = (long)C * R * E;
+    const bool bounded = qrange != nullptr;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long cr = e / E;
+        const int i = (int)(e - cr * E), c = (int)(cr / R);
+        const long s = sample[cr];
+        double v = 0.0;
+        if (s >= 0) {
+            const double ts = (double)s / freq, w = wf[c];
+            const double *g = gq + cr * n, *ca = a + (long)c * n * nh, *cb = b + (long)c * n * nh;
+            if (i == 0) {
+                for (int j = 0; j < n; j++)
+                    if (g[j] != 0.0) v += g[j] * fbr_fourier_dq_dp(0, 0, bounded, nh, w, ts, ca + j * nh, cb + j * nh, bounded ? qrange[(long)c * n + j] : 0.0);
+            } else {
+                int j, kind, l = 0;
+                if (i < 1 + 2 * n) {
+                    j = (i - 1) % n;
+                    kind = 1 + (i - 1) / n;
+                } else {
+                    const int r = i - 1 - 2 * n, isb = r >= n * nh, rr = r - isb * n * nh;
+                    j = rr / nh;
+                    kind = 3 + isb;
+                    l = 1 + (rr - j * nh);
+                }
+                if (g[j] != 0.0) v = g[j] * fbr_fourier_dq_dp(kind, l, bounded, nh, w, ts, ca + j * nh, cb + j * nh, bounded ? qrange[(long)c * n + j] : 0.0);
+            }
+            v *= scale ? scale[cr] : 1.0;
+        }
+        out[e] = v;
+    }
 }
 
 #endif  // FBR_KERNELS_CORE

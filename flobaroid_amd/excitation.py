@@ -11,7 +11,9 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``candidate_collision_constraints`` -- its collision block in capsule mode (``collisionMode: "capsule"``, robot links) from
   ``Engine.candidate_capsule_distances``; ``candidate_objectives(..., collision=...)`` appends it to ``g``;
 * ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
-  candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``.
+  candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``;
+* ``candidate_collision_gradient`` -- the collision rows of the constraint Jacobian in capsule mode (analyticalGradient.py:955-1027) from
+  ``Engine.capsule_distance_gradients`` + ``Engine.fourier_position_chain``.
 """
 from __future__ import annotations
 
@@ -258,7 +260,10 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
     (C, P) (1e10 where no configuration won), ``idx`` (C, P): the winning sample, or the reference's negative count -1, -2, ... of a
     transition configuration (-1 also stands for "none won": then g is 1e10), ``argmin`` (C, P): the winning main-trajectory sample (-1:
     none), ``dist`` (C, P): the raw main-trajectory minima.  ``margins`` (P,): per-pair clearance subtracted from the distances
-    (``_collision_pair_margins``; None: 0).  Not covered: the mesh modes, world links, the distance gradient."""
+    (``_collision_pair_margins``; None: 0).  ``eval_sample``, ``eval_scale``, ``eval_pose`` (C, P) describe the winning configuration
+    ``eval_scale * q[eval_sample]`` at the base pose of sample ``eval_pose`` -- (idx, 1, idx) on the main trajectory, (0 or T - 1,
+    s(tau), the pose's sample) for a transition configuration, -1 where none won: the arguments of ``Engine.capsule_distance_gradients``
+    (``candidate_collision_gradient``).  Not covered: the mesh modes, world links."""
     _check_config(config)
     C = int(ncand)
     q = states["q"]
@@ -272,6 +277,7 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
     m = np.zeros(P) if margins is None else np.asarray(margins, dtype=np.float64).reshape(P)
     g = np.where(idx >= 0, dist - m, 1e10)
     out_idx = idx.copy()
+    ev_sample, ev_scale, ev_pose = idx.copy(), np.where(idx >= 0, 1.0, -1.0), idx.copy()
     ns = int(config.get("transitionCollisionSamples", 10))
     if config.get("transitionDuration", 3.0) > 0 and ns > 0 and S == C * T and T > 0:
         torch_in = hasattr(q, "cpu")
@@ -316,7 +322,13 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
         take = (it >= 0) & (gt < g)
         g = np.where(take, gt, g)
         out_idx = np.where(take, ref_idx, out_idx)
-    return {"g": g, "idx": out_idx, "argmin": idx, "dist": dist}
+        # the winning transition configuration s(tau) q[boundary] at the base pose of sample poses[.]: flat index ((boundary, tau), pose)
+        tr_sample = np.where(kk // (ns * npose) == 0, 0, T - 1)
+        ev_sample = np.where(take, tr_sample, ev_sample)
+        ev_scale = np.where(take, sv[(kk // npose) % ns], ev_scale)
+        ev_pose = np.where(take, np.take_along_axis(poses, kk % npose, axis=1) if rpy is not None else tr_sample, ev_pose)
+    return {"g": g, "idx": out_idx, "argmin": idx, "dist": dist, "eval_sample": ev_sample.astype(np.int64), "eval_scale": ev_scale,
+            "eval_pose": ev_pose.astype(np.int64)}
 
 
 def _collision_block(engine, states, ncand, config, collision):
@@ -365,8 +377,8 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
 # ------------------------------------------------------------------------------------------------------------------------------------
 # The D-optimality term of the optimiser's gradient per candidate (analyticalGradient.py compute_analytical_gradient, Phases 1, A and B,
 # lines 538-762): weight rows on the device (Engine.regressor_weights), the finite-difference sweep (Engine.fd_scores) and the chain with
-# the Jacobian of the Fourier series (Engine.fourier_gradient).  Not covered: the soft-cost / constraint gradients of Phase C, the
-# collision gradient, the suspended base.
+# the Jacobian of the Fourier series (Engine.fourier_gradient).  The collision rows of the constraint Jacobian: candidate_collision_gradient
+# below.  Not covered: the soft-cost, torque and limit gradients of Phase C, the suspended base.
 # ------------------------------------------------------------------------------------------------------------------------------------
 def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4, dopt_scale=1.0, YtY_prior=None, B=None):
     """The constant matrices of ``Engine.regressor_weights`` for C candidates from their Grams ``G`` (C, Pa, Pa) (``Engine.gram_grouped``):
@@ -491,3 +503,96 @@ def gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bo
             dq0 = (gq + np.asarray(grad["q_range"], dtype=np.float64).reshape(n) * dqr) * inside * deg
     ga, gb = np.asarray(grad["a"], dtype=np.float64), np.asarray(grad["b"], dtype=np.float64)
     return np.concatenate([[float(np.asarray(grad["wf"]))], dq0] + [ga[j, :nf[j]] for j in range(n)] + [gb[j, :nf[j]] for j in range(n)])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The collision rows of the constraint Jacobian per candidate (analyticalGradient.py:955-1027, capsule.py capsule_distance_and_gradient):
+# the distance gradient at each pair's winning configuration (Engine.capsule_distance_gradients) chained with the position Jacobian of the
+# Fourier series at that configuration's time (Engine.fourier_position_chain).  Two deliberate deviations from the reference:
+# the lever arm of a closest point is v + omega x r, and a transition configuration s(tau) q[boundary] is chained with s(tau) times the
+# Jacobian at the boundary sample, not with the Jacobian at an index wrapped round from the end of the time array.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _padded_coefficients(candidates: list, n: int):
+    C = len(candidates)
+    nh = max(c["a"].shape[1] for c in candidates)
+    A, B = np.zeros((C, n, nh)), np.zeros((C, n, nh))
+    for i, c in enumerate(candidates):
+        A[i, :, : c["a"].shape[1]] = c["a"]
+        B[i, :, : c["b"].shape[1]] = c["b"]
+    bounded = [c["q_range"] is not None for c in candidates]
+    if any(bounded) and not all(bounded):
+        raise ValueError("classic and bounded candidates cannot share one batch")
+    return A, B, nh, (np.stack([c["q_range"] for c in candidates]) if all(bounded) else None)
+
+
+def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: list, freq: float, config: dict, collision: dict,
+                                 constraints: dict | None = None, max_bytes: int = 2**31) -> dict:
+    """The collision block ``g = distance - margin`` (C, P) of ``ncand`` equal candidates stacked in ``states`` and its derivative with
+    respect to the entries of the candidates' ``fourier_coefficients`` dicts, from which ``states`` were generated at ``freq`` Hz
+    (``candidate_states``).  ``collision``: capsules, pairs and optionally margins (``flobaroid_amd.collision.collision_set``);
+    ``constraints``: the result of ``candidate_collision_constraints`` for the same states and set, when the caller has it (None: computed).
+
+    Returns ``{"g": (C, P), "grad": {"wf": (C, P), "q_offset": (C, P, n), "q_range": (C, P, n) (zeros for classic candidates), "a" / "b":
+    (C, P, n, nh)}, "grad_q": (C, P, n)}`` as NumPy arrays: the margins are constants, so a row of ``grad`` is the derivative of the
+    pair's distance at its winning configuration, held fixed (the reference's rule); a pair without a winner has a zero row.  ``grad_q`` is
+    the derivative with respect to the evaluated configuration itself.  The chain runs over chunks of whole candidates whose output stays
+    within ``max_bytes``; columns that only pad ``a`` / ``b`` to a common width are removed (nh = the widest candidate's).  The base pose
+    of a floating base is held constant, as in the reference."""
+    _check_config(config)
+    if config.get("collisionMode", "capsule") != "capsule":
+        raise ValueError("the collision gradient on the device covers collisionMode 'capsule' only (no mesh code: DESIGN 9)")
+    C, n = int(ncand), engine.n
+    engine.set_capsules(collision["capsules"], collision["pairs"])
+    cons = constraints if constraints is not None else candidate_collision_constraints(engine, states, C, config, margins=collision.get("margins"))
+    bpos = states.get("base_position") if engine.floating else None
+    dg = engine.capsule_distance_gradients(states, C, cons["eval_sample"], scale=cons["eval_scale"], pose_sample=cons["eval_pose"], base_pos=bpos)
+    A, B, nh, qr = _padded_coefficients(candidates, n)
+    wf = np.array([c["wf"] for c in candidates], dtype=np.float64)
+    P = int(cons["g"].shape[1])
+    E = 1 + 2 * n + 2 * n * nh
+    cc = max(1, min(C, int(max_bytes) // max(P * E * 8, 1)))
+    out = np.empty((C, P, E))
+    for c0 in range(0, C, cc):
+        c1 = min(C, c0 + cc)
+        out[c0:c1] = _host(engine.fourier_position_chain(wf[c0:c1], A[c0:c1], B[c0:c1], cons["eval_sample"][c0:c1], dg["grad_q"][c0:c1], float(freq),
+                                                         scale=cons["eval_scale"][c0:c1], q_range=None if qr is None else qr[c0:c1]))
+    grad = {"wf": out[..., 0].copy(), "q_offset": out[..., 1:1 + n].copy(), "q_range": out[..., 1 + n:1 + 2 * n].copy(),
+            "a": out[..., 1 + 2 * n:1 + 2 * n + n * nh].reshape(C, P, n, nh).copy(), "b": out[..., 1 + 2 * n + n * nh:].reshape(C, P, n, nh).copy()}
+    return {"g": np.asarray(cons["g"]), "grad": grad, "grad_q": np.asarray(_host(dg["grad_q"]))}
+
+
+def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
+                                                   max_bytes: int = 2**31) -> dict:
+    """``candidate_collision_gradient`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
+    (``candidate_states``) and never leave it; only the per-pair rows come back."""
+    st = candidate_states(engine, candidates, int(T), float(freq), device=True)
+    return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes)
+
+
+def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
+                                               joint_limits=None, q0=None) -> np.ndarray:
+    """``gradient_to_optimizer_variables`` for every row of ONE candidate's constraint block at once: ``grad`` holds ``wf`` (P,),
+    ``q_offset`` / ``q_range`` (P, n), ``a`` / ``b`` (P, n, nh) (``{k: v[c] for k, v in candidate_collision_gradient(...)["grad"].items()}``);
+    returns (P, n_vars) on the reference's variable vector ``[wf | q0 (n) | a_0[:nf_0] .. | b_0[:nf_0] ..]`` -- the block that goes at rows
+    ``constraint_layout(...)["collision"]`` of its ``con_grad``.  The other arguments as for ``gradient_to_optimizer_variables``."""
+    nf = [int(x) for x in nf]
+    n = len(nf)
+    if bounded is None:
+        bounded = candidate.get("q_range") is not None
+    deg = np.pi / 180.0 if use_deg else 1.0
+    gq = np.asarray(grad["q_offset"], dtype=np.float64).reshape(-1, n)
+    if not bounded:
+        dq0 = gq * np.asarray(nf, dtype=np.float64)[None] * deg
+    else:
+        dq0 = gq * deg
+        if exact:
+            lo = np.array([l[0] for l in joint_limits], dtype=np.float64)
+            hi = np.array([l[1] for l in joint_limits], dtype=np.float64)
+            raw = 0.5 * (lo + hi) + np.asarray(q0, dtype=np.float64) * deg
+            inside = ((raw > lo) & (raw < hi)).astype(np.float64)
+            qc = np.clip(raw, lo, hi)
+            dqr = 0.95 * np.where(qc - lo <= hi - qc, 1.0, -1.0)
+            dq0 = (gq + np.asarray(grad["q_range"], dtype=np.float64).reshape(-1, n) * dqr[None]) * inside[None] * deg
+    ga, gb = np.asarray(grad["a"], dtype=np.float64), np.asarray(grad["b"], dtype=np.float64)
+    return np.concatenate([np.asarray(grad["wf"], dtype=np.float64).reshape(-1, 1), dq0] + [ga[:, j, :nf[j]] for j in range(n)]
+                          + [gb[:, j, :nf[j]] for j in range(n)], axis=1)

@@ -86,7 +86,7 @@ typedef struct {
  * the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info, option "fused_id"; 102: fbr_gram_lane_info, options
  * "gram_lane" / "gram_force_tiles"; 103: fbr_candidate_extrema; 104: fbr_model_set_capsules, fbr_candidate_capsule_distances, and -- added under the same number, which
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
- * fbr_fourier_gradient. */
+ * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -168,6 +168,29 @@ int fbr_model_set_capsules(fbr_model *m, int32_t ncaps, const int32_t *link, con
  */
 int fbr_candidate_capsule_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step,
                                     double *dist_out, int64_t *idx_out, int32_t out_mem);
+
+/*
+ * Capsule distance and its derivative with respect to the joint positions at ONE chosen configuration per candidate and pair -- the
+ * collision block of the reference's analytical gradient (excitation/analyticalGradient.py:955-1027 with capsule.py
+ * capsule_distance_and_gradient), for the configurations fbr_candidate_capsule_distances found.  st, base_pos, ncand as there (ncand equal
+ * candidates of T = num_samples / ncand samples; only q and base_rpy are read).  Arrays [ncand][npairs], in st->mem:
+ *   sample       int64: the sample inside the candidate whose row of q is taken; -1: no evaluation (dist_out 1e10, a zero gradient row)
+ *   scale        or NULL (1): the evaluated configuration is scale * q[sample] (a transition ramp s(tau) q)
+ *   pose_sample  int64 or NULL (= sample; an entry -1 also means sample): the sample whose base pose (base_rpy, base_pos) is used
+ * Outputs (out_mem):
+ *   dist_out [ncand][npairs]       the capsule distance there: the segment routine of fbr_candidate_capsule_distances, minus the radii
+ *   grad_q_out [ncand][npairs][n]  d dist / d(the evaluated configuration): n . (dp_A/dq_j - dp_B/dq_j), n the unit vector between the closest
+ *                                  points p_A, p_B, each moving rigidly with its link (revolute joint j above the link: z_j x (p - o_j);
+ *                                  prismatic: z_j).  Joints that are not on the tree path between the two links are exact zeros.  The
+ *                                  base pose is held constant.  Multiply by scale for the derivative with respect to q[sample].
+ * Zero row where |p_A - p_B| < 1e-12 (the reference's rule); a NaN pose gives NaN in dist_out and in the path joints' entries.  The
+ * lever arm is v + omega x r: the reference's _point_jacobian has the opposite sign of the cross product.  No atomics:
+ * the same bits on every run.
+ * FBR_E_INVALID: no capsule set or one without pairs, ncand < 1, num_samples 0 or not a multiple of ncand, a sample or pose_sample outside
+ * -1 .. T - 1 (found on the device, which reads such an entry clamped; the outputs are then undefined).
+ */
+int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                   const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem);
 
 /*
  * tau_out [S][rows] = Y_s . x for an identified-parameter vector x (host, length cols) WITHOUT
@@ -274,6 +297,19 @@ int fbr_fourier_states(fbr_model *m, int32_t ncand, int64_t T, int32_t nharm, do
 int fbr_fourier_gradient(fbr_model *m, int32_t ncand, int64_t T, int32_t tstride, int32_t nharm, double freq, const double *wf, const double *a,
                          const double *b, const double *q_range, const double *sens_q, const double *sens_dq, const double *sens_ddq,
                          int32_t sens_mem, double *out, int32_t out_mem);
+
+/*
+ * Chain of rows of position sensitivities, each taken at ONE time, with the position Jacobian of the same series: nrows rows per candidate
+ * (the collision pairs of fbr_capsule_distance_gradients), sample / scale [ncand][nrows] and grad_q [ncand][nrows][n] in `mem` space
+ * (sample int64; scale may be NULL: 1); wf, a, b, q_range host arrays as for fbr_fourier_gradient.
+ *   out [ncand][nrows][1 + 2 n + 2 n nharm] (out_mem), the column layout and conventions of fbr_fourier_gradient (padding harmonics
+ *   differentiated too, the q_range columns zero when q_range == NULL):  entry = scale * sum_d grad_q[d] * dq_d/dp at t = sample / freq,
+ *   every derivative analytic (wf too).  A row with sample < 0 is zero.  The wf entry adds its joints in ascending order: the same bits on
+ *   every run.
+ */
+int fbr_fourier_position_chain(fbr_model *m, int32_t ncand, int64_t nrows, int32_t nharm, double freq, const double *wf, const double *a,
+                               const double *b, const double *q_range, const int64_t *sample, const double *scale, const double *grad_q,
+                               int32_t mem, double *out, int32_t out_mem);
 
 /*
  * R_out [(cols+k)][(cols+k)] upper triangular with R^T R = [Y|rhs]^T [Y|rhs], by blocked Householder
