@@ -574,6 +574,7 @@ static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGr
 // The producer's rhs moments for k rhs columns (k <= FBR_G64_MAXK): per producer workgroup and lane, running sum r * cols + c =
 // (w Y_c)^T (w rhs_r), then the upper triangle of (w rhs_i)^T (w rhs_j) row by row (k = 2: 00, 01, 11).  k = 1: [cols + 1].
 #define FBR_G64_MAXK 2
+#include "fbr_mom_lanes.h"  // fbr_gram64_mom_lane, fbr_mom_lanes_sum: the sum of a moment over the lanes of a wave
 FBR_HD int fbr_gram64_mom_count(int cols, int k) { return k * cols + k * (k + 1) / 2; }
 // the entry (row, col), row <= col, of the (cols + k)^2 Gram that running sum idx belongs to (its mirror image too when row != col)
 FBR_HD void fbr_gram64_mom_target(int cols, int k, int idx, int *row, int *col)
@@ -589,7 +590,69 @@ FBR_HD void fbr_gram64_mom_target(int cols, int k, int idx, int *row, int *col)
     *col = cols + i + e;
 }
 
+// What the lanes of a producer wave add a link's moments to, [nparts][L][64]: lane fbr_gram64_mom_lane(p, r) of (part, link) holds column
+// lcol[p] of that part and link | r << 24 (r: the rhs column), lane fbr_gram64_mom_fric_lane(pf, r) the friction column pf of the link's
+// joint; every other lane, and the lane of a column the part does not write, -1.  One coalesced load per link gives a lane its running sum.
+#define FBR_G64_LANECOL_RHS 24
+static inline std::vector<int> fbr_gram64_lane_columns(const FbrGram64Producer &pr, int L)
+{
+    std::vector<int> t((size_t)pr.nparts * L * 64, -1);
+    for (int pq = 0; pq < pr.nparts; pq++)
+        for (int l = 0; l < L; l++)
+            for (int r = 0; r < FBR_G64_MAXK; r++) {
+                int *row = &t[((size_t)pq * L + l) * 64];
+                for (int p = 0; p < 10; p++) {
+                    const int c = pr.lcol[((size_t)pq * L + l) * 10 + p];
+                    if (c >= 0) row[fbr_gram64_mom_lane(p, r)] = c | r << FBR_G64_LANECOL_RHS;
+                }
+                for (int pf = 0; pf < FBR_G64_FRIC; pf++) {
+                    const int c = pr.lcol[(size_t)pr.nparts * 10 * L + ((size_t)pq * L + l) * FBR_G64_FRIC + pf];
+                    if (c >= 0) row[fbr_gram64_mom_fric_lane(pf, r)] = c | r << FBR_G64_LANECOL_RHS;
+                }
+            }
+    return t;
+}
+
 #if defined(__HIPCC__) && defined(FBR_KERNELS_GRAM)
+// The exchanges of fbr_mom_lanes_sum on the device: register moves only (v_permlane32_swap / v_permlane16_swap of gfx950 for the halves
+// and the rows, DPP moves inside a row) -- nothing through the LDS, nothing on lgkmcnt.  Every lane of the wave must be running.
+struct FbrMomLanesDev {
+    int lane;
+    template <int CTRL>
+    static __device__ __forceinline__ double dpp(double v)
+    {
+        const long b = __builtin_bit_cast(long, v);
+        const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, true), hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
+        return __builtin_bit_cast(double, ((long)(unsigned)hi << 32) | (long)(unsigned)lo);
+    }
+    static __device__ __forceinline__ void put(double &a, double &b, unsigned l0, unsigned l1, unsigned h0, unsigned h1)
+    {
+        a = __builtin_bit_cast(double, ((long)h0 << 32) | (long)l0);
+        b = __builtin_bit_cast(double, ((long)h1 << 32) | (long)l1);
+    }
+    __device__ __forceinline__ void swap32(double &a, double &b) const
+    {
+        const long x = __builtin_bit_cast(long, a), y = __builtin_bit_cast(long, b);
+        const auto l = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)y, false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap((unsigned)(x >> 32), (unsigned)(y >> 32), false, false);
+        put(a, b, l[0], l[1], h[0], h[1]);
+    }
+    __device__ __forceinline__ void swap16(double &a, double &b) const
+    {
+        const long x = __builtin_bit_cast(long, a), y = __builtin_bit_cast(long, b);
+        const auto l = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)y, false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap((unsigned)(x >> 32), (unsigned)(y >> 32), false, false);
+        put(a, b, l[0], l[1], h[0], h[1]);
+    }
+    __device__ __forceinline__ double get8(double a) const { return dpp<0x128>(a); }  // row_ror:8
+    __device__ __forceinline__ double get7(double a) const { return dpp<0x141>(a); }  // row_half_mirror
+    __device__ __forceinline__ double get2(double a) const { return dpp<0x4E>(a); }   // quad_perm:[2,3,0,1]
+    __device__ __forceinline__ double get1(double a) const { return dpp<0xB1>(a); }   // quad_perm:[1,0,3,2]
+    __device__ __forceinline__ double live0(bool live, double a) const { return live ? a : 0.0; }
+    __device__ __forceinline__ double bit8(double a, double b) const { return (lane & 8) ? b : a; }
+    __device__ __forceinline__ double zero() const { return 0.0; }
+};
+
 struct DevGram64 {
     int NT, nlev, maxact, npieces, nstage;  // NT: main + force tiles
     long blk_doubles;
@@ -600,9 +663,13 @@ struct DevGram64 {
 // ------------------------------------------------------------------------------------------------
 // Producer: the lane writer of fbr_kinid.h with the image addressing of this pass.  Destination word of a (column, row): address of the
 // slab position of column slot c, sample 0 (256-byte aligned) | the slot's swizzle in its low byte; sample slot s of block b goes to
-// + b * blk_doubles + (s >> 5) * 512 + ((s & 31) ^ x).  The positions of the lanes behind the last sample of the last block are cleared by the host before the launch (the Gram
-// kernel runs whole blocks).  mom (k >= 1; KR = max(k, 1) rhs columns, row-major [S rows][k]): [workgroup][fbr_gram64_mom_count][64] per-lane running sums of
-// (w Y)^T (w rhs_r) per column and of (w rhs_i)^T (w rhs_j), added in block order.  The KR = 1 instances serve k = 0 and k = 1.
+// + b * blk_doubles + (s >> 5) * 512 + ((s & 31) ^ x).  ALL 64 lanes of the last block of a group run: the lanes behind its last sample walk the tree on that
+// sample (the wave-wide sums below exchange registers between lanes, which must be defined) and write its values to their own positions, which
+// fbr_gram64_tail_zero_kernel clears AFTER this kernel (the Gram kernel runs whole blocks).  mom (k >= 1; KR = max(k, 1) rhs columns, row-major [S rows][k]):
+// [workgroup][fbr_gram64_mom_count] running sums of (w Y)^T (w rhs_r) per column and of (w rhs_i)^T (w rhs_j).  A link's products are summed over the live lanes
+// of the wave in registers (fbr_mom_lanes_sum: a fixed order), lane fbr_gram64_mom_lane(p, r) ends up with the sum of parameter p for rhs column r, and ONE no-return atomic per
+// (part, link) adds them, each lane to the running sum of its own column; one wave adds to an address, in block order.  The KR = 1 instances serve
+// k = 0 and k = 1.
 // ------------------------------------------------------------------------------------------------
 template <int MAXD, bool HASW, int KR = 1>
 __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void fbr_kinimg_kernel(DevModel m, DevKinId p, DevKinWrite wr, long S, long blk_doubles,
@@ -619,12 +686,15 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
     double *sq = smem, *sdq = sq + 64 * ldn, *sddq = sdq + 64 * ldn, *sw = sddq + 64 * ldn;  // sw [64][ldw] row weights (has_w)
     double *st = sw + (HASW ? 64 * ldw : 0);                                             // st [KR][64][ldw] w^2 rhs_r (k >= 1)
     double *scr = scratch + ((long)blockIdx.x * wr.nparts + part) * p.nslots * FBR_LINK_REC * 64 + lane;
-    double *mo = mom ? mom + (long)blockIdx.x * (KR * wr.cols + KR * (KR + 1) / 2) * 64 : nullptr;  // [fbr_gram64_mom_count(cols, KR)][64 lanes]
+    double *mo = mom ? mom + (long)blockIdx.x * (KR * wr.cols + KR * (KR + 1) / 2) : nullptr;  // [fbr_gram64_mom_count(cols, KR)]
+    const bool domom = KR > 1 || wr.k != 0;
+    const FbrMomLanesDev mx{lane};
     // sample groups (fbr_gram_grouped): every group starts a block -- block b = (group b / bpg, block b % bpg of the group)
     const long Sg = wr.group_samples > 0 ? wr.group_samples : S, bpg = (Sg + 63) >> 6;
     const long nblk = (S / Sg) * bpg;
     const fbr_clong_ptr cdst = (fbr_clong_ptr)(unsigned long)wr.dst;
-    const fbr_cint_ptr ccol = (fbr_cint_ptr)(unsigned long)(wr.lcol10 + (long)part * 10 * m.L);
+    // what this lane adds the moments of (part, link 0) to (fbr_gram64_lane_columns); a global load: vmcnt only
+    const __attribute__((address_space(1))) int *glcol = (const __attribute__((address_space(1))) int *)(unsigned long)wr.lanecol + (long)part * m.L * 64 + lane;
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const long grp = blk / bpg, lb = blk - grp * bpg;
         const long base = grp * Sg + (lb << 6);
@@ -707,7 +777,22 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
             // Every vector load of the step (branch records, states) is waited for HERE, once: the stores below share the loads' counter, and
             // behind the branches of the column code the compiler cannot tell how many of them sit in front of a load it still expects --
             // it would wait for counter 0, i.e. for the store before, at every store (measured: 7.4 -> 5.4 ms per 1 M WALK-MAN samples).
+            // (the running sum this lane adds to at the end of the link, or -1: one vector load, in front of the wait, which it shares)
+            int mycol = -1;
+            if (domom) mycol = glcol[l * 64];
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt untouched
+            // what this lane adds: the groups' sums land in it by lane pattern (fbr_gram64_mom_lane: parameters 0 .. 3 in lanes 0 mod 16, 4 .. 9 in lanes 1 mod
+            // 8, rhs column 1 six lanes further on; the classes of absent columns hold exact zeros), the lanes that matter are those with a column
+            double macc = 0.0;
+            // the products of parameters P0 .. P0 + NQ - 1 (v: [NQ]) summed over the wave, at their places in the group of NG parameters that starts at G0
+            auto mom_sum = [&](auto g0c, auto ngc, auto p0c, auto nqc, const double *v, int r) {
+                constexpr int G0 = decltype(g0c)::value, NG = decltype(ngc)::value, P0 = decltype(p0c)::value, NQ = decltype(nqc)::value;
+                double u[NG];
+#pragma unroll
+                for (int i = 0; i < NG; i++) u[i] = (G0 + i >= P0 && G0 + i < P0 + NQ) ? v[G0 + i - P0] : 0.0;
+                const double sum = fbr_mom_lanes_sum<NG>(u, live, mx);
+                if (G0 == 0 ? (lane & 15) == 6 * r : (lane & 7) == 1 + 6 * r) macc += sum;
+            };
             long d10[10], dF[4];
 #pragma unroll
             for (int pp = 0; pp < 10; pp++) d10[pp] = cdst[((long)part * m.L + l) * FBR_G64_WORDS + pp];
@@ -755,6 +840,7 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
             // One value to (column q of the group, level lv).  Scalar base (the column's word, 8192 bytes per level) + this lane's 32-bit
             // offset with the column's swizzle; a column the part does not write (word 0) skips the store only -- the products of a level
             // are computed for the whole group first, branch-free, so that their dependent chains overlap.
+            using std::integral_constant;
             auto store = [&](long d0, int lv, double v) {
                 if (d0 == 0) return;
                 const unsigned vo = vlane ^ ((unsigned)(d0 & 0xff) << 3);
@@ -782,20 +868,23 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) store(d10[Q0 + qq], m.fb + j, HASW ? v[qq] * wj : v[qq]);
                     }
-                if constexpr (KR == 1) {
-                    if (wr.k) {
+                long any = 0;  // (a group none of whose columns the part writes has no sums)
 #pragma unroll
-                        for (int qq = 0; qq < NQ; qq++)
-                            if (d10[Q0 + qq]) unsafeAtomicAdd(mo + (long)ccol[10 * l + Q0 + qq] * 64 + lane, fbr_dot6(Ft, wA[qq]));  // this lane's own running sum
-                    }
+                for (int qq = 0; qq < NQ; qq++) any |= d10[Q0 + qq];
+                if (!domom || any == 0) return;
+                double v[NQ];
+                if constexpr (KR == 1) {
+#pragma unroll
+                    for (int qq = 0; qq < NQ; qq++) v[qq] = fbr_dot6(Ft, wA[qq]);
+                    mom_sum(integral_constant<int, 0>{}, integral_constant<int, 4>{}, q0c, nqc, v, 0);
                 } else {
 #pragma unroll
                     for (int r = 0; r < KR; r++) {
                         double F[6];
                         ft_group(r, F);
 #pragma unroll
-                        for (int qq = 0; qq < NQ; qq++)
-                            if (d10[Q0 + qq]) unsafeAtomicAdd(mo + ((long)r * wr.cols + ccol[10 * l + Q0 + qq]) * 64 + lane, fbr_dot6(F, wA[qq]));
+                        for (int qq = 0; qq < NQ; qq++) v[qq] = fbr_dot6(F, wA[qq]);
+                        mom_sum(integral_constant<int, 0>{}, integral_constant<int, 4>{}, q0c, nqc, v, r);
                     }
                 }
             };
@@ -822,27 +911,26 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
 #pragma unroll
                         for (int qq = 0; qq < NQ; qq++) store(d10[4 + Q0 + qq], m.fb + j, HASW ? v[qq] * wj : v[qq]);
                     }
-                if constexpr (KR == 1) {
-                    if (wr.k) {
+                long any = 0;
 #pragma unroll
-                        for (int qq = 0; qq < NQ; qq++)
-                            if (d10[4 + Q0 + qq])
-                                unsafeAtomicAdd(mo + (long)ccol[10 * l + 4 + Q0 + qq] * 64 + lane, Ft[3] * nB[qq][0] + Ft[4] * nB[qq][1] + Ft[5] * nB[qq][2]);
-                    }
+                for (int qq = 0; qq < NQ; qq++) any |= d10[4 + Q0 + qq];
+                if (!domom || any == 0) return;
+                double v[NQ];
+                if constexpr (KR == 1) {
+#pragma unroll
+                    for (int qq = 0; qq < NQ; qq++) v[qq] = Ft[3] * nB[qq][0] + Ft[4] * nB[qq][1] + Ft[5] * nB[qq][2];
+                    mom_sum(integral_constant<int, 4>{}, integral_constant<int, 6>{}, integral_constant<int, 4 + Q0>{}, nqc, v, 0);
                 } else {
 #pragma unroll
                     for (int r = 0; r < KR; r++) {
                         double F[6];
                         ft_group(r, F);
 #pragma unroll
-                        for (int qq = 0; qq < NQ; qq++)
-                            if (d10[4 + Q0 + qq])
-                                unsafeAtomicAdd(mo + ((long)r * wr.cols + ccol[10 * l + 4 + Q0 + qq]) * 64 + lane,
-                                                F[3] * nB[qq][0] + F[4] * nB[qq][1] + F[5] * nB[qq][2]);
+                        for (int qq = 0; qq < NQ; qq++) v[qq] = F[3] * nB[qq][0] + F[4] * nB[qq][1] + F[5] * nB[qq][2];
+                        mom_sum(integral_constant<int, 4>{}, integral_constant<int, 6>{}, integral_constant<int, 4 + Q0>{}, nqc, v, r);
                     }
                 }
             };
-            using std::integral_constant;
             if constexpr (MAXD > 8 && MAXD <= 10) {  // (the instance that has to fit 256 registers for two waves per SIMD: smaller groups)
                 full_group(integral_constant<int, 0>{}, integral_constant<int, 2>{});
                 full_group(integral_constant<int, 2>{}, integral_constant<int, 2>{});
@@ -865,18 +953,22 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
                         const int c = cfr[pf];
                         const double fv = fbr_friction_value(m.coldesc[c].z, mysdq[dj], sign ? sign[s * n + dj] : 0.0, m.stribeck);
                         store(dfw, m.fb + depth - 1, HASW ? fv * myw[m.fb + dj] : fv);
-                        if constexpr (KR == 1) {
-                            if (wr.k) unsafeAtomicAdd(mo + (long)c * 64 + lane, fv * myt[m.fb + dj]);
-                        } else {
+                        if (!domom) continue;
 #pragma unroll
-                            for (int r = 0; r < KR; r++) unsafeAtomicAdd(mo + ((long)r * wr.cols + c) * 64 + lane, fv * myt[r * 64 * ldw + m.fb + dj]);
+                        for (int r = 0; r < KR; r++) {  // (one value: every lane gets the sum, lane fbr_gram64_mom_fric_lane(pf, r) keeps it)
+                            const double v = fv * myt[r * 64 * ldw + m.fb + dj], sum = fbr_mom_lanes_sum<1>(&v, live, mx);
+                            if (lane == fbr_gram64_mom_fric_lane(pf, r)) macc = sum;
                         }
                     }
             }
+            // the link's sums: lane fbr_gram64_mom_lane(p, r) adds parameter p's for rhs column r, to the running sum of its column (-1: the part does not
+            // write it) -- one atomic per link
+            if (domom && mycol >= 0 && (KR > 1 || mycol < (1 << FBR_G64_LANECOL_RHS)))
+                unsafeAtomicAdd(mo + (mycol >> FBR_G64_LANECOL_RHS) * wr.cols + (mycol & ((1 << FBR_G64_LANECOL_RHS) - 1)), macc);
         };
         auto emit = [&](int, double) {};
-        // lanes behind the last sample of the last block take no part (EXEC off): their image positions were cleared by the host
-        if (live) {
+        // (all lanes: the ones behind the last sample of the last block repeat that sample, see above)
+        {
             fbr_kinid_lane<MAXD, false>(wr.part_nsteps[part], p.maxlvl, p.steps + wr.part_step0[part] * FBR_KINID_STEP, p.endflush, m.floating, m.g, m.fb,
                                         state, basest, save, load, link, emit, consts);
             if constexpr (KR == 1) {
@@ -886,7 +978,8 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
                         const double wv = HASW ? myw[r] : 1.0, tv = rhs[s * rows + r] * wv;
                         tt += tv * tv;
                     }
-                    unsafeAtomicAdd(mo + (long)wr.cols * 64 + lane, tt);
+                    const double sum = fbr_mom_lanes_sum<1>(&tt, live, mx);
+                    if (lane == 0) unsafeAtomicAdd(mo + wr.cols, sum);
                 }
             } else if (part == wr.nparts - 1) {  // (w rhs_i)^T (w rhs_j), i <= j, row by row
                 double tt[KR * (KR + 1) / 2];
@@ -902,8 +995,13 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
 #pragma unroll
                         for (int j = i; j < KR; j++, e++) tt[e] += tv[i] * tv[j];
                 }
+                double mine = 0.0;  // (entry e in lane e, one atomic for the corner)
 #pragma unroll
-                for (int e = 0; e < KR * (KR + 1) / 2; e++) unsafeAtomicAdd(mo + ((long)KR * wr.cols + e) * 64 + lane, tt[e]);
+                for (int e = 0; e < KR * (KR + 1) / 2; e++) {
+                    const double sum = fbr_mom_lanes_sum<1>(&tt[e], live, mx);
+                    if (lane == e) mine = sum;
+                }
+                if (lane < KR * (KR + 1) / 2) unsafeAtomicAdd(mo + (long)KR * wr.cols + lane, mine);
             }
         }
     }
@@ -921,33 +1019,35 @@ __global__ __launch_bounds__(256) void fbr_gram64_tail_zero_kernel(double *__res
     }
 }
 
-// rhs moments of a call -> G (k rhs columns): one workgroup per running sum (fbr_gram64_mom_count of them) adds up that sum's per-lane
-// copies of the producer's workgroups in a fixed order; where it goes in G: fbr_gram64_mom_target
+// rhs moments of a call -> G (k rhs columns): one wave per running sum (fbr_gram64_mom_count of them, four to a workgroup) adds up that
+// sum's copies of the producer's nwg workgroups in a fixed order; where it goes in G: fbr_gram64_mom_target
 __global__ __launch_bounds__(256) void fbr_gram64_mom_reduce_kernel(int P, int k, int nwg, const double *__restrict__ mom, double *__restrict__ G)
 {
-    __shared__ double part[256];
-    const int c = blockIdx.x, t = threadIdx.x, nm = fbr_gram64_mom_count(P, k);
+    __shared__ double part[4][64];
+    const int w = threadIdx.x >> 6, t = threadIdx.x & 63, nm = fbr_gram64_mom_count(P, k), c = blockIdx.x * 4 + w;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;  // (independent running sums: the loads are far apart)
-    int i = t;
-    for (; i + 768 < nwg * 64; i += 1024) {
-        s0 += mom[((long)(i >> 6) * nm + c) * 64 + (i & 63)];
-        s1 += mom[((long)((i + 256) >> 6) * nm + c) * 64 + ((i + 256) & 63)];
-        s2 += mom[((long)((i + 512) >> 6) * nm + c) * 64 + ((i + 512) & 63)];
-        s3 += mom[((long)((i + 768) >> 6) * nm + c) * 64 + ((i + 768) & 63)];
+    if (c < nm) {
+        int i = t;
+        for (; i + 192 < nwg; i += 256) {
+            s0 += mom[(long)i * nm + c];
+            s1 += mom[(long)(i + 64) * nm + c];
+            s2 += mom[(long)(i + 128) * nm + c];
+            s3 += mom[(long)(i + 192) * nm + c];
+        }
+        for (; i < nwg; i += 64) s0 += mom[(long)i * nm + c];
     }
-    for (; i < nwg * 64; i += 256) s0 += mom[((long)(i >> 6) * nm + c) * 64 + (i & 63)];
-    part[t] = (s0 + s1) + (s2 + s3);
+    part[w][t] = (s0 + s1) + (s2 + s3);
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) part[t] += part[t + o];
+    for (int o = 32; o > 0; o >>= 1) {
+        if (t < o) part[w][t] += part[w][t + o];
         __syncthreads();
     }
-    if (t) return;
+    if (t || c >= nm) return;
     const int Pa = P + k;
     int row, col;
     fbr_gram64_mom_target(P, k, c, &row, &col);
-    G[(long)row * Pa + col] += part[0];
-    if (row != col) G[(long)col * Pa + row] += part[0];
+    G[(long)row * Pa + col] += part[w][0];
+    if (row != col) G[(long)col * Pa + row] += part[w][0];
 }
 
 // ------------------------------------------------------------------------------------------------

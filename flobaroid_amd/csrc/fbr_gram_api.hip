@@ -318,6 +318,7 @@ static int get_gram64(fbr_model *m, GramHolder *h)
     int rc;
     if ((rc = upload(h->pool, g.slab, &h->d64_slab)) || (rc = upload(h->pool, g.lev_begin, &h->d64_levb)) || (rc = upload(h->pool, g.pieces, &h->d64_pieces)) ||
         (rc = upload(h->pool, g.wmeta, &h->d64_wmeta)) || (rc = upload(h->pool, h->g64p.lcol, &h->d64_lcol)) ||
+        (rc = upload(h->pool, fbr_gram64_lane_columns(h->g64p, hm.L), &h->d64_lanecol)) ||
         (rc = upload(h->pool, h->g64p.steps, &h->d64_steps)) ||
         (rc = upload(h->pool, g.slot_tiles, &h->d64_slot_tiles)) || (rc = upload(h->pool, g.tilecol, &h->d64_tilecol)) ||
         (rc = upload(h->pool, g.stage_lev, &h->d64_stagelev)) || (!g.runs.empty() && (rc = upload(h->pool, g.runs, &h->d64_runs))))
@@ -420,6 +421,7 @@ static DevKinWrite gram64_kinwrite(const fbr_model *m, const GramHolder *h, int 
 {
     DevKinWrite kw{};
     kw.lcol10 = h->d64_lcol;
+    kw.lanecol = h->d64_lanecol;
     kw.dst = (const long *)h->dst64[b].p;
     kw.ninert = m->hm.ninert;
     kw.cols = m->hm.cols;
@@ -558,8 +560,8 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     const int pblocks = (int)std::min<long>(chb, (long)L.pgrid_max);
     const int gwgs = (int)std::min<long>(chb, (long)m->num_cus);
     if (k) {
-        if ((rc = h->mom64.ensure((size_t)L.pgrid_max * fbr_gram64_mom_count(hm.cols, k) * 64 * sizeof(double)))) return rc;
-        HIPCHK(hipMemsetAsync(h->mom64.p, 0, (size_t)pblocks * fbr_gram64_mom_count(hm.cols, k) * 64 * sizeof(double), m->stream));  // (the producer grid of this call)
+        if ((rc = h->mom64.ensure((size_t)L.pgrid_max * fbr_gram64_mom_count(hm.cols, k) * sizeof(double)))) return rc;
+        HIPCHK(hipMemsetAsync(h->mom64.p, 0, (size_t)pblocks * fbr_gram64_mom_count(hm.cols, k) * sizeof(double), m->stream));  // (the producer grid of this call)
     }
     if ((rc = m->partial.ensure((size_t)m->num_cus * g.wpb * g.npw * 256 * sizeof(double)))) return rc;
     int launches = 0, first_wgs = 0;
@@ -594,13 +596,15 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
         cur = nxt;
         if (s0 + chs < S && (rc = stage(launches + 1, nxt))) return rc;  // the copy of the next chunk is enqueued before this chunk's kernels
         if (h2d_chunked) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_h2d[b], 0));
-        if (cs & 63)  // the block the producer fills partly: what its idle lanes would have written (a buffer is reused from chunk to chunk)
-            HIPCHK(hipMemsetAsync(h->img64[b].as<double>() + (nb - 1) * g.blk_doubles, 0, (size_t)g.blk_doubles * sizeof(double), m->stream));
         {
             ProfScope ps(m, FBR_PROF_PACK);
             if ((rc = gram64_produce(m, h, L, gram64_kinwrite(m, h, b, k, dw != nullptr, base_only, 0), pblocks, plds, cs, cur.dc, cur.o, cur.rhs, k,
                                      cur.w, k ? h->mom64.as<double>() : nullptr)))
                 return rc;
+            if (cs & 63) {  // the block the producer fills partly: the lanes behind its last sample have written that sample again (all lanes run)
+                hipLaunchKernelGGL(fbr_gram64_tail_zero_kernel, dim3(16, 1), dim3(256), 0, m->stream, h->img64[b].as<double>(), g.blk_doubles, nb, g.ntr, (int)(cs & 63));
+                HIPCHK(hipGetLastError());
+            }
             if (h2d_chunked) {  // (the staging buffer may be refilled once this launch is through)
                 HIPCHK(hipEventRecord(m->ev_pack[b], m->stream));
                 m->ev_pack_rec[b] = true;
@@ -625,7 +629,7 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
         const int *wgb = nullptr;
         if ((rc = gram64_wg_table(h, first_wgs, &wgb)) || (rc = gram64_reduce(m, h, L, first_wgs, wgb, 1, G))) return rc;
         if (k) {
-            hipLaunchKernelGGL(fbr_gram64_mom_reduce_kernel, dim3(fbr_gram64_mom_count(hm.cols, k)), dim3(256), 0, m->stream, hm.cols, k, pblocks,
+            hipLaunchKernelGGL(fbr_gram64_mom_reduce_kernel, dim3((fbr_gram64_mom_count(hm.cols, k) + 3) / 4), dim3(256), 0, m->stream, hm.cols, k, pblocks,
                                h->mom64.as<double>(), G);
             HIPCHK(hipGetLastError());
         }
@@ -657,15 +661,15 @@ static int gram64_grouped_pass(fbr_model *m, GramHolder *h, const DevStates &d, 
     for (int g0 = 0, launches = 0; g0 < ngroups; g0 += gpc, launches++) {
         const int ng = std::min(gpc, ngroups - g0), b = launches & 1;
         const long s0 = (long)g0 * Sg, cs = (long)ng * Sg, nb = (long)ng * bpg;
-        if (Sg & 63) {  // every group ends in a block the producer fills partly: what its idle lanes would have written
-            hipLaunchKernelGGL(fbr_gram64_tail_zero_kernel, dim3(16, ng), dim3(256), 0, m->stream, h->img64[b].as<double>(), g.blk_doubles, bpg, g.ntr, (int)(Sg & 63));
-            HIPCHK(hipGetLastError());
-        }
         {
             ProfScope ps(m, FBR_PROF_PACK);
             if ((rc = gram64_produce(m, h, L, gram64_kinwrite(m, h, b, 0, dw != nullptr, false, Sg), (int)std::min<long>(nb, (long)L.pgrid_max), plds, cs,
                                      d, s0, nullptr, 0, dw, nullptr)))
                 return rc;
+            if (Sg & 63) {  // every group ends in a block the producer fills partly: its last lanes have written the group's last sample again
+                hipLaunchKernelGGL(fbr_gram64_tail_zero_kernel, dim3(16, ng), dim3(256), 0, m->stream, h->img64[b].as<double>(), g.blk_doubles, bpg, g.ntr, (int)(Sg & 63));
+                HIPCHK(hipGetLastError());
+            }
         }
         {
             ProfScope ps(m, FBR_PROF_GRAM);

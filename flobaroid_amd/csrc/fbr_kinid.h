@@ -294,6 +294,7 @@ typedef __attribute__((address_space(1))) char *fbr_gchar_ptr;
 typedef __attribute__((address_space(1))) double *fbr_gdouble_ptr;
 struct DevKinWrite {
     const int *lcol10, *colrec;  // lcol10 [parts][10 L]: the columns a part's wave writes; colrec [cols + 1][2]
+    const int *lanecol = nullptr;  // (fbr_kinimg_kernel) [parts][L][64]: the running sum a lane adds a link's moment to (fbr_gram64_lane_columns)
     const long *dst;
     int ninert, cols, k, has_w;
     int flev;  // (fbr_kinimg_kernel) base rows below this level go through the force-tile words
