@@ -492,9 +492,97 @@ struct FbrGram64Producer {
     std::vector<long long> rel;  // [nparts][L][14]
     std::vector<int> lcol;       // [nparts][10 L] the column (for the rhs moments) or -1, then [nparts][4 L] the friction columns of the link's joint
     std::vector<int> steps;      // the parts' step programs, one after the other
+    std::vector<int> none;       // [nparts][L] 1: the part writes no column of the link -- all 18 words zero, every lane column -1 (the producer skips the link's columns)
+    std::vector<int> starts;     // [nparts + 1] part p owns positions [starts[p], starts[p + 1]) of the depth-first order
 };
 
-static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGram64 &g, FbrGram64Producer &pr)
+// What a part of the producer costs its wave per block, in fp64 instructions counted from the kernel's code (not fitted to launch times):
+// a per step walked (the kinematic step: ancestors included), b per owned link (its column words, ten unit wrenches and moments),
+// c per owned entry (one dot product, weight and store: an inertial column has fb + depth of them, a friction column one), d per owned
+// entry more with rhs columns (the link's w^2 rhs vector, the columns' products with it and their sums over the wave).
+struct FbrGram64PartModel {
+    double a = 300.0, b = 400.0, c = 5.0, d = 1.0;
+};
+struct FbrGram64PartStats {
+    int steps = 0, links = 0, entries = 0, unowned = 0, discarded = 0;  // discarded: the 10 (fb + depth) entries a producer without the skip forms for each unowned link it walks
+    double cost = 0.0;
+};
+// the parts of cut points `starts` (fbr_kinid_build_parts_at) under model pm: ncol[l] inertial columns and nfr[l] friction columns written of link l
+static inline std::vector<FbrGram64PartStats> fbr_gram64_part_stats(const FbrHostModel &hm, const std::vector<int> &ncol, const std::vector<int> &nfr,
+                                                                    const std::vector<int> &starts, int k, const FbrGram64PartModel &pm)
+{
+    std::vector<FbrGram64PartStats> st(starts.size() - 1);
+    for (size_t p = 0; p + 1 < starts.size(); p++) {
+        std::vector<char> keep(hm.L, 0), mine(hm.L, 0);
+        for (int i = starts[p]; i < starts[p + 1]; i++) {
+            const int l = hm.order[i];
+            mine[l] = 1;
+            for (int a = l; a >= 0 && !keep[a]; a = hm.parent[a]) keep[a] = 1;
+        }
+        for (int l = 0; l < hm.L; l++) {
+            if (!keep[l]) continue;
+            const int e = ncol[l] * (hm.fb + (int)hm.path[l].size()) + nfr[l];
+            st[p].steps++;
+            if (mine[l]) {
+                st[p].links++;
+                st[p].entries += e;
+            } else {
+                st[p].unowned++;
+                st[p].discarded += 10 * (hm.fb + (int)hm.path[l].size());
+            }
+        }
+        st[p].cost = pm.a * st[p].steps + pm.b * st[p].links + (pm.c + (k > 0 ? pm.d : 0.0)) * st[p].entries;
+    }
+    return st;
+}
+// The cut that minimises the slowest part under pm, ancestors included: every choice of nparts contiguous ranges of the depth-first order
+// is tried (a model has a few dozen links; above 256 links, or with fewer links than parts, `old` stays).  Ties stay with `old`, the cut
+// fbr_kinid_build_parts made, then go to the cut nearest to it, then to the first one in the order of the search: the same cut every time.
+static inline std::vector<int> fbr_gram64_cut_parts(const FbrHostModel &hm, const std::vector<int> &ncol, const std::vector<int> &nfr,
+                                                    const std::vector<int> &old, int k, const FbrGram64PartModel &pm)
+{
+    const int L = hm.L, np = (int)old.size() - 1;
+    if (np != FBR_KINWRITE_PARTS || L > 256 || L < np) return old;
+    // cost of the range [i, j) as a part, for every i < j: links join one at a time, each bringing the ancestors not yet walked
+    std::vector<double> rc((size_t)(L + 1) * (L + 1), 0.0);
+    const double ce = pm.c + (k > 0 ? pm.d : 0.0);
+    std::vector<char> keep(L);
+    for (int i = 0; i < L; i++) {
+        std::fill(keep.begin(), keep.end(), 0);
+        double cost = 0.0;
+        for (int j = i; j < L; j++) {
+            const int l = hm.order[j];
+            for (int a = l; a >= 0 && !keep[a]; a = hm.parent[a]) keep[a] = 1, cost += pm.a;
+            cost += pm.b + ce * (ncol[l] * (hm.fb + (int)hm.path[l].size()) + nfr[l]);
+            rc[(size_t)i * (L + 1) + j + 1] = cost;
+        }
+    }
+    auto R = [&](int i, int j) { return rc[(size_t)i * (L + 1) + j]; };
+    auto worst = [&](int c1, int c2, int c3) { return std::max(std::max(R(0, c1), R(c1, c2)), std::max(R(c2, c3), R(c3, L))); };
+    int best[3] = {old[1], old[2], old[3]}, bestdist = 0;
+    double bestmax = worst(old[1], old[2], old[3]);
+    for (int c1 = 1; c1 < L - 2; c1++) {
+        if (R(0, c1) > bestmax) break;  // (a range only grows dearer)
+        for (int c2 = c1 + 1; c2 < L - 1; c2++) {
+            if (R(c1, c2) > bestmax) break;
+            for (int c3 = c2 + 1; c3 < L; c3++) {
+                const double w = worst(c1, c2, c3);
+                const int dist = std::abs(c1 - old[1]) + std::abs(c2 - old[2]) + std::abs(c3 - old[3]);
+                if (w < bestmax || (w == bestmax && dist < bestdist)) {
+                    bestmax = w;
+                    bestdist = dist;
+                    best[0] = c1, best[1] = c2, best[2] = c3;
+                }
+            }
+        }
+    }
+    return {0, best[0], best[1], best[2], L};
+}
+
+// cut (option gram_lane_parts_cut) 0: the parts of fbr_kinid_build_parts (about equal cost of the OWNED links).  1: fbr_gram64_cut_parts.
+// Which part writes a column changes neither the image nor any running sum.
+static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGram64 &g, FbrGram64Producer &pr, int cut = 0, int k = 1,
+                                             const std::vector<int> *force_starts = nullptr)
 {
     std::vector<int> tile_of(hm.cols, -1), slot_of(hm.cols, -1);
     for (int t = 0; t < g.NT; t++)
@@ -510,6 +598,24 @@ static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGr
     std::vector<std::vector<char>> own;
     try {
         fbr_kinid_build_parts(hm, lcost, FBR_KINWRITE_PARTS, progs, own);
+        pr.starts = fbr_kinid_parts_starts(hm, own);
+        if (cut || force_starts) {
+            std::vector<int> ncol(hm.L, 0), nfr(hm.L, 0);
+            for (int c = 0; c < hm.cols; c++) {
+                if (tile_of[c] < 0) continue;
+                if (c < hm.ninert) {
+                    ncol[hm.coldesc[c].link]++;
+                } else {
+                    for (int x = 0; x < hm.L; x++)
+                        if (hm.dof[x] == hm.coldesc[c].joint) nfr[x]++;
+                }
+            }
+            const std::vector<int> starts = force_starts ? *force_starts : fbr_gram64_cut_parts(hm, ncol, nfr, pr.starts, k, FbrGram64PartModel());
+            if (starts != pr.starts) {
+                fbr_kinid_build_parts_at(hm, starts, progs, own);
+                pr.starts = starts;
+            }
+        }
     } catch (const std::exception &) {
         return false;
     }
@@ -554,6 +660,11 @@ static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGr
                 pr.lcol[(size_t)pr.nparts * 10 * hm.L + ((size_t)pq * hm.L + l) * FBR_G64_FRIC + p] = c;
             }
     }
+    pr.none.assign((size_t)pr.nparts * hm.L, 1);
+    for (int pq = 0; pq < pr.nparts; pq++)
+        for (int l = 0; l < hm.L; l++)
+            for (int i = 0; i < FBR_G64_WORDS; i++)
+                if (pr.rel[((size_t)pq * hm.L + l) * FBR_G64_WORDS + i]) pr.none[(size_t)pq * hm.L + l] = 0;
     pr.steps.clear();
     pr.nslots = 1;
     for (int pq = 0; pq < pr.nparts; pq++) {
@@ -563,6 +674,43 @@ static inline bool fbr_gram64_build_producer(const FbrHostModel &hm, const FbrGr
         pr.steps.insert(pr.steps.end(), progs[pq].steps.begin(), progs[pq].steps.begin() + (size_t)progs[pq].nsteps * FBR_KINID_STEP);
     }
     return true;
+}
+
+// The chunks of a call of nblocks blocks that does not fit one chunk of `cap` blocks (cap >= num_cus): every chunk but the last has *chb
+// blocks, a multiple of num_cus, and the last takes what is left once that is at most *last_cap.  The Gram kernel runs a chunk in rounds
+// of num_cus workgroups, the producer in rounds of min(*chb, pgrid_max).
+// rule (option gram_lane_chunk_rounds) 0: chunks as large as the cap allows, the last one no larger.  1: the fewest Gram rounds, then
+// the fewest producer rounds, then the fewest chunks, then the largest chunks; the last chunk may be the largest (at most cap).
+struct FbrGram64ChunkPlan {
+    long chb = 0, last_cap = 0, chunks = 0, gram_rounds = 0, prod_rounds = 0;
+};
+static inline FbrGram64ChunkPlan fbr_gram64_chunk_plan(long nblocks, long cap, long num_cus, long pgrid_max, int rule)
+{
+    auto plan = [&](long chb, long last_cap) {
+        FbrGram64ChunkPlan p;
+        p.chb = chb;
+        p.last_cap = last_cap;
+        const long pb = std::min(chb, pgrid_max);
+        for (long left = nblocks; left > 0;) {
+            const long nb = left <= last_cap ? left : chb;
+            p.chunks++;
+            p.gram_rounds += (nb + num_cus - 1) / num_cus;
+            p.prod_rounds += (nb + pb - 1) / pb;
+            left -= nb;
+        }
+        return p;
+    };
+    const long a0 = cap / num_cus;
+    FbrGram64ChunkPlan best = plan(a0 * num_cus, a0 * num_cus);
+    if (!rule) return best;
+    for (long a = a0; a >= 1; a--) {
+        const FbrGram64ChunkPlan p = plan(a * num_cus, cap);
+        if (p.gram_rounds != best.gram_rounds ? p.gram_rounds < best.gram_rounds
+            : p.prod_rounds != best.prod_rounds ? p.prod_rounds < best.prod_rounds
+                                                : p.chunks < best.chunks)
+            best = p;
+    }
+    return best;
 }
 
 // (the form that takes the tile program too: the pass's tiles are its own, g.tiles)
@@ -774,6 +922,9 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
         auto link = [&](int l, int depth, const double *rec, const double (*Sst)[6], const int *lvd, double *F) {
             (void)F;
             if (wr.base_only) depth = 0;  // (row weights switch every joint row off: identifier.py:629-636 -- only the base-wrench rows are produced)
+            // (option gram_lane_skip_unowned) a link none of whose columns this part writes -- an ancestor walked for its kinematics: nothing
+            // to load, wait for, form or add.  The flag is the wave's: one scalar load.
+            if (wr.none && ((fbr_cint_ptr)(unsigned long)wr.none)[(long)part * m.L + l]) return;
             // Every vector load of the step (branch records, states) is waited for HERE, once: the stores below share the loads' counter, and
             // behind the branches of the column code the compiler cannot tell how many of them sit in front of a load it still expects --
             // it would wait for counter 0, i.e. for the store before, at every store (measured: 7.4 -> 5.4 ms per 1 M WALK-MAN samples).
@@ -839,7 +990,8 @@ __global__ __launch_bounds__(64 * FBR_KINWRITE_PARTS, MAXD <= 10 ? 2 : 1) void f
             };
             // One value to (column q of the group, level lv).  Scalar base (the column's word, 8192 bytes per level) + this lane's 32-bit
             // offset with the column's swizzle; a column the part does not write (word 0) skips the store only -- the products of a level
-            // are computed for the whole group first, branch-free, so that their dependent chains overlap.
+            // are computed for the whole group first, branch-free, so that their dependent chains overlap (the compiler keeps them outside
+            // the store branches).  A link with no written column at all has returned before it got here (wr.none).
             using std::integral_constant;
             auto store = [&](long d0, int lv, double v) {
                 if (d0 == 0) return;

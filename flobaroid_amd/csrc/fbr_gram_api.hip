@@ -313,13 +313,13 @@ static int get_gram64(fbr_model *m, GramHolder *h)
     // producer could not launch (a CU has 160 KB) stays on the per-sample-image pass: with two rhs columns that is 3 n' + 3 rows' > 320,
     // e.g. 54 joints on a floating base; with at most one column the tile program's 60 rows bound it to 156 160 bytes
     if (gram64_plds(hm, h->prog.k, true) > 160 * 1024) return FBR_OK;
-    if (!fbr_gram64_build_producer(hm, g, h->g64p)) return FBR_OK;
+    if (!fbr_gram64_build_producer(hm, g, h->g64p, m->opt.gram_lane_parts_cut != 0, h->prog.k)) return FBR_OK;
     std::vector<int> wgbegin{0, 0};  // (filled per launch: one part)
     int rc;
     if ((rc = upload(h->pool, g.slab, &h->d64_slab)) || (rc = upload(h->pool, g.lev_begin, &h->d64_levb)) || (rc = upload(h->pool, g.pieces, &h->d64_pieces)) ||
         (rc = upload(h->pool, g.wmeta, &h->d64_wmeta)) || (rc = upload(h->pool, h->g64p.lcol, &h->d64_lcol)) ||
         (rc = upload(h->pool, fbr_gram64_lane_columns(h->g64p, hm.L), &h->d64_lanecol)) ||
-        (rc = upload(h->pool, h->g64p.steps, &h->d64_steps)) ||
+        (rc = upload(h->pool, h->g64p.steps, &h->d64_steps)) || (rc = upload(h->pool, h->g64p.none, &h->d64_none)) ||
         (rc = upload(h->pool, g.slot_tiles, &h->d64_slot_tiles)) || (rc = upload(h->pool, g.tilecol, &h->d64_tilecol)) ||
         (rc = upload(h->pool, g.stage_lev, &h->d64_stagelev)) || (!g.runs.empty() && (rc = upload(h->pool, g.runs, &h->d64_runs))))
         return rc;
@@ -422,6 +422,7 @@ static DevKinWrite gram64_kinwrite(const fbr_model *m, const GramHolder *h, int 
     DevKinWrite kw{};
     kw.lcol10 = h->d64_lcol;
     kw.lanecol = h->d64_lanecol;
+    kw.none = m->opt.gram_lane_skip_unowned != 0 ? h->d64_none : nullptr;
     kw.dst = (const long *)h->dst64[b].p;
     kw.ninert = m->hm.ninert;
     kw.cols = m->hm.cols;
@@ -549,13 +550,23 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     if (m->opt.chunk_samples >= 1) chb = std::min(gram64_chunk_blocks(g), std::max<long>(1, ((long)m->opt.chunk_samples + 63) / 64));
     chb = std::min(nblocks, chb);
     if (chb < nblocks && chb > m->num_cus) chb = chb / m->num_cus * m->num_cus;
+    Gram64Launch L;
+    if ((rc = gram64_setup(m, h, base_only, &L))) return rc;
+    // device-resident inputs cut by memory alone: chunk sizes by the rounds of BOTH grids (fbr_gram64_chunk_plan; option gram_lane_chunk_rounds) --
+    // the last chunk may then be the largest.  Every chunk stays a multiple of num_cus but the last, so a block's Gram workgroup does not change.
+    long last_blocks = 0;  // > 0: the last chunk takes what is left once that is at most this many blocks (0: it is no larger than the others)
+    if (m->opt.gram_lane_chunk_rounds != 0 && !h2d_chunked && m->opt.chunk_samples < 1 && chb < nblocks && chb >= m->num_cus) {
+        const FbrGram64ChunkPlan cp = fbr_gram64_chunk_plan(nblocks, gram64_chunk_blocks(g), m->num_cus, L.pgrid_max, 1);
+        chb = cp.chb;
+        last_blocks = cp.last_cap;
+    }
     // samples per chunk: whole blocks -- or what the option asks for, as the per-sample-image pass chunks it (one staging copy group and
     // one producer launch per chunk_samples samples whichever pass serves the call); such a chunk ends in a partly filled block
     long chs = chb * 64;
     if (m->opt.chunk_samples >= 1) chs = std::min(chs, (long)m->opt.chunk_samples);
-    if ((rc = gram64_ensure_images(m, h, chb))) return rc;
-    Gram64Launch L;
-    if ((rc = gram64_setup(m, h, base_only, &L))) return rc;
+    const long last_s = last_blocks > 0 ? last_blocks * 64 : chs;
+    auto chunk_len = [&](long s0) { return S - s0 <= last_s ? S - s0 : chs; };
+    if ((rc = gram64_ensure_images(m, h, std::min(nblocks, std::max(chb, last_blocks))))) return rc;
     const size_t plds = gram64_plds(hm, k, dw != nullptr);
     const int pblocks = (int)std::min<long>(chb, (long)L.pgrid_max);
     const int gwgs = (int)std::min<long>(chb, (long)m->num_cus);
@@ -576,7 +587,7 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
         const double *rhs, *w;
     };
     auto stage = [&](long c, Staged &out) -> int {
-        const long s0 = c * chs, cs = std::min(chs, S - s0);
+        const long s0 = c * chs, cs = chunk_len(s0);
         const int b = (int)(c & 1);
         out = {d, s0, drhs, dw};
         if (!h2d_chunked) return FBR_OK;
@@ -590,11 +601,12 @@ static int gram64_pass(fbr_model *m, GramHolder *h, const DevStates &d, const do
     };
     Staged cur, nxt;
     if (S > 0 && (rc = stage(0, nxt))) return rc;
-    for (long s0 = 0; s0 < S; s0 += chs, launches++) {
-        const long cs = std::min(chs, S - s0), nb = (cs + 63) / 64;
+    for (long s0 = 0, cs = 0; s0 < S; s0 += cs, launches++) {
+        cs = chunk_len(s0);
+        const long nb = (cs + 63) / 64;
         const int b = launches & 1;
         cur = nxt;
-        if (s0 + chs < S && (rc = stage(launches + 1, nxt))) return rc;  // the copy of the next chunk is enqueued before this chunk's kernels
+        if (s0 + cs < S && (rc = stage(launches + 1, nxt))) return rc;  // the copy of the next chunk is enqueued before this chunk's kernels
         if (h2d_chunked) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_h2d[b], 0));
         {
             ProfScope ps(m, FBR_PROF_PACK);

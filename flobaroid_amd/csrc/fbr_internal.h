@@ -110,7 +110,7 @@ struct GramHolder {
     int g64_state = 0;        // 0 not looked at, 1 ready, -1 not applicable
     FbrGram64 g64;
     FbrGram64Producer g64p;   // producer tables (parts, destination words relative to an image buffer)
-    const int *d64_slab = nullptr, *d64_levb = nullptr, *d64_pieces = nullptr, *d64_wmeta = nullptr, *d64_lcol = nullptr, *d64_lanecol = nullptr,
+    const int *d64_slab = nullptr, *d64_levb = nullptr, *d64_pieces = nullptr, *d64_wmeta = nullptr, *d64_lcol = nullptr, *d64_lanecol = nullptr, *d64_none = nullptr,
               *d64_steps = nullptr, *d64_slot_tiles = nullptr, *d64_tilecol = nullptr, *d64_stagelev = nullptr,
               *d64_runs = nullptr;
     DevBuf img64[2], dst64[2], mom64, scr64;

@@ -142,6 +142,37 @@ static inline void fbr_kinid_build_parts(const FbrHostModel &hm, const std::vect
     }
 }
 
+// The same parts from given cut points: part p owns positions [starts[p], starts[p + 1]) of the depth-first order (starts: nparts + 1
+// non-decreasing positions from 0 to L; an empty part walks nothing).
+static inline void fbr_kinid_build_parts_at(const FbrHostModel &hm, const std::vector<int> &starts, std::vector<FbrKinIdProgram> &progs,
+                                            std::vector<std::vector<char>> &own)
+{
+    const int nparts = (int)starts.size() - 1;
+    if (nparts < 1 || starts[0] != 0 || starts[nparts] != hm.L) throw std::runtime_error("fbr_kinid_build_parts_at: cut points outside the order");
+    progs.assign(nparts, FbrKinIdProgram());
+    own.assign(nparts, std::vector<char>(hm.L, 0));
+    for (int p = 0; p < nparts; p++) {
+        if (starts[p + 1] < starts[p]) throw std::runtime_error("fbr_kinid_build_parts_at: cut points out of order");
+        for (int k = starts[p]; k < starts[p + 1]; k++) own[p][hm.order[k]] = 1;
+        std::vector<char> keep = own[p];
+        for (int l = 0; l < hm.L; l++)
+            if (own[p][l])
+                for (int a = hm.parent[l]; a >= 0 && !keep[a]; a = hm.parent[a]) keep[a] = 1;
+        fbr_kinid_build(hm, progs[p], &keep);
+    }
+}
+// the cut points of an assignment fbr_kinid_build_parts made (contiguous ranges of the order)
+static inline std::vector<int> fbr_kinid_parts_starts(const FbrHostModel &hm, const std::vector<std::vector<char>> &own)
+{
+    std::vector<int> starts{0};  // (a trailing part may be empty: a dear last link leaves the parts before it short of their share)
+    for (size_t p = 0; p < own.size(); p++) {
+        int cnt = 0;
+        for (int l = 0; l < hm.L; l++) cnt += own[p][l] != 0;
+        starts.push_back(starts.back() + cnt);
+    }
+    return starts;
+}
+
 #if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
 #define FBR_UNI(x) __builtin_amdgcn_readfirstlane(x)  // the program is the same for every lane: keep it in scalar registers
 #else
@@ -300,6 +331,7 @@ struct DevKinWrite {
     int flev;  // (fbr_kinimg_kernel) base rows below this level go through the force-tile words
     int base_only;  // (fbr_kinimg_kernel) the joint rows carry weight 0 in every sample: not produced
     long group_samples;  // (fbr_kinimg_kernel) samples per group of a grouped pass (every group starts a block), 0: one group
+    const int *none = nullptr;  // (fbr_kinimg_kernel) [parts][L]: 1 = the part writes no column of the link (FbrGram64Producer::none); null: not consulted
     int nparts, part_nsteps[FBR_KINWRITE_PARTS], part_step0[FBR_KINWRITE_PARTS];  // wave w of a workgroup walks steps [step0, step0 + nsteps) of p.steps
 };
 #endif

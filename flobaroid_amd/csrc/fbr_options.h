@@ -21,6 +21,9 @@ struct FbrOptions {
     double gram_force_tiles = 1;            // gram_lane: the force rows of the base wrench run on tiles of the columns that have a force (fbr_gram64.h)
     double gram_lane = 1;                   // fused Gram over sample-contiguous images with the one-lane-per-sample producer where the model allows (fbr_gram64.h)
     double gram_lane_tiling = 1;            // gram_lane: column tiles built for the pass's cost (fbr_gram64_build); 0: the tile program's
+    double gram_lane_skip_unowned = 1;      // gram_lane producer: a wave forms nothing for a link none of whose columns it writes (0: products formed, stores skipped)
+    double gram_lane_parts_cut = 0;         // gram_lane producer: 1: the tree cut so that the slowest wave, ancestors included, is fastest under the cost model (fbr_gram64_cut_parts; measured slower); 0: equal owned cost
+    double gram_lane_chunk_rounds = 0;      // gram_lane: 1: chunk sizes by the rounds of both kernels' grids (fbr_gram64_chunk_plan; measured no faster); 0: as large as memory allows
     double gram_shape = 0;                  // 0: by model, 1: one workgroup per CU (18 accumulators), 2: two per CU (10)
     double gram_rhs_tile = 0;               // 1: dense rhs tiles even for k <= 2 (default: tau's products come from the pack kernel)
     double gram_orient = 1;                 // pairs turned so that the row segments fill up
@@ -63,6 +66,9 @@ static inline const FbrOptionKey *fbr_option_keys(int *count)
         {"gram_force_tiles", &FbrOptions::gram_force_tiles, true},   // (these three shape the program of the sample-contiguous pass, get_gram64)
         {"gram_lane_waves", &FbrOptions::gram_lane_waves, true},
         {"gram_lane_tiling", &FbrOptions::gram_lane_tiling, true},
+        {"gram_lane_skip_unowned", &FbrOptions::gram_lane_skip_unowned, true},  // (the producer's tables, cached per holder)
+        {"gram_lane_parts_cut", &FbrOptions::gram_lane_parts_cut, true},
+        {"gram_lane_chunk_rounds", &FbrOptions::gram_lane_chunk_rounds, true},
         {"gram_shape", &FbrOptions::gram_shape, true},
         {"gram_rhs_tile", &FbrOptions::gram_rhs_tile, true},
         {"gram_orient", &FbrOptions::gram_orient, true},

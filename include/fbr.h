@@ -451,6 +451,14 @@ int fbr_model_link_merge_info(const fbr_model *m, int64_t num_samples, int32_t *
  *   "gram_lane_tiling"           1     gram_lane: column tiles of its own for the pass (a bottom-up fill: a column may sit in any tile whose
  *                                      joint path contains its own), kept when they need fewer MFMAs than the tile program's (0: the tile
  *                                      program's tiles and pairs)
+ *   "gram_lane_skip_unowned"     1     gram_lane producer: a wave forms no column of a link it walks only as an ancestor of its own links
+ *                                      (0: formed and not stored); same bits
+ *   "gram_lane_parts_cut"        0     gram_lane producer: 1: the tree is cut for its four waves so that the slowest one, ancestors included,
+ *                                      is as fast as an instruction-count model allows (0: parts of equal owned cost); same bits; measured
+ *                                      0.13 ms slower per 1 M WALK-MAN samples
+ *   "gram_lane_chunk_rounds"     0     gram_lane, device-resident inputs that need several chunks: 1: chunk sizes with the fewest rounds of
+ *                                      the Gram grid, then of the producer grid, then the fewest chunks (0: chunks as large as memory
+ *                                      allows); measured no faster
  *   "gram_shape"                0     fused Gram kernel shape: 0 by model, 1 one workgroup per CU, 2 two per CU
  *   "gram_rhs_tile"              0     1: dense tiles for the rhs columns even for k <= 2 (default: their products come from the packer)
  *   "gram_orient"                1     tile pairs turned so that the row segments fill up
