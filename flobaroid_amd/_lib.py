@@ -80,6 +80,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_int32],
     ),
+    "fbr_torque_row_sweep": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, _dp, ctypes.c_int32,
+         ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_model_set_capsules": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip]),
     "fbr_candidate_capsule_distances": (
         ctypes.c_int,
@@ -134,6 +139,11 @@ _SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32],
+    ),
+    "fbr_fourier_state_chain": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32],
     ),
     "fbr_tsqr": (
         ctypes.c_int,
@@ -461,6 +471,31 @@ class Engine:
             out[name + "_idx"] = idx[:, k]
         return out
 
+    def torque_row_sweep(self, st: dict, ncand: int, sample, x_std, eps: float, joint=None, vel_sign=None, device_out: bool | None = None):
+        """Joint torque rows of chosen samples under the finite-difference sweep (``fbr_torque_row_sweep``): a (C, R, 1 + 3 n) array whose
+        entry ``[c, r, 0]`` is torque row ``joint[c, r]`` of ``inverse_dynamics`` at sample ``sample[c, r]`` of candidate c and entry
+        ``[c, r, 1 + kind * n + d]`` the same row with +eps on q_d / dq_d / ddq_d (the entry order of ``fd_scores``); the sign series,
+        ``vel_sign`` and the base state stay the sample's own.  ``sample`` (C, R) int, 0 .. T - 1; ``joint`` (C, R) int, 0 .. n - 1, or None:
+        R = n and row r is joint r.  An index out of range raises ``FbrError``.  A CUDA tensor when the states are on the device
+        (``device_out`` overrides), else NumPy; the index arrays are brought to the memory space of the states."""
+        s, keep, S, mem = self._states(st)
+        x = np.ascontiguousarray(x_std, dtype=np.float64)
+        vs = _Ref(vel_sign, (S, self.n), "vel_sign") if vel_sign is not None else _Ref(None)
+        if vs.mem is not None and vs.mem != mem:
+            raise ValueError("vel_sign must live in the same memory space as the states")
+        C = int(ncand)
+        shp = tuple(sample.shape)
+        if len(shp) != 2 or shp[0] != max(C, 1):
+            raise ValueError(f"sample: expected ({C}, R), got {shp}")
+        R = int(shp[1])
+        smp, psmp = self._index_array(sample, shp, mem, "sample")
+        jnt, pjnt = (None, None) if joint is None else self._index_array(joint, shp, mem, "joint", dtype=np.int32)
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        r, ret = self._out(None, shp + (1 + 3 * self.n,), out_mem)
+        _check(self._lib.fbr_torque_row_sweep(self._h, ctypes.byref(s), C, R, psmp, pjnt, x.ctypes.data_as(_dp), int(x.size), vs.ptr, float(eps),
+                                              r.ptr, out_mem), "fbr_torque_row_sweep")
+        return ret
+
     def set_capsules(self, capsules, pairs) -> None:
         """Capsule collision set of the handle (``fbr_model_set_capsules``).  ``capsules``: a sequence of ``(link, p0, p1, radius)`` -- link
         an index into the topology's links or a link name, p0 / p1 in that link's frame -- or of objects with ``link`` / ``link_name``,
@@ -516,16 +551,16 @@ class Engine:
                "fbr_candidate_capsule_distances")
         return {"dist": val, "idx": idx}
 
-    def _index_array(self, x, shape, mem, name):
-        """an int64 index array in the memory space ``mem``: (keep-alive object, pointer)"""
+    def _index_array(self, x, shape, mem, name, dtype=np.int64):
+        """an int64 (or ``dtype`` int32) index array in the memory space ``mem``: (keep-alive object, pointer)"""
         if mem == FBR_DEVICE:
             import torch
 
-            t = torch.as_tensor(x, device=f"cuda:{self.device}").to(torch.int64).contiguous()
+            t = torch.as_tensor(x, device=f"cuda:{self.device}").to(torch.int64 if dtype == np.int64 else torch.int32).contiguous()
             if tuple(t.shape) != tuple(shape):
                 raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
             return t, t.data_ptr()
-        a = np.ascontiguousarray(x.cpu().numpy() if _is_torch(x) else x, dtype=np.int64)
+        a = np.ascontiguousarray(x.cpu().numpy() if _is_torch(x) else x, dtype=dtype)
         if a.shape != tuple(shape):
             raise ValueError(f"{name}: expected shape {shape}, got {a.shape}")
         return a, a.ctypes.data
@@ -598,6 +633,37 @@ class Engine:
         _check(self._lib.fbr_fourier_position_chain(self._h, C, R, nh, float(freq), wf.ctypes.data_as(_dp), a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
                                                     None if qr is None else qr.ctypes.data_as(_dp), psmp, sc.ptr, g.ptr, mem, r.ptr, r.mem),
                "fbr_fourier_position_chain")
+        return ret
+
+    def fourier_state_chain(self, wf, a, b, sample, freq: float, grad_q=None, grad_dq=None, grad_ddq=None, scale=None, q_range=None,
+                            device_out: bool | None = None):
+        """``fourier_position_chain`` for rows with sensitivities to the joint velocities and accelerations as well
+        (``fbr_fourier_state_chain``): entry = ``scale[c, r] * sum_d (grad_q[c, r, d] * dq_d/dp + grad_dq[c, r, d] * d(dq_d)/dp +
+        grad_ddq[c, r, d] * d(ddq_d)/dp)`` at time ``sample[c, r] / freq``, every derivative analytic; each of ``grad_q`` / ``grad_dq`` /
+        ``grad_ddq`` (C, R, n) may be None (zero), at least one is given and all live in one memory space.  Equal to
+        ``fourier_position_chain`` entry for entry when only ``grad_q`` is given."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        C, n, nh = a.shape
+        if n != self.n or b.shape != a.shape:
+            raise ValueError(f"a / b: expected (C, {self.n}, nharm)")
+        wf = np.ascontiguousarray(np.broadcast_to(np.asarray(wf, dtype=np.float64), (C,)))
+        qr = None if q_range is None else np.ascontiguousarray(q_range, dtype=np.float64).reshape(C, n)
+        given = [x for x in (grad_q, grad_dq, grad_ddq) if x is not None]
+        if not given or len(given[0].shape) != 3 or given[0].shape[0] != C or given[0].shape[2] != n:
+            raise ValueError(f"grad_q / grad_dq / grad_ddq: at least one array ({C}, R, {n})")
+        R = int(given[0].shape[1])
+        g = [_Ref(x, (C, R, n), name) if x is not None else _Ref(None) for x, name in ((grad_q, "grad_q"), (grad_dq, "grad_dq"), (grad_ddq, "grad_ddq"))]
+        mem = _same_space(g)
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        smp, psmp = self._index_array(sample, (C, R), mem, "sample")
+        sc = _Ref(self._to_space(scale, mem), (C, R), "scale")
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        r, ret = self._out(None, (C, R, 1 + 2 * n + 2 * n * nh), out_mem)
+        _check(self._lib.fbr_fourier_state_chain(self._h, C, R, nh, float(freq), wf.ctypes.data_as(_dp), a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
+                                                 None if qr is None else qr.ctypes.data_as(_dp), psmp, sc.ptr, g[0].ptr, g[1].ptr, g[2].ptr, mem, r.ptr,
+                                                 r.mem), "fbr_fourier_state_chain")
         return ret
 
     def predict(self, st: dict, x, out=None):

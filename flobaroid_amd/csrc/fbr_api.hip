@@ -11,7 +11,8 @@ thread_local std::string g_fbr_err;
 // 101 (round 6): fbr_topology.joint_type, the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info (both added in
 // round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
 // 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
-// fbr_capsule_distance_gradients, fbr_fourier_position_chain).
+// fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain: added symbols change no
+// signature, and _lib.py names a library that lacks one).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
 
@@ -619,30 +620,66 @@ static int finish_extrema(fbr_model *m, const DevKinExt &ex, const ExtremaReq &r
     return FBR_OK;
 }
 
+// Y x = Y_red (E x): torques are linear in the parameters, and the parameters of a link welded to a moving body are parameters of that
+// body (build_reduction, merged model rdm[0]: every moving link keeps its ten columns).  The kinematics and the per-link wrench loop
+// then run over the moving bodies only (WALK-MAN: 30 of 48 links) -- same rows, same result to rounding.  Returns the merged model that
+// serves x (on m's stream, its parameters in xr / *nxr), or nullptr: the call runs on m itself unless *rc is set.
+static fbr_model *merged_for_torques(fbr_model *m, const fbr_states *st, const double *x, int nx, int mode, std::vector<double> &xr, int *nxr, int *rc)
+{
+    if (!(m && x && st && m->rdm[0] && m->opt.link_merge && m->pid == getpid())) return nullptr;
+    fbr_model *r = m->rdm[0].get();
+    const FbrHostModel &hm = m->hm, &rh = r->hm;
+    const int ninert = hm.cpl * hm.L, rin = rh.cpl * rh.L;
+    const int full = mode == 0 ? ninert : hm.cols;  // mode 0: the inertial block of x_std; mode 1: every identified column
+    if (hm.cpl != 10 || nx < full) return nullptr;
+    xr.assign((size_t)std::max(rin + (nx - ninert), rh.cols), 0.0);
+    const std::vector<int> &eb = m->hE_beg[0], &er = m->hE_row[0];
+    const std::vector<double> &ev = m->hE_val[0];
+    for (int j = 0; j < ninert; j++)
+        for (int e = eb[j]; e < eb[j + 1]; e++) xr[er[e]] += ev[e] * x[j];
+    for (int j = ninert; j < nx; j++) xr[rin + (j - ninert)] = x[j];  // friction slots / columns: the same joints in the same layout
+    if ((*rc = enter_blocking(m))) return nullptr;
+    r->stream = m->stream;
+    r->prof = m->prof;
+    *nxr = rin + (nx - ninert);
+    return r;
+}
+
+// the two-kernel torques of S staged samples (kinematic records through HBM, chunk by chunk): tau [S][rows] to dst (device)
+static int launch_id_two_kernel(fbr_model *m, const DevStates &d, long S, const double *dvs, const double *x, int mode, double *dst)
+{
+    const FbrHostModel &hm = m->hm;
+    // one wave per sample, each with its record and link forces in the LDS: up to four waves per workgroup, fewer for large trees
+    const size_t per_wave = (size_t)(hm.rec_size() + 6 * hm.L) * sizeof(double);
+    const int waves = (int)std::min<size_t>(4, (size_t)160 * 1024 / per_wave);
+    if (waves < 1) {
+        set_err("model too large: the inverse dynamics of one sample needs more than 160 KiB of LDS");
+        return FBR_E_UNSUPPORTED;
+    }
+    const size_t lds = (size_t)waves * per_wave;
+    HIPCHK(hipFuncSetAttribute((const void *)fbr_id_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long ch = chunk_size(m, S);
+    for (long s0 = 0; s0 < S; s0 += ch) {
+        const long cs = std::min(ch, S - s0);
+        if (int rc = run_kin(m, d, s0, cs)) return rc;
+        const int blocks = (int)std::min<long>((cs + waves - 1) / waves, (long)m->num_cus * 8);
+        ProfScope ps(m, FBR_PROF_ID);
+        hipLaunchKernelGGL(fbr_id_kernel, dim3(blocks), dim3(64 * waves), lds, m->stream, m->dm, cs, m->rec.as<double>(),
+                           d.dq + s0 * hm.n, d.sign ? d.sign + s0 * hm.n : nullptr, dvs ? dvs + s0 * hm.n : nullptr, x, mode, dst + (size_t)s0 * hm.rows);
+        HIPCHK(hipGetLastError());
+    }
+    return FBR_OK;
+}
+
 // ext: the candidate extrema of the torques (fbr_candidate_extrema) instead of the torques -- the same route, the same kernels' arithmetic
 static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, const double *vel_sign, int mode,
                   double *tau_out, int32_t out_mem, const ExtremaReq *ext = nullptr)
 {
-    // Y x = Y_red (E x): torques are linear in the parameters, and the parameters of a link welded to a moving body are parameters of that
-    // body (build_reduction, merged model rdm[0]: every moving link keeps its ten columns).  The kinematics and the per-link wrench loop
-    // then run over the moving bodies only (WALK-MAN: 30 of 48 links) -- same rows, same result to rounding.
-    if (m && x && st && m->rdm[0] && m->opt.link_merge && m->pid == getpid()) {
-        fbr_model *r = m->rdm[0].get();
-        const FbrHostModel &hm = m->hm, &rh = r->hm;
-        const int ninert = hm.cpl * hm.L, rin = rh.cpl * rh.L;
-        const int full = mode == 0 ? ninert : hm.cols;  // mode 0: the inertial block of x_std; mode 1: every identified column
-        if (hm.cpl == 10 && nx >= full) {
-            std::vector<double> xr((size_t)std::max(rin + (nx - ninert), rh.cols), 0.0);
-            const std::vector<int> &eb = m->hE_beg[0], &er = m->hE_row[0];
-            const std::vector<double> &ev = m->hE_val[0];
-            for (int j = 0; j < ninert; j++)
-                for (int e = eb[j]; e < eb[j + 1]; e++) xr[er[e]] += ev[e] * x[j];
-            for (int j = ninert; j < nx; j++) xr[rin + (j - ninert)] = x[j];  // friction slots / columns: the same joints in the same layout
-            if (int rc = enter_blocking(m)) return rc;
-            r->stream = m->stream;
-            r->prof = m->prof;
-            return run_id(r, st, xr.data(), rin + (nx - ninert), vel_sign, mode, tau_out, out_mem, ext);
-        }
+    {
+        std::vector<double> xr;
+        int nxr = 0, rc = FBR_OK;
+        if (fbr_model *r = merged_for_torques(m, st, x, nx, mode, xr, &nxr, &rc)) return run_id(r, st, xr.data(), nxr, vel_sign, mode, tau_out, out_mem, ext);
+        if (rc) return rc;
     }
     DevStates d;
     int rc = stage_states(m, st, &d);
@@ -680,26 +717,7 @@ static int run_id(fbr_model *m, const fbr_states *st, const double *x, int nx, c
         if ((rc = launch_kinid(m, d, S, dvs, m->st_x.as<double>(), mode, ext ? nullptr : dst, 0, nullptr, ext ? &ex : nullptr))) return rc;
         return ext ? finish_extrema(m, ex, *ext, out_mem) : finish_output(m, dst, tau_out, (size_t)S * hm.rows, out_mem);
     }
-    // one wave per sample, each with its record and link forces in the LDS: up to four waves per workgroup, fewer for large trees
-    const size_t per_wave = (size_t)(hm.rec_size() + 6 * hm.L) * sizeof(double);
-    const int waves = (int)std::min<size_t>(4, (size_t)160 * 1024 / per_wave);
-    if (waves < 1) {
-        set_err("model too large: the inverse dynamics of one sample needs more than 160 KiB of LDS");
-        return FBR_E_UNSUPPORTED;
-    }
-    const size_t lds = (size_t)waves * per_wave;
-    HIPCHK(hipFuncSetAttribute((const void *)fbr_id_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long ch = chunk_size(m, S);
-    for (long s0 = 0; s0 < S; s0 += ch) {
-        const long cs = std::min(ch, S - s0);
-        if ((rc = run_kin(m, d, s0, cs))) return rc;
-        const int blocks = (int)std::min<long>((cs + waves - 1) / waves, (long)m->num_cus * 8);
-        ProfScope ps(m, FBR_PROF_ID);
-        hipLaunchKernelGGL(fbr_id_kernel, dim3(blocks), dim3(64 * waves), lds, m->stream, m->dm, cs, m->rec.as<double>(),
-                           d.dq + s0 * hm.n, d.sign ? d.sign + s0 * hm.n : nullptr, dvs ? dvs + s0 * hm.n : nullptr,
-                           m->st_x.as<double>(), mode, dst + (size_t)s0 * hm.rows);
-        HIPCHK(hipGetLastError());
-    }
+    if ((rc = launch_id_two_kernel(m, d, S, dvs, m->st_x.as<double>(), mode, dst))) return rc;
     if (ext) {
         {
             ProfScope ps(m, FBR_PROF_ID);
@@ -735,6 +753,137 @@ extern "C" int fbr_candidate_extrema(fbr_model *m, const fbr_states *st, int32_t
     }
     const ExtremaReq rq{ncand, val_out, idx_out};
     return run_id(m, st, x_std, num_x, vel_sign, 0, nullptr, out_mem, &rq);
+}
+
+// ---- torque rows of chosen samples under the finite-difference sweep (fbr.h; fbr_kintau_kernel, csrc/fbr_kinid.h) ------------------------
+static int run_torque_sweep(fbr_model *m, const fbr_states *st, long ncand, long nrows, const int64_t *sample, const int32_t *joint, const double *x, int nx,
+                            const double *vel_sign, double eps, double *out, int32_t out_mem)
+{
+    {
+        std::vector<double> xr;
+        int nxr = 0, rc = FBR_OK;
+        if (fbr_model *r = merged_for_torques(m, st, x, nx, 0, xr, &nxr, &rc))
+            return run_torque_sweep(r, st, ncand, nrows, sample, joint, xr.data(), nxr, vel_sign, eps, out, out_mem);
+        if (rc) return rc;
+    }
+    DevStates d;
+    int rc = stage_states(m, st, &d);
+    if (rc) return rc;
+    const FbrHostModel &hm = m->hm;
+    const int n = hm.n, nper = 1 + 3 * n;
+    const int need = hm.fric ? hm.friction_start() + (hm.cols - hm.cpl * hm.L) : 10 * hm.L;
+    if (n < 1 || nx < std::max(need, 10 * hm.L)) {
+        set_err("fbr_torque_row_sweep: a model without joints, or x_std too short for this model layout");
+        return FBR_E_INVALID;
+    }
+    const long S = d.S, T = S / ncand, items = ncand * nrows;
+    if ((rc = m->st_x.ensure((size_t)nx * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(m->st_x.p, x, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    const double *dx = m->st_x.as<double>(), *dvs = nullptr, *dsmp = nullptr;
+    if (hm.fric && hm.stribeck > 0) {
+        if (!vel_sign) {
+            set_err("Stribeck model needs vel_sign");
+            return FBR_E_INVALID;
+        }
+        if ((rc = stage_one(m, m->st_aux, vel_sign, (size_t)S * n, st->mem, &dvs))) return rc;
+    }
+    if ((rc = stage_one(m, m->st_aux2, (const double *)sample, (size_t)items, st->mem, &dsmp))) return rc;  // (8 bytes an entry, like a double)
+    const int *djnt = joint;
+    if (joint && st->mem == FBR_HOST) {
+        if ((rc = m->st_bpos.ensure((size_t)items * sizeof(int32_t)))) return rc;
+        HIPCHK(hipMemcpyAsync(m->st_bpos.p, joint, (size_t)items * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+        djnt = m->st_bpos.as<int>();
+    }
+    double *dout = out;
+    if (out_mem == FBR_HOST) {
+        if ((rc = m->g_tmp.ensure((size_t)items * nper * sizeof(double)))) return rc;
+        dout = m->g_tmp.as<double>();
+    }
+    if ((rc = m->capg_flag.ensure(sizeof(int)))) return rc;
+    int flag = 0;
+    HIPCHK(hipMemsetAsync(m->capg_flag.p, 0, sizeof(int), m->stream));
+    const DevKinTau tr{T, nrows, (const long *)dsmp, djnt, m->capg_flag.as<int>()};
+    if (kinid_fits(m)) {
+        // one lane per evaluation, nothing staged: no LDS, so the 105-DOF limit of the staged states does not apply, but kinid_fits is
+        // the one rule for "the fused lane kernels serve this model"
+        const DevKinId kp = kinid_params(m);
+        const long nblk = (items * nper + 63) / 64;
+        const int blocks = (int)std::min<long>(nblk, (long)m->num_cus * 8);
+        if ((rc = m->kinid_scratch.ensure((size_t)blocks * std::max(kp.nslots, 1) * FBR_LINK_REC * 64 * sizeof(double)))) return rc;
+        ProfScope ps(m, FBR_PROF_ID);
+        fbr_by_depth<4, 8, 12, FBR_KINID_MAXD>(kp.maxlvl, [&](auto D) {
+            hipLaunchKernelGGL(fbr_kintau_kernel<D>, dim3(blocks), dim3(64), 0, m->stream, m->dm, kp, tr, items, nper, eps, d.q, d.dq, d.ddq, d.bv, d.ba, d.rpy,
+                               d.sign, dvs, dx, dout, m->kinid_scratch.as<double>());
+        });
+        HIPCHK(hipGetLastError());
+    } else {
+        // chunks of items whose expanded records stay within the usual chunk
+        const long ch = std::max(1L, chunk_size(m, items * nper) / nper);
+        const size_t cnt[7] = {(size_t)n, (size_t)n, (size_t)n, 6, 6, 3, (size_t)n};
+        for (long i0 = 0; i0 < items; i0 += ch) {
+            const long ci = std::min(ch, items - i0), ce = ci * nper;
+            for (int i = 0; i < 7; i++)
+                if ((rc = m->fd[i].ensure((size_t)ce * cnt[i] * sizeof(double)))) return rc;
+            if ((rc = m->fd_part.ensure((size_t)ce * n * sizeof(double)))) return rc;           // vel_sign of the evaluations
+            if ((rc = m->out_tmp.ensure((size_t)ce * hm.rows * sizeof(double)))) return rc;  // their torques
+            DevStates de;
+            de.S = ce;
+            de.q = m->fd[0].as<double>();
+            de.dq = m->fd[1].as<double>();
+            de.ddq = m->fd[2].as<double>();
+            if (d.bv) {
+                de.bv = m->fd[3].as<double>();
+                de.ba = m->fd[4].as<double>();
+                de.rpy = m->fd[5].as<double>();
+            }
+            if (d.sign) de.sign = m->fd[6].as<double>();
+            const unsigned grid = (unsigned)std::min<long>((ce + 255) / 256, 4096);
+            hipLaunchKernelGGL(fbr_tau_expand_kernel, dim3(grid), dim3(256), 0, m->stream, tr, i0, ci, n, eps, d.q, d.dq, d.ddq, d.bv, d.ba, d.rpy, d.sign, dvs,
+                               m->fd[0].as<double>(), m->fd[1].as<double>(), m->fd[2].as<double>(), m->fd[3].as<double>(), m->fd[4].as<double>(),
+                               m->fd[5].as<double>(), m->fd[6].as<double>(), m->fd_part.as<double>());
+            HIPCHK(hipGetLastError());
+            if ((rc = launch_id_two_kernel(m, de, ce, dvs ? m->fd_part.as<double>() : nullptr, dx, 0, m->out_tmp.as<double>()))) return rc;
+            hipLaunchKernelGGL(fbr_tau_gather_kernel, dim3(grid), dim3(256), 0, m->stream, tr, i0, ci, n, hm.fb, hm.rows, m->out_tmp.as<double>(), dout);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    HIPCHK(hipMemcpyAsync(&flag, m->capg_flag.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if ((rc = finish_output(m, dout, out, (size_t)items * nper, out_mem))) return rc;
+    if (flag) {
+        set_err("fbr_torque_row_sweep: a sample index lies outside 0 .. T - 1 or a joint index outside 0 .. n - 1");
+        return FBR_E_INVALID;
+    }
+    return FBR_OK;
+}
+
+extern "C" int fbr_torque_row_sweep(fbr_model *m, const fbr_states *st, int32_t ncand, int64_t nrows, const int64_t *sample, const int32_t *joint,
+                                    const double *x_std, int32_t num_x, const double *vel_sign, double eps, double *out, int32_t out_mem)
+{
+    if (!m || !st || !sample || !x_std || !out) {
+        set_err("null model / states / sample / x_std / out");
+        return FBR_E_INVALID;
+    }
+    if (out_mem != FBR_HOST && out_mem != FBR_DEVICE) {
+        set_err("bad memory space of out");
+        return FBR_E_INVALID;
+    }
+    if (ncand < 1 || nrows < 1) {
+        set_err("ncand and nrows must be at least 1");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
+        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
+        return FBR_E_INVALID;
+    }
+    if (!joint && nrows != m->hm.n) {
+        set_err("joint == NULL needs nrows == number of joints");
+        return FBR_E_INVALID;
+    }
+    if (!std::isfinite(eps) || eps == 0.0) {
+        set_err("eps must be finite and not zero");
+        return FBR_E_INVALID;
+    }
+    return run_torque_sweep(m, st, ncand, nrows, sample, joint, x_std, num_x, vel_sign, eps, out, out_mem);
 }
 
 // ---- capsule collision distances (csrc/fbr_capsule.h) --------------------------------------------------------------------------------
@@ -1458,6 +1607,53 @@ extern "C" int fbr_fourier_position_chain(fbr_model *m, int32_t ncand, int64_t n
         ProfScope ps(m, FBR_PROF_REDUCE);
         hipLaunchKernelGGL(fbr_fourier_poschain_kernel, dim3((unsigned)std::min<size_t>((nout + 255) / 256, (size_t)m->num_cus * 32)), dim3(256), 0, m->stream,
                            (int)ncand, (long)nrows, n, (int)nharm, freq, dwf, da, db, drng, (const long *)dsmp, dscale, dg, dout);
+    }
+    HIPCHK(hipGetLastError());
+    return finish_output(m, dout, out, nout, out_mem);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same chain for rows that carry velocity and acceleration sensitivities as well (fbr.h; fbr_fourier_statechain_kernel)
+// ------------------------------------------------------------------------------------------------
+extern "C" int fbr_fourier_state_chain(fbr_model *m, int32_t ncand, int64_t nrows, int32_t nharm, double freq, const double *wf, const double *a,
+                                       const double *b, const double *q_range, const int64_t *sample, const double *scale, const double *grad_q,
+                                       const double *grad_dq, const double *grad_ddq, int32_t mem, double *out, int32_t out_mem)
+{
+    if (!m || ncand < 1 || nrows < 1 || nharm < 1 || !(freq > 0) || !wf || !a || !b || !sample || !out || (mem != FBR_HOST && mem != FBR_DEVICE) ||
+        (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
+        set_err("fbr_fourier_state_chain: bad arguments");
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;
+    const int n = m->hm.n;
+    const size_t nc = (size_t)ncand * n, ncoef = nc * nharm, rows = (size_t)ncand * (size_t)nrows, E = 1 + 2 * (size_t)n + 2 * (size_t)n * nharm,
+                 nout = rows * E;
+    std::vector<double> h;  // [wf (C) | a | b | q_range]
+    h.insert(h.end(), wf, wf + ncand);
+    h.insert(h.end(), a, a + ncoef);
+    h.insert(h.end(), b, b + ncoef);
+    if (q_range) h.insert(h.end(), q_range, q_range + nc);
+    int rc;
+    if ((rc = m->st_x.ensure(h.size() * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(m->st_x.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));  // (h is a local)
+    const double *dc = m->st_x.as<double>();
+    const double *dwf = dc, *da = dc + ncand, *db = da + ncoef, *drng = q_range ? db + ncoef : nullptr;
+    const double *dsmp, *dscale, *dg, *dgd, *dgdd;
+    if ((rc = stage_one(m, m->st_aux2, (const double *)sample, rows, mem, &dsmp))) return rc;  // (8 bytes an entry, like a double)
+    if ((rc = stage_one(m, m->st_aux, scale, rows, mem, &dscale))) return rc;
+    if ((rc = stage_one(m, m->st_q, grad_q, rows * n, mem, &dg))) return rc;
+    if ((rc = stage_one(m, m->st_dq, grad_dq, rows * n, mem, &dgd))) return rc;
+    if ((rc = stage_one(m, m->st_ddq, grad_ddq, rows * n, mem, &dgdd))) return rc;
+    double *dout = out;
+    if (out_mem == FBR_HOST) {
+        if ((rc = m->g_tmp.ensure(nout * sizeof(double)))) return rc;
+        dout = m->g_tmp.as<double>();
+    }
+    {
+        ProfScope ps(m, FBR_PROF_REDUCE);
+        hipLaunchKernelGGL(fbr_fourier_statechain_kernel, dim3((unsigned)std::min<size_t>((nout + 255) / 256, (size_t)m->num_cus * 32)), dim3(256), 0, m->stream,
+                           (int)ncand, (long)nrows, n, (int)nharm, freq, dwf, da, db, drng, (const long *)dsmp, dscale, dg, dgd, dgdd, dout);
     }
     HIPCHK(hipGetLastError());
     return finish_output(m, dout, out, nout, out_mem);

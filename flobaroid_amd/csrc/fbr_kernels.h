@@ -966,6 +966,18 @@ __device__ __forceinline__ void fbr_fourier_dwf_add(bool bounded, double w, doub
     }
 }
 
+// The bounded form's chain through the tanh for sensitivities (s0, s1, s2) of one joint's (q, dq, ddq) at one time: the factors (e0, e1, e2) of a
+// parameter's (r0, r1, r2) and the q_range term er (the formulas of the K6b header); th = tanh(raw), sech2 = 1 - th^2
+__device__ __forceinline__ void fbr_fourier_tanh_chain(double th, double sech2, double qr, double rd, double rdd, double s0, double s1, double s2,
+                                                       double &e0, double &e1, double &e2, double &er)
+{
+    const double f = qr * sech2;
+    e0 = f * (s0 - 2.0 * th * rd * s1 + (-2.0 * th * rdd - 2.0 * sech2 * rd * rd + 4.0 * th * th * rd * rd) * s2);
+    e1 = f * (s1 - 4.0 * th * rd * s2);
+    e2 = f * s2;
+    er = s0 * th + s1 * (sech2 * rd) + s2 * (sech2 * rdd - 2.0 * th * sech2 * rd * rd);
+}
+
 __global__ __launch_bounds__(256) void fbr_fourier_grad_kernel(int C, long T, int tstride, int n, int nh, int TB, long ntb, double freq,
                                                                const double *__restrict__ wf, const double *__restrict__ a,
                                                                const double *__restrict__ b, const double *__restrict__ qrange,
@@ -996,12 +1008,9 @@ __global__ __launch_bounds__(256) void fbr_fourier_grad_kernel(int C, long T, in
                 const double *aa = a + ((long)c * n + j) * nh, *bb = b + ((long)c * n + j) * nh;
                 double raw, rd, rdd;
                 fbr_fourier_raw(nh, w, ts, aa, bb, raw, rd, rdd);
-                const double th = tanh(raw), sech2 = 1.0 - th * th, qr = qrange[(long)c * n + j], f = qr * sech2;
-                E0[i] = f * (s0 - 2.0 * th * rd * s1 + (-2.0 * th * rdd - 2.0 * sech2 * rd * rd + 4.0 * th * th * rd * rd) * s2);
-                E1[i] = f * (s1 - 4.0 * th * rd * s2);
-                E2[i] = f * s2;
+                const double th = tanh(raw);
+                fbr_fourier_tanh_chain(th, 1.0 - th * th, qrange[(long)c * n + j], rd, rdd, s0, s1, s2, E0[i], E1[i], E2[i], ER[i]);
                 EQ[i] = s0;
-                ER[i] = s0 * th + s1 * (sech2 * rd) + s2 * (sech2 * rdd - 2.0 * th * sech2 * rd * rd);
             }
         }
         __syncthreads();
@@ -1077,6 +1086,24 @@ __global__ __launch_bounds__(256) void fbr_fourier_grad_finish_kernel(int C, int
 // (the layout and conventions of K6b's output).  One thread per entry; a joint whose grad_q entry is an exact 0 (most: a collision pair
 // moves with the joints between its two links only) costs nothing.  The wf entry adds its joints in ascending order: no atomics.
 // ------------------------------------------------------------------------------------------------
+// (r0, r1, r2) of parameter kind 0 wf, 3 a_l, 4 b_l at time ts
+__device__ __forceinline__ void fbr_fourier_dr(int kind, int l, bool bounded, int nh, double w, double ts, const double *aa, const double *bb, double &r0,
+                                               double &r1, double &r2)
+{
+    double sn, cs;
+    r0 = r1 = r2 = 0.0;
+    if (kind == 0) {
+        for (int h = 1; h <= nh; h++) {
+            const double dl = (double)h;
+            sincos(w * (ts * dl), &sn, &cs);
+            fbr_fourier_dwf_add(bounded, w, ts, dl, aa[h - 1], bb[h - 1], sn, cs, r0, r1, r2);
+        }
+    } else {
+        const double dl = (double)l;
+        sincos(w * (ts * dl), &sn, &cs);
+        fbr_fourier_dcoef(bounded, kind == 4, w * dl, sn, cs, r0, r1, r2);
+    }
+}
 __device__ __forceinline__ double fbr_fourier_dq_dp(int kind, int l, bool bounded, int nh, double w, double ts, const double *aa, const double *bb,
                                                     double qr)
 {  // kind 0 wf, 1 q_offset, 2 q_range, 3 a_l, 4 b_l
@@ -1089,18 +1116,8 @@ __device__ __forceinline__ double fbr_fourier_dq_dp(int kind, int l, bool bounde
         f = qr * (1.0 - th * th);
     }
     if (kind == 2) return bounded ? th : 0.0;
-    double r0 = 0.0, r1 = 0.0, r2 = 0.0, sn, cs;
-    if (kind == 0) {
-        for (int h = 1; h <= nh; h++) {
-            const double dl = (double)h;
-            sincos(w * (ts * dl), &sn, &cs);
-            fbr_fourier_dwf_add(bounded, w, ts, dl, aa[h - 1], bb[h - 1], sn, cs, r0, r1, r2);
-        }
-    } else {
-        const double dl = (double)l;
-        sincos(w * (ts * dl), &sn, &cs);
-        fbr_fourier_dcoef(bounded, kind == 4, w * dl, sn, cs, r0, r1, r2);
-    }
+    double r0, r1, r2;
+    fbr_fourier_dr(kind, l, bounded, nh, w, ts, aa, bb, r0, r1, r2);
     return bounded ? f * r0 : r0;
 }
 
@@ -1136,6 +1153,71 @@ __global__ __launch_bounds__(256) void fbr_fourier_poschain_kernel(int C, long R
                     l = 1 + (rr - j * nh);
                 }
                 if (g[j] != 0.0) v = g[j] * fbr_fourier_dq_dp(kind, l, bounded, nh, w, ts, ca + j * nh, cb + j * nh, bounded ? qrange[(long)c * n + j] : 0.0);
+            }
+            v *= scale ? scale[cr] : 1.0;
+        }
+        out[e] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K6d: K6c for rows that carry sensitivities to the velocity and the acceleration as well (fbr_fourier_state_chain: the torque, position and
+// velocity rows of the constraint Jacobian, analyticalGradient.py:764-953):
+//   out [c][r][p] = scale sum_d gq[d] dq_d/dp + gdq[d] d(dq_d)/dp + gddq[d] d(ddq_d)/dp      at t = sample / freq,
+// K6c's layout, one thread per entry, joints in ascending order, exact zeros skipped.  The position share is K6c's own expression
+// (fbr_fourier_dq_dp), so that rows with gdq == gddq == NULL equal K6c's (a zero entry may carry the other sign); the velocity and acceleration share goes through the factors
+// of K6b (fbr_fourier_tanh_chain with no position sensitivity).  Any of gq / gdq / gddq may be NULL.
+// ------------------------------------------------------------------------------------------------
+// s1 d(dq_j)/dp + s2 d(ddq_j)/dp of one joint; kind as for fbr_fourier_dq_dp
+__device__ __forceinline__ double fbr_fourier_dvel_dp(int kind, int l, bool bounded, int nh, double w, double ts, const double *aa, const double *bb,
+                                                      double qr, double s1, double s2)
+{
+    if (kind == 1 || (kind == 2 && !bounded)) return 0.0;
+    double e0 = 0.0, e1 = s1, e2 = s2, er = 0.0;
+    if (bounded) {
+        double raw, rd, rdd;
+        fbr_fourier_raw(nh, w, ts, aa, bb, raw, rd, rdd);
+        const double th = tanh(raw);
+        fbr_fourier_tanh_chain(th, 1.0 - th * th, qr, rd, rdd, 0.0, s1, s2, e0, e1, e2, er);
+    }
+    if (kind == 2) return er;
+    double r0, r1, r2;
+    fbr_fourier_dr(kind, l, bounded, nh, w, ts, aa, bb, r0, r1, r2);
+    return e0 * r0 + e1 * r1 + e2 * r2;
+}
+
+__global__ __launch_bounds__(256) void fbr_fourier_statechain_kernel(int C, long R, int n, int nh, double freq, const double *__restrict__ wf,
+                                                                     const double *__restrict__ a, const double *__restrict__ b,
+                                                                     const double *__restrict__ qrange, const long *__restrict__ sample,
+                                                                     const double *__restrict__ scale, const double *__restrict__ gq,
+                                                                     const double *__restrict__ gdq, const double *__restrict__ gddq,
+                                                                     double *__restrict__ out)
+{
+    const int E = 1 + 2 * n + 2 * n * nh;
+    const long total = (long)C * R * E;
+    const bool bounded = qrange != nullptr;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long cr = e / E;
+        const int i = (int)(e - cr * E), c = (int)(cr / R);
+        const long s = sample[cr];
+        double v = 0.0;
+        if (s >= 0) {
+            const double ts = (double)s / freq, w = wf[c];
+            const double *ca = a + (long)c * n * nh, *cb = b + (long)c * n * nh;
+            // one joint's share of the entry of parameter (kind, l)
+            auto joint = [&](int j, int kind, int l) {
+                const double g0 = gq ? gq[cr * n + j] : 0.0, g1 = gdq ? gdq[cr * n + j] : 0.0, g2 = gddq ? gddq[cr * n + j] : 0.0;
+                const double qr = bounded ? qrange[(long)c * n + j] : 0.0;
+                if (g0 != 0.0) v += g0 * fbr_fourier_dq_dp(kind, l, bounded, nh, w, ts, ca + j * nh, cb + j * nh, qr);
+                if (g1 != 0.0 || g2 != 0.0) v += fbr_fourier_dvel_dp(kind, l, bounded, nh, w, ts, ca + j * nh, cb + j * nh, qr, g1, g2);
+            };
+            if (i == 0) {
+                for (int j = 0; j < n; j++) joint(j, 0, 0);
+            } else if (i < 1 + 2 * n) {
+                joint((i - 1) % n, 1 + (i - 1) / n, 0);
+            } else {
+                const int r = i - 1 - 2 * n, isb = r >= n * nh, rr = r - isb * n * nh, j = rr / nh;
+                joint(j, 3 + isb, 1 + (rr - j * nh));
             }
             v *= scale ? scale[cr] : 1.0;
         }

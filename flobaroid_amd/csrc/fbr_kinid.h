@@ -347,6 +347,24 @@ struct DevKinWrite {
 // LDS (over its staged ddq, read by then) instead of HBM, and the block's extrema of q, |dq| and |tau| are scanned from the LDS after the
 // lane body -- nothing per sample leaves the CU.  The lane body and `emit`'s arithmetic are the plain instance's: the torques compared are
 // the ones fbr_inverse_dynamics_batch returns, bit for bit.
+// friction torque of joint d from the standard-parameter vector (mode 0, model.py:299-326): Coulomb, and unless gravity-only the viscous
+// term, the constant offset and the Stribeck term; vs: the joint's vel_sign entry, read under Stribeck friction only
+__device__ __forceinline__ double fbr_friction_std(const DevModel &m, const double *__restrict__ x, int d, double dqv, double sg, const double *vs)
+{
+    const int n = m.n;
+    double t = sg * x[m.fstart + d];
+    if (!m.grav_only) {
+        t += x[m.fstart + n + d] * dqv;
+        const int poff = m.fstart + 2 * n;
+        t += x[poff + d];
+        if (m.stribeck > 0) {
+            const double sgn = (sg > 0) - (sg < 0);
+            t += x[poff + n + d] * exp(-fabs(*vs) / m.stribeck) * sgn;
+        }
+    }
+    return t;
+}
+
 template <int MAXD, bool EXT = false>
 __global__ __launch_bounds__(64) void fbr_kinid_kernel(DevModel m, DevKinId p, long S, const double *__restrict__ q, const double *__restrict__ dq,
                                                        const double *__restrict__ ddq, const double *__restrict__ bv,
@@ -451,17 +469,7 @@ __global__ __launch_bounds__(64) void fbr_kinid_kernel(DevModel m, DevKinId p, l
                 const double dqv = mysdq[d];
                 const double sg = sign[s * n + d];
                 if (mode == 0) {
-                    double t = sg * x[m.fstart + d];
-                    if (!m.grav_only) {
-                        t += x[m.fstart + n + d] * dqv;
-                        const int poff = m.fstart + 2 * n;
-                        t += x[poff + d];
-                        if (m.stribeck > 0) {
-                            const double sgn = (sg > 0) - (sg < 0);
-                            t += x[poff + n + d] * exp(-fabs(vel_sign[s * n + d]) / m.stribeck) * sgn;
-                        }
-                    }
-                    v += t;
+                    v += fbr_friction_std(m, x, d, dqv, sg, vel_sign + s * n + d);
                 } else {
                     for (int c = m.cpl * m.L; c < m.cols; c++) {
                         const int4 cd = m.coldesc[c];
@@ -621,6 +629,126 @@ __global__ __launch_bounds__(64) void fbr_kinfd_kernel(DevModel m, DevKinId p, l
             score += Ws[(long)(m.fb + jj) * m.cols + c] * fbr_friction_value(cd.z, dqv, sign ? sign[s * n + jj] : 0.0, m.stribeck);
         }
         if (live) out[e] = score;
+    }
+}
+// Torque rows under the same sweep (fbr_torque_row_sweep; analyticalGradient.py:114-183 at the sample where |tau_n| peaks): one lane per
+// EVALUATION e = item (1 + 3 n) + j of item = (candidate c, row r) -- sample tr.sample[item] of candidate c, state perturbed as in
+// fbr_kinfd_kernel -- out[e] = joint torque row tr.joint[item] (NULL: r) of the inverse dynamics of x (mode 0 of fbr_kinid_kernel: the same
+// lane body, link wrench and friction term; the sign series, vel_sign and the base state stay the sample's own).  Nothing is expanded in
+// memory; every other row the lane body emits is dropped.  An index outside its range is read clamped and raises *tr.flag.
+struct DevKinTau {
+    long T, R;           // samples per candidate, rows per candidate
+    const long *sample;  // [C][R]
+    const int *joint;    // [C][R] or NULL
+    int *flag;
+};
+template <int MAXD>
+__global__ __launch_bounds__(64) void fbr_kintau_kernel(DevModel m, DevKinId p, DevKinTau tr, long items, int nper, double eps, const double *__restrict__ q,
+                                                        const double *__restrict__ dq, const double *__restrict__ ddq, const double *__restrict__ bv,
+                                                        const double *__restrict__ ba, const double *__restrict__ rpy, const double *__restrict__ sign,
+                                                        const double *__restrict__ vel_sign, const double *__restrict__ x, double *__restrict__ out,
+                                                        double *__restrict__ scratch)
+{
+    const int lane = threadIdx.x, n = m.n;
+    double *scr = scratch + (long)blockIdx.x * p.nslots * FBR_LINK_REC * 64 + lane;
+    const long total = items * nper, nblk = (total + 63) >> 6;
+    for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const long e = min((blk << 6) + lane, total - 1);
+        const bool live = (blk << 6) + lane < total;
+        const long item = e / nper, c = item / tr.R;
+        const int j = (int)(e - item * nper);
+        const int kind = (j == 0) ? -1 : (j - 1) / n, dj = (j == 0) ? -1 : (j - 1) % n;
+        const long smp = tr.sample[item], smpc = min(max(smp, 0L), tr.T - 1);
+        const int jn = tr.joint ? tr.joint[item] : (int)(item - c * tr.R), jnc = min(max(jn, 0), n - 1);
+        if ((smp != smpc || jn != jnc) && live) *tr.flag = 1;
+        const long s = c * tr.T + smpc;
+        double row = 0.0;
+        auto state = [&](int d, double &a, double &b, double &cc) {
+            a = q[s * n + d] + ((kind == 0 && d == dj) ? eps : 0.0);
+            b = dq[s * n + d] + ((kind == 1 && d == dj) ? eps : 0.0);
+            cc = ddq[s * n + d] + ((kind == 2 && d == dj) ? eps : 0.0);
+        };
+        auto basest = [&](double *v6, double *a6, double *e3) {
+            for (int i = 0; i < 6; i++) {
+                v6[i] = bv[s * 6 + i];
+                a6[i] = ba[s * 6 + i];
+            }
+            for (int i = 0; i < 3; i++) e3[i] = rpy[s * 3 + i];
+        };
+        auto save = [&](int b, int i, double v) { scr[(b * FBR_LINK_REC + i) * 64] = v; };
+        auto load = [&](int b, int i) { return scr[(b * FBR_LINK_REC + i) * 64]; };
+        auto consts = [&](int l, double *rR, double *rp, double *ax) {  // (l is wave-uniform: scalar loads through the constant address space)
+            const fbr_cdouble_ptr cR = (fbr_cdouble_ptr)(unsigned long)m.restR, cp = (fbr_cdouble_ptr)(unsigned long)m.restp,
+                                  ca = (fbr_cdouble_ptr)(unsigned long)m.axis;
+            for (int i = 0; i < 9; i++) rR[i] = cR[9 * l + i];
+            for (int i = 0; i < 3; i++) {
+                rp[i] = cp[3 * l + i];
+                ax[i] = ca[3 * l + i];
+            }
+        };
+        auto link = [&](int l, int depth, const double *rec, const double (*Sst)[6], const int *lvd, double *F) {
+            (void)depth; (void)Sst; (void)lvd;
+            double pi[10];
+            for (int i = 0; i < 10; i++) pi[i] = x[10 * l + i];
+            fbr_link_wrench(rec, pi, F);
+        };
+        auto emit = [&](int r, double v) {
+            if (r != m.fb + jnc) return;
+            if (m.fric) {
+                const double dqv = dq[s * n + jnc] + ((kind == 1 && jnc == dj) ? eps : 0.0);
+                v += fbr_friction_std(m, x, jnc, dqv, sign[s * n + jnc], vel_sign + s * n + jnc);
+            }
+            row = v;
+        };
+        fbr_kinid_lane<MAXD, true>(p.nsteps, p.maxlvl, p.steps, p.endflush, m.floating, m.g, m.fb, state, basest, save, load, link, emit, consts);
+        if (live) out[e] = row;
+    }
+}
+// The two-kernel route of the same sweep (fused_id = 0, joint paths beyond FBR_KINID_MAXD, more than 105 DOF): the perturbed states of the
+// items [i0, i0 + ci) written out for fbr_kin_kernel + fbr_id_kernel (one thread per evaluation; es / evs only with friction / Stribeck) ...
+__global__ __launch_bounds__(256) void fbr_tau_expand_kernel(DevKinTau tr, long i0, long ci, int n, double eps, const double *__restrict__ q,
+                                                             const double *__restrict__ dq, const double *__restrict__ ddq, const double *__restrict__ bv,
+                                                             const double *__restrict__ ba, const double *__restrict__ rpy, const double *__restrict__ sign,
+                                                             const double *__restrict__ vel_sign, double *__restrict__ eq, double *__restrict__ edq,
+                                                             double *__restrict__ eddq, double *__restrict__ ebv, double *__restrict__ eba,
+                                                             double *__restrict__ erpy, double *__restrict__ es, double *__restrict__ evs)
+{
+    const int nper = 1 + 3 * n;
+    const long total = ci * nper;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long item = i0 + e / nper, c = item / tr.R;
+        const int j = (int)(e % nper);
+        const int kind = (j == 0) ? -1 : (j - 1) / n, dj = (j == 0) ? -1 : (j - 1) % n;
+        const long smp = tr.sample[item], smpc = min(max(smp, 0L), tr.T - 1);
+        if (smp != smpc) *tr.flag = 1;
+        const long s = c * tr.T + smpc;
+        for (int i = 0; i < n; i++) {
+            eq[e * n + i] = q[s * n + i] + ((kind == 0 && i == dj) ? eps : 0.0);
+            edq[e * n + i] = dq[s * n + i] + ((kind == 1 && i == dj) ? eps : 0.0);
+            eddq[e * n + i] = ddq[s * n + i] + ((kind == 2 && i == dj) ? eps : 0.0);
+            if (sign) es[e * n + i] = sign[s * n + i];
+            if (vel_sign) evs[e * n + i] = vel_sign[s * n + i];
+        }
+        if (bv) {
+            for (int i = 0; i < 6; i++) {
+                ebv[e * 6 + i] = bv[s * 6 + i];
+                eba[e * 6 + i] = ba[s * 6 + i];
+            }
+            for (int i = 0; i < 3; i++) erpy[e * 3 + i] = rpy[s * 3 + i];
+        }
+    }
+}
+// ... and the requested rows gathered from their torques tau [ci (1 + 3 n)][rows]
+__global__ __launch_bounds__(256) void fbr_tau_gather_kernel(DevKinTau tr, long i0, long ci, int n, int fb, int rows, const double *__restrict__ tau,
+                                                             double *__restrict__ out)
+{
+    const int nper = 1 + 3 * n;
+    const long total = ci * nper;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long item = i0 + e / nper;
+        const int jn = tr.joint ? tr.joint[item] : (int)(item % tr.R), jnc = min(max(jn, 0), n - 1);
+        if (jn != jnc) *tr.flag = 1;
+        out[i0 * nper + e] = tau[e * rows + fb + jnc];
     }
 }
 #endif

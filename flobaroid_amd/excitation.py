@@ -13,7 +13,10 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
   candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``;
 * ``candidate_collision_gradient`` -- the collision rows of the constraint Jacobian in capsule mode (analyticalGradient.py:955-1027) from
-  ``Engine.capsule_distance_gradients`` + ``Engine.fourier_position_chain``.
+  ``Engine.capsule_distance_gradients`` + ``Engine.fourier_position_chain``;
+* ``candidate_gradients_from_coefficients`` -- everything ``IpoptProblem.gradient`` / ``.jacobian`` need of many candidates: the above plus
+  the soft-cost gradients and the position, velocity and torque rows of the constraint Jacobian (analyticalGradient.py:764-953) from
+  ``Engine.torque_row_sweep`` + ``Engine.fourier_state_chain``.
 """
 from __future__ import annotations
 
@@ -348,12 +351,18 @@ def candidate_objectives(engine, states: dict, ncand: int, independent_cols, x_s
     reduced on the device) over the same states.  ``vel_sign``: Stribeck friction, as for ``Engine.inverse_dynamics``.  ``collision``
     (``flobaroid_amd.collision.collision_set``: capsules, pairs, margins): the collision block of capsule mode is appended to ``g``
     (``candidate_collision_constraints``); None: no collision block, every array as without the argument."""
+    return _candidate_objective_parts(engine, states, ncand, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign,
+                                      collision)[0]
+
+
+def _candidate_objective_parts(engine, states, ncand, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign, collision):
+    """``candidate_objectives`` together with what the gradients reuse: (result, the grouped Gram on the host, the collision block or None)"""
     _check_config(config)
     G = _host(engine.gram_grouped(states, int(ncand)))
     nld, _, nobs = est.d_optimality_batch_terms(G, independent_cols, config.get("doptRegularization", 1e-4), YtY_prior)
     ext = engine.candidate_extrema(states, int(ncand), x_std, vel_sign=vel_sign)
-    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale,
-                                   collision=_collision_block(engine, states, ncand, config, collision))
+    coll = _collision_block(engine, states, ncand, config, collision)
+    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale, collision=coll), G, coll
 
 
 def candidate_objectives_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict,
@@ -364,11 +373,7 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
     parameters, or an object with ``xStdModel`` (``Model``)."""
     _check_config(config)
     x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
-    st = candidate_states(engine, candidates, T, freq, device=True)
-    if engine.friction:
-        import torch
-
-        st["sign"] = torch.tanh(st["dq"] / float(config.get("frictionSignThreshold", 0.02)))
+    st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02))
     vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
     return candidate_objectives(engine, st, len(candidates), independent_cols, x_std, limits, joint_names, config, dopt_scale=dopt_scale,
                                 YtY_prior=YtY_prior, vel_sign=vel_sign, collision=collision)
@@ -378,7 +383,7 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
 # The D-optimality term of the optimiser's gradient per candidate (analyticalGradient.py compute_analytical_gradient, Phases 1, A and B,
 # lines 538-762): weight rows on the device (Engine.regressor_weights), the finite-difference sweep (Engine.fd_scores) and the chain with
 # the Jacobian of the Fourier series (Engine.fourier_gradient).  The collision rows of the constraint Jacobian: candidate_collision_gradient
-# below.  Not covered: the soft-cost, torque and limit gradients of Phase C, the suspended base.
+# below; Phase C and the whole gradient: candidate_gradients_from_coefficients at the end.  Not covered: the suspended base.
 # ------------------------------------------------------------------------------------------------------------------------------------
 def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4, dopt_scale=1.0, YtY_prior=None, B=None):
     """The constant matrices of ``Engine.regressor_weights`` for C candidates from their Grams ``G`` (C, Pa, Pa) (``Engine.gram_grouped``):
@@ -432,17 +437,38 @@ def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, 
     ``subsample`` = k sweeps the samples 0, k, 2 k, ... only and scales the result by k (``analyticalGradientSubsample``); the Gram, f and
     C always use every sample.  Friction engines: the viscous column is linear in dq and sits in W, so the sweep carries its derivative
     (the reference adds it analytically, ``W_visc``); the Coulomb sign tanh(dq / threshold) is held at its baseline value, as there."""
+    st = _coefficient_states(engine, candidates, T, freq, friction_sign_threshold)
+    G = _host(engine.gram_grouped(st, len(candidates)))
+    nld = est.d_optimality_batch(G, independent_cols, dopt_regularization, YtY_prior)
+    scale = 1.0 if dopt_scale is None else float(dopt_scale)
+    return nld * scale, _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale, YtY_prior, epsilon, subsample,
+                                       max_weight_bytes)
+
+
+def _coefficient_states(engine, candidates, T, freq, friction_sign_threshold):
+    """``candidate_states`` on the device with the Coulomb column tanh(dq / threshold) of a friction engine"""
+    st = candidate_states(engine, candidates, int(T), freq, device=True)
+    if engine.friction:
+        import torch
+
+        st["sign"] = torch.tanh(st["dq"] / float(friction_sign_threshold))
+    return st
+
+
+def _gradient_dict(g, n: int, nh: int) -> dict:
+    """the columns [wf | q_offset (n) | q_range (n) | a (n, nh) | b (n, nh)] of ``g`` (..., 1 + 2 n + 2 n nh) as the dict of the gradients"""
+    lead = g.shape[:-1]
+    return {"wf": g[..., 0].copy(), "q_offset": g[..., 1:1 + n].copy(), "q_range": g[..., 1 + n:1 + 2 * n].copy(),
+            "a": g[..., 1 + 2 * n:1 + 2 * n + n * nh].reshape(lead + (n, nh)).copy(), "b": g[..., 1 + 2 * n + n * nh:].reshape(lead + (n, nh)).copy()}
+
+
+def _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale, YtY_prior, epsilon, subsample, max_weight_bytes):
+    """the gradient dict of ``candidate_dopt_gradient_from_coefficients`` from the candidates' device states and grouped Gram"""
     import torch
 
     C = len(candidates)
     n = engine.n
     T, k = int(T), max(int(subsample), 1)
-    st = candidate_states(engine, candidates, T, freq, device=True)
-    if engine.friction:
-        st["sign"] = torch.tanh(st["dq"] / float(friction_sign_threshold))
-    G = _host(engine.gram_grouped(st, C))
-    nld = est.d_optimality_batch(G, independent_cols, dopt_regularization, YtY_prior)
-    scale = 1.0 if dopt_scale is None else float(dopt_scale)
     Cm, cols = dopt_weight_matrices(G, independent_cols, dopt_regularization, scale, YtY_prior)
     Ts = (T + k - 1) // k
     if k > 1:
@@ -467,9 +493,7 @@ def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, 
     bounded = all(c["q_range"] is not None for c in candidates)
     g = _host(engine.fourier_gradient([c["wf"] for c in candidates], A, B, sens[0], sens[1], sens[2], Ts, float(freq),
                                       q_range=np.stack([c["q_range"] for c in candidates]) if bounded else None, tstride=k))
-    grad = {"wf": g[:, 0].copy(), "q_offset": g[:, 1:1 + n].copy(), "q_range": g[:, 1 + n:1 + 2 * n].copy(),
-            "a": g[:, 1 + 2 * n:1 + 2 * n + n * nh].reshape(C, n, nh).copy(), "b": g[:, 1 + 2 * n + n * nh:].reshape(C, n, nh).copy()}
-    return nld * scale, grad
+    return _gradient_dict(g, n, nh)
 
 
 def gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
@@ -556,9 +580,7 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
         c1 = min(C, c0 + cc)
         out[c0:c1] = _host(engine.fourier_position_chain(wf[c0:c1], A[c0:c1], B[c0:c1], cons["eval_sample"][c0:c1], dg["grad_q"][c0:c1], float(freq),
                                                          scale=cons["eval_scale"][c0:c1], q_range=None if qr is None else qr[c0:c1]))
-    grad = {"wf": out[..., 0].copy(), "q_offset": out[..., 1:1 + n].copy(), "q_range": out[..., 1 + n:1 + 2 * n].copy(),
-            "a": out[..., 1 + 2 * n:1 + 2 * n + n * nh].reshape(C, P, n, nh).copy(), "b": out[..., 1 + 2 * n + n * nh:].reshape(C, P, n, nh).copy()}
-    return {"g": np.asarray(cons["g"]), "grad": grad, "grad_q": np.asarray(_host(dg["grad_q"]))}
+    return {"g": np.asarray(cons["g"]), "grad": _gradient_dict(out, n, nh), "grad_q": np.asarray(_host(dg["grad_q"]))}
 
 
 def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
@@ -596,3 +618,159 @@ def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, 
     ga, gb = np.asarray(grad["a"], dtype=np.float64), np.asarray(grad["b"], dtype=np.float64)
     return np.concatenate([np.asarray(grad["wf"], dtype=np.float64).reshape(-1, 1), dq0] + [ga[:, j, :nf[j]] for j in range(n)]
                           + [gb[:, j, :nf[j]] for j in range(n)], axis=1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Phase C of the analytical gradient (analyticalGradient.py:764-953) per candidate: the soft costs f1 .. f4 and the position, velocity, torque,
+# minimum-velocity and minimum-torque-utilisation rows of the constraint Jacobian.  Every one of them is a combination of 4 n rows per
+# candidate, each the derivative of ONE extremum with respect to the joint states at the sample where it is reached, chained with the
+# Jacobian of the Fourier series at that sample's time (Engine.fourier_state_chain); the torque rows come from forward differences of
+# Engine.torque_row_sweep.  Deliberate deviations from the reference: the wf column is analytic (there: central differences
+# of the whole trajectory); the torque Jacobians are the clean derivative (the reference's acceleration sweep still carries dq_{n-1} + eps
+# from its velocity sweep, see dopt_sensitivities: no flag reproduces that here); candidates whose D-optimality term failed get the
+# soft-cost gradient only.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def candidate_torque_jacobians(engine, states: dict, ncand: int, sample, x_std, epsilon: float = 1e-7, vel_sign=None) -> dict:
+    """The ``torque_sens`` of the reference's gradient worker (``_dopt_gradient_worker_func``, the ``need_torque`` branches, analyticalGradient.py:114-183) for ``ncand`` equal candidates stacked in ``states``:
+    joint n's torque at sample ``sample[c, n]`` of candidate c and its forward differences over the joint states, from one
+    ``Engine.torque_row_sweep``.  Returns ``tau`` (C, n), the baseline values whose ``np.sign`` is the reference's ``sign_n``, and
+    ``dtau_dq``, ``dtau_ddq_state``, ``dtau_dddq`` (C, n, n): row n holds the derivatives of tau_n with respect to q, dq and ddq (the
+    reference's names), in the memory space of the states.  The Coulomb sign series, ``vel_sign`` and the base state are held at the
+    sample's values; the clean derivative, without the reference's carried-over dq_{n-1} + eps in the acceleration sweep."""
+    n = engine.n
+    sw = engine.torque_row_sweep(states, int(ncand), sample, x_std, float(epsilon), vel_sign=vel_sign)
+    d = (sw[..., 1:] - sw[..., :1]) / float(epsilon)
+    return {"tau": sw[..., 0], "dtau_dq": d[..., :n], "dtau_ddq_state": d[..., n:2 * n], "dtau_dddq": d[..., 2 * n:]}
+
+
+def _like(ref, a, dtype=None):
+    """``a`` as an array of ``ref``'s kind: a torch tensor on ``ref``'s device, or NumPy; float64 unless ``dtype`` (a NumPy type) says int64"""
+    if hasattr(ref, "cpu"):
+        import torch
+
+        return torch.as_tensor(a, dtype=torch.int64 if dtype == np.int64 else torch.float64, device=ref.device)
+    return np.asarray(_host(a), dtype=dtype or np.float64)
+
+
+def _cat(parts, axis: int):
+    if hasattr(parts[0], "cpu"):
+        import torch
+
+        return torch.cat(parts, dim=axis)
+    return np.concatenate(parts, axis=axis)
+
+
+def constraint_chain_rows(ag_cache: dict, torque_jacobians: dict, vel_at_peak):
+    """The 4 n rows per candidate that Phase C chains with the Jacobian of the Fourier series, in the order [|tau| peak (n) | position
+    minimum (n) | position maximum (n) | |dq| peak (n)]: returns ``(sample, grad_q, grad_dq, grad_ddq)`` -- (C, 4 n) int64 and three
+    (C, 4 n, n) arrays, the arguments of ``Engine.fourier_state_chain`` -- of the kind (NumPy / torch) of ``torque_jacobians``.
+
+    torque rows: sign(tau_n) (dtau_dq[n], dtau_ddq_state[n], dtau_dddq[n]) at ``torque_absmax_idx[n]``; position rows: e_n on q at
+    ``pos_min_idx[n]`` / ``pos_max_idx[n]``; velocity rows: sign(dq_n) e_n on dq at ``vel_absmax_idx[n]``, ``vel_at_peak`` (C, n) being the
+    velocities there."""
+    tau = torque_jacobians["tau"]
+    C, n = int(tau.shape[0]), int(tau.shape[1])
+    sgn = lambda v: (v > 0) * _like(tau, 1.0) - (v < 0) * _like(tau, 1.0)  # noqa: E731  (np.sign for both kinds; a NaN gives 0)
+    st = sgn(tau)[:, :, None]
+    eye = _like(tau, np.eye(n))[None] + 0.0 * st
+    zero = 0.0 * eye
+    sv = sgn(_like(tau, vel_at_peak))[:, :, None]
+    sample = _cat([_like(tau, ag_cache[k], np.int64).reshape(C, n) for k in ("torque_absmax_idx", "pos_min_idx", "pos_max_idx", "vel_absmax_idx")], 1)
+    grad_q = _cat([st * torque_jacobians["dtau_dq"], eye, eye, zero], 1)
+    grad_dq = _cat([st * torque_jacobians["dtau_ddq_state"], zero, zero, sv * eye], 1)
+    grad_ddq = _cat([st * torque_jacobians["dtau_dddq"], zero, zero, zero], 1)
+    return sample, grad_q, grad_dq, grad_ddq
+
+
+def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_at_peak, chain, limits: dict, joint_names, config: dict) -> dict:
+    """The arithmetic of Phase C (analyticalGradient.py:764-953) for C candidates, arrays in and arrays out (NumPy or torch, the kind of
+    ``torque_jacobians``), no engine.  ``ag_cache``: the entry ``ag_cache`` of ``objectives_from_extrema``; ``torque_jacobians``:
+    ``candidate_torque_jacobians`` at ``ag_cache["torque_absmax_idx"]``; ``vel_at_peak`` (C, n): dq_n at ``vel_absmax_idx[n]``; ``limits``,
+    ``joint_names``, ``config`` as for ``objectives_from_extrema``.  ``chain(sample, grad_q, grad_dq, grad_ddq)`` chains the rows of
+    ``constraint_chain_rows`` with the Jacobian of the trajectory series and returns (C, 4 n, E) -- ``Engine.fourier_state_chain`` with the
+    candidates' coefficients bound, or any restatement of it; E is whatever parameter axis it produces.
+
+    Returns ``obj_grad`` (C, E) = 10 df1 + 10 df3 + df2 + 10 df4 (f2 carries its factor 10 already) with the reference's conditions -- f1
+    only where util_mean > 0 and util_std > 0, f3 only where f3 > 0, f4 only with ``trajectoryTargetVelocity`` > 0 and for joints with
+    vel_absmax < the target -- its terms ``df1`` .. ``df4`` (C, E) before those factors (``df2`` of the x10 f2), and ``con_grad``
+    (C, 5 n or 6 n, E) in ``constraint_layout`` order: -dq at the argmin, +dq at the argmax, sign d(dq), d|tau|, [-sign d(dq) with
+    ``minVelocityConstraint``,] -d|tau|."""
+    _check_config(config)
+    tau = torque_jacobians["tau"]
+    n = int(tau.shape[1])
+    jn = list(joint_names)
+    if len(jn) != n:
+        raise ValueError(f"{len(jn)} joint names for {n} joints")
+    rows = chain(*constraint_chain_rows(ag_cache, torque_jacobians, vel_at_peak))
+    dT, dPmin, dPmax, dV = rows[:, :n], rows[:, n:2 * n], rows[:, 2 * n:3 * n], rows[:, 3 * n:]
+    A = lambda k: _like(rows, ag_cache[k])  # noqa: E731
+    tlim = _like(rows, np.array([limits[j]["torque"] for j in jn], dtype=np.float64))
+    util, mean, std, f1, f3 = A("utilization"), A("util_mean"), A("util_std"), A("f1"), A("f3")
+    one = _like(rows, 1.0)
+    dutil = dT / tlim[None, :, None]
+    on1 = ((mean > 0) & (std > 0)) * one
+    m1, s1 = mean * on1 + (1.0 - on1), std * on1 + (1.0 - on1)  # (1 where the term is off: nothing is divided by zero)
+    df1_dutil = ((util - mean[:, None]) / s1[:, None] - f1[:, None]) / (n * m1[:, None])
+    df1 = on1[:, None] * (df1_dutil[:, :, None] * dutil).sum(1)
+    df3 = ((f3 > 0) * one)[:, None] * (-1.0 / config.get("trajectoryTargetTorqueUtil", 0.25)) * dutil.mean(1)
+    df2 = -10.0 * ((dPmax - dPmin) / A("pos_range_available")[None, :, None]).mean(1)
+    vt = float(config.get("trajectoryTargetVelocity", 0.0))
+    df4 = 0.0 * df2
+    if vt > 0:
+        df4 = (-1.0 / (n * vt)) * (((A("vel_absmax") < vt) * one)[:, :, None] * dV).sum(1)
+    blocks = [-dPmin, dPmax, dV, dT] + ([-dV] if config.get("minVelocityConstraint", False) else []) + [-dT]
+    return {"obj_grad": 10.0 * df1 + 10.0 * df3 + df2 + 10.0 * df4, "df1": df1, "df2": df2, "df3": df3, "df4": df4, "con_grad": _cat(blocks, 1)}
+
+
+def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict, joint_names,
+                                          config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1) -> dict:
+    """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
+    and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
+    one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
+    (``candidate_dopt_gradient_from_coefficients``'s, from the same states and Gram); ``candidate_torque_jacobians`` at the torque peaks; one
+    ``Engine.fourier_state_chain`` over the 4 n rows of ``constraint_chain_rows``; ``constraint_gradients_from_rows``; with ``collision``
+    the rows of ``candidate_collision_gradient`` at ``layout["collision"]``.  Only per-candidate arrays cross PCIe.
+
+    Returns ``f`` (C,) and ``g`` (C, len), identical to ``candidate_objectives_from_coefficients``; ``obj_grad``: a dict ``wf`` (C,),
+    ``q_offset`` / ``q_range`` (C, n), ``a`` / ``b`` (C, n, nh) (the format of ``candidate_dopt_gradient_from_coefficients``), the
+    D-optimality term included; ``dopt_grad`` and ``soft_grad``: its two terms (``dopt_grad`` zeros for ``failed`` candidates, whose
+    ``obj_grad`` is the soft-cost gradient only); ``con_grad``: the same dict with a leading constraint axis, ``wf`` (C, len), ... in ``constraint_layout`` order;
+    ``layout``; ``ag_cache``; ``objectives``: the whole result of ``candidate_objectives``.  ``gradient_to_optimizer_variables`` /
+    ``constraint_gradient_to_optimizer_variables`` map ``{k: v[c] ...}`` of both onto the reference's variable vector.
+
+    ``epsilon``: the forward-difference step of both sweeps, None: ``config.get("analyticalGradientEpsilon", 1e-7)``; ``subsample``: of the
+    D-optimality sweep (``analyticalGradientSubsample``).  Deviations from the reference: the wf column is analytic, the torque Jacobians
+    are the clean derivative (no carried-over dq_{n-1} + eps), the Coulomb sign and the Stribeck exponent are held at their baseline;
+    a ``failed`` candidate gets the soft-cost gradient only.  Not covered: the suspended base, gravity-only models (refused), mesh
+    collision modes, world links."""
+    _check_config(config)
+    x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
+    C, n, T = len(candidates), engine.n, int(T)
+    eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)
+    st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02))
+    vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
+    obj, G, coll = _candidate_objective_parts(engine, st, C, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign,
+                                              collision)
+    ag = obj["ag_cache"]
+    dopt = _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, config.get("doptRegularization", 1e-4), obj["dopt_scale"], YtY_prior,
+                          eps, subsample, 2**31)
+    ok = ~obj["failed"]
+    dopt = {k: np.where(ok.reshape((C,) + (1,) * (v.ndim - 1)), v, 0.0) for k, v in dopt.items()}
+    jac = {k: _host(v) for k, v in candidate_torque_jacobians(engine, st, C, ag["torque_absmax_idx"], x_std, eps, vel_sign=vel_sign).items()}
+    import torch
+
+    vidx = torch.as_tensor(np.asarray(ag["vel_absmax_idx"], dtype=np.int64), device=st["dq"].device).reshape(C, 1, n)
+    vel_at_peak = _host(torch.gather(st["dq"].reshape(C, T, n), 1, vidx)[:, 0])
+    A, B, nh, qr = _padded_coefficients(candidates, n)
+    wf = np.array([c["wf"] for c in candidates], dtype=np.float64)
+    chain = lambda smp, gq, gdq, gddq: _host(engine.fourier_state_chain(wf, A, B, smp, float(freq), gq, gdq, gddq, q_range=qr))  # noqa: E731
+    pc = constraint_gradients_from_rows(ag, jac, vel_at_peak, chain, limits, joint_names, config)
+    soft = _gradient_dict(pc["obj_grad"], n, nh)
+    con = pc["con_grad"]
+    lay = constraint_layout(n, bool(config.get("minVelocityConstraint", False)), None if coll is None else int(np.asarray(coll["g"]).shape[1]))
+    con_grad = _gradient_dict(con, n, nh)
+    if coll is not None:
+        cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll)["grad"]
+        con_grad = {k: np.concatenate([v, cg[k]], axis=1) for k, v in con_grad.items()}
+    return {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
+            "layout": lay, "ag_cache": ag, "objectives": obj}

@@ -86,7 +86,8 @@ typedef struct {
  * the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info, option "fused_id"; 102: fbr_gram_lane_info, options
  * "gram_lane" / "gram_force_tiles"; 103: fbr_candidate_extrema; 104: fbr_model_set_capsules, fbr_candidate_capsule_distances, and -- added under the same number, which
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
- * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain. */
+ * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
+ * fbr_fourier_state_chain. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -131,6 +132,24 @@ int fbr_inverse_dynamics_batch(fbr_model *m, const fbr_states *st, const double 
  */
 int fbr_candidate_extrema(fbr_model *m, const fbr_states *st, int32_t ncand, const double *x_std, int32_t num_x,
                           const double *vel_sign, double *val_out, int64_t *idx_out, int32_t out_mem);
+
+/*
+ * Joint torque rows of chosen samples under the finite-difference sweep of the analytical gradient's torque Jacobians (excitation/
+ * analyticalGradient.py:114-183: 1 + 3 n inverse dynamics at the sample where |tau_n| peaks; Phase C, lines 764-953, chains their forward
+ * differences).  The states are ncand equal candidates of T = num_samples / ncand samples (the layout of fbr_candidate_extrema); x_std,
+ * vel_sign and the sign series as for fbr_inverse_dynamics_batch.  sample [ncand][nrows] (int64, 0 .. T-1: the sample inside the candidate)
+ * and joint [ncand][nrows] (int32, 0 .. n-1; NULL: nrows == n and joint = column index) live in st->mem.
+ *   out [ncand][nrows][1 + 3 n] (out_mem): joint torque row fb + joint of the inverse dynamics of x_std -- entry 0 at the state of the
+ *   sample, entry 1 + kind * n + d with +eps on q_d (kind 0) / dq_d (1) / ddq_d (2): the entry order of fbr_fd_scores.  Held at the
+ *   sample's own values, as in the reference: the sign series, vel_sign (the Stribeck exponent) and the base state; the viscous term moves
+ *   with dq.  One lane per evaluation on the route of fbr_inverse_dynamics_batch (merged links included), nothing expanded in memory; the
+ *   two-kernel form expands chunk by chunk (option "fused_id" 0, joint paths beyond 24 joints, more than 105 DOF).  No atomics: the same
+ *   bits on every run.
+ * FBR_E_INVALID: as for fbr_candidate_extrema, nrows < 1, joint == NULL with nrows != n, eps zero or not finite, and a sample or joint
+ * index out of range (read clamped on the device, never out of bounds, and reported after the call; out is then unspecified).
+ */
+int fbr_torque_row_sweep(fbr_model *m, const fbr_states *st, int32_t ncand, int64_t nrows, const int64_t *sample, const int32_t *joint,
+                         const double *x_std, int32_t num_x, const double *vel_sign, double eps, double *out, int32_t out_mem);
 
 /*
  * Capsule collision geometry of the robot, for fbr_candidate_capsule_distances: the reference's collisionMode "capsule"
@@ -310,6 +329,21 @@ int fbr_fourier_gradient(fbr_model *m, int32_t ncand, int64_t T, int32_t tstride
 int fbr_fourier_position_chain(fbr_model *m, int32_t ncand, int64_t nrows, int32_t nharm, double freq, const double *wf, const double *a,
                                const double *b, const double *q_range, const int64_t *sample, const double *scale, const double *grad_q,
                                int32_t mem, double *out, int32_t out_mem);
+
+/*
+ * The same chain for rows that carry sensitivities to the joint velocities and accelerations as well -- the torque, position and velocity
+ * rows of the constraint Jacobian and of the soft-cost gradients (analyticalGradient.py:764-953, there a Python loop per row over joints
+ * and harmonics).  grad_q / grad_dq / grad_ddq [ncand][nrows][n] in `mem` space, each may be NULL (zero); everything else as for
+ * fbr_fourier_position_chain.
+ *   out [ncand][nrows][1 + 2 n + 2 n nharm]:  entry = scale * sum_d (grad_q[d] dq_d/dp + grad_dq[d] d(dq_d)/dp + grad_ddq[d] d(ddq_d)/dp)
+ *   at t = sample / freq, every derivative analytic (wf too: the reference takes central differences of the whole trajectory there).  A
+ *   row with sample < 0 is zero; exact-zero entries of the grad arrays cost nothing; the wf entry adds its joints in ascending order.
+ *   With grad_dq == grad_ddq == NULL every entry equals fbr_fourier_position_chain's (the same expression; an entry that is zero may carry
+ *   the other sign).
+ */
+int fbr_fourier_state_chain(fbr_model *m, int32_t ncand, int64_t nrows, int32_t nharm, double freq, const double *wf, const double *a,
+                            const double *b, const double *q_range, const int64_t *sample, const double *scale, const double *grad_q,
+                            const double *grad_dq, const double *grad_ddq, int32_t mem, double *out, int32_t out_mem);
 
 /*
  * R_out [(cols+k)][(cols+k)] upper triangular with R^T R = [Y|rhs]^T [Y|rhs], by blocked Householder
