@@ -85,6 +85,15 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, _dp, ctypes.c_int32,
          ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_suspended_base_motion": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
+    "fbr_suspended_records": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_model_set_capsules": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip]),
     "fbr_candidate_capsule_distances": (
         ctypes.c_int,
@@ -494,6 +503,70 @@ class Engine:
         r, ret = self._out(None, shp + (1 + 3 * self.n,), out_mem)
         _check(self._lib.fbr_torque_row_sweep(self._h, ctypes.byref(s), C, R, psmp, pjnt, x.ctypes.data_as(_dp), int(x.size), vs.ptr, float(eps),
                                               r.ptr, out_mem), "fbr_torque_row_sweep")
+        return ret
+
+    def _joint_states(self, st: dict):
+        """q, dq, ddq of ``st`` alone as an ``fbr_states`` (the base arrays stay NULL): (struct, keep-alive refs, S, memory space)"""
+        q = _Ref(st["q"], None, "q")
+        if len(q.obj.shape) != 2 or q.obj.shape[1] != self.n:
+            raise ValueError(f"q: expected (S, {self.n}), got {tuple(q.obj.shape)}")
+        S = int(q.obj.shape[0])
+        dq, ddq = _Ref(st["dq"], (S, self.n), "dq"), _Ref(st["ddq"], (S, self.n), "ddq")
+        mem = _same_space([q, dq, ddq])
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        s = fbr_states()
+        s.num_samples, s.mem, s.q, s.dq, s.ddq = S, mem, q.ptr, dq.ptr, ddq.ptr
+        return s, [q, dq, ddq], S, mem
+
+    def _link_index(self, link) -> int:
+        return list(self.topo.link_names).index(link) if isinstance(link, str) else int(link)
+
+    def suspended_base_motion(self, st: dict, ncand: int, x_std, att_link, dt: float, damping: float, device_out: bool | None = None,
+                              with_info: bool = False) -> dict:
+        """Base motion of ``ncand`` equal candidates stacked in ``st`` (``q``, ``dq``, ``ddq``) of a robot hanging from a ball joint at the
+        origin of ``att_link`` (a link index or name) -- ``fbr_suspended_base_motion``, the reference's ``simulate_suspended_base_motion`` per
+        candidate with time step ``dt`` and ball-joint ``damping``.  Returns ``rpy`` (S, 3), ``base_position`` (S, 3), ``base_vel`` (S, 6),
+        ``base_acc`` (S, 6) -- the base state arrays of the other candidate calls -- and with ``with_info`` ``att_state`` (S, 6): the
+        attachment's rpy and angular velocity at each step, ``info`` (C, 2) int64: equilibrium iterations, clamp events.  Torch tensors when
+        the states are on the device, NumPy arrays otherwise (``device_out`` overrides)."""
+        s, keep, S, mem = self._joint_states(st)
+        x = np.ascontiguousarray(x_std, dtype=np.float64)
+        C = int(ncand)
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        shapes = {"rpy": (S, 3), "base_position": (S, 3), "base_vel": (S, 6), "base_acc": (S, 6)}
+        if with_info:
+            shapes["att_state"] = (S, 6)
+        out = {k: self._out(None, shp, out_mem) for k, shp in shapes.items()}
+        pinfo, info = None, None
+        if with_info:
+            if out_mem == FBR_DEVICE:
+                import torch
+
+                info = torch.empty((max(C, 1), 2), dtype=torch.int64, device=f"cuda:{self.device}")
+                pinfo = info.data_ptr()
+            else:
+                info = np.empty((max(C, 1), 2), dtype=np.int64)
+                pinfo = info.ctypes.data
+        _check(self._lib.fbr_suspended_base_motion(self._h, ctypes.byref(s), C, x.ctypes.data_as(_dp), int(x.size), self._link_index(att_link),
+                                                   float(dt), float(damping), out["rpy"][0].ptr, out["base_position"][0].ptr, out["base_vel"][0].ptr,
+                                                   out["base_acc"][0].ptr, out["att_state"][0].ptr if with_info else None, pinfo, out_mem),
+               "fbr_suspended_base_motion")
+        res = {k: v[1] for k, v in out.items()}
+        if with_info:
+            res["info"] = info
+        return res
+
+    def suspended_records(self, st: dict, x_std, att_link, device_out: bool | None = None):
+        """The (S, 39) per-sample records ``suspended_base_motion`` steps through (``fbr_suspended_records``; tests, tooling): composite
+        inertia about the attachment origin (xx xy xz yy yz zz) | Coriolis coupling (3 x 3) | joint-motion moment | first mass moment | pose
+        R (3 x 3), p and twist of the base link relative to the attachment frame, in the attachment link's axes."""
+        s, keep, S, mem = self._joint_states(st)
+        x = np.ascontiguousarray(x_std, dtype=np.float64)
+        out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
+        r, ret = self._out(None, (S, 39), out_mem)
+        _check(self._lib.fbr_suspended_records(self._h, ctypes.byref(s), x.ctypes.data_as(_dp), int(x.size), self._link_index(att_link), r.ptr, out_mem),
+               "fbr_suspended_records")
         return ret
 
     def set_capsules(self, capsules, pairs) -> None:

@@ -886,6 +886,151 @@ extern "C" int fbr_torque_row_sweep(fbr_model *m, const fbr_states *st, int32_t 
     return run_torque_sweep(m, st, ncand, nrows, sample, joint, x_std, num_x, vel_sign, eps, out, out_mem);
 }
 
+// ---- base motion of a suspended robot (fbr.h; fbr_kinsusp_kernel + fbr_susp_scan_kernel, csrc/fbr_kinid.h) -------------------------------
+// the argument checks both entry points share, then q / dq / ddq and the inertial parameters on the device and kernel 1: the records in
+// m->susp_rec (or rec_dst, device memory, when given)
+static int suspended_records(fbr_model *m, const fbr_states *st, const double *x_std, int32_t num_x, int32_t att_link, const char *who, double *rec_dst)
+{
+    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q || !st->dq || !st->ddq) {
+        set_err(std::string(who) + ": bad fbr_states header, or q / dq / ddq is NULL");
+        return FBR_E_INVALID;
+    }
+    const FbrHostModel &hm = m->hm;
+    if (!hm.floating) {
+        set_err(std::string(who) + ": the model has no floating base");
+        return FBR_E_INVALID;
+    }
+    if (att_link < 0 || att_link >= hm.L) {
+        set_err(std::string(who) + ": att_link out of range");
+        return FBR_E_INVALID;
+    }
+    if (num_x < 10 * hm.L) {
+        set_err(std::string(who) + ": x_std too short (10 inertial parameters per link)");
+        return FBR_E_INVALID;
+    }
+    if (!kinid_fits(m)) {
+        set_err(std::string(who) + ": needs the one-lane-per-sample kernels -- option fused_id = 0, or joint paths of more than " +
+                std::to_string(FBR_KINID_MAXD) + " joints; there is no two-kernel form");
+        return FBR_E_UNSUPPORTED;
+    }
+    if (int rc = enter_blocking(m)) return rc;
+    int rc;
+    if (m->susp_att != att_link) {
+        std::vector<char> keep(hm.L, 0);
+        for (int a = att_link; a >= 0; a = hm.parent[a]) keep[a] = 1;
+        try {
+            fbr_kinid_build(hm, m->susp_prog, &keep);
+        } catch (const std::exception &e) {
+            set_err(e.what());
+            return FBR_E_INVALID;
+        }
+        HIPCHK(hipStreamSynchronize(m->stream));
+        m->susp_att = -1;
+        if ((rc = m->susp_tab.ensure(m->susp_prog.steps.size() * sizeof(int)))) return rc;
+        HIPCHK(hipMemcpy(m->susp_tab.p, m->susp_prog.steps.data(), m->susp_prog.steps.size() * sizeof(int), hipMemcpyHostToDevice));
+        m->susp_att = att_link;
+    }
+    const long S = st->num_samples;
+    const double *dq = nullptr, *ddq = nullptr, *dddq = nullptr;
+    if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
+    if ((rc = stage_one(m, m->st_dq, st->dq, (size_t)S * hm.n, st->mem, &ddq))) return rc;
+    if ((rc = stage_one(m, m->st_ddq, st->ddq, (size_t)S * hm.n, st->mem, &dddq))) return rc;
+    if ((rc = m->st_x.ensure((size_t)10 * hm.L * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(m->st_x.p, x_std, (size_t)10 * hm.L * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    if (!rec_dst) {
+        if ((rc = m->susp_rec.ensure((size_t)S * FBR_SUSP_REC * sizeof(double)))) return rc;
+        rec_dst = m->susp_rec.as<double>();
+    }
+    const DevKinId kp = kinid_params(m);
+    const DevKinSusp su{att_link, m->susp_prog.nsteps, m->susp_prog.maxlvl, m->susp_tab.as<int>()};
+    const long nblk = (S + 63) / 64;
+    const int blocks = (int)std::min<long>(nblk, (long)m->num_cus * 8);
+    if ((rc = m->kinid_scratch.ensure((size_t)blocks * std::max(std::max(kp.nslots, m->susp_prog.nslots), 1) * FBR_LINK_REC * 64 * sizeof(double)))) return rc;
+    ProfScope ps(m, FBR_PROF_KIN);
+    fbr_by_depth<4, 8, 12, FBR_KINID_MAXD>(kp.maxlvl, [&](auto D) {
+        hipLaunchKernelGGL(fbr_kinsusp_kernel<D>, dim3(blocks), dim3(64), 0, m->stream, m->dm, kp, su, S, dq, ddq, dddq, (const double *)m->st_x.as<double>(),
+                           rec_dst, m->kinid_scratch.as<double>());
+    });
+    HIPCHK(hipGetLastError());
+    return FBR_OK;
+}
+
+extern "C" int fbr_suspended_records(fbr_model *m, const fbr_states *st, const double *x_std, int32_t num_x, int32_t att_link, double *rec_out,
+                                     int32_t out_mem)
+{
+    if (!m || !st || !x_std || !rec_out || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
+        set_err("fbr_suspended_records: null model / states / x_std / rec_out, or a bad memory space");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples <= 0) {
+        set_err("fbr_suspended_records: num_samples must be positive");
+        return FBR_E_INVALID;
+    }
+    if (int rc = suspended_records(m, st, x_std, num_x, att_link, "fbr_suspended_records", out_mem == FBR_DEVICE ? rec_out : nullptr)) return rc;
+    return finish_output(m, m->susp_rec.as<double>(), rec_out, (size_t)st->num_samples * FBR_SUSP_REC, out_mem);
+}
+
+extern "C" int fbr_suspended_base_motion(fbr_model *m, const fbr_states *st, int32_t ncand, const double *x_std, int32_t num_x, int32_t att_link,
+                                         double dt, double damping, double *base_rpy, double *base_pos, double *base_vel, double *base_acc,
+                                         double *att_state, int64_t *info, int32_t out_mem)
+{
+    if (!m || !st || !x_std || !base_rpy || !base_pos || !base_vel || !base_acc || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
+        set_err("fbr_suspended_base_motion: null model / states / x_std / output, or a bad memory space");
+        return FBR_E_INVALID;
+    }
+    if (!std::isfinite(dt) || dt <= 0.0 || !std::isfinite(damping) || damping < 0.0) {
+        set_err("fbr_suspended_base_motion: dt must be finite and positive, damping finite and not negative");
+        return FBR_E_INVALID;
+    }
+    if (ncand < 1) {
+        set_err("fbr_suspended_base_motion: ncand must be at least 1");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
+        set_err("fbr_suspended_base_motion: num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
+        return FBR_E_INVALID;
+    }
+    if (int rc = suspended_records(m, st, x_std, num_x, att_link, "fbr_suspended_base_motion", nullptr)) return rc;
+    const long S = st->num_samples, C = ncand, T = S / C;
+    int rc;
+    double *drpy = base_rpy, *dpos = base_pos, *dvel = base_vel, *dacc = base_acc, *datt = att_state;
+    long *dinfo = (long *)info;
+    if (out_mem == FBR_HOST) {
+        // rpy 3 | pos 3 | vel 6 | acc 6 | att 6 per sample, then info
+        if ((rc = m->susp_out.ensure((size_t)S * 24 * sizeof(double) + (size_t)C * 2 * sizeof(long)))) return rc;
+        drpy = m->susp_out.as<double>();
+        dpos = drpy + S * 3;
+        dvel = dpos + S * 3;
+        dacc = dvel + S * 6;
+        datt = att_state ? dacc + S * 6 : nullptr;
+        dinfo = info ? (long *)(dacc + S * 12) : nullptr;
+    }
+    const double *g = m->hm.gravity;
+    {
+        ProfScope ps(m, FBR_PROF_ID);
+        hipLaunchKernelGGL(fbr_susp_scan_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, m->stream, C, T, g[0], g[1], g[2], dt, damping,
+                           (const double *)m->susp_rec.as<double>(), drpy, dpos, dvel, datt, dinfo);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(m, FBR_PROF_REDUCE);
+        hipLaunchKernelGGL(fbr_susp_acc_kernel, dim3((unsigned)std::min<long>((S * 6 + 255) / 256, 4096)), dim3(256), 0, m->stream, C, T, dt,
+                           (const double *)dvel, dacc);
+        HIPCHK(hipGetLastError());
+    }
+    if (out_mem == FBR_HOST) {
+        HIPCHK(hipMemcpyAsync(base_rpy, drpy, (size_t)S * 3 * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(base_pos, dpos, (size_t)S * 3 * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(base_vel, dvel, (size_t)S * 6 * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(base_acc, dacc, (size_t)S * 6 * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        if (att_state) HIPCHK(hipMemcpyAsync(att_state, datt, (size_t)S * 6 * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        if (info) HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)C * 2 * sizeof(long), hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    prof_collect(m);
+    return FBR_OK;
+}
+
 // ---- capsule collision distances (csrc/fbr_capsule.h) --------------------------------------------------------------------------------
 extern "C" int fbr_model_set_capsules(fbr_model *m, int32_t ncaps, const int32_t *link, const double *seg, const double *radius, int32_t npairs,
                                       const int32_t *pairs)

@@ -157,6 +157,11 @@ struct fbr_model {
     DevBuf cap_tab, cap_ep, cap_part, cap_scratch, cap_out, st_bpos;
     DevCapGrad capg = {0, nullptr, nullptr};  // fbr_capsule_distance_gradients: ancestor masks and per-pair steps / slots of the set above
     DevBuf capg_tab, capg_flag;
+    // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its
+    // steps on the device, the per-sample records, the results of a host-memory call
+    FbrKinIdProgram susp_prog;
+    int susp_att = -1;
+    DevBuf susp_tab, susp_rec, susp_out;
     DevBuf fd_tab, fd_part;   // sub-tree column lists of every joint [n + 1 | entries] (built on first use), baseline partial sums [S][n]
     int fd_tab_entries = -1;
     DevBuf wt_tab;            // fbr_regressor_weights: [selected columns | the others] of the call

@@ -31,6 +31,18 @@
 
 #define FBR_KINWRITE_PARTS 4  // waves of a lane-WRITER workgroup = parts the tree is cut into (fbr_kinid_build_parts)
 
+// per-sample record of the suspended base (fbr_kinsusp_kernel -> fbr_susp_scan_kernel), everything in the attachment link's axes about its
+// origin O: composite inertia I (xx xy xz yy yz zz), Coriolis coupling B (3 x 3, row-major), joint-motion moment c0, first mass moment mc,
+// the base link's pose R (3 x 3) | p and twist [lin; ang] relative to the attachment frame.  Sample-major: the scan reads one record per step.
+#define FBR_SUSP_REC 39
+#define FBR_SUSP_I 0
+#define FBR_SUSP_B 6
+#define FBR_SUSP_C0 15
+#define FBR_SUSP_MC 18
+#define FBR_SUSP_R 21
+#define FBR_SUSP_P 30
+#define FBR_SUSP_V 33
+
 // (host) the register-stack instance of a lane kernel for a program of depth maxlvl: f(std::integral_constant<int, D>()) with the first
 // of the instance depths D... that is >= maxlvl, or the last one
 template <int D, int... Ds, class F> inline auto fbr_by_depth(int maxlvl, F &&f)
@@ -749,6 +761,359 @@ __global__ __launch_bounds__(256) void fbr_tau_gather_kernel(DevKinTau tr, long 
         const int jn = tr.joint ? tr.joint[item] : (int)(item % tr.R), jnc = min(max(jn, 0), n - 1);
         if (jn != jnc) *tr.flag = 1;
         out[i0 * nper + e] = tau[e * rows + fb + jnc];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Suspended base (fbr_suspended_base_motion; excitation/suspendedDynamics.py simulate_suspended_base_motion): the robot hangs from a ball
+// joint at the origin O of the attachment link.  Per sample, the moment about O that inverse dynamics asks for, in the attachment's axes, is
+//     N = c0 + B w + w x (I w) + I dw - mc x u        (w, dw: the attachment's angular velocity / acceleration in its own axes, u = R^T g)
+// with I, B, c0, mc functions of the sample's (q, dq, ddq) and the parameters only.  fbr_kinsusp_kernel writes them, with the base
+// link's pose and twist relative to the attachment frame, as a record of FBR_SUSP_REC doubles per sample; fbr_susp_scan_kernel then steps
+// every candidate through its records at O(1) per step.
+//
+// One lane per sample on the lane body: a walk down the attachment's path with the base at rest gives the attachment's pose, velocity and
+// acceleration relative to the base; four full walks at zero gravity follow, the base link in the state that holds the attachment frame at
+// O with zero linear velocity / acceleration, zero angular acceleration and angular velocity 0, e_x, e_y, e_z (its own axes).  Their base
+// rows, moved to O and turned into the attachment's axes, are c0 and c0 + B e_i + e_i x I e_i; I and mc are sums over the link records of
+// the first full walk.  The walks run in the BASE link's axes (base orientation 1): the lane body needs no rpy of a rotation matrix then.
+// ------------------------------------------------------------------------------------------------
+struct DevKinSusp {
+    int att;             // the attachment link
+    int nsteps, maxlvl;  // the program that walks the attachment's path only (fbr_kinid_build with keep = the link and its ancestors)
+    const int *steps;
+};
+template <int MAXD>
+__global__ __launch_bounds__(64) void fbr_kinsusp_kernel(DevModel m, DevKinId p, DevKinSusp su, long S, const double *__restrict__ q,
+                                                         const double *__restrict__ dq, const double *__restrict__ ddq, const double *__restrict__ x,
+                                                         double *__restrict__ rec, double *__restrict__ scratch)
+{
+    const int lane = threadIdx.x, n = m.n;
+    double *scr = scratch + (long)blockIdx.x * p.nslots * FBR_LINK_REC * 64 + lane;
+    const long nblk = (S + 63) >> 6;
+    const double g0[3] = {0.0, 0.0, 0.0};
+    for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const long s = min((blk << 6) + lane, S - 1);
+        const bool live = (blk << 6) + lane < S;
+        auto state = [&](int d, double &a, double &b, double &c) {
+            a = q[s * n + d];
+            b = dq[s * n + d];
+            c = ddq[s * n + d];
+        };
+        auto save = [&](int b, int i, double v) { scr[(b * FBR_LINK_REC + i) * 64] = v; };
+        auto load = [&](int b, int i) { return scr[(b * FBR_LINK_REC + i) * 64]; };
+        auto consts = [&](int l, double *rR, double *rp, double *ax) {  // (l is wave-uniform: scalar loads through the constant address space)
+            const fbr_cdouble_ptr cR = (fbr_cdouble_ptr)(unsigned long)m.restR, cp = (fbr_cdouble_ptr)(unsigned long)m.restp,
+                                  ca = (fbr_cdouble_ptr)(unsigned long)m.axis;
+            for (int i = 0; i < 9; i++) rR[i] = cR[9 * l + i];
+            for (int i = 0; i < 3; i++) {
+                rp[i] = cp[3 * l + i];
+                ax[i] = ca[3 * l + i];
+            }
+        };
+        // ---- the attachment relative to the base: Ra, pa (pose), wa, dwa (its own axes), va, aa (origin, base axes)
+        double Ra[9], pa[3], wa[3], dwa[3], va[3], aa[3];
+        for (int i = 0; i < 9; i++) Ra[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        for (int i = 0; i < 3; i++) pa[i] = wa[i] = dwa[i] = va[i] = aa[i] = 0.0;
+        {
+            auto basest = [&](double *, double *, double *) {};
+            auto link = [&](int l, int depth, const double *r, const double (*Sst)[6], const int *lvd, double *F) {
+                (void)F;
+                if (l != su.att) return;
+                for (int i = 0; i < 9; i++) Ra[i] = r[FBR_OFF_R + i];
+                double tw[6] = {0, 0, 0, 0, 0, 0}, t[3];
+                for (int i = 0; i < 3; i++) {
+                    pa[i] = r[FBR_OFF_P + i];
+                    wa[i] = r[FBR_OFF_W + i];
+                    dwa[i] = r[FBR_OFF_DW + i];
+                }
+                fbr_mv(Ra, r + FBR_OFF_A, aa);  // (zero gravity, base at rest: the proper acceleration is the acceleration)
+#pragma unroll
+                for (int j = 0; j < MAXD; j++)
+                    if (j < depth) {
+                        const double dqj = dq[s * n + lvd[j]];
+                        for (int i = 0; i < 6; i++) tw[i] += Sst[j][i] * dqj;
+                    }
+                fbr_cross(tw + 3, pa, t);
+                for (int i = 0; i < 3; i++) va[i] = tw[i] + t[i];
+            };
+            auto emit = [&](int, double) {};
+            fbr_kinid_lane<MAXD, false>(su.nsteps, su.maxlvl, su.steps, p.endflush, 0, g0, 0, state, basest, save, load, link, emit, consts);
+        }
+        double wrel[3], arel[3];
+        fbr_mv(Ra, wa, wrel);
+        fbr_mv(Ra, dwa, arel);
+        // ---- four probes; the first one also sums the composite inertia and first moment about O (base axes)
+        double Nk[12], Io[6] = {0, 0, 0, 0, 0, 0}, mc[3] = {0, 0, 0};
+#pragma nounroll
+        for (int k = 0; k < 4; k++) {
+            double om[3], wB[3], dwB[3], aB[3], t1[3], t2[3], t3[3], T6[6] = {0, 0, 0, 0, 0, 0};
+            for (int i = 0; i < 3; i++) om[i] = ((k == i + 1) ? 1.0 : 0.0) - wa[i];
+            fbr_mv(Ra, om, wB);
+            fbr_cross(wB, wrel, t1);
+            for (int i = 0; i < 3; i++) dwB[i] = -t1[i] - arel[i];
+            fbr_cross(dwB, pa, t1);
+            fbr_cross(wB, pa, t2);
+            fbr_cross(wB, t2, t3);
+            fbr_cross(wB, va, t2);
+            for (int i = 0; i < 3; i++) aB[i] = -(t1[i] + t3[i] + 2.0 * t2[i] + aa[i]);
+            auto basest = [&](double *v6, double *a6, double *e3) {
+                for (int i = 0; i < 3; i++) {
+                    v6[i] = 0.0;
+                    v6[3 + i] = wB[i];
+                    a6[i] = aB[i];
+                    a6[3 + i] = dwB[i];
+                    e3[i] = 0.0;
+                }
+            };
+            auto link = [&](int l, int depth, const double *r, const double (*Sst)[6], const int *lvd, double *F) {
+                (void)depth; (void)Sst; (void)lvd;
+                double pi[10];
+                for (int i = 0; i < 10; i++) pi[i] = x[10 * l + i];
+                fbr_link_wrench(r, pi, F);
+                if (k == 0) {
+                    const double *R = r + FBR_OFF_R;
+                    double d[3], h[3];
+                    for (int i = 0; i < 3; i++) d[i] = r[FBR_OFF_P + i] - pa[i];
+                    fbr_mv(R, pi + 1, h);
+                    for (int i = 0; i < 3; i++) mc[i] += pi[0] * d[i] + h[i];
+                    // R Ibar R^T, then the shift of the reference point from the link origin to O by d
+                    const double Ib[9] = {pi[4], pi[5], pi[6], pi[5], pi[7], pi[8], pi[6], pi[8], pi[9]};
+                    double RI[9];
+                    fbr_mm(R, Ib, RI);
+                    const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2], dh = d[0] * h[0] + d[1] * h[1] + d[2] * h[2];
+                    int e = 0;
+                    for (int a = 0; a < 3; a++)
+                        for (int b = a; b < 3; b++, e++) {
+                            double v = RI[3 * a] * R[3 * b] + RI[3 * a + 1] * R[3 * b + 1] + RI[3 * a + 2] * R[3 * b + 2];
+                            v -= pi[0] * d[a] * d[b] + d[a] * h[b] + h[a] * d[b];
+                            if (a == b) v += pi[0] * dd + 2.0 * dh;
+                            Io[e] += v;
+                        }
+                }
+            };
+            auto emit = [&](int r, double v) {
+#pragma unroll
+                for (int i = 0; i < 6; i++)
+                    if (r == i) T6[i] = v;
+            };
+            fbr_kinid_lane<MAXD, true>(p.nsteps, p.maxlvl, p.steps, p.endflush, 1, g0, 6, state, basest, save, load, link, emit, consts);
+            fbr_cross(pa, T6, t1);
+            for (int i = 0; i < 3; i++) t2[i] = T6[3 + i] - t1[i];  // the moment about O (base axes) ...
+            fbr_mtv(Ra, t2, t3);                                     // ... in the attachment's axes
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++)
+                if (kk == k)
+                    for (int i = 0; i < 3; i++) Nk[3 * kk + i] = t3[i];
+        }
+        // ---- the record
+        double out[FBR_SUSP_REC];
+        {
+            const double If[9] = {Io[0], Io[1], Io[2], Io[1], Io[3], Io[4], Io[2], Io[4], Io[5]};
+            double IR[9], Ia[9];
+            fbr_mm(If, Ra, IR);
+            for (int a = 0; a < 3; a++)
+                for (int b = 0; b < 3; b++) Ia[3 * a + b] = Ra[a] * IR[b] + Ra[3 + a] * IR[3 + b] + Ra[6 + a] * IR[6 + b];  // Ra^T I Ra
+            out[FBR_SUSP_I + 0] = Ia[0];
+            out[FBR_SUSP_I + 1] = 0.5 * (Ia[1] + Ia[3]);
+            out[FBR_SUSP_I + 2] = 0.5 * (Ia[2] + Ia[6]);
+            out[FBR_SUSP_I + 3] = Ia[4];
+            out[FBR_SUSP_I + 4] = 0.5 * (Ia[5] + Ia[7]);
+            out[FBR_SUSP_I + 5] = Ia[8];
+            const double Is[9] = {out[0], out[1], out[2], out[1], out[3], out[4], out[2], out[4], out[5]};
+            for (int i = 0; i < 3; i++) out[FBR_SUSP_C0 + i] = Nk[i];
+            for (int c = 0; c < 3; c++) {
+                // B e_c = N(e_c) - c0 - e_c x (I e_c)
+                const double e[3] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0}, Ie[3] = {Is[c], Is[3 + c], Is[6 + c]};
+                double ex[3];
+                fbr_cross(e, Ie, ex);
+                for (int r = 0; r < 3; r++) out[FBR_SUSP_B + 3 * r + c] = Nk[3 * (c + 1) + r] - Nk[r] - ex[r];
+            }
+            fbr_mtv(Ra, mc, out + FBR_SUSP_MC);
+            double t[3], u[3];
+            for (int a = 0; a < 3; a++)
+                for (int b = 0; b < 3; b++) out[FBR_SUSP_R + 3 * a + b] = Ra[3 * b + a];
+            fbr_mtv(Ra, pa, t);
+            for (int i = 0; i < 3; i++) out[FBR_SUSP_P + i] = -t[i];
+            // the base link relative to the attachment frame: angular velocity -wa, origin velocity (-wa) x p_rel - Ra^T va
+            fbr_mtv(Ra, va, t);
+            const double wr[3] = {-wa[0], -wa[1], -wa[2]};
+            fbr_cross(wr, out + FBR_SUSP_P, u);
+            for (int i = 0; i < 3; i++) {
+                out[FBR_SUSP_V + i] = u[i] - t[i];
+                out[FBR_SUSP_V + 3 + i] = wr[i];
+            }
+        }
+        if (live)
+            for (int i = 0; i < FBR_SUSP_REC; i++) rec[s * FBR_SUSP_REC + i] = out[i];
+    }
+}
+
+// rotation Rz(y) Ry(p) Rx(r) (iDynTree Rotation::RPY), row-major
+FBR_HD void fbr_susp_rpy_R(const double *e, double *R)
+{
+    const double cr = cos(e[0]), sr = sin(e[0]), cp = cos(e[1]), sp = sin(e[1]), cy = cos(e[2]), sy = sin(e[2]);
+    R[0] = cy * cp;
+    R[1] = cy * sp * sr - sy * cr;
+    R[2] = cy * sp * cr + sy * sr;
+    R[3] = sy * cp;
+    R[4] = sy * sp * sr + cy * cr;
+    R[5] = sy * sp * cr - cy * sr;
+    R[6] = -sp;
+    R[7] = cp * sr;
+    R[8] = cp * cr;
+}
+// x = M^-1 b for a symmetric 3 x 3 M (the cofactor form: no pivoting, no branch; M = R I R^T + d dt 1 is positive definite)
+FBR_HD void fbr_susp_solve3(const double *M, const double *b, double *x)
+{
+    const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
+    const double c11 = M[0] * M[8] - M[2] * M[6], c12 = M[1] * M[6] - M[0] * M[7], c22 = M[0] * M[4] - M[1] * M[3];
+    const double inv = 1.0 / (M[0] * c00 + M[1] * c01 + M[2] * c02);
+    x[0] = (c00 * b[0] + c01 * b[1] + c02 * b[2]) * inv;
+    x[1] = (c01 * b[0] + c11 * b[1] + c12 * b[2]) * inv;
+    x[2] = (c02 * b[0] + c12 * b[1] + c22 * b[2]) * inv;
+}
+// the moment R (c0 + B w + w x (I w) - mc x (R^T g)) about O in world axes at angular velocity om (world), angular acceleration 0; rest:
+// the static moment of the equilibrium search (zero joint velocities and accelerations: c0 and B drop out)
+FBR_HD void fbr_susp_moment(const double *r39, const double *R, const double *om, const double *g, bool rest, double *Nw)
+{
+    double u[3], t[3], Nb[3];
+    fbr_mtv(R, g, u);
+    fbr_cross(r39 + FBR_SUSP_MC, u, t);
+    for (int i = 0; i < 3; i++) Nb[i] = -t[i];
+    if (!rest) {
+        const double *I = r39 + FBR_SUSP_I, *B = r39 + FBR_SUSP_B;
+        double w[3], Bw[3], wx[3];
+        fbr_mtv(R, om, w);
+        const double Iw[3] = {I[0] * w[0] + I[1] * w[1] + I[2] * w[2], I[1] * w[0] + I[3] * w[1] + I[4] * w[2], I[2] * w[0] + I[4] * w[1] + I[5] * w[2]};
+        fbr_mv(B, w, Bw);
+        fbr_cross(w, Iw, wx);
+        for (int i = 0; i < 3; i++) Nb[i] += r39[FBR_SUSP_C0 + i] + Bw[i] + wx[i];
+    }
+    fbr_mv(R, Nb, Nw);
+}
+FBR_HD double fbr_susp_clip(double v, double lim) { return v > lim ? lim : (v < -lim ? -lim : v); }  // (a NaN stays a NaN)
+
+// One lane per candidate: the equilibrium search on the record of its sample 0, then T steps of the reference's loop, each on one record
+// (read a step ahead).  No cross-lane traffic; the loop bounds are T and FBR_SUSP_EQ_MAX_ITER.  att_state / info may be NULL.
+__global__ __launch_bounds__(64) void fbr_susp_scan_kernel(long C, long T, double gx, double gy, double gz, double dt, double damping,
+                                                           const double *__restrict__ rec, double *__restrict__ base_rpy, double *__restrict__ base_pos,
+                                                           double *__restrict__ base_vel, double *__restrict__ att_state, long *__restrict__ info)
+{
+    const long c = (long)blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    const double g[3] = {gx, gy, gz};
+    const double *rc = rec + c * T * FBR_SUSP_REC;
+    double cur[FBR_SUSP_REC];
+    for (int i = 0; i < FBR_SUSP_REC; i++) cur[i] = rc[i];
+    double e[3] = {0, 0, 0}, om[3] = {0, 0, 0}, R[9], Nw[3];
+    const double eqlim = FBR_SUSP_EQ_CLIP_DEG * (M_PI / 180.0), swing = FBR_SUSP_MAX_SWING_DEG * (M_PI / 180.0);
+    long iters = FBR_SUSP_EQ_MAX_ITER, clamps = 0;
+    for (int it = 0; it < FBR_SUSP_EQ_MAX_ITER; it++) {
+        fbr_susp_rpy_R(e, R);
+        fbr_susp_moment(cur, R, om, g, true, Nw);
+        if (sqrt(Nw[0] * Nw[0] + Nw[1] * Nw[1] + Nw[2] * Nw[2]) < FBR_SUSP_EQ_TOL) {
+            iters = it + 1;
+            break;
+        }
+        for (int i = 0; i < 3; i++) e[i] = fbr_susp_clip(e[i] - FBR_SUSP_EQ_STEP * Nw[i], eqlim);
+    }
+    for (long t = 0; t < T; t++) {
+        double nxt[FBR_SUSP_REC];
+        const double *rn = rc + min(t + 1, T - 1) * FBR_SUSP_REC;
+        for (int i = 0; i < FBR_SUSP_REC; i++) nxt[i] = rn[i];
+        const long s = c * T + t;
+        fbr_susp_rpy_R(e, R);
+        fbr_susp_moment(cur, R, om, g, false, Nw);
+        // (M_bb + d dt 1) alpha = -(M_bj ddq + h_b) - d omega,  M_bb = R I R^T
+        const double *I = cur + FBR_SUSP_I;
+        const double If[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
+        double RI[9], M[9], rhs[3], al[3];
+        fbr_mm(R, If, RI);
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) M[3 * a + b] = RI[3 * a] * R[3 * b] + RI[3 * a + 1] * R[3 * b + 1] + RI[3 * a + 2] * R[3 * b + 2];
+        M[1] = M[3] = 0.5 * (M[1] + M[3]);
+        M[2] = M[6] = 0.5 * (M[2] + M[6]);
+        M[5] = M[7] = 0.5 * (M[5] + M[7]);
+        for (int i = 0; i < 3; i++) {
+            M[4 * i] += damping * dt;
+            rhs[i] = -Nw[i] - damping * om[i];
+        }
+        fbr_susp_solve3(M, rhs, al);
+        // the base link before integrating: world_R_base = R R_rel, position R p_rel, twist [om x (R p_rel) + R v_rel; om + R w_rel]
+        double Rb[9], pb[3], vl[3], va[3], t3[3];
+        fbr_mm(R, cur + FBR_SUSP_R, Rb);
+        fbr_mv(R, cur + FBR_SUSP_P, pb);
+        fbr_mv(R, cur + FBR_SUSP_V, vl);
+        fbr_mv(R, cur + FBR_SUSP_V + 3, va);
+        fbr_cross(om, pb, t3);
+        // rpy of world_R_base^T (iDynTree asRPY, general branch; at |R20| >= 1: pitch +-pi/2, roll 0, the whole turn about z in yaw)
+        const double m20 = Rb[2], m21 = Rb[5], m22 = Rb[8], m10 = Rb[1], m00 = Rb[0];  // (entries of the transpose)
+        double br, bp, by;
+        if (fabs(m20) >= 1.0) {
+            br = 0.0;
+            bp = m20 < 0 ? 0.5 * M_PI : -0.5 * M_PI;
+            by = atan2(-Rb[3], Rb[4]);
+        } else {
+            br = atan2(m21, m22);
+            bp = asin(-m20);
+            by = atan2(m10, m00);
+        }
+        base_rpy[s * 3] = br;
+        base_rpy[s * 3 + 1] = bp;
+        base_rpy[s * 3 + 2] = by;
+        for (int i = 0; i < 3; i++) {
+            base_pos[s * 3 + i] = pb[i];
+            base_vel[s * 6 + i] = t3[i] + vl[i];
+            base_vel[s * 6 + 3 + i] = om[i] + va[i];
+        }
+        if (att_state)
+            for (int i = 0; i < 3; i++) {
+                att_state[s * 6 + i] = e[i];
+                att_state[s * 6 + 3 + i] = om[i];
+            }
+        if (t < T - 1) {
+            // semi-implicit Euler; the rpy rates as angular_velocity_to_rpy_rates forms them: ((1 / cp) E) omega
+            for (int i = 0; i < 3; i++) om[i] += al[i] * dt;
+            const double cr = cos(e[0]), sr = sin(e[0]), cp = cos(e[1]), sp = sin(e[1]), ic = 1.0 / cp;
+            const double d0 = (ic * cp) * om[0] + (ic * (sr * sp)) * om[1] + (ic * (cr * sp)) * om[2];
+            const double d1 = (ic * 0.0) * om[0] + (ic * (cr * cp)) * om[1] + (ic * (-sr * cp)) * om[2];
+            const double d2 = (ic * 0.0) * om[0] + (ic * sr) * om[1] + (ic * cr) * om[2];
+            e[0] += d0 * dt;
+            e[1] += d1 * dt;
+            e[2] += d2 * dt;
+            for (int i = 0; i < 3; i++) {
+                if (e[i] > swing) {
+                    e[i] = swing;
+                    if (om[i] > 0) om[i] *= FBR_SUSP_BOUNCE;
+                    clamps++;
+                } else if (e[i] < -swing) {
+                    e[i] = -swing;
+                    if (om[i] < 0) om[i] *= FBR_SUSP_BOUNCE;
+                    clamps++;
+                }
+            }
+        }
+        for (int i = 0; i < FBR_SUSP_REC; i++) cur[i] = nxt[i];
+    }
+    if (info) {
+        info[2 * c] = iters;
+        info[2 * c + 1] = clamps;
+    }
+}
+// base_acc: central differences of base_vel with dt inside every candidate, one-sided at its two ends; zeros when T <= 2 (the reference's rule)
+__global__ __launch_bounds__(256) void fbr_susp_acc_kernel(long C, long T, double dt, const double *__restrict__ vel, double *__restrict__ acc)
+{
+    const long total = C * T * 6;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long s = e / 6, t = s % T;
+        double v = 0.0;
+        if (T > 2) {
+            if (t == 0) v = (vel[e + 6] - vel[e]) / dt;
+            else if (t == T - 1) v = (vel[e] - vel[e - 6]) / dt;
+            else v = (vel[e + 6] - vel[e - 6]) / (2 * dt);
+        }
+        acc[e] = v;
     }
 }
 #endif

@@ -90,10 +90,39 @@ def fourier_coefficients(a, b, q, nf, wf: float = 1.0, joint_limits=None, use_de
     return {"wf": float(wf), "a": A, "b": B, "q_offset": qc, "q_range": np.minimum(qc - lo, hi - qc) * 0.95}
 
 
-def candidate_states(engine, candidates: list, T: int, freq: float, device: bool = True, use_deg_vectorised_quirk: bool = False) -> dict:
+def suspended_spec(engine, suspended: dict) -> tuple:
+    """``(att_link, damping, x_std)`` of a ``suspended=`` argument: a dict with ``x_std`` (the standard parameters whose inertial part
+    swings) and optionally ``attachment_frame`` (a link name of the topology; default ``crane_ft``) or ``att_link`` (a link index) and
+    ``damping`` (default 2000.0) -- the defaults are what ``simulateTrajectory`` passes (trajectoryGenerator.py:171-187:
+    ``floatingBaseAttachmentFrame``, ``suspendedDamping``)."""
+    unknown = set(suspended) - {"attachment_frame", "att_link", "damping", "x_std"}
+    if unknown:
+        raise ValueError(f"suspended: unknown keys {sorted(unknown)}")
+    if "x_std" not in suspended:
+        raise ValueError("suspended: x_std (the standard parameters) is required")
+    if "att_link" in suspended and "attachment_frame" in suspended:
+        raise ValueError("suspended: give attachment_frame or att_link, not both")
+    if "att_link" in suspended:
+        att = int(suspended["att_link"])
+    else:
+        name = suspended.get("attachment_frame", "crane_ft")
+        names = list(engine.topo.link_names)
+        if name not in names:
+            raise ValueError(f"suspended: attachment frame '{name}' is not a link of the topology")
+        att = names.index(name)
+    x_std = suspended["x_std"]
+    return att, float(suspended.get("damping", 2000.0)), getattr(x_std, "xStdModel", x_std)
+
+
+def candidate_states(engine, candidates: list, T: int, freq: float, device: bool = True, use_deg_vectorised_quirk: bool = False,
+                     suspended: dict | None = None) -> dict:
     """States of ``len(candidates)`` candidate trajectories (dicts of ``fourier_coefficients``), T samples each at ``freq`` Hz, as ONE
     stacked batch ready for ``Engine.gram_grouped`` / ``candidate_dopt`` -- what ``computeTrajectoryDynamics`` builds per candidate on the
     host (trajectoryGenerator.py:83-155): joint states from the Fourier series, a stationary base (zero twist / acceleration / rpy).
+
+    ``suspended`` (``suspended_spec``; floating base only): the base swings from a ball joint at the attachment frame instead --
+    ``rpy``, ``base_vel``, ``base_acc`` and ``base_position`` come from one ``Engine.suspended_base_motion`` with dt = 1 / freq
+    (``simulate_suspended_base_motion`` per candidate, trajectoryGenerator.py:171-187).  None: the stationary base, nothing changed.
 
     ``use_deg_vectorised_quirk``: with ``useDeg`` the reference's vectorised evaluation converts radians with ``deg2rad`` once more
     (lines 126-128 after a block that never produced degrees), i.e. its q, dq, ddq are pi / 180 of the per-sample generators' values;
@@ -121,6 +150,11 @@ def candidate_states(engine, candidates: list, T: int, freq: float, device: bool
         else:
             z = lambda k: np.zeros((S, k))  # noqa: E731
         st.update(base_vel=z(6), base_acc=z(6), rpy=z(3))
+    if suspended is not None:
+        if not engine.floating:
+            raise ValueError("suspended: the engine has no floating base")
+        att, damping, x_std = suspended_spec(engine, suspended)
+        st.update(engine.suspended_base_motion(st, C, x_std, att, 1.0 / float(freq), damping))
     return st
 
 
@@ -156,8 +190,8 @@ def constraint_layout(n: int, min_velocity_constraint: bool, num_collision_pairs
     return lay
 
 
-def _check_config(config: dict) -> None:
-    if config.get("floatingBaseAttachment") == "suspended":
+def _check_config(config: dict, suspended=None) -> None:
+    if config.get("floatingBaseAttachment") == "suspended" and suspended is None:
         raise ValueError("floatingBaseAttachment 'suspended' simulates the base motion with a sequential ODE (suspendedDynamics.py): "
                          "not supported by the batched objective")
     if config.get("identifyGravityParamsOnly"):
@@ -168,7 +202,8 @@ def _host(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
 
 
-def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, joint_names, config: dict, dopt_scale=None, collision=None) -> dict:
+def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, joint_names, config: dict, dopt_scale=None, collision=None,
+                            suspended=None) -> dict:
     """``objectiveFunc``'s f, g and soft costs of C candidates from their D-optimality terms and the extrema of ``Engine.candidate_extrema``
     (values and indices, (C, n) each) -- pure host arithmetic.
 
@@ -185,8 +220,11 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
 
     ``collision``: the dict ``candidate_collision_constraints`` returns.  Its ``g`` (C, P) is appended after ``min_torque_util`` (layout key
     ``collision``), and ``ag_cache`` gains ``collision_argmin_idx`` (C, P): per pair the main-trajectory sample of its smallest distance
-    (-1: none), what the reference's ``_ag_collision_cache`` holds.  None: everything is what it is without the argument."""
-    _check_config(config)
+    (-1: none), what the reference's ``_ag_collision_cache`` holds.  None: everything is what it is without the argument.
+
+    ``suspended``: not None says that the extrema come from states with the simulated base motion (``candidate_states(..., suspended=)``);
+    ``floatingBaseAttachment: "suspended"`` is then accepted.  The arithmetic is the same."""
+    _check_config(config, suspended)
     nld = np.asarray(neg_log_det, dtype=np.float64).reshape(-1)
     C = nld.shape[0]
     e = {k: _host(v) for k, v in ext.items()}
@@ -249,7 +287,7 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
             "failed": failed, "dopt_scale": dopt_scale, "ag_cache": ag}
 
 
-def candidate_collision_constraints(engine, states: dict, ncand: int, config: dict, margins=None) -> dict:
+def candidate_collision_constraints(engine, states: dict, ncand: int, config: dict, margins=None, suspended=None) -> dict:
     """The collision block of ``objectiveFunc`` in capsule mode for ``ncand`` equal candidates stacked in ``states``, for the capsule set of
     the engine (``Engine.set_capsules``; pairs of robot links): per candidate and pair the smallest ``distance - margin`` over
 
@@ -266,8 +304,12 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
     (``_collision_pair_margins``; None: 0).  ``eval_sample``, ``eval_scale``, ``eval_pose`` (C, P) describe the winning configuration
     ``eval_scale * q[eval_sample]`` at the base pose of sample ``eval_pose`` -- (idx, 1, idx) on the main trajectory, (0 or T - 1,
     s(tau), the pose's sample) for a transition configuration, -1 where none won: the arguments of ``Engine.capsule_distance_gradients``
-    (``candidate_collision_gradient``).  Not covered: the mesh modes, world links."""
-    _check_config(config)
+    (``candidate_collision_gradient``).  Not covered: the mesh modes, world links.
+
+    ``suspended``: not None says that ``states`` carry the simulated base motion of the suspended base (``rpy`` and ``base_position`` of
+    ``candidate_states(..., suspended=)``); ``floatingBaseAttachment: "suspended"`` is then accepted.  The poses of the main trajectory
+    and the seven base poses of the transition configurations are those of ``states``, as in the reference."""
+    _check_config(config, suspended)
     C = int(ncand)
     q = states["q"]
     S, n = int(q.shape[0]), int(q.shape[1])
@@ -334,56 +376,62 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
             "eval_pose": ev_pose.astype(np.int64)}
 
 
-def _collision_block(engine, states, ncand, config, collision):
+def _collision_block(engine, states, ncand, config, collision, suspended=None):
     """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins`` (``flobaroid_amd.collision.collision_set``)"""
     if collision is None:
         return None
     if config.get("collisionMode", "capsule") != "capsule":
         raise ValueError("collision constraints on the device cover collisionMode 'capsule' only (no mesh code: DESIGN 9)")
     engine.set_capsules(collision["capsules"], collision["pairs"])
-    return candidate_collision_constraints(engine, states, ncand, config, margins=collision.get("margins"))
+    return candidate_collision_constraints(engine, states, ncand, config, margins=collision.get("margins"), suspended=suspended)
 
 
 def candidate_objectives(engine, states: dict, ncand: int, independent_cols, x_std, limits: dict, joint_names, config: dict, dopt_scale=None,
-                         YtY_prior=None, vel_sign=None, collision=None) -> dict:
+                         YtY_prior=None, vel_sign=None, collision=None, suspended=None) -> dict:
     """``objectives_from_extrema`` of ``ncand`` equal candidates stacked in ``states``: one ``gram_grouped`` (D-optimality, lambda_max,
     n_observable per candidate with ``doptRegularization``, default 1e-4) and one ``candidate_extrema`` (the a-priori torques of ``x_std``
     reduced on the device) over the same states.  ``vel_sign``: Stribeck friction, as for ``Engine.inverse_dynamics``.  ``collision``
     (``flobaroid_amd.collision.collision_set``: capsules, pairs, margins): the collision block of capsule mode is appended to ``g``
-    (``candidate_collision_constraints``); None: no collision block, every array as without the argument."""
+    (``candidate_collision_constraints``); None: no collision block, every array as without the argument.  ``suspended``: not None says
+    that ``states`` carry the simulated base motion (``candidate_states(..., suspended=)``: ``rpy``, ``base_vel``, ``base_acc``, and
+    ``base_position`` for the collision block); ``floatingBaseAttachment: "suspended"`` is then accepted."""
     return _candidate_objective_parts(engine, states, ncand, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign,
-                                      collision)[0]
+                                      collision, suspended)[0]
 
 
-def _candidate_objective_parts(engine, states, ncand, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign, collision):
+def _candidate_objective_parts(engine, states, ncand, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign, collision,
+                               suspended=None):
     """``candidate_objectives`` together with what the gradients reuse: (result, the grouped Gram on the host, the collision block or None)"""
-    _check_config(config)
+    _check_config(config, suspended)
     G = _host(engine.gram_grouped(states, int(ncand)))
     nld, _, nobs = est.d_optimality_batch_terms(G, independent_cols, config.get("doptRegularization", 1e-4), YtY_prior)
     ext = engine.candidate_extrema(states, int(ncand), x_std, vel_sign=vel_sign)
-    coll = _collision_block(engine, states, ncand, config, collision)
-    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale, collision=coll), G, coll
+    coll = _collision_block(engine, states, ncand, config, collision, suspended)
+    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale, collision=coll, suspended=suspended), G, coll
 
 
 def candidate_objectives_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict,
-                                           joint_names, config: dict, dopt_scale=None, YtY_prior=None, collision=None) -> dict:
+                                           joint_names, config: dict, dopt_scale=None, YtY_prior=None, collision=None, suspended=None) -> dict:
     """``candidate_objectives`` from Fourier coefficients (``fourier_coefficients`` dicts): states generated on the device
     (``candidate_states``), the Coulomb column tanh(dq / ``frictionSignThreshold``) as ``candidate_dopt_from_coefficients`` sets it and
     ``vel_sign`` = dq under Stribeck friction -- only per-candidate arrays come back to the host.  ``model_or_x_std``: the a-priori standard
-    parameters, or an object with ``xStdModel`` (``Model``)."""
-    _check_config(config)
+    parameters, or an object with ``xStdModel`` (``Model``).  ``suspended`` (``suspended_spec``): the base motion of every candidate is
+    simulated on the device (``candidate_states(..., suspended=)``) and ``floatingBaseAttachment: "suspended"`` accepted; None: the
+    stationary base, and that configuration is refused."""
+    _check_config(config, suspended)
     x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
-    st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02))
+    st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02), suspended)
     vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
     return candidate_objectives(engine, st, len(candidates), independent_cols, x_std, limits, joint_names, config, dopt_scale=dopt_scale,
-                                YtY_prior=YtY_prior, vel_sign=vel_sign, collision=collision)
+                                YtY_prior=YtY_prior, vel_sign=vel_sign, collision=collision, suspended=suspended)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # The D-optimality term of the optimiser's gradient per candidate (analyticalGradient.py compute_analytical_gradient, Phases 1, A and B,
 # lines 538-762): weight rows on the device (Engine.regressor_weights), the finite-difference sweep (Engine.fd_scores) and the chain with
 # the Jacobian of the Fourier series (Engine.fourier_gradient).  The collision rows of the constraint Jacobian: candidate_collision_gradient
-# below; Phase C and the whole gradient: candidate_gradients_from_coefficients at the end.  Not covered: the suspended base.
+# below; Phase C and the whole gradient: candidate_gradients_from_coefficients at the end.  Not covered: the suspended base (the reference's
+# sweeps hold the simulated base pose fixed or evaluate at an identity base; the gradient entry points keep refusing that configuration).
 # ------------------------------------------------------------------------------------------------------------------------------------
 def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4, dopt_scale=1.0, YtY_prior=None, B=None):
     """The constant matrices of ``Engine.regressor_weights`` for C candidates from their Grams ``G`` (C, Pa, Pa) (``Engine.gram_grouped``):
@@ -445,9 +493,9 @@ def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, 
                                        max_weight_bytes)
 
 
-def _coefficient_states(engine, candidates, T, freq, friction_sign_threshold):
+def _coefficient_states(engine, candidates, T, freq, friction_sign_threshold, suspended=None):
     """``candidate_states`` on the device with the Coulomb column tanh(dq / threshold) of a friction engine"""
-    st = candidate_states(engine, candidates, int(T), freq, device=True)
+    st = candidate_states(engine, candidates, int(T), freq, device=True, suspended=suspended)
     if engine.friction:
         import torch
 

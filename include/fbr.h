@@ -87,7 +87,7 @@ typedef struct {
  * "gram_lane" / "gram_force_tiles"; 103: fbr_candidate_extrema; 104: fbr_model_set_capsules, fbr_candidate_capsule_distances, and -- added under the same number, which
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
- * fbr_fourier_state_chain. */
+ * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -150,6 +150,46 @@ int fbr_candidate_extrema(fbr_model *m, const fbr_states *st, int32_t ncand, con
  */
 int fbr_torque_row_sweep(fbr_model *m, const fbr_states *st, int32_t ncand, int64_t nrows, const int64_t *sample, const int32_t *joint,
                          const double *x_std, int32_t num_x, const double *vel_sign, double eps, double *out, int32_t out_mem);
+
+/*
+ * Base motion of candidate trajectories of a robot that hangs from a ball joint at the origin O of link att_link -- the reference's
+ * simulate_suspended_base_motion (excitation/suspendedDynamics.py; called by simulateTrajectory, excitation/trajectoryGenerator.py:171-187,
+ * on every objective evaluation under floatingBaseAttachment "suspended": one Python iteration per sample, each with a mass matrix and an
+ * inverse dynamics from iDynTree).  The states are ncand equal candidates of T = num_samples / ncand consecutive samples (the layout of
+ * fbr_candidate_extrema), in host or device memory; only q, dq, ddq are read.  x_std: the full standard parameter vector (host) as for
+ * fbr_inverse_dynamics_batch; its inertial part (10 per link) is used, no friction.  att_link: a link in the caller's numbering (the
+ * UNMERGED links, like the capsules' links) -- the base itself, a moving link or one behind fixed joints.  Gravity is the model's.
+ * Per candidate, line for line:
+ *   equilibrium search at sample 0 with zero velocities: at most FBR_SUSP_EQ_MAX_ITER iterations rpy -= FBR_SUSP_EQ_STEP * moment, clipped to
+ *     +-FBR_SUSP_EQ_CLIP_DEG, until |moment| < FBR_SUSP_EQ_TOL;
+ *   for t = 0 .. T-1: solve (M_bb_rot + damping dt 1) alpha = -(M_bj ddq + h_b)_rot - damping omega; record the base link's pose and twist;
+ *     then (t < T-1) omega += alpha dt, rpy += rpy_rates(rpy, omega) dt (angular_velocity_to_rpy_rates as written), each angle clamped to
+ *     +-FBR_SUSP_MAX_SWING_DEG, its velocity multiplied by FBR_SUSP_BOUNCE when it points outwards.
+ * Outputs (out_mem), S = num_samples:
+ *   base_rpy [S][3]  rpy of the INVERSE of world_R_base (the convention of fbr_states.base_rpy; Rotation.RPY = Rz(y) Ry(p) Rx(r)), by
+ *                    r = atan2(R21, R22), p = asin(-R20), y = atan2(R10, R00); at |R20| >= 1: p = +-pi/2, r = 0, y = atan2(-R01, R11)
+ *   base_pos [S][3]  base link origin in the world frame, the attachment at the origin
+ *   base_vel [S][6]  mixed twist [lin; ang]
+ *   base_acc [S][6]  central differences of base_vel with dt, one-sided at a candidate's two ends; all zeros when T <= 2
+ *   att_state [S][6] or NULL: the attachment's rpy and angular velocity (world) as used at each step
+ *   info [ncand][2] or NULL: moment evaluations of the equilibrium search (FBR_SUSP_EQ_MAX_ITER: not converged), clamp events
+ * Two kernels (csrc/fbr_kinid.h): one lane per sample reduces the sample to a record of 39 doubles (the composite inertia, Coriolis
+ * coupling, joint-motion moment and first mass moment about O, the base link's pose and twist relative to the attachment); one lane per
+ * candidate then steps through its records at O(1) per step.  A candidate's result does not depend on the rest of the batch; no atomics:
+ * the same bits on every run.  NaN inputs give NaN outputs.
+ * FBR_E_INVALID: a model without a floating base, att_link out of range, dt not finite or <= 0, damping not finite or < 0, ncand < 1,
+ * num_samples 0 or not a multiple of ncand, x_std shorter than 10 per link.  FBR_E_UNSUPPORTED: the lane kernels do not serve the model
+ * (option "fused_id" 0, or joint paths of more than 24 joints); there is no two-kernel form.
+ */
+#define FBR_SUSP_EQ_MAX_ITER 200
+#define FBR_SUSP_EQ_TOL 0.01
+#define FBR_SUSP_EQ_STEP (1.0 / 700.0)
+#define FBR_SUSP_EQ_CLIP_DEG 30.0
+#define FBR_SUSP_MAX_SWING_DEG 25.0
+#define FBR_SUSP_BOUNCE (-0.3)
+int fbr_suspended_base_motion(fbr_model *m, const fbr_states *st, int32_t ncand, const double *x_std, int32_t num_x, int32_t att_link, double dt,
+                              double damping, double *base_rpy, double *base_pos, double *base_vel, double *base_acc, double *att_state,
+                              int64_t *info, int32_t out_mem);
 
 /*
  * Capsule collision geometry of the robot, for fbr_candidate_capsule_distances: the reference's collisionMode "capsule"
@@ -457,6 +497,13 @@ int fbr_gram_lane_info(const fbr_model *m, int32_t k, int64_t num_samples, int64
  * runs on (< 0: a batch large enough for the reductions; == the model's own counts when nothing is reduced).
  */
 int fbr_model_link_merge_info(const fbr_model *m, int64_t num_samples, int32_t *moving_links, int32_t *reduced_cols);
+
+/* The per-sample records fbr_suspended_base_motion steps through (tests, tooling): rec_out [num_samples][39] (out_mem) = composite inertia
+   about the attachment origin O (xx xy xz yy yz zz) | Coriolis coupling B (3 x 3 row-major) | joint-motion moment c0 | first mass moment mc |
+   pose R (3 x 3) | p and twist [lin; ang] of the base link relative to the attachment frame; everything in the attachment link's axes.
+   Arguments and errors as there. */
+int fbr_suspended_records(fbr_model *m, const fbr_states *st, const double *x_std, int32_t num_x, int32_t att_link, double *rec_out,
+                          int32_t out_mem);
 
 /* ---- options ------------------------------------------------------------------------------------ */
 /*
