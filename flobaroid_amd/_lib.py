@@ -105,6 +105,12 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_model_set_boxes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _ip]),
+    "fbr_candidate_box_distances": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -592,11 +598,54 @@ class Engine:
                                                 int(pr.shape[0]), pr.ctypes.data_as(_ip)), "fbr_model_set_capsules")
         self.num_capsules, self.num_capsule_pairs = int(link.size), int(pr.shape[0])
 
+    def set_boxes(self, boxes, pairs, center_in_link_axes: bool = False) -> None:
+        """Box collision set of the handle (``fbr_model_set_boxes``), independent of the capsule set.  ``boxes``: a sequence of
+        ``(link, half, center, rot)`` -- link an index into the topology's links, a link name, or None / -1 for a world box; half extents;
+        centre (robot box: offset from the link origin; world box: in the world); rot (3, 3) with the box axes as columns (world boxes; None
+        otherwise) -- or of objects with ``link`` / ``link_name``, ``half``, ``center``, ``rot`` (``flobaroid_amd.collision.Box``);
+        ``pairs``: (P, 2) indices into that sequence.  ``center_in_link_axes``: False places a robot box at ``p_link + center`` (the
+        reference's sum in world axes), True at ``p_link + R_link center``.  Replaces the set in place; an empty ``boxes`` clears it."""
+        names = list(self.topo.link_names)
+        link, half, cen, rot, any_world = [], [], [], [], False
+        for b in boxes:
+            if hasattr(b, "half"):
+                l, h, c, r = (b.link if getattr(b, "link", None) is not None else getattr(b, "link_name", None)), b.half, b.center, b.rot
+            else:
+                l, h, c, r = b
+            l = -1 if l is None else (names.index(l) if isinstance(l, str) else int(l))
+            link.append(l)
+            half.append(np.asarray(h, dtype=np.float64).reshape(3))
+            cen.append(np.asarray(c, dtype=np.float64).reshape(3))
+            if l < 0 and r is None:
+                raise ValueError("a world box needs its rotation")
+            any_world |= l < 0
+            rot.append(np.eye(3).reshape(9) if r is None else np.asarray(r, dtype=np.float64).reshape(9))
+        link = np.ascontiguousarray(link, dtype=np.int32)
+        half = np.ascontiguousarray(np.array(half, dtype=np.float64).reshape(-1, 3))
+        cen = np.ascontiguousarray(np.array(cen, dtype=np.float64).reshape(-1, 3))
+        rot = np.ascontiguousarray(np.array(rot, dtype=np.float64).reshape(-1, 9))
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        _check(self._lib.fbr_model_set_boxes(self._h, int(link.size), link.ctypes.data_as(_ip), half.ctypes.data_as(_dp), cen.ctypes.data_as(_dp),
+                                             rot.ctypes.data_as(_dp) if any_world else None, int(bool(center_in_link_axes)), int(pr.shape[0]),
+                                             pr.ctypes.data_as(_ip)), "fbr_model_set_boxes")
+        self.num_boxes, self.num_box_pairs = int(link.size), int(pr.shape[0])
+
+    def candidate_box_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:
+        """Per candidate and box pair, the smallest signed box distance over every ``step``-th sample of the candidate and the sample index
+        where it is reached (``fbr_candidate_box_distances``): ``{"dist": (C, P), "idx": (C, P) int64}``, arguments and rules as for
+        ``candidate_capsule_distances``.  Separated boxes: the exact Euclidean distance; overlapping: minus the minimum translation."""
+        return self._candidate_distances("fbr_candidate_box_distances", int(getattr(self, "num_box_pairs", 0)), st, ncand, step, base_pos, device_out)
+
     def candidate_capsule_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:
         """Per candidate and capsule pair, the smallest capsule distance over every ``step``-th sample of the candidate and the sample index
         (inside the candidate) where it is reached (``fbr_candidate_capsule_distances``): ``{"dist": (C, P), "idx": (C, P) int64}``; 1e10 / -1
         for a pair no sample won (NaN poses).  ``st`` needs ``q`` and, with a floating base, ``rpy`` only; ``base_pos`` (S, 3) places the
         base (None: the origin).  Torch tensors when the states are on the device, NumPy arrays otherwise (``device_out`` overrides)."""
+        return self._candidate_distances("fbr_candidate_capsule_distances", int(getattr(self, "num_capsule_pairs", 0)), st, ncand, step, base_pos,
+                                         device_out)
+
+    def _candidate_distances(self, entry: str, P: int, st: dict, ncand: int, step: int, base_pos, device_out) -> dict:
+        """the capsule and the box call share their arguments: ``entry`` names the library's function, ``P`` the pairs of its set"""
         q = _Ref(st["q"], None, "q")
         if len(q.obj.shape) != 2 or q.obj.shape[1] != self.n:
             raise ValueError(f"q: expected (S, {self.n}), got {tuple(q.obj.shape)}")
@@ -608,7 +657,7 @@ class Engine:
             self._sync_torch()
         s = fbr_states()
         s.num_samples, s.mem, s.q, s.base_rpy = S, mem, q.ptr, rpy.ptr
-        C, P = int(ncand), int(getattr(self, "num_capsule_pairs", 0))
+        C = int(ncand)
         shape = (max(C, 1), P)
         out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
         if out_mem == FBR_DEVICE:
@@ -620,8 +669,7 @@ class Engine:
         else:
             val, idx = np.empty(shape), np.empty(shape, dtype=np.int64)
             pv, pi = val.ctypes.data, idx.ctypes.data
-        _check(self._lib.fbr_candidate_capsule_distances(self._h, ctypes.byref(s), bp.ptr, C, int(step), pv, pi, out_mem),
-               "fbr_candidate_capsule_distances")
+        _check(getattr(self._lib, entry)(self._h, ctypes.byref(s), bp.ptr, C, int(step), pv, pi, out_mem), entry)
         return {"dist": val, "idx": idx}
 
     def _index_array(self, x, shape, mem, name, dtype=np.int64):

@@ -1,15 +1,21 @@
-"""Host side of the capsule collision constraints (the reference's ``collisionMode: "capsule"``): capsules fitted to the collision geometry
-of a URDF and the list of link pairs the trajectory optimiser checks.  NumPy and ElementTree only.
+"""Host side of the collision constraints that need no mesh code (the reference's ``collisionMode: "capsule"`` and ``"box"``, robot and world
+links): capsules and boxes from the collision geometry of a URDF, the boxes of a world URDF, and the list of link pairs the trajectory
+optimiser checks.  NumPy and ElementTree only.
 
 * ``fit_capsules_from_urdf`` -- excitation/capsule.py ``fit_capsules_from_urdf`` for ``cylinder``, ``sphere`` and ``box`` geometry and the
   merge of several primitives of one link.  There is no mesh code in this project: a link whose only collision geometry is a mesh gets no
   capsule and is reported (callers may add capsules of their own, e.g. fitted to a bounding box they have).
-* ``collision_pairs`` -- excitation/trajectoryOptimizer.py ``_buildCollisionPairs`` for the robot's own links: ``ignoreLinksForCollision``,
-  ``ignoreLinkPairsForCollision``, ``ignoreCollisionBetweenGroups``, neighbours skipped, ``collisionMaxKinematicDistance``, in the
-  reference's pair order.  World links have no capsules in the reference either (they go to its mesh library): out of scope.
-* ``collision_set`` -- both in the form ``Engine.set_capsules`` and the ``collision`` argument of ``excitation.candidate_objectives`` take.
+* ``boxes_from_hulls`` / ``boxes_from_urdf`` -- the box fallback of optimizer.py ``_getLinkCollisionGeometry`` from the reference's own
+  ``link_cuboid_hulls``, or from the no-mesh branches of ``getBoundingBox`` / ``getLinkGeometry``.
+* ``world_boxes_from_urdf`` -- the static boxes of a world URDF (``getLinkWorldTransforms`` composed with the visual origin).
+* ``collision_pairs`` -- excitation/trajectoryOptimizer.py ``_buildCollisionPairs``: ``ignoreLinksForCollision``,
+  ``ignoreLinkPairsForCollision``, ``ignoreCollisionBetweenGroups``, neighbours skipped, ``collisionMaxKinematicDistance``, world-world pairs
+  skipped, in the reference's pair order.
+* ``collision_set`` -- all of it in the form ``Engine.set_capsules`` / ``Engine.set_boxes`` and the ``collision`` argument of
+  ``excitation.candidate_objectives`` take.
 
-The distances themselves are computed on the device (``Engine.candidate_capsule_distances``, csrc/fbr_capsule.h).
+The distances themselves are computed on the device (``Engine.candidate_capsule_distances``, csrc/fbr_capsule.h;
+``Engine.candidate_box_distances``, csrc/fbr_box.h).  Not covered: the mesh modes ``convex`` and ``full``.
 """
 from __future__ import annotations
 
@@ -27,6 +33,18 @@ class Capsule:
     p0_local: np.ndarray
     p1_local: np.ndarray
     radius: float
+
+
+@dataclass
+class Box:
+    """An oriented box.  ``link_name`` a robot link: the box has the link's axes and sits ``center`` off the link origin (``rot`` is None);
+    ``link_name`` None: a world box, ``center`` and ``rot`` (3, 3, columns = box axes) in the world, ``name`` the world link it came from."""
+
+    link_name: str | None
+    half: np.ndarray
+    center: np.ndarray
+    rot: np.ndarray | None = None
+    name: str | None = None
 
 
 def _origin(element):
@@ -149,13 +167,17 @@ def link_neighbors(topology) -> dict:
     return out
 
 
-def collision_pairs(topology, capsules, config: dict) -> list:
-    """Link pairs ``(l0, l1)`` (names, l0 before l1 in ``topology.link_names``) the optimiser checks, in its order.  Skipped: links
-    without a capsule or in ``ignoreLinksForCollision``; pairs in ``ignoreLinkPairsForCollision`` (either order) or across two groups of
-    ``ignoreCollisionBetweenGroups``; neighbours (``link_neighbors``); with ``collisionMaxKinematicDistance`` > 0, pairs further apart
-    than that many steps of the neighbour graph."""
+def collision_pairs(topology, capsules, config: dict, world_links=(), boxes=None) -> list:
+    """Link pairs ``(l0, l1)`` (names, l0 before l1 in ``topology.link_names + world_links``) the optimiser checks, in its order.  Skipped:
+    robot links without geometry (neither in ``capsules`` nor in ``boxes``) or in ``ignoreLinksForCollision``; pairs in
+    ``ignoreLinkPairsForCollision`` (either order) or across two groups of ``ignoreCollisionBetweenGroups``; neighbours
+    (``link_neighbors``); with ``collisionMaxKinematicDistance`` > 0, pairs further apart than that many steps of the neighbour graph --
+    which, as in the reference, drops EVERY pair with a world link (a world link is not in the graph: distance 999); world-world pairs."""
     names = list(topology.link_names)
-    ignore_links = set(config.get("ignoreLinksForCollision", [])) | {n for n in names if n not in capsules}
+    nrobot = len(names)
+    all_links = names + [w for w in world_links]
+    have = set(capsules) | set(boxes or {})
+    ignore_links = set(config.get("ignoreLinksForCollision", [])) | {n for n in names if n not in have}
     ignore_pairs = set()
     for a, b in config.get("ignoreLinkPairsForCollision", []):
         ignore_pairs |= {(a, b), (b, a)}
@@ -181,13 +203,16 @@ def collision_pairs(topology, capsules, config: dict) -> list:
         return 999
 
     pairs = []
-    for i, l0 in enumerate(names):
-        for l1 in names[i + 1:]:
+    for i, l0 in enumerate(all_links):
+        for j in range(i + 1, len(all_links)):
+            l1 = all_links[j]
+            if i >= nrobot and j >= nrobot:
+                continue
             if l0 in ignore_links or l1 in ignore_links:
                 continue
             if (l0, l1) in ignore_pairs or (l0, l1) in group_ignore:
                 continue
-            if l0 in nbs[l1] or l1 in nbs[l0]:
+            if i < nrobot and j < nrobot and (l0 in nbs[l1] or l1 in nbs[l0]):
                 continue
             if max_dist > 0 and kin_distance(l0, l1) > max_dist:
                 continue
@@ -195,13 +220,185 @@ def collision_pairs(topology, capsules, config: dict) -> list:
     return pairs
 
 
-def collision_set(topology, capsules, config: dict, margins=None) -> dict:
-    """What ``Engine.set_capsules`` and the ``collision`` argument of ``excitation.candidate_objectives`` take: ``capsules`` (a list, one per
-    link that has one, in link order), ``pairs`` ((P, 2) indices into that list, from ``collision_pairs``), ``pair_names`` and ``margins``
-    ((P,), default 0: the reference's ``_collision_pair_margins`` are zero for pairs of robot links)."""
+def _euler_to_matrix(rpy):
+    return _origin(type("O", (), {"attrib": {"rpy": " ".join(repr(float(v)) for v in rpy)}})())[1]
+
+
+def _matrix_to_euler(R):
+    """the reference's rotationMatrixToEulerAngles (its singular branch included)"""
+    sy = np.sqrt(R[0, 0] * R[0, 0] + R[1, 0] * R[1, 0])
+    if sy >= 1e-6:
+        return np.array([np.arctan2(R[2, 1], R[2, 2]), np.arctan2(-R[2, 0], sy), np.arctan2(R[1, 0], R[0, 0])])
+    return np.array([np.arctan2(-R[1, 2], R[1, 1]), np.arctan2(-R[2, 0], sy), 0.0])
+
+
+def _link_geometry(link):
+    """getLinkGeometry for one <link>: (size (3,), position, rpy-matrix) of the first box / cylinder / sphere -- visual geometry before
+    collision geometry, the origin always the VISUAL one -- or None; and whether the link names a mesh."""
+    vo = link.find("visual/origin")
+    pos, rot = _origin(vo)
+    has_mesh = link.find("visual/geometry/mesh") is not None or link.find("collision/geometry/mesh") is not None
+    for prefix in ("visual/geometry", "collision/geometry"):
+        m = link.find(prefix + "/box")
+        if m is not None:
+            return np.array([float(v) for v in m.attrib["size"].split()]), pos, rot, has_mesh
+        m = link.find(prefix + "/cylinder")
+        if m is not None:
+            r, length = float(m.attrib["radius"]), float(m.attrib["length"])
+            return np.array([2 * r, 2 * r, length]), pos, rot, has_mesh
+        m = link.find(prefix + "/sphere")
+        if m is not None:
+            r = float(m.attrib["radius"])
+            return np.array([2 * r, 2 * r, 2 * r]), pos, rot, has_mesh
+    return None, pos, rot, has_mesh
+
+
+def boxes_from_hulls(link_cuboid_hulls: dict, robot_links, scale: float = 1.0):
+    """``(boxes, world_boxes)`` from the reference's ``link_cuboid_hulls`` ({link: [box (2, 3) min | max, pos, rot]}, what a caller with
+    trimesh has): the arithmetic of optimizer.py:629-633.  A robot link's box is scaled by ``scale`` (``scaleCollisionHull``), its centre
+    ``0.5 (b0 + b1) scale + pos`` is an offset from the link origin; every other entry is a world box, unscaled, placed as the reference
+    places it: at ``pos + (0.5 (b0 + b1) + pos)`` with the rotation of ``rot`` (Euler angles or a matrix)."""
+    robot = set(robot_links)
+    boxes, world = {}, {}
+    for name, (box, pos, rot) in link_cuboid_hulls.items():
+        b = np.asarray(box, dtype=np.float64) * (scale if name in robot else 1.0)
+        p = np.asarray(pos, dtype=np.float64)
+        center = 0.5 * (b[0] + b[1]) + p
+        if name in robot:
+            boxes[name] = Box(name, 0.5 * (b[1] - b[0]), center)
+        else:
+            R = _euler_to_matrix(rot) if np.ndim(rot) == 1 else np.asarray(rot, dtype=np.float64)
+            world[name] = Box(None, 0.5 * (b[1] - b[0]), p + center, R, name)
+    return boxes, world
+
+
+def boxes_from_urdf(urdf, link_names, x_std=None, cube_size=None, scale: float = 1.0):
+    """``(boxes, mesh_links)``: the boxes ``boxes_from_hulls`` gives for the hulls the reference builds WITHOUT a mesh: a link with
+    ``box`` / ``cylinder`` / ``sphere`` geometry gets that primitive's bounding box at the visual origin's position (its rotation is not
+    used, as in the reference).  A link that names a mesh is listed in ``mesh_links`` (there is no mesh code here); with ``cube_size`` and
+    ``x_std`` it gets what the reference falls back to when the mesh file is missing: the cube of that edge around the a-priori centre of
+    mass.  Links without any geometry get no box (the reference skips them: ``hasVisualGeometry``)."""
+    tree = ET.parse(urdf)
+    wanted = list(link_names)
+    hulls, mesh_links = {}, []
+    for link in tree.findall("link"):
+        name = link.attrib["name"]
+        if name not in wanted:
+            continue
+        size, pos, _, has_mesh = _link_geometry(link)
+        if has_mesh:
+            mesh_links.append(name)
+            if cube_size is not None and x_std is not None:
+                i = wanted.index(name)
+                m = float(x_std[10 * i])
+                com = np.asarray(x_std[10 * i + 1:10 * i + 4], dtype=np.float64) / m if m != 0 else np.zeros(3)
+                hulls[name] = [np.array([com - 0.5 * cube_size, com + 0.5 * cube_size]), np.zeros(3), np.eye(3)]
+        elif size is not None and np.any(size != 0):
+            hulls[name] = [np.array([-0.5 * size, 0.5 * size]), pos, np.eye(3)]
+    return boxes_from_hulls(hulls, wanted, scale)[0], mesh_links
+
+
+def world_boxes_from_urdf(world_urdf, placement: str = "reference", cube_size=None) -> dict:
+    """{world link: Box} of a static world URDF, in document order -- every link with child elements (``getLinkNames``), its primitive's
+    bounding box (``cube_size``: the cube a link without one gets; None: such a link is an error), the joint chain's transform
+    (``getLinkWorldTransforms``: fixed joints, from the root) composed with the visual origin as optimizer.py:507-525 does:
+    ``pos = link_pos + link_rot visual_pos``, ``rot = link_rot visual_rot``.
+
+    ``placement="reference"`` reproduces where the reference's collision loop puts the box: ``_getLinkTransform`` returns ``pos`` and
+    ``_getLinkCollisionGeometry`` returns the offset ``mid + pos``, and the loop adds the two -- the box lands at ``2 pos + mid``, with the
+    rotation taken through Euler angles and back.  ``"geometric"`` places it where the URDF says: ``pos + rot mid``."""
+    if placement not in ("reference", "geometric"):
+        raise ValueError("placement: 'reference' or 'geometric'")
+    root = ET.parse(world_urdf).getroot()
+    parent = {}
+    for joint in root.findall("joint"):
+        p, c = joint.find("parent"), joint.find("child")
+        if p is None or c is None:
+            continue
+        parent[c.attrib["link"]] = (p.attrib["link"],) + _origin(joint.find("origin"))
+    done = {}
+
+    def transform(name):
+        if name not in done:
+            if name not in parent:
+                done[name] = (np.zeros(3), np.eye(3))
+            else:
+                pn, xyz, R = parent[name]
+                pp, pR = transform(pn)
+                done[name] = (pp + pR @ xyz, pR @ R)
+        return done[name]
+
+    out = {}
+    for link in root.findall("link"):
+        if len(list(link)) == 0:  # (a frame only)
+            continue
+        name = link.attrib["name"]
+        size, vpos, vrot, _ = _link_geometry(link)
+        if size is not None and np.any(size != 0):
+            b = np.array([-0.5 * size, 0.5 * size])
+        elif cube_size is not None:
+            b, vpos, vrot = np.array([np.full(3, -0.5 * cube_size), np.full(3, 0.5 * cube_size)]), np.zeros(3), np.eye(3)
+        else:
+            raise ValueError(f"world link {name} has no box, cylinder or sphere geometry (cube_size: the cube the reference gives it)")
+        lpos, lrot = transform(name)
+        pos, R = lpos + lrot @ vpos, lrot @ vrot
+        mid = 0.5 * (b[0] + b[1])
+        if placement == "reference":
+            out[name] = Box(None, 0.5 * (b[1] - b[0]), pos + (mid + pos), _euler_to_matrix(_matrix_to_euler(R)), name)
+        else:
+            out[name] = Box(None, 0.5 * (b[1] - b[0]), pos + R @ mid, R, name)
+    return out
+
+
+def collision_set(topology, capsules, config: dict, margins=None, boxes=None, world_boxes=None) -> dict:
+    """What ``Engine.set_capsules`` / ``Engine.set_boxes`` and the ``collision`` argument of ``excitation.candidate_objectives`` take.
+
+    Without ``boxes`` and ``world_boxes``: ``capsules`` (a list, one per link that has one, in link order), ``pairs`` ((P, 2) indices into
+    that list, from ``collision_pairs``), ``pair_names`` and ``margins`` ((P,), default 0: the reference's ``_collision_pair_margins`` are
+    zero for pairs of robot links).
+
+    With ``boxes`` ({robot link: Box}) and / or ``world_boxes`` ({world link: Box}, their order is the order of the world links):
+    ``pair_names`` is the reference's list over robot and world links, and every pair is served as the reference serves it -- in
+    ``collisionMode: "capsule"`` by the capsule routine when both links have a capsule, by the box routine otherwise; in ``"box"`` always
+    by the box routine.  ``pairs`` then holds the capsule pairs only, and there are in addition ``boxes`` (a list: robot boxes in link
+    order, then the world boxes), ``box_pairs`` ((Pb, 2) into that list), ``columns`` ((P, 2): per pair of ``pair_names`` the set -- 0
+    capsules, 1 boxes -- and the column of that set's result that serves it) and ``margins`` default to ``worldCollisionMargin`` on pairs
+    with a world link, 0 elsewhere.  A pair that needs a box for a link that has none is an error."""
     names = [n for n in topology.link_names if n in capsules]
     pos = {n: i for i, n in enumerate(names)}
-    pair_names = collision_pairs(topology, capsules, config)
-    pairs = np.array([(pos[a], pos[b]) for a, b in pair_names], dtype=np.int32).reshape(-1, 2)
-    m = np.zeros(len(pair_names)) if margins is None else np.asarray(margins, dtype=np.float64).reshape(len(pair_names))
-    return {"capsules": [capsules[n] for n in names], "pairs": pairs, "pair_names": pair_names, "margins": m}
+    if boxes is None and world_boxes is None:
+        pair_names = collision_pairs(topology, capsules, config)
+        pairs = np.array([(pos[a], pos[b]) for a, b in pair_names], dtype=np.int32).reshape(-1, 2)
+        m = np.zeros(len(pair_names)) if margins is None else np.asarray(margins, dtype=np.float64).reshape(len(pair_names))
+        return {"capsules": [capsules[n] for n in names], "pairs": pairs, "pair_names": pair_names, "margins": m}
+    mode = config.get("collisionMode", "capsule")
+    if mode not in ("capsule", "box"):
+        raise ValueError("collision sets cover collisionMode 'capsule' and 'box' (no mesh code)")
+    boxes, world_boxes = dict(boxes or {}), dict(world_boxes or {})
+    clash = set(world_boxes) & set(topology.link_names)
+    if clash:
+        raise ValueError(f"link(s) {sorted(clash)} declared in the model and in the world")
+    caps = capsules if mode == "capsule" else {}
+    pair_names = collision_pairs(topology, capsules, config, world_links=list(world_boxes), boxes=boxes)
+    bnames = [n for n in topology.link_names if n in boxes] + list(world_boxes)
+    bpos = {n: i for i, n in enumerate(bnames)}
+    cap_pairs, box_pairs, columns = [], [], []
+    for a, b in pair_names:
+        if a in caps and b in caps:
+            columns.append((0, len(cap_pairs)))
+            cap_pairs.append((pos[a], pos[b]))
+        else:
+            for n in (a, b):
+                if n not in bpos:
+                    raise ValueError(f"pair ({a}, {b}) goes to the box routine, but {n} has no box")
+            columns.append((1, len(box_pairs)))
+            box_pairs.append((bpos[a], bpos[b]))
+    if margins is None:
+        wm = float(config.get("worldCollisionMargin", 0.0))
+        m = np.array([wm if (a in world_boxes or b in world_boxes) else 0.0 for a, b in pair_names])
+    else:
+        m = np.asarray(margins, dtype=np.float64).reshape(len(pair_names))
+    return {"capsules": [capsules[n] for n in names] if mode == "capsule" else [],
+            "pairs": np.array(cap_pairs, dtype=np.int32).reshape(-1, 2), "pair_names": pair_names, "margins": m,
+            "boxes": [boxes[n] if n in boxes else world_boxes[n] for n in bnames], "box_pairs": np.array(box_pairs, dtype=np.int32).reshape(-1, 2),
+            "columns": np.array(columns, dtype=np.int64).reshape(-1, 2)}

@@ -11,8 +11,9 @@ thread_local std::string g_fbr_err;
 // 101 (round 6): fbr_topology.joint_type, the num_samples argument of fbr_gram_program_info / fbr_model_link_merge_info (both added in
 // round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
 // 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
-// fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain: added symbols change no
-// signature, and _lib.py names a library that lacks one).
+// fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain, fbr_suspended_base_motion,
+// fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances: added symbols change no signature, and _lib.py names a library
+// that lacks one).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
 
@@ -1218,6 +1219,226 @@ extern "C" int fbr_candidate_capsule_distances(fbr_model *m, const fbr_states *s
             ProfScope ps(m, FBR_PROF_REDUCE);
             hipLaunchKernelGGL(fbr_capsule_pairs_kernel, dim3((unsigned)std::min<long>(nb * nbatch, (long)m->num_cus * 16)), dim3(64), 0, m->stream, cp, tl,
                                b0, nb, (const double *)m->cap_ep.as<double>(), pval, pidx);
+            HIPCHK(hipGetLastError());
+            const long cands = (b0 + nb - 1) / tl.tiles - b0 / tl.tiles + 1;
+            hipLaunchKernelGGL(fbr_capsule_finish_kernel, dim3((unsigned)((cands * P + 255) / 256)), dim3(256), 0, m->stream, tl, (int)P, b0, nb,
+                               (const double *)pval, (const long *)pidx, val, idx);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (out_mem == FBR_HOST) {
+        HIPCHK(hipMemcpyAsync(dist_out, val, cnt * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(idx_out, idx, cnt * sizeof(long), hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    prof_collect(m);
+    return FBR_OK;
+}
+
+// ---- box collision distances (csrc/fbr_box.h) ----------------------------------------------------------------------------------------
+extern "C" int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *link, const double *half, const double *center, const double *rot,
+                                   int32_t center_in_link_axes, int32_t npairs, const int32_t *pairs)
+{
+    if (!m) {
+        set_err("null model");
+        return FBR_E_INVALID;
+    }
+    if (nboxes < 0 || npairs < 0 || nboxes > FBR_MAX_BOXES || npairs > FBR_MAX_BOX_PAIRS) {
+        set_err("box set: at most " + std::to_string(FBR_MAX_BOXES) + " boxes and " + std::to_string(FBR_MAX_BOX_PAIRS) + " pairs");
+        return FBR_E_INVALID;
+    }
+    if ((nboxes > 0 && (!link || !half || !center)) || (npairs > 0 && !pairs)) {
+        set_err("box set: null array");
+        return FBR_E_INVALID;
+    }
+    const FbrHostModel &hm = m->hm;
+    int nrob = 0, nworld = 0;
+    std::vector<int> code(nboxes);  // robot-box number, or -1 - (world-box number)
+    for (int c = 0; c < nboxes; c++) {
+        if (link[c] < -1 || link[c] >= hm.L) {
+            set_err("box " + std::to_string(c) + ": link index out of range (-1: a world box)");
+            return FBR_E_INVALID;
+        }
+        for (int i = 0; i < 3; i++) {
+            if (!(half[3 * c + i] > 0.0) || !std::isfinite(half[3 * c + i])) {
+                set_err("box " + std::to_string(c) + ": the half extents must be finite and positive");
+                return FBR_E_INVALID;
+            }
+            if (!std::isfinite(center[3 * c + i])) {
+                set_err("box " + std::to_string(c) + ": non-finite centre");
+                return FBR_E_INVALID;
+            }
+        }
+        if (link[c] < 0) {
+            if (!rot) {
+                set_err("box " + std::to_string(c) + ": a world box needs rot");
+                return FBR_E_INVALID;
+            }
+            for (int i = 0; i < 9; i++)
+                if (!std::isfinite(rot[9 * c + i])) {
+                    set_err("box " + std::to_string(c) + ": non-finite rotation");
+                    return FBR_E_INVALID;
+                }
+            code[c] = -1 - nworld++;
+        } else {
+            code[c] = nrob++;
+        }
+    }
+    for (int k = 0; k < npairs; k++) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a < 0 || a >= nboxes || b < 0 || b >= nboxes || a == b) {
+            set_err("box pair " + std::to_string(k) + ": box index out of range, or a box paired with itself");
+            return FBR_E_INVALID;
+        }
+        if (link[a] < 0 && link[b] < 0) {
+            set_err("box pair " + std::to_string(k) + ": two world boxes");
+            return FBR_E_INVALID;
+        }
+    }
+    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->boxes = DevBoxes{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (nboxes == 0) return FBR_OK;
+    FbrKinIdProgram prog;
+    try {
+        fbr_kinid_build(hm, prog);
+    } catch (const std::exception &e) {
+        set_err(e.what());
+        return FBR_E_INVALID;
+    }
+    // robot boxes sorted by the step of their link (stable: the caller's order within a link)
+    std::vector<int> stepof(hm.L, 0), boxbeg(prog.nsteps + 1, 0), boxid(std::max(nrob, 1), 0);
+    for (int k = 0; k < prog.nsteps; k++) stepof[prog.steps[(size_t)k * FBR_KINID_STEP]] = k;
+    for (int c = 0; c < nboxes; c++)
+        if (link[c] >= 0) boxbeg[stepof[link[c]] + 1]++;
+    for (int k = 0; k < prog.nsteps; k++) boxbeg[k + 1] += boxbeg[k];
+    std::vector<int> fill(boxbeg.begin(), boxbeg.end() - 1);
+    // one allocation: cen | half | world | steps | boxbeg | boxid | pairs  (doubles first: every table keeps its alignment)
+    const size_t nr = (size_t)std::max(nrob, 1), nw = (size_t)std::max(nworld, 1), nd = nr * 6 + nw * 15;
+    const size_t ni = prog.steps.size() + boxbeg.size() + nr + 1 + 2 * (size_t)std::max(npairs, 1);  // (+ 1: the padding in front of the pairs)
+    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int), 0);
+    double *hcen = (double *)host.data(), *hhalf = hcen + nr * 3, *hworld = hhalf + nr * 3;
+    for (int c = 0; c < nboxes; c++) {
+        if (link[c] >= 0) {
+            const int slot = fill[stepof[link[c]]]++;
+            boxid[slot] = code[c];
+            for (int i = 0; i < 3; i++) {
+                hcen[(size_t)slot * 3 + i] = center[3 * c + i];
+                hhalf[(size_t)code[c] * 3 + i] = half[3 * c + i];
+            }
+        } else {
+            double *w = hworld + (size_t)(-1 - code[c]) * 15;
+            for (int i = 0; i < 9; i++) w[i] = rot[9 * c + i];
+            for (int i = 0; i < 3; i++) {
+                w[9 + i] = center[3 * c + i];
+                w[12 + i] = half[3 * c + i];
+            }
+        }
+    }
+    int *hi = (int *)(hcen + nd), *hsteps = hi, *hboxbeg = hsteps + prog.steps.size(), *hboxid = hboxbeg + boxbeg.size();
+    int *hpairs = hboxid + nr + ((prog.steps.size() + boxbeg.size() + nr) & 1);  // (int2: 8-byte aligned)
+    std::copy(prog.steps.begin(), prog.steps.end(), hsteps);
+    std::copy(boxbeg.begin(), boxbeg.end(), hboxbeg);
+    std::copy(boxid.begin(), boxid.end(), hboxid);
+    for (size_t k = 0; k < 2 * (size_t)npairs; k++) hpairs[k] = code[pairs[k]];
+    if (int rc = m->box_tab.ensure(host.size() + 8)) return rc;
+    HIPCHK(hipMemcpy(m->box_tab.p, host.data(), host.size(), hipMemcpyHostToDevice));
+    const char *base = (const char *)m->box_tab.p;
+    DevBoxes db;
+    db.nsteps = prog.nsteps;
+    db.nslots = prog.nslots;
+    db.nrob = nrob;
+    db.nworld = nworld;
+    db.npairs = npairs;
+    db.cmode = center_in_link_axes ? 1 : 0;
+    db.cen = (const double *)base;
+    db.half = db.cen + nr * 3;
+    db.world = db.half + nr * 3;
+    db.steps = (const int *)(base + ((const char *)hsteps - host.data()));
+    db.boxbeg = (const int *)(base + ((const char *)hboxbeg - host.data()));
+    db.boxid = (const int *)(base + ((const char *)hboxid - host.data()));
+    db.pairs = (const int2 *)(base + ((const char *)hpairs - host.data()));
+    m->boxes = db;
+    return FBR_OK;
+}
+
+extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
+                                           int64_t *idx_out, int32_t out_mem)
+{
+    if (!m || !st || !dist_out || !idx_out) {
+        set_err("null model / states / dist_out / idx_out");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q) {
+        set_err("bad fbr_states header, or q is NULL");
+        return FBR_E_INVALID;
+    }
+    if (m->boxes.nrob == 0 || m->boxes.npairs == 0) {
+        set_err("no box set with at least one pair (fbr_model_set_boxes)");
+        return FBR_E_INVALID;
+    }
+    if (ncand < 1 || step < 1) {
+        set_err("ncand and step must be at least 1");
+        return FBR_E_INVALID;
+    }
+    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
+        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;
+    const FbrHostModel &hm = m->hm;
+    const DevBoxes &bx = m->boxes;
+    const long S = st->num_samples, C = ncand, P = bx.npairs;
+    const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr;
+    int rc;
+    if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
+    if (hm.floating && st->base_rpy) {
+        if ((rc = stage_one(m, m->st_rpy, st->base_rpy, (size_t)S * 3, st->mem, &drpy))) return rc;
+        if ((rc = stage_one(m, m->st_bpos, base_pos, (size_t)S * 3, st->mem, &dbp))) return rc;
+    }
+    DevCapTiles tl;
+    tl.T = S / C;
+    tl.step = step;
+    tl.Tc = (tl.T + step - 1) / step;
+    tl.tiles = (tl.Tc + 63) / 64;
+    tl.nblk = C * tl.tiles;
+    // blocks per launch: the frames of the blocks in flight stay below 256 MB, their partials below 64 MB
+    const size_t fr_blk = (size_t)bx.nrob * 12 * 64 * sizeof(double), part_blk = (size_t)P * (sizeof(double) + sizeof(long));
+    long ch = (long)std::min((size_t)(256u << 20) / fr_blk, (size_t)(64u << 20) / part_blk);
+    if (m->opt.chunk_samples >= 1) ch = (long)m->opt.chunk_samples / 64;  // (tests: the multi-launch path at small sizes)
+    ch = std::max(1L, std::min(ch, tl.nblk));
+    if ((rc = m->box_fr.ensure((size_t)ch * fr_blk))) return rc;
+    if ((rc = m->cap_part.ensure((size_t)ch * part_blk))) return rc;
+    double *pval = m->cap_part.as<double>();
+    long *pidx = (long *)(pval + (size_t)ch * P);
+    const size_t cnt = (size_t)C * P;
+    double *val = dist_out;
+    long *idx = (long *)idx_out;
+    if (out_mem == FBR_HOST) {
+        if ((rc = m->cap_out.ensure(cnt * (sizeof(double) + sizeof(long))))) return rc;
+        val = m->cap_out.as<double>();
+        idx = (long *)(val + cnt);
+    }
+    const int ldn = std::max(hm.n, 1) | 1;
+    const size_t lds_want = (size_t)64 * ldn * sizeof(double);
+    const int stage = lds_want <= (size_t)64 * 1024;  // up to 127 DOF; beyond, the lanes read their rows from memory
+    const size_t lds = stage ? lds_want : 0;
+    const int pgrid = (int)std::min<long>(ch, (long)m->num_cus * 8);
+    if ((rc = m->cap_scratch.ensure((size_t)pgrid * std::max(bx.nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
+    const long nbatch = (P + FBR_BOX_BATCH - 1) / FBR_BOX_BATCH;
+    if (lds) HIPCHK(hipFuncSetAttribute((const void *)fbr_box_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (long b0 = 0; b0 < tl.nblk; b0 += ch) {
+        const long nb = std::min(ch, tl.nblk - b0);
+        {
+            ProfScope ps(m, FBR_PROF_KIN);
+            hipLaunchKernelGGL(fbr_box_frames_kernel, dim3((unsigned)std::min<long>(nb, pgrid)), dim3(64), lds, m->stream, m->dm, bx, tl, b0, nb, stage, ldn,
+                               dq, drpy, dbp, m->box_fr.as<double>(), m->cap_scratch.as<double>());
+            HIPCHK(hipGetLastError());
+        }
+        {
+            ProfScope ps(m, FBR_PROF_REDUCE);
+            hipLaunchKernelGGL(fbr_box_pairs_kernel, dim3((unsigned)std::min<long>(nb * nbatch, (long)m->num_cus * 32)), dim3(64), 0, m->stream, bx, tl, b0,
+                               nb, (const double *)m->box_fr.as<double>(), pval, pidx);
             HIPCHK(hipGetLastError());
             const long cands = (b0 + nb - 1) / tl.tiles - b0 / tl.tiles + 1;
             hipLaunchKernelGGL(fbr_capsule_finish_kernel, dim3((unsigned)((cands * P + 255) / 256)), dim3(256), 0, m->stream, tl, (int)P, b0, nb,

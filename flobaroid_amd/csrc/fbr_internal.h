@@ -21,6 +21,7 @@
 #include "fbr_kinid.h"
 #include "fbr_capsule.h"
 #include "fbr_capsule_grad.h"
+#include "fbr_box.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -157,6 +158,10 @@ struct fbr_model {
     DevBuf cap_tab, cap_ep, cap_part, cap_scratch, cap_out, st_bpos;
     DevCapGrad capg = {0, nullptr, nullptr};  // fbr_capsule_distance_gradients: ancestor masks and per-pair steps / slots of the set above
     DevBuf capg_tab, capg_flag;
+    // box collision set (fbr_model_set_boxes; csrc/fbr_box.h), independent of the capsule set: its tables and the frames of the robot boxes
+    // of the blocks in flight; the partials, the branch-point poses and the host results share the capsule call's workspaces
+    DevBoxes boxes = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf box_tab, box_fr;
     // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its
     // steps on the device, the per-sample records, the results of a host-memory call
     FbrKinIdProgram susp_prog;

@@ -8,8 +8,9 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``dopt_sensitivities``  -- the worker's ``sens_q, sens_dq, sens_ddq`` from ``Engine.fd_scores``;
 * ``candidate_objectives`` -- the whole ``objectiveFunc`` (f, g, soft costs) of many candidates from ``Engine.gram_grouped`` +
   ``Engine.candidate_extrema``: only per-candidate numbers reach the host;
-* ``candidate_collision_constraints`` -- its collision block in capsule mode (``collisionMode: "capsule"``, robot links) from
-  ``Engine.candidate_capsule_distances``; ``candidate_objectives(..., collision=...)`` appends it to ``g``;
+* ``candidate_collision_constraints`` -- its collision block from ``Engine.candidate_capsule_distances`` (``collisionMode: "capsule"``,
+  pairs of links with capsules) and ``Engine.candidate_box_distances`` (``collisionMode: "box"``, world links, capsule-less links);
+  ``candidate_objectives(..., collision=...)`` appends it to ``g``;
 * ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
   candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``;
 * ``candidate_collision_gradient`` -- the collision rows of the constraint Jacobian in capsule mode (analyticalGradient.py:955-1027) from
@@ -287,7 +288,7 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
             "failed": failed, "dopt_scale": dopt_scale, "ag_cache": ag}
 
 
-def candidate_collision_constraints(engine, states: dict, ncand: int, config: dict, margins=None, suspended=None) -> dict:
+def candidate_collision_constraints(engine, states: dict, ncand: int, config: dict, margins=None, suspended=None, boxes: bool = False) -> dict:
     """The collision block of ``objectiveFunc`` in capsule mode for ``ncand`` equal candidates stacked in ``states``, for the capsule set of
     the engine (``Engine.set_capsules``; pairs of robot links): per candidate and pair the smallest ``distance - margin`` over
 
@@ -304,19 +305,29 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
     (``_collision_pair_margins``; None: 0).  ``eval_sample``, ``eval_scale``, ``eval_pose`` (C, P) describe the winning configuration
     ``eval_scale * q[eval_sample]`` at the base pose of sample ``eval_pose`` -- (idx, 1, idx) on the main trajectory, (0 or T - 1,
     s(tau), the pose's sample) for a transition configuration, -1 where none won: the arguments of ``Engine.capsule_distance_gradients``
-    (``candidate_collision_gradient``).  Not covered: the mesh modes, world links.
+    (``candidate_collision_gradient``).
+
+    ``boxes=True``: the same block for the BOX set of the engine (``Engine.set_boxes``: the pairs the reference sends to its box
+    fallback -- ``collisionMode: "box"``, world links, capsule-less links) from ``Engine.candidate_box_distances``; the main trajectory and
+    the transition configurations are walked once per set, each with its set's distance call.  Not covered: the mesh modes ``convex`` and
+    ``full``.
 
     ``suspended``: not None says that ``states`` carry the simulated base motion of the suspended base (``rpy`` and ``base_position`` of
     ``candidate_states(..., suspended=)``); ``floatingBaseAttachment: "suspended"`` is then accepted.  The poses of the main trajectory
     and the seven base poses of the transition configurations are those of ``states``, as in the reference."""
     _check_config(config, suspended)
+    return _collision_constraints(engine, engine.candidate_box_distances if boxes else engine.candidate_capsule_distances, states, ncand, config, margins)
+
+
+def _collision_constraints(engine, distances, states, ncand, config, margins):
+    """``candidate_collision_constraints`` with the distance call of one set: ``distances(states, ncand, step, base_pos=)``"""
     C = int(ncand)
     q = states["q"]
     S, n = int(q.shape[0]), int(q.shape[1])
     T = S // max(C, 1)
     rpy = states.get("rpy", states.get("base_rpy")) if engine.floating else None
     bpos = states.get("base_position") if engine.floating else None
-    main = engine.candidate_capsule_distances(states, C, int(config.get("collisionCheckStep", 3)), base_pos=bpos)
+    main = distances(states, C, int(config.get("collisionCheckStep", 3)), base_pos=bpos)
     dist, idx = _host(main["dist"]), _host(main["idx"]).astype(np.int64)
     P = dist.shape[1]
     m = np.zeros(P) if margins is None else np.asarray(margins, dtype=np.float64).reshape(P)
@@ -359,7 +370,7 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
             st_tr["rpy"] = expand(r3[ci, pi][:, None, None], shape + (3,))
             if bpos is not None:
                 bp_tr = expand(bpos.reshape(C, T, 3)[ci, pi][:, None, None], shape + (3,))
-        tr = engine.candidate_capsule_distances(st_tr, C, 1, base_pos=bp_tr)
+        tr = distances(st_tr, C, 1, base_pos=bp_tr)
         dt, it = _host(tr["dist"]), _host(tr["idx"]).astype(np.int64)
         kk = np.maximum(it, 0)
         ref_idx = -((kk // npose) * nuniq[:, None] + np.take_along_axis(rank, kk % npose, axis=1) + 1)
@@ -376,14 +387,46 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
             "eval_pose": ev_pose.astype(np.int64)}
 
 
+def _has_box_pairs(collision) -> bool:
+    return collision is not None and len(collision.get("box_pairs", ())) > 0
+
+
 def _collision_block(engine, states, ncand, config, collision, suspended=None):
-    """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins`` (``flobaroid_amd.collision.collision_set``)"""
+    """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins``, and for sets with boxes ``boxes``, ``box_pairs``, ``columns``
+    and optionally ``center_in_link_axes`` (``flobaroid_amd.collision.collision_set``).  Both sets are installed, each is walked with its own
+    distance call, and the two (C, P_set) results are merged into the reference's pair order."""
     if collision is None:
         return None
-    if config.get("collisionMode", "capsule") != "capsule":
-        raise ValueError("collision constraints on the device cover collisionMode 'capsule' only (no mesh code: DESIGN 9)")
-    engine.set_capsules(collision["capsules"], collision["pairs"])
-    return candidate_collision_constraints(engine, states, ncand, config, margins=collision.get("margins"), suspended=suspended)
+    mode = config.get("collisionMode", "capsule")
+    if mode not in ("capsule", "box"):
+        raise ValueError("collision constraints on the device cover collisionMode 'capsule' and 'box' only (no mesh code: DESIGN 9)")
+    if "columns" not in collision:
+        if mode != "capsule":
+            raise ValueError("collisionMode 'box' needs a collision set with boxes (flobaroid_amd.collision.collision_set(..., boxes=))")
+        engine.set_capsules(collision["capsules"], collision["pairs"])
+        return candidate_collision_constraints(engine, states, ncand, config, margins=collision.get("margins"), suspended=suspended)
+    cols = np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)
+    P = cols.shape[0]
+    if mode == "box" and (cols[:, 0] == 0).any():
+        raise ValueError("collisionMode 'box': the collision set was built for capsule mode (it has capsule pairs)")
+    m = np.zeros(P) if collision.get("margins") is None else np.asarray(collision["margins"], dtype=np.float64).reshape(P)
+    out = None
+    for which in (0, 1):
+        sel = np.nonzero(cols[:, 0] == which)[0]
+        if sel.size == 0:
+            continue
+        if which == 0:
+            engine.set_capsules(collision["capsules"], collision["pairs"])
+        else:
+            engine.set_boxes(collision["boxes"], collision["box_pairs"], center_in_link_axes=bool(collision.get("center_in_link_axes", False)))
+        part = candidate_collision_constraints(engine, states, ncand, config, margins=m[sel], suspended=suspended, boxes=bool(which))
+        if out is None:
+            out = {k: np.zeros((np.asarray(v).shape[0], P), dtype=np.asarray(v).dtype) for k, v in part.items()}
+        for k, v in part.items():
+            out[k][:, sel] = np.asarray(v)[:, cols[sel, 1]]
+    if out is None:
+        raise ValueError("the collision set has no pairs")
+    return out
 
 
 def candidate_objectives(engine, states: dict, ncand: int, independent_cols, x_std, limits: dict, joint_names, config: dict, dopt_scale=None,
@@ -609,10 +652,16 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     pair's distance at its winning configuration, held fixed (the reference's rule); a pair without a winner has a zero row.  ``grad_q`` is
     the derivative with respect to the evaluated configuration itself.  The chain runs over chunks of whole candidates whose output stays
     within ``max_bytes``; columns that only pad ``a`` / ``b`` to a common width are removed (nh = the widest candidate's).  The base pose
-    of a floating base is held constant, as in the reference."""
+    of a floating base is held constant, as in the reference.
+
+    A set with box pairs (``collision_set(..., boxes=, world_boxes=)``) raises ``ValueError``: the reference differentiates those pairs by
+    central differences of its mesh library's distance, which is not built here."""
     _check_config(config)
     if config.get("collisionMode", "capsule") != "capsule":
         raise ValueError("the collision gradient on the device covers collisionMode 'capsule' only (no mesh code: DESIGN 9)")
+    if _has_box_pairs(collision):
+        raise ValueError("the collision gradient on the device covers capsule pairs only: the set has box pairs (the reference differentiates "
+                         "those by central differences)")
     C, n = int(ncand), engine.n
     engine.set_capsules(collision["capsules"], collision["pairs"])
     cons = constraints if constraints is not None else candidate_collision_constraints(engine, states, C, config, margins=collision.get("margins"))
@@ -790,8 +839,12 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     D-optimality sweep (``analyticalGradientSubsample``).  Deviations from the reference: the wf column is analytic, the torque Jacobians
     are the clean derivative (no carried-over dq_{n-1} + eps), the Coulomb sign and the Stribeck exponent are held at their baseline;
     a ``failed`` candidate gets the soft-cost gradient only.  Not covered: the suspended base, gravity-only models (refused), mesh
-    collision modes, world links."""
+    collision modes, and box pairs (world links, ``collisionMode: "box"``): a ``collision`` set with box pairs raises ``ValueError`` -- the
+    reference differentiates those by central differences."""
     _check_config(config)
+    if _has_box_pairs(collision):
+        raise ValueError("gradients on the device cover capsule pairs only: the collision set has box pairs (the reference differentiates those "
+                         "by central differences)")
     x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
     C, n, T = len(candidates), engine.n, int(T)
     eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)

@@ -229,6 +229,39 @@ int fbr_candidate_capsule_distances(fbr_model *m, const fbr_states *st, const do
                                     double *dist_out, int64_t *idx_out, int32_t out_mem);
 
 /*
+ * Box collision geometry, for fbr_candidate_box_distances: the pairs of the reference's collision block that go to fcl.distance on the box
+ * fallback of optimizer.py _getLinkCollisionGeometry -- every pair of collisionMode "box", and in collisionMode "capsule" every pair with a
+ * world link or with a robot link that has no capsule.  Independent of the capsule set: both can be in place at once.  Host arrays, copied:
+ *   link [nboxes]       index of the box's link among the UNMERGED links (as for fbr_model_set_capsules), or -1: a world box, fixed in space
+ *   half [nboxes][3]    half extents along the box axes (positive, finite)
+ *   center [nboxes][3]  robot box: the centre's offset from the link origin, see center_in_link_axes; world box: the centre in the world
+ *   rot [nboxes][9]     row-major, columns = box axes; read for world boxes only (a robot box has its link's axes); may be NULL without any
+ *   center_in_link_axes 0: a robot box sits at p_link + center, the offset added in WORLD axes (the reference's Transform(rot, pos + offset));
+ *                       1: at p_link + R_link center, the geometrically correct placement
+ *   pairs [npairs][2]   indices into the BOX list; a pair's first box stays in registers while it does not change
+ * A second call replaces the set; nboxes = 0 clears it.  FBR_E_INVALID: more than FBR_MAX_BOXES boxes or FBR_MAX_BOX_PAIRS pairs, a link or a
+ * pair index out of range, a box paired with itself, a pair of two world boxes, a world box without rot, a non-positive or non-finite half
+ * extent, a non-finite centre or rotation; the set in place before a refused call stays.
+ */
+#define FBR_MAX_BOXES 4096
+#define FBR_MAX_BOX_PAIRS 262144
+int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *link, const double *half, const double *center, const double *rot,
+                        int32_t center_in_link_axes, int32_t npairs, const int32_t *pairs);
+
+/*
+ * Per candidate and box pair, the smallest signed box distance over the candidate's checked samples and the sample index where it is
+ * reached: states, base_pos, ncand, step, outputs and the comparison rules (strict < from 1e10, first sample wins a tie, a NaN never wins,
+ * 1e10 / -1 when no sample wins, the same bits on every run) exactly as for fbr_candidate_capsule_distances.
+ *   dist_out [ncand][npairs]  separated boxes: their exact Euclidean distance; touching or overlapping: the largest (least negative) gap over
+ *                             the 15 separating axes, i.e. minus the minimum translation that separates them (cross axes of squared length
+ *                             below 1e-12 are skipped).  The reference's FCL returns a GJK distance of tolerance 1e-6 and a build-dependent
+ *                             negative value: the sign agrees.
+ * FBR_E_INVALID: no box set or one without pairs, ncand < 1, step < 1, num_samples 0 or not a multiple of ncand.
+ */
+int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
+                                int64_t *idx_out, int32_t out_mem);
+
+/*
  * Capsule distance and its derivative with respect to the joint positions at ONE chosen configuration per candidate and pair -- the
  * collision block of the reference's analytical gradient (excitation/analyticalGradient.py:955-1027 with capsule.py
  * capsule_distance_and_gradient), for the configurations fbr_candidate_capsule_distances found.  st, base_pos, ncand as there (ncand equal
