@@ -111,6 +111,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_int32],
     ),
+    "fbr_box_distance_gradients": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -705,6 +710,21 @@ class Engine:
         derivative with respect to the EVALUATED configuration; joints off the tree path between a pair's links are exact zeros.  ``st``,
         ``base_pos`` and the result's memory space as for ``candidate_capsule_distances``; the index and scale arrays are brought to the
         memory space of the states."""
+        return self._distance_gradients("fbr_capsule_distance_gradients", int(getattr(self, "num_capsule_pairs", 0)), (), st, ncand, sample, scale,
+                                        pose_sample, base_pos, device_out)
+
+    def box_distance_gradients(self, st: dict, ncand: int, sample, scale=None, pose_sample=None, base_pos=None, epsilon: float = 1e-7,
+                               device_out: bool | None = None) -> dict:
+        """Signed box distance and its central-difference derivative with respect to the joint positions at one chosen configuration per
+        candidate and box pair (``fbr_box_distance_gradients``): ``{"dist": (C, P_box), "grad_q": (C, P_box, n)}``, arguments and rules as
+        for ``capsule_distance_gradients``.  ``epsilon``: the step of the difference (the reference's ``analyticalGradientEpsilon``).  Joints
+        off the tree path between a pair's links, joints above both links and fixed joints are exact zeros."""
+        return self._distance_gradients("fbr_box_distance_gradients", int(getattr(self, "num_box_pairs", 0)), (float(epsilon),), st, ncand, sample,
+                                        scale, pose_sample, base_pos, device_out)
+
+    def _distance_gradients(self, entry: str, P: int, extra: tuple, st: dict, ncand: int, sample, scale, pose_sample, base_pos, device_out) -> dict:
+        """the capsule and the box call share their arguments: ``entry`` names the library's function, ``P`` the pairs of its set, ``extra``
+        what the function takes between ``pose_sample`` and the outputs"""
         q = _Ref(st["q"], None, "q")
         if len(q.obj.shape) != 2 or q.obj.shape[1] != self.n:
             raise ValueError(f"q: expected (S, {self.n}), got {tuple(q.obj.shape)}")
@@ -716,7 +736,7 @@ class Engine:
             self._sync_torch()
         s = fbr_states()
         s.num_samples, s.mem, s.q, s.base_rpy = S, mem, q.ptr, rpy.ptr
-        C, P = int(ncand), int(getattr(self, "num_capsule_pairs", 0))
+        C = int(ncand)
         shape = (max(C, 1), P)
         smp, psmp = self._index_array(sample, shape, mem, "sample")
         pose, ppose = (None, None) if pose_sample is None else self._index_array(pose_sample, shape, mem, "pose_sample")
@@ -724,8 +744,7 @@ class Engine:
         out_mem = mem if device_out is None else (FBR_DEVICE if device_out else FBR_HOST)
         rd, dist = self._out(None, shape, out_mem)
         rg, grad = self._out(None, shape + (self.n,), out_mem)
-        _check(self._lib.fbr_capsule_distance_gradients(self._h, ctypes.byref(s), bp.ptr, C, psmp, sc.ptr, ppose, rd.ptr, rg.ptr, out_mem),
-               "fbr_capsule_distance_gradients")
+        _check(getattr(self._lib, entry)(self._h, ctypes.byref(s), bp.ptr, C, psmp, sc.ptr, ppose, *extra, rd.ptr, rg.ptr, out_mem), entry)
         return {"dist": dist, "grad_q": grad}
 
     def fourier_position_chain(self, wf, a, b, sample, grad_q, freq: float, scale=None, q_range=None, device_out: bool | None = None):

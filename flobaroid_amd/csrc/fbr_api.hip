@@ -12,7 +12,7 @@ thread_local std::string g_fbr_err;
 // round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
 // 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
 // fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain, fbr_suspended_base_motion,
-// fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances: added symbols change no signature, and _lib.py names a library
+// fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances, fbr_box_distance_gradients: added symbols change no signature, and _lib.py names a library
 // that lacks one).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
@@ -1298,6 +1298,7 @@ extern "C" int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *
     if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
     HIPCHK(hipStreamSynchronize(m->stream));
     m->boxes = DevBoxes{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    m->boxg = DevBoxGrad{0, nullptr, nullptr};
     if (nboxes == 0) return FBR_OK;
     FbrKinIdProgram prog;
     try {
@@ -1358,6 +1359,24 @@ extern "C" int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *
     db.boxbeg = (const int *)(base + ((const char *)hboxbeg - host.data()));
     db.boxid = (const int *)(base + ((const char *)hboxid - host.data()));
     db.pairs = (const int2 *)(base + ((const char *)hpairs - host.data()));
+    // tables of fbr_box_distance_gradients, in an allocation of their own: per pair the steps of the two members' links (-1: a world box)
+    // and the slots of their centres (a world box: its number) | ancestor masks
+    std::vector<int> stepof2, anc, slotof(nr, 0);
+    fbr_capgrad_ancestors(hm, prog, stepof2, anc);
+    for (int sl = 0; sl < nrob; sl++) slotof[boxid[sl]] = sl;
+    std::vector<int> gt((size_t)4 * std::max(npairs, 1) + anc.size(), 0);
+    for (int k = 0; k < npairs; k++)
+        for (int j = 0; j < 2; j++) {
+            const int c = pairs[2 * k + j];
+            gt[4 * (size_t)k + j] = link[c] < 0 ? -1 : stepof[link[c]];
+            gt[4 * (size_t)k + 2 + j] = link[c] < 0 ? -1 - code[c] : slotof[code[c]];
+        }
+    std::copy(anc.begin(), anc.end(), gt.begin() + (size_t)4 * std::max(npairs, 1));
+    if (int rc = m->boxg_tab.ensure(gt.size() * sizeof(int))) return rc;
+    HIPCHK(hipMemcpy(m->boxg_tab.p, gt.data(), gt.size() * sizeof(int), hipMemcpyHostToDevice));
+    m->boxg.W = fbr_capgrad_words(prog.nsteps);
+    m->boxg.pair = (const int4 *)m->boxg_tab.p;
+    m->boxg.anc = m->boxg_tab.as<int>() + (size_t)4 * std::max(npairs, 1);
     m->boxes = db;
     return FBR_OK;
 }
@@ -1455,22 +1474,14 @@ extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, c
     return FBR_OK;
 }
 
-// ---- capsule distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h) ---------------------------------
-extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
-                                              const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem)
+// ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, csrc/fbr_box_grad.h) --------------------
+// The capsule and the box call share everything but the set and the kernel: `name` the entry point, P / nslots the pairs and the branch
+// points of its set, launch(grid, C, T, q, rpy, bpos, sample, scale, pose, dist, grad) the kernel.
+template <class Launch>
+static int distance_gradients(fbr_model *m, const char *name, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                              const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem, long P, int nslots,
+                              Launch launch)
 {
-    if (!m || !st || !sample || !dist_out || !grad_q_out) {
-        set_err("null model / states / sample / dist_out / grad_q_out");
-        return FBR_E_INVALID;
-    }
-    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
-        set_err("bad fbr_states header or memory space, or q is NULL");
-        return FBR_E_INVALID;
-    }
-    if (m->caps.ncaps == 0 || m->caps.npairs == 0) {
-        set_err("no capsule set with at least one pair (fbr_model_set_capsules)");
-        return FBR_E_INVALID;
-    }
     if (ncand < 1) {
         set_err("ncand must be at least 1");
         return FBR_E_INVALID;
@@ -1481,8 +1492,7 @@ extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st
     }
     if (int rc = enter_blocking(m)) return rc;
     const FbrHostModel &hm = m->hm;
-    const DevCapsules &cp = m->caps;
-    const long S = st->num_samples, C = ncand, P = cp.npairs, T = S / C;
+    const long S = st->num_samples, C = ncand, T = S / C;
     const size_t items = (size_t)C * P;
     const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr, *dsmp = nullptr, *dscale = nullptr, *dpose = nullptr;
     int rc;
@@ -1503,15 +1513,14 @@ extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st
     }
     const long tiles = (C + 63) / 64;
     const int grid = (int)std::min<long>(P * tiles, (long)m->num_cus * 8);
-    if ((rc = m->cap_scratch.ensure((size_t)grid * std::max(cp.nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
+    if ((rc = m->cap_scratch.ensure((size_t)grid * std::max(nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
     if ((rc = m->capg_flag.ensure(sizeof(int)))) return rc;
     int flag = 0;
     HIPCHK(hipMemsetAsync(m->capg_flag.p, 0, sizeof(int), m->stream));
     HIPCHK(hipMemsetAsync(dgrad, 0, items * hm.n * sizeof(double), m->stream));  // (joints off a pair's path: exact zeros, never touched by the kernel)
     {
         ProfScope ps(m, FBR_PROF_KIN);
-        hipLaunchKernelGGL(fbr_capsule_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, cp, m->capg, C, T, dq, drpy, dbp, (const long *)dsmp,
-                           dscale, (const long *)dpose, ddist, dgrad, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+        launch(grid, C, T, dq, drpy, dbp, (const long *)dsmp, dscale, (const long *)dpose, ddist, dgrad);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(&flag, m->capg_flag.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
@@ -1522,10 +1531,66 @@ extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st
     HIPCHK(hipStreamSynchronize(m->stream));
     prof_collect(m);
     if (flag) {
-        set_err("fbr_capsule_distance_gradients: a sample or pose_sample index lies outside -1 .. T - 1");
+        set_err(std::string(name) + ": a sample or pose_sample index lies outside -1 .. T - 1");
         return FBR_E_INVALID;
     }
     return FBR_OK;
+}
+
+static bool distance_gradient_args(const fbr_model *m, const fbr_states *st, const int64_t *sample, const double *dist_out, const double *grad_q_out,
+                                   int32_t out_mem)
+{
+    if (!m || !st || !sample || !dist_out || !grad_q_out) {
+        set_err("null model / states / sample / dist_out / grad_q_out");
+        return false;
+    }
+    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
+        set_err("bad fbr_states header or memory space, or q is NULL");
+        return false;
+    }
+    return true;
+}
+
+extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                              const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem)
+{
+    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
+    if (m->caps.ncaps == 0 || m->caps.npairs == 0) {
+        set_err("no capsule set with at least one pair (fbr_model_set_capsules)");
+        return FBR_E_INVALID;
+    }
+    return distance_gradients(m, "fbr_capsule_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem,
+                              m->caps.npairs, m->caps.nslots,
+                              [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
+                                  const long *dpose, double *ddist, double *dgrad) {
+                                  hipLaunchKernelGGL(fbr_capsule_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->caps, m->capg, C, T, dq,
+                                                     drpy, dbp, dsmp, dscale, dpose, ddist, dgrad, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+                              });
+}
+
+extern "C" int fbr_box_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                          const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                          int32_t out_mem)
+{
+    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
+        set_err("epsilon must be finite and positive");
+        return FBR_E_INVALID;
+    }
+    if (m->boxes.nrob == 0 || m->boxes.npairs == 0) {
+        set_err("no box set with at least one pair (fbr_model_set_boxes)");
+        return FBR_E_INVALID;
+    }
+    double se, omc;
+    fbr_boxgrad_trig(epsilon, &se, &omc);
+    return distance_gradients(m, "fbr_box_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem,
+                              m->boxes.npairs, m->boxes.nslots,
+                              [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
+                                  const long *dpose, double *ddist, double *dgrad) {
+                                  hipLaunchKernelGGL(fbr_box_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->boxes, m->boxg, C, T, dq, drpy,
+                                                     dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
+                                                     m->capg_flag.as<int>());
+                              });
 }
 
 extern "C" int fbr_predict(fbr_model *m, const fbr_states *st, const double *x, double *tau_out, int32_t out_mem)

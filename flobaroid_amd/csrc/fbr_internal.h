@@ -22,6 +22,7 @@
 #include "fbr_capsule.h"
 #include "fbr_capsule_grad.h"
 #include "fbr_box.h"
+#include "fbr_box_grad.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -162,6 +163,8 @@ struct fbr_model {
     // of the blocks in flight; the partials, the branch-point poses and the host results share the capsule call's workspaces
     DevBoxes boxes = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     DevBuf box_tab, box_fr;
+    DevBoxGrad boxg = {0, nullptr, nullptr};  // fbr_box_distance_gradients: ancestor masks and per-pair steps / centre slots of the set above
+    DevBuf boxg_tab;
     // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its
     // steps on the device, the per-sample records, the results of a host-memory call
     FbrKinIdProgram susp_prog;

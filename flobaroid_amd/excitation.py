@@ -640,8 +640,25 @@ def _padded_coefficients(candidates: list, n: int):
     return A, B, nh, (np.stack([c["q_range"] for c in candidates]) if all(bounded) else None)
 
 
+def _chain_positions(engine, candidates, freq, sample, scale, grad_q, max_bytes):
+    """rows ``grad_q`` (C, P, n) at ``scale * q[sample]`` chained with the position Jacobian of the series, over chunks of whole candidates:
+    (C, P, 1 + 2 n + 2 n nh) on the host, and nh"""
+    n = engine.n
+    A, B, nh, qr = _padded_coefficients(candidates, n)
+    wf = np.array([c["wf"] for c in candidates], dtype=np.float64)
+    C, P = int(sample.shape[0]), int(sample.shape[1])
+    E = 1 + 2 * n + 2 * n * nh
+    cc = max(1, min(C, int(max_bytes) // max(P * E * 8, 1)))
+    out = np.empty((C, P, E))
+    for c0 in range(0, C, cc):
+        c1 = min(C, c0 + cc)
+        out[c0:c1] = _host(engine.fourier_position_chain(wf[c0:c1], A[c0:c1], B[c0:c1], sample[c0:c1], grad_q[c0:c1], float(freq),
+                                                         scale=scale[c0:c1], q_range=None if qr is None else qr[c0:c1]))
+    return out, nh
+
+
 def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: list, freq: float, config: dict, collision: dict,
-                                 constraints: dict | None = None, max_bytes: int = 2**31) -> dict:
+                                 constraints: dict | None = None, max_bytes: int = 2**31, box_gradient: bool = False, epsilon=None) -> dict:
     """The collision block ``g = distance - margin`` (C, P) of ``ncand`` equal candidates stacked in ``states`` and its derivative with
     respect to the entries of the candidates' ``fourier_coefficients`` dicts, from which ``states`` were generated at ``freq`` Hz
     (``candidate_states``).  ``collision``: capsules, pairs and optionally margins (``flobaroid_amd.collision.collision_set``);
@@ -654,38 +671,67 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     within ``max_bytes``; columns that only pad ``a`` / ``b`` to a common width are removed (nh = the widest candidate's).  The base pose
     of a floating base is held constant, as in the reference.
 
-    A set with box pairs (``collision_set(..., boxes=, world_boxes=)``) raises ``ValueError``: the reference differentiates those pairs by
-    central differences of its mesh library's distance, which is not built here."""
+    ``box_gradient=False``: a set with box pairs (``collision_set(..., boxes=, world_boxes=)``) raises ``ValueError``, as does any
+    ``collisionMode`` but ``"capsule"``.  ``box_gradient=True``: ``collisionMode`` ``"capsule"`` or ``"box"``; the rows of the box pairs
+    (world links, capsule-less links, every pair of box mode) are the reference's central differences of the box distance over
+    ``epsilon`` (None: ``config.get("analyticalGradientEpsilon", 1e-7)``) from ``Engine.box_distance_gradients``.  Each of the two sets of
+    ``collision["columns"]`` is installed, evaluated at its columns of the constraint block (``constraints``: then the merged block of
+    ``candidate_objectives``) and chained; ``g``, ``grad`` and ``grad_q`` come back in the reference's pair order.  A set without
+    ``columns`` goes the capsule way unchanged.  Joints off a pair's path are exact zeros where the reference has difference noise."""
     _check_config(config)
-    if config.get("collisionMode", "capsule") != "capsule":
-        raise ValueError("the collision gradient on the device covers collisionMode 'capsule' only (no mesh code: DESIGN 9)")
-    if _has_box_pairs(collision):
-        raise ValueError("the collision gradient on the device covers capsule pairs only: the set has box pairs (the reference differentiates "
-                         "those by central differences)")
+    mode = config.get("collisionMode", "capsule")
+    if not box_gradient:
+        if mode != "capsule":
+            raise ValueError("the collision gradient on the device covers collisionMode 'capsule' only (no mesh code: DESIGN 9)")
+        if _has_box_pairs(collision):
+            raise ValueError("the collision gradient on the device covers capsule pairs only: the set has box pairs (the reference differentiates "
+                             "those by central differences; box_gradient=True does the same on the device)")
+    elif mode not in ("capsule", "box"):
+        raise ValueError("the collision gradient on the device covers collisionMode 'capsule' and 'box' only (no mesh code: DESIGN 9)")
     C, n = int(ncand), engine.n
-    engine.set_capsules(collision["capsules"], collision["pairs"])
-    cons = constraints if constraints is not None else candidate_collision_constraints(engine, states, C, config, margins=collision.get("margins"))
     bpos = states.get("base_position") if engine.floating else None
-    dg = engine.capsule_distance_gradients(states, C, cons["eval_sample"], scale=cons["eval_scale"], pose_sample=cons["eval_pose"], base_pos=bpos)
-    A, B, nh, qr = _padded_coefficients(candidates, n)
-    wf = np.array([c["wf"] for c in candidates], dtype=np.float64)
-    P = int(cons["g"].shape[1])
-    E = 1 + 2 * n + 2 * n * nh
-    cc = max(1, min(C, int(max_bytes) // max(P * E * 8, 1)))
-    out = np.empty((C, P, E))
-    for c0 in range(0, C, cc):
-        c1 = min(C, c0 + cc)
-        out[c0:c1] = _host(engine.fourier_position_chain(wf[c0:c1], A[c0:c1], B[c0:c1], cons["eval_sample"][c0:c1], dg["grad_q"][c0:c1], float(freq),
-                                                         scale=cons["eval_scale"][c0:c1], q_range=None if qr is None else qr[c0:c1]))
-    return {"g": np.asarray(cons["g"]), "grad": _gradient_dict(out, n, nh), "grad_q": np.asarray(_host(dg["grad_q"]))}
+    if not box_gradient or "columns" not in collision:
+        if mode != "capsule":
+            raise ValueError("collisionMode 'box' needs a collision set with boxes (flobaroid_amd.collision.collision_set(..., boxes=))")
+        engine.set_capsules(collision["capsules"], collision["pairs"])
+        cons = constraints if constraints is not None else candidate_collision_constraints(engine, states, C, config, margins=collision.get("margins"))
+        dg = engine.capsule_distance_gradients(states, C, cons["eval_sample"], scale=cons["eval_scale"], pose_sample=cons["eval_pose"], base_pos=bpos)
+        out, nh = _chain_positions(engine, candidates, freq, cons["eval_sample"], cons["eval_scale"], dg["grad_q"], max_bytes)
+        return {"g": np.asarray(cons["g"]), "grad": _gradient_dict(out, n, nh), "grad_q": np.asarray(_host(dg["grad_q"]))}
+    cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision)
+    eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)
+    cols = np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)
+    P = cols.shape[0]
+    out, grad_q, nh = None, np.zeros((C, P, n)), 0
+    for which in (0, 1):
+        sel = np.nonzero(cols[:, 0] == which)[0]
+        if sel.size == 0:
+            continue
+        sel = sel[np.argsort(cols[sel, 1], kind="stable")]  # (the set's own pair order)
+        smp, sc, pose = (np.ascontiguousarray(np.asarray(cons[k])[:, sel]) for k in ("eval_sample", "eval_scale", "eval_pose"))
+        if which == 0:
+            engine.set_capsules(collision["capsules"], collision["pairs"])
+            dg = engine.capsule_distance_gradients(states, C, smp, scale=sc, pose_sample=pose, base_pos=bpos)
+        else:
+            engine.set_boxes(collision["boxes"], collision["box_pairs"], center_in_link_axes=bool(collision.get("center_in_link_axes", False)))
+            dg = engine.box_distance_gradients(states, C, smp, scale=sc, pose_sample=pose, base_pos=bpos, epsilon=eps)
+        part, nh = _chain_positions(engine, candidates, freq, smp, sc, dg["grad_q"], max_bytes)
+        if out is None:
+            out = np.zeros((C, P, part.shape[2]))
+        out[:, sel] = part
+        grad_q[:, sel] = _host(dg["grad_q"])
+    if out is None:
+        raise ValueError("the collision set has no pairs")
+    return {"g": np.asarray(cons["g"]), "grad": _gradient_dict(out, n, nh), "grad_q": grad_q}
 
 
 def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
-                                                   max_bytes: int = 2**31) -> dict:
+                                                   max_bytes: int = 2**31, box_gradient: bool = False) -> dict:
     """``candidate_collision_gradient`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
-    (``candidate_states``) and never leave it; only the per-pair rows come back."""
+    (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``: as there."""
     st = candidate_states(engine, candidates, int(T), float(freq), device=True)
-    return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes)
+    return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes,
+                                        box_gradient=box_gradient)
 
 
 def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
@@ -820,7 +866,8 @@ def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_a
 
 
 def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict, joint_names,
-                                          config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1) -> dict:
+                                          config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1,
+                                          box_gradient: bool = False) -> dict:
     """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
     and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
     one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
@@ -838,13 +885,14 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     ``epsilon``: the forward-difference step of both sweeps, None: ``config.get("analyticalGradientEpsilon", 1e-7)``; ``subsample``: of the
     D-optimality sweep (``analyticalGradientSubsample``).  Deviations from the reference: the wf column is analytic, the torque Jacobians
     are the clean derivative (no carried-over dq_{n-1} + eps), the Coulomb sign and the Stribeck exponent are held at their baseline;
-    a ``failed`` candidate gets the soft-cost gradient only.  Not covered: the suspended base, gravity-only models (refused), mesh
-    collision modes, and box pairs (world links, ``collisionMode: "box"``): a ``collision`` set with box pairs raises ``ValueError`` -- the
-    reference differentiates those by central differences."""
+    a ``failed`` candidate gets the soft-cost gradient only.  ``box_gradient=False``: a ``collision`` set with box pairs (world links,
+    capsule-less links, ``collisionMode: "box"``) raises ``ValueError``; ``True``: their rows are the reference's central differences of
+    the box distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base, gravity-only models
+    (refused), mesh collision modes."""
     _check_config(config)
-    if _has_box_pairs(collision):
+    if _has_box_pairs(collision) and not box_gradient:
         raise ValueError("gradients on the device cover capsule pairs only: the collision set has box pairs (the reference differentiates those "
-                         "by central differences)")
+                         "by central differences; box_gradient=True does the same on the device)")
     x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
     C, n, T = len(candidates), engine.n, int(T)
     eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)
@@ -871,7 +919,8 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     lay = constraint_layout(n, bool(config.get("minVelocityConstraint", False)), None if coll is None else int(np.asarray(coll["g"]).shape[1]))
     con_grad = _gradient_dict(con, n, nh)
     if coll is not None:
-        cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll)["grad"]
+        cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll, box_gradient=box_gradient,
+                                          epsilon=eps)["grad"]
         con_grad = {k: np.concatenate([v, cg[k]], axis=1) for k, v in con_grad.items()}
     return {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
             "layout": lay, "ag_cache": ag, "objectives": obj}

@@ -87,7 +87,8 @@ typedef struct {
  * "gram_lane" / "gram_force_tiles"; 103: fbr_candidate_extrema; 104: fbr_model_set_capsules, fbr_candidate_capsule_distances, and -- added under the same number, which
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
- * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records. */
+ * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
+ * fbr_box_distance_gradients. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -283,6 +284,28 @@ int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double
  */
 int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                    const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem);
+
+/*
+ * Signed box distance and its derivative with respect to the joint positions at ONE chosen configuration per candidate and box pair -- the
+ * box pairs of the collision block of the reference's analytical gradient (excitation/analyticalGradient.py _collision_fd_single_pair: central
+ * differences with analyticalGradientEpsilon), for the configurations fbr_candidate_box_distances found.  st, base_pos, ncand, sample, scale,
+ * pose_sample, the memory spaces and the zeroing of grad_q_out exactly as for fbr_capsule_distance_gradients; npairs is the box set's.
+ *   epsilon                        the step of the central difference (finite, positive; the reference's default 1e-7)
+ *   dist_out [ncand][npairs]       the box distance of fbr_candidate_box_distances at the configuration
+ *   grad_q_out [ncand][npairs][n]  (dist(q + epsilon e_j) - dist(q - epsilon e_j)) / (2 epsilon), the links below joint j moved rigidly: by
+ *                                  the rotation through epsilon about the joint's world axis (revolute) or the translation along it
+ *                                  (prismatic).  A robot box's centre follows center_in_link_axes (0: the offset keeps its world direction).
+ *                                  Exact zeros, never evaluated: fixed joints, joints above neither link, and joints above BOTH links
+ *                                  when they move the pair rigidly -- always with center_in_link_axes 1, prismatic joints with 0; with 0 a
+ *                                  revolute joint above both links turns the links but not the offsets and IS evaluated.  With a world
+ *                                  box every moving joint above the robot link is evaluated.  The base pose is held constant.
+ * A NaN pose gives NaN in dist_out and in the path joints' entries.  No atomics: the same bits on every run.
+ * FBR_E_INVALID: epsilon not finite or not positive, no box set or one without pairs, ncand < 1, num_samples 0 or not a multiple of ncand, a
+ * sample or pose_sample outside -1 .. T - 1 (found on the device, which reads such an entry clamped; the outputs are then undefined).
+ */
+int fbr_box_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                               const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                               int32_t out_mem);
 
 /*
  * tau_out [S][rows] = Y_s . x for an identified-parameter vector x (host, length cols) WITHOUT
