@@ -111,6 +111,13 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_int32],
     ),
+    "fbr_model_set_hulls": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip, _dp, _ip, _dp, _ip, _ip, ctypes.c_int32,
+                                           _ip]),
+    "fbr_candidate_hull_distances": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int32],
+    ),
     "fbr_box_distance_gradients": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -640,6 +647,48 @@ class Engine:
         where it is reached (``fbr_candidate_box_distances``): ``{"dist": (C, P), "idx": (C, P) int64}``, arguments and rules as for
         ``candidate_capsule_distances``.  Separated boxes: the exact Euclidean distance; overlapping: minus the minimum translation."""
         return self._candidate_distances("fbr_candidate_box_distances", int(getattr(self, "num_box_pairs", 0)), st, ncand, step, base_pos, device_out)
+
+    def set_hulls(self, hulls, pairs, offset_in_link_axes: bool = False) -> None:
+        """Convex-hull collision set of the handle (``fbr_model_set_hulls``), independent of the capsule and the box set.  ``hulls``: a
+        sequence of ``flobaroid_amd.collision.Hull`` (``link_name`` None: a world hull with ``rot``), or of tuples ``(link, offset, rot,
+        vertices, planes, edges)`` -- link an index, a name, or None / -1; the tables as ``Hull`` derives them.  ``pairs``: (P, 2) indices
+        into that sequence.  ``offset_in_link_axes``: False places a robot hull at ``p_link + offset`` (the reference's sum in world
+        axes), True at ``p_link + R_link offset``.  Replaces the set in place; an empty ``hulls`` clears it."""
+        names = list(self.topo.link_names)
+        link, off, rot, V, F, E, any_world = [], [], [], [], [], [], False
+        for h in hulls:
+            if hasattr(h, "vertices"):
+                l, o, r, v, f, e = h.link_name, h.offset, h.rot, h.vertices, h.planes, h.edges
+            else:
+                l, o, r, v, f, e = h
+            l = -1 if l is None else (names.index(l) if isinstance(l, str) else int(l))
+            if l < 0 and r is None:
+                raise ValueError("a world hull needs its rotation")
+            any_world |= l < 0
+            link.append(l)
+            off.append(np.asarray(o, dtype=np.float64).reshape(3))
+            rot.append(np.eye(3).reshape(9) if r is None else np.asarray(r, dtype=np.float64).reshape(9))
+            V.append(np.asarray(v, dtype=np.float64).reshape(-1, 3))
+            F.append(np.asarray(f, dtype=np.float64).reshape(-1, 4))
+            E.append(np.asarray(e, dtype=np.int32).reshape(-1, 4))
+        cat = lambda parts, w, t: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, w)), dtype=t)  # noqa: E731
+        beg = lambda parts: np.ascontiguousarray(np.cumsum([0] + [len(x) for x in parts]), dtype=np.int32)  # noqa: E731
+        link = np.ascontiguousarray(link, dtype=np.int32)
+        off, rot = cat([o[None] for o in off], 3, np.float64), cat([r[None] for r in rot], 9, np.float64)
+        verts, planes, edges = cat(V, 3, np.float64), cat(F, 4, np.float64), cat(E, 4, np.int32)
+        vbeg, fbeg, ebeg = beg(V), beg(F), beg(E)
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        _check(self._lib.fbr_model_set_hulls(self._h, int(link.size), link.ctypes.data_as(_ip), off.ctypes.data_as(_dp),
+                                             rot.ctypes.data_as(_dp) if any_world else None, int(bool(offset_in_link_axes)), vbeg.ctypes.data_as(_ip),
+                                             verts.ctypes.data_as(_dp), fbeg.ctypes.data_as(_ip), planes.ctypes.data_as(_dp), ebeg.ctypes.data_as(_ip),
+                                             edges.ctypes.data_as(_ip), int(pr.shape[0]), pr.ctypes.data_as(_ip)), "fbr_model_set_hulls")
+        self.num_hulls, self.num_hull_pairs = int(link.size), int(pr.shape[0])
+
+    def candidate_hull_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:
+        """Per candidate and hull pair, the smallest signed hull distance over every ``step``-th sample of the candidate and the sample
+        index where it is reached (``fbr_candidate_hull_distances``): ``{"dist": (C, P), "idx": (C, P) int64}``, arguments and rules as
+        for ``candidate_box_distances``.  Separated hulls: the Euclidean distance; touching or overlapping: minus the minimum translation."""
+        return self._candidate_distances("fbr_candidate_hull_distances", int(getattr(self, "num_hull_pairs", 0)), st, ncand, step, base_pos, device_out)
 
     def candidate_capsule_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:
         """Per candidate and capsule pair, the smallest capsule distance over every ``step``-th sample of the candidate and the sample index

@@ -1,9 +1,9 @@
-"""Host side of the collision constraints that need no mesh code (the reference's ``collisionMode: "capsule"`` and ``"box"``, robot and world
-links): capsules and boxes from the collision geometry of a URDF, the boxes of a world URDF, and the list of link pairs the trajectory
-optimiser checks.  NumPy and ElementTree only.
+"""Host side of the collision constraints (the reference's ``collisionMode: "capsule"``, ``"box"`` and ``"convex"``, robot and world links):
+capsules, boxes and convex hulls from the collision geometry of a URDF, the boxes of a world URDF, and the list of link pairs the trajectory
+optimiser checks.  NumPy and ElementTree; the hulls come from ``scipy.spatial.ConvexHull`` and a built-in STL reader (no trimesh, no FCL).
 
 * ``fit_capsules_from_urdf`` -- excitation/capsule.py ``fit_capsules_from_urdf`` for ``cylinder``, ``sphere`` and ``box`` geometry and the
-  merge of several primitives of one link.  There is no mesh code in this project: a link whose only collision geometry is a mesh gets no
+  merge of several primitives of one link.  No capsule is fitted to a mesh: a link whose only collision geometry is a mesh gets no
   capsule and is reported (callers may add capsules of their own, e.g. fitted to a bounding box they have).
 * ``boxes_from_hulls`` / ``boxes_from_urdf`` -- the box fallback of optimizer.py ``_getLinkCollisionGeometry`` from the reference's own
   ``link_cuboid_hulls``, or from the no-mesh branches of ``getBoundingBox`` / ``getLinkGeometry``.
@@ -11,18 +11,26 @@ optimiser checks.  NumPy and ElementTree only.
 * ``collision_pairs`` -- excitation/trajectoryOptimizer.py ``_buildCollisionPairs``: ``ignoreLinksForCollision``,
   ``ignoreLinkPairsForCollision``, ``ignoreCollisionBetweenGroups``, neighbours skipped, ``collisionMaxKinematicDistance``, world-world pairs
   skipped, in the reference's pair order.
-* ``collision_set`` -- all of it in the form ``Engine.set_capsules`` / ``Engine.set_boxes`` and the ``collision`` argument of
-  ``excitation.candidate_objectives`` take.
+* ``read_stl``, ``Hull``, ``hull_from_box``, ``hulls_from_urdf``, ``world_hulls_from_urdf`` -- optimizer.py ``_getLinkCollisionGeometry``
+  for ``collisionMode: "convex"``: the convex hull of the link's collision (else visual) mesh times the URDF scale, a box for links
+  without a mesh and for all world links.
+* ``collision_set`` -- all of it in the form ``Engine.set_capsules`` / ``Engine.set_boxes`` / ``Engine.set_hulls`` and the ``collision``
+  argument of ``excitation.candidate_objectives`` take.
 
 The distances themselves are computed on the device (``Engine.candidate_capsule_distances``, csrc/fbr_capsule.h;
-``Engine.candidate_box_distances``, csrc/fbr_box.h).  Not covered: the mesh modes ``convex`` and ``full``.
+``Engine.candidate_box_distances``, csrc/fbr_box.h; ``Engine.candidate_hull_distances``, csrc/fbr_hull.h).  Not covered: ``collisionMode:
+"full"`` and ``fullMeshLinks`` (triangle meshes), meshes whose hull has more than ``FBR_MAX_HULL_VERTICES`` vertices, formats other than STL.
 """
 from __future__ import annotations
 
+import os
 import xml.etree.ElementTree as ET
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
+
+FBR_MAX_HULL_VERTICES = 128  # include/fbr.h
+_COPLANAR = 1e-10            # x the hull's diameter: neighbouring triangles this flat against each other are one face
 
 
 @dataclass
@@ -45,6 +53,165 @@ class Box:
     center: np.ndarray
     rot: np.ndarray | None = None
     name: str | None = None
+
+
+@dataclass
+class Hull:
+    """A convex polytope.  ``vertices`` (V, 3) in the axes of link ``link_name``, relative to a point ``offset`` off the link origin
+    (``rot`` is None); ``link_name`` None: a world hull, ``offset`` and ``rot`` (3, 3) in the world, ``name`` the world link it came from.
+    The points given are reduced to the vertices of their convex hull (Qhull), and the tables the device needs are derived:
+    ``planes`` (F, 4), unit outward normal | offset (n . x <= o inside), one row per MERGED face -- Qhull's triangles are joined while the
+    opposite vertex of a neighbour lies within 1e-10 x the diameter of the plane --, and ``edges`` (E, 4) int32, the two end vertices and
+    the two merged faces that meet there (edges between triangles of one face are dropped).  ``bounds`` (2, 3): the axis-aligned
+    bounding box of the points, when the hull came from a mesh.  Fewer than 4 points, or a flat set, raise ValueError."""
+
+    link_name: str | None
+    vertices: np.ndarray
+    offset: np.ndarray
+    rot: np.ndarray | None = None
+    name: str | None = None
+    bounds: np.ndarray | None = None
+    planes: np.ndarray = field(init=False, repr=False)
+    edges: np.ndarray = field(init=False, repr=False)
+
+    def __post_init__(self):
+        from scipy.spatial import ConvexHull, QhullError
+
+        pts = np.asarray(self.vertices, dtype=np.float64).reshape(-1, 3)
+        self.offset = np.asarray(self.offset, dtype=np.float64).reshape(3)
+        who = self.link_name or self.name or "hull"
+        if len(pts) < 4 or not np.isfinite(pts).all():
+            raise ValueError(f"{who}: a hull needs 4 finite points at least")
+        try:
+            qh = ConvexHull(pts)
+        except (QhullError, ValueError) as e:
+            raise ValueError(f"{who}: no convex hull of these points (flat?): {str(e).splitlines()[0]}") from None
+        diam = float(np.linalg.norm(pts[qh.vertices][:, None] - pts[qh.vertices][None], axis=2).max())
+        tri, eq, nb = qh.simplices, qh.equations, qh.neighbors
+        group = list(range(len(tri)))
+
+        def find(i):
+            while group[i] != i:
+                group[i] = group[group[i]]
+                i = group[i]
+            return i
+
+        for i in range(len(tri)):
+            for k in range(3):  # (neighbour k lies opposite vertex k: its own vertex that is not shared is the one to test)
+                j = int(nb[i, k])
+                far = [x for x in tri[j] if x not in tri[i]]
+                if j > i and far and abs(eq[i, :3] @ pts[far[0]] + eq[i, 3]) <= _COPLANAR * diam and eq[i, :3] @ eq[j, :3] > 0:
+                    group[find(j)] = find(i)
+        roots = sorted({find(i) for i in range(len(tri))})
+        face_of = {r: f for f, r in enumerate(roots)}
+        area = np.linalg.norm(np.cross(pts[tri[:, 1]] - pts[tri[:, 0]], pts[tri[:, 2]] - pts[tri[:, 0]]), axis=1)
+        planes = np.zeros((len(roots), 4))
+        for r in roots:  # the plane of a merged face: that of its largest triangle
+            members = [i for i in range(len(tri)) if find(i) == r]
+            i = members[int(np.argmax(area[members]))]
+            nrm = eq[i, :3] / np.linalg.norm(eq[i, :3])
+            planes[face_of[r]] = [*nrm, -eq[i, 3] / np.linalg.norm(eq[i, :3])]
+        edges = []
+        for i in range(len(tri)):
+            for k in range(3):
+                j = int(nb[i, k])
+                if j > i and find(i) != find(j):
+                    a, b = (int(x) for x in tri[i] if x != tri[i][k])
+                    edges.append((a, b, face_of[find(i)], face_of[find(j)]))
+        used = sorted({v for e in edges for v in e[:2]})  # (a point inside a merged face is no vertex)
+        renum = {v: i for i, v in enumerate(used)}
+        self.vertices = np.ascontiguousarray(pts[used])
+        self.planes = planes
+        self.edges = np.array([(renum[a], renum[b], f, g) for a, b, f, g in edges], dtype=np.int32).reshape(-1, 4)
+        if len(used) < 4 or len(planes) < 4:
+            raise ValueError(f"{who}: the hull of these points is flat")
+
+    @property
+    def diameter(self) -> float:
+        return float(np.linalg.norm(self.vertices[:, None] - self.vertices[None], axis=2).max())
+
+
+def read_stl(path) -> np.ndarray:
+    """The triangles (ntri, 3, 3) float64 of a binary or an ASCII STL file.  Any other mesh format raises ValueError naming the file."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    if len(raw) >= 84:
+        ntri = int(np.frombuffer(raw, dtype="<u4", count=1, offset=80)[0])
+        if len(raw) == 84 + 50 * ntri:  # 80 bytes of header, the count, 50 bytes a triangle: normal, three vertices, two bytes
+            rec = np.frombuffer(raw, dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("a", "<u2")]), count=ntri, offset=84)
+            return rec["v"].astype(np.float64)
+    if raw.lstrip()[:5].lower() == b"solid":
+        try:
+            v = [[float(x) for x in ln.split()[1:4]] for ln in raw.decode("ascii", "replace").splitlines() if ln.strip().lower().startswith("vertex")]
+        except ValueError:
+            v = []
+        if v and len(v) % 3 == 0:
+            return np.array(v, dtype=np.float64).reshape(-1, 3, 3)
+    raise ValueError(f"{path}: neither a binary nor an ASCII STL file (other mesh formats are not read)")
+
+
+def hull_from_box(box: Box) -> Hull:
+    """The 8 vertices, 6 faces and 12 edges of ``box``; ``offset`` is the box centre."""
+    corners = np.array([[sx, sy, sz] for sx in (-1.0, 1.0) for sy in (-1.0, 1.0) for sz in (-1.0, 1.0)]) * np.asarray(box.half, dtype=np.float64)
+    return Hull(box.link_name, corners, box.center, None if box.rot is None else np.asarray(box.rot, dtype=np.float64), box.name)
+
+
+def _mesh_file(urdf, link, mesh_base_dir):
+    """(path or None, scale (3,)) of the link's collision mesh, else its visual mesh -- ``_getMeshPathFromTag`` without ROS: a
+    ``package://`` / ``model://`` name is cut from ``mesh_base_dir`` on and taken relative to the URDF's directory."""
+    for tag in ("collision/geometry/mesh", "visual/geometry/mesh"):
+        m = link.find(tag)
+        if m is None:
+            continue
+        path = m.attrib["filename"]
+        if path.startswith("package") or path.startswith("model"):
+            parts = path.split("/")
+            if mesh_base_dir not in parts:
+                continue
+            path = os.path.join(os.path.dirname(os.path.abspath(urdf)), *parts[parts.index(mesh_base_dir):])
+        if os.path.exists(path):
+            return path, np.array([float(v) for v in m.attrib.get("scale", "1 1 1").split()])
+    return None, None
+
+
+def hulls_from_urdf(urdf, link_names, mesh_base_dir: str = "meshes", x_std=None, cube_size=None, scale: float = 1.0,
+                    max_vertices: int = FBR_MAX_HULL_VERTICES):
+    """``(hulls, box_links)``: optimizer.py ``_getLinkCollisionGeometry`` for ``link_mode == "convex"``.  A link whose collision mesh, else
+    visual mesh, is an STL file that exists gets the convex hull of the mesh vertices times the URDF ``scale`` (signs included); its
+    ``offset`` is the position ``getBoundingBox`` returns -- ``visual/origin`` xyz, else ``collision/origin`` xyz -- and the rotation of
+    that origin is NOT applied to the vertices, as in the reference.  ``Hull.bounds`` is ``mesh.bounding_box.bounds * scale``.  Every
+    other link (no mesh, or the file is missing) is listed in ``box_links`` and gets the box of ``boxes_from_urdf`` (``x_std``,
+    ``cube_size``, ``scale`` = ``scaleCollisionHull`` as there) through ``hull_from_box``; a link without any geometry gets nothing.  A
+    hull with more than ``max_vertices`` vertices raises ValueError naming the link and its count: no simplification is attempted."""
+    tree = ET.parse(urdf)
+    wanted = list(link_names)
+    boxes, _ = boxes_from_urdf(urdf, wanted, x_std=x_std, cube_size=cube_size, scale=scale)
+    found, box_links = {}, []
+    for link in tree.findall("link"):
+        name = link.attrib["name"]
+        if name not in wanted:
+            continue
+        path, mscale = _mesh_file(urdf, link, mesh_base_dir)
+        if path is None:
+            box_links.append(name)
+            if name in boxes:
+                found[name] = hull_from_box(boxes[name])
+            continue
+        pts = read_stl(path).reshape(-1, 3) * mscale
+        origin = link.find("visual/origin")
+        if origin is None:
+            origin = link.find("collision/origin")
+        h = Hull(name, pts, _origin(origin)[0], bounds=np.array([pts.min(axis=0), pts.max(axis=0)]))
+        if len(h.vertices) > max_vertices:
+            raise ValueError(f"link {name}: the hull of {os.path.basename(path)} has {len(h.vertices)} vertices, more than {max_vertices}")
+        found[name] = h
+    return {n: found[n] for n in wanted if n in found}, box_links
+
+
+def world_hulls_from_urdf(world_urdf, placement: str = "reference", cube_size=None) -> dict:
+    """{world link: Hull}: world links are always boxes in the reference (it looks their mesh up in the ROBOT's URDF) --
+    ``world_boxes_from_urdf`` in either placement, through ``hull_from_box``."""
+    return {n: hull_from_box(b) for n, b in world_boxes_from_urdf(world_urdf, placement, cube_size).items()}
 
 
 def _origin(element):
@@ -350,7 +517,7 @@ def world_boxes_from_urdf(world_urdf, placement: str = "reference", cube_size=No
     return out
 
 
-def collision_set(topology, capsules, config: dict, margins=None, boxes=None, world_boxes=None) -> dict:
+def collision_set(topology, capsules, config: dict, margins=None, boxes=None, world_boxes=None, hulls=None, world_hulls=None) -> dict:
     """What ``Engine.set_capsules`` / ``Engine.set_boxes`` and the ``collision`` argument of ``excitation.candidate_objectives`` take.
 
     Without ``boxes`` and ``world_boxes``: ``capsules`` (a list, one per link that has one, in link order), ``pairs`` ((P, 2) indices into
@@ -363,7 +530,39 @@ def collision_set(topology, capsules, config: dict, margins=None, boxes=None, wo
     by the box routine.  ``pairs`` then holds the capsule pairs only, and there are in addition ``boxes`` (a list: robot boxes in link
     order, then the world boxes), ``box_pairs`` ((Pb, 2) into that list), ``columns`` ((P, 2): per pair of ``pair_names`` the set -- 0
     capsules, 1 boxes -- and the column of that set's result that serves it) and ``margins`` default to ``worldCollisionMargin`` on pairs
-    with a world link, 0 elsewhere.  A pair that needs a box for a link that has none is an error."""
+    with a world link, 0 elsewhere.  A pair that needs a box for a link that has none is an error.
+
+    With ``hulls`` ({robot link: Hull}, and ``world_hulls`` {world link: Hull}): ``collisionMode: "convex"``.  ``pair_names`` is the
+    reference's list with the hull links in the role the box links play in box mode, every pair is served by the hull routine
+    (``columns[:, 0] == 2``), and there are ``hulls`` (a list: robot hulls in link order, then the world hulls), ``hull_pairs`` ((P, 2)
+    into that list, sorted so that a pair's first hull changes rarely; ``columns[:, 1]`` says where a pair of ``pair_names`` went) and
+    ``offset_in_link_axes`` (False: the reference's placement).  Margins default as for boxes.  ``fullMeshLinks`` is refused."""
+    if hulls is not None:
+        mode = config.get("collisionMode", "convex")
+        if config.get("fullMeshLinks") or mode == "full":
+            raise ValueError(f"collisionMode 'full' and fullMeshLinks {list(config.get('fullMeshLinks', []))} need triangle meshes: not covered")
+        if mode != "convex":
+            raise ValueError("hulls serve collisionMode 'convex' (boxes= / world_boxes= serve 'capsule' and 'box')")
+        hulls, world_hulls = dict(hulls), dict(world_hulls or {})
+        clash = set(world_hulls) & set(topology.link_names)
+        if clash:
+            raise ValueError(f"link(s) {sorted(clash)} declared in the model and in the world")
+        pair_names = collision_pairs(topology, {}, config, world_links=list(world_hulls), boxes=hulls)
+        hnames = [n for n in topology.link_names if n in hulls] + list(world_hulls)
+        hpos = {n: i for i, n in enumerate(hnames)}
+        raw = [(hpos[a], hpos[b]) for a, b in pair_names]
+        order = sorted(range(len(raw)), key=lambda k: (raw[k][0], k))
+        columns = np.zeros((len(raw), 2), dtype=np.int64)
+        columns[:, 0] = 2
+        columns[order, 1] = np.arange(len(raw))
+        if margins is None:
+            wm = float(config.get("worldCollisionMargin", 0.0))
+            m = np.array([wm if (a in world_hulls or b in world_hulls) else 0.0 for a, b in pair_names])
+        else:
+            m = np.asarray(margins, dtype=np.float64).reshape(len(pair_names))
+        return {"capsules": [], "pairs": np.zeros((0, 2), dtype=np.int32), "pair_names": pair_names, "margins": m,
+                "hulls": [hulls[n] if n in hulls else world_hulls[n] for n in hnames],
+                "hull_pairs": np.array([raw[k] for k in order], dtype=np.int32).reshape(-1, 2), "columns": columns, "offset_in_link_axes": False}
     names = [n for n in topology.link_names if n in capsules]
     pos = {n: i for i, n in enumerate(names)}
     if boxes is None and world_boxes is None:
@@ -373,7 +572,7 @@ def collision_set(topology, capsules, config: dict, margins=None, boxes=None, wo
         return {"capsules": [capsules[n] for n in names], "pairs": pairs, "pair_names": pair_names, "margins": m}
     mode = config.get("collisionMode", "capsule")
     if mode not in ("capsule", "box"):
-        raise ValueError("collision sets cover collisionMode 'capsule' and 'box' (no mesh code)")
+        raise ValueError("collision sets cover collisionMode 'capsule' and 'box' (no mesh code); 'convex' needs hulls=")
     boxes, world_boxes = dict(boxes or {}), dict(world_boxes or {})
     clash = set(world_boxes) & set(topology.link_names)
     if clash:

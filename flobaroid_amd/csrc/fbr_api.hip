@@ -12,7 +12,7 @@ thread_local std::string g_fbr_err;
 // round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
 // 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
 // fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain, fbr_suspended_base_motion,
-// fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances, fbr_box_distance_gradients: added symbols change no signature, and _lib.py names a library
+// fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances, fbr_box_distance_gradients, fbr_model_set_hulls, fbr_candidate_hull_distances: added symbols change no signature, and _lib.py names a library
 // that lacks one).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
@@ -1381,8 +1381,13 @@ extern "C" int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *
     return FBR_OK;
 }
 
-extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
-                                           int64_t *idx_out, int32_t out_mem)
+// The box and the hull call share everything but the set and the pairs kernel: bx the frames (for the hulls: the DevBoxes view of the set),
+// P the pairs, nbatch the batches of pairs a block of samples is cut into, launch_pairs(grid, tl, b0, nb, frames, pval, pidx) the kernel;
+// missing: the message when there is no set (null: there is one).
+template <class LaunchPairs>
+static int candidate_frame_distances(fbr_model *m, const char *missing, const DevBoxes &bx, long P, long nbatch, const fbr_states *st,
+                                     const double *base_pos, int32_t ncand, int32_t step, double *dist_out, int64_t *idx_out, int32_t out_mem,
+                                     LaunchPairs launch_pairs)
 {
     if (!m || !st || !dist_out || !idx_out) {
         set_err("null model / states / dist_out / idx_out");
@@ -1392,8 +1397,8 @@ extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, c
         set_err("bad fbr_states header, or q is NULL");
         return FBR_E_INVALID;
     }
-    if (m->boxes.nrob == 0 || m->boxes.npairs == 0) {
-        set_err("no box set with at least one pair (fbr_model_set_boxes)");
+    if (missing) {
+        set_err(missing);
         return FBR_E_INVALID;
     }
     if (ncand < 1 || step < 1) {
@@ -1406,8 +1411,7 @@ extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, c
     }
     if (int rc = enter_blocking(m)) return rc;
     const FbrHostModel &hm = m->hm;
-    const DevBoxes &bx = m->boxes;
-    const long S = st->num_samples, C = ncand, P = bx.npairs;
+    const long S = st->num_samples, C = ncand;
     const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr;
     int rc;
     if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
@@ -1444,7 +1448,6 @@ extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, c
     const size_t lds = stage ? lds_want : 0;
     const int pgrid = (int)std::min<long>(ch, (long)m->num_cus * 8);
     if ((rc = m->cap_scratch.ensure((size_t)pgrid * std::max(bx.nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
-    const long nbatch = (P + FBR_BOX_BATCH - 1) / FBR_BOX_BATCH;
     if (lds) HIPCHK(hipFuncSetAttribute((const void *)fbr_box_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     for (long b0 = 0; b0 < tl.nblk; b0 += ch) {
         const long nb = std::min(ch, tl.nblk - b0);
@@ -1456,8 +1459,7 @@ extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, c
         }
         {
             ProfScope ps(m, FBR_PROF_REDUCE);
-            hipLaunchKernelGGL(fbr_box_pairs_kernel, dim3((unsigned)std::min<long>(nb * nbatch, (long)m->num_cus * 32)), dim3(64), 0, m->stream, bx, tl, b0,
-                               nb, (const double *)m->box_fr.as<double>(), pval, pidx);
+            launch_pairs((unsigned)std::min<long>(nb * nbatch, (long)m->num_cus * 32), tl, b0, nb, (const double *)m->box_fr.as<double>(), pval, pidx);
             HIPCHK(hipGetLastError());
             const long cands = (b0 + nb - 1) / tl.tiles - b0 / tl.tiles + 1;
             hipLaunchKernelGGL(fbr_capsule_finish_kernel, dim3((unsigned)((cands * P + 255) / 256)), dim3(256), 0, m->stream, tl, (int)P, b0, nb,
@@ -1472,6 +1474,121 @@ extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, c
     HIPCHK(hipStreamSynchronize(m->stream));
     prof_collect(m);
     return FBR_OK;
+}
+
+extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
+                                           int64_t *idx_out, int32_t out_mem)
+{
+    static const DevBoxes none = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const bool have = m && m->boxes.nrob != 0 && m->boxes.npairs != 0;
+    const DevBoxes &bx = m ? m->boxes : none;
+    return candidate_frame_distances(m, !m || have ? nullptr : "no box set with at least one pair (fbr_model_set_boxes)", bx, bx.npairs,
+                                     (bx.npairs + FBR_BOX_BATCH - 1) / FBR_BOX_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
+                                     [&](unsigned grid, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
+                                         hipLaunchKernelGGL(fbr_box_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, bx, tl, b0, nb, fr, pval, pidx);
+                                     });
+}
+
+// ---- convex-hull collision distances (csrc/fbr_hull.h) -------------------------------------------------------------------------------------
+extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
+                                   int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg, const double *planes,
+                                   const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs)
+{
+    if (!m) {
+        set_err("null model");
+        return FBR_E_INVALID;
+    }
+    const FbrHostModel &hm = m->hm;
+    std::vector<double> diam((size_t)std::max(std::min(nhulls, FBR_MAX_HULLS), 1), 0.0);
+    const std::string bad = fbr_hull_validate(hm.L, FBR_MAX_HULLS, FBR_MAX_HULL_PAIRS, FBR_MAX_HULL_VERTICES, nhulls, link, offset, rot, vbeg, verts, fbeg,
+                                              planes, ebeg, edges, npairs, pairs, diam.data());
+    if (!bad.empty()) {
+        set_err(bad);
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->hulls = DevHulls{{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, nullptr};
+    if (nhulls == 0) return FBR_OK;
+    FbrKinIdProgram prog;
+    try {
+        fbr_kinid_build(hm, prog);
+    } catch (const std::exception &e) {
+        set_err(e.what());
+        return FBR_E_INVALID;
+    }
+    // robot hulls sorted by the step of their link (stable), as the robot boxes are: the frames kernel walks them by slot
+    int nrob = 0, nworld = 0;
+    std::vector<int> code(nhulls), stepof(hm.L, 0), beg(prog.nsteps + 1, 0);
+    for (int h = 0; h < nhulls; h++) code[h] = link[h] < 0 ? -1 - nworld++ : nrob++;
+    for (int k = 0; k < prog.nsteps; k++) stepof[prog.steps[(size_t)k * FBR_KINID_STEP]] = k;
+    for (int h = 0; h < nhulls; h++)
+        if (link[h] >= 0) beg[stepof[link[h]] + 1]++;
+    for (int k = 0; k < prog.nsteps; k++) beg[k + 1] += beg[k];
+    std::vector<int> fill(beg.begin(), beg.end() - 1);
+    // one allocation, doubles first: cen | diam | world | verts | planes || steps | beg | slot ids | tab | edges | (padding) pairs
+    const size_t nr = (size_t)std::max(nrob, 1), nw = (size_t)std::max(nworld, 1), NV = (size_t)vbeg[nhulls], NF = (size_t)fbeg[nhulls], NE = (size_t)ebeg[nhulls];
+    const size_t nd = nr * 3 + (size_t)nhulls + nw * 12 + NV * 3 + NF * 4;
+    const size_t ni_front = prog.steps.size() + beg.size() + nr + (size_t)nhulls * 8 + NE * 4;
+    const size_t ni = ni_front + 1 + 2 * (size_t)std::max(npairs, 1);
+    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int), 0);
+    double *hcen = (double *)host.data(), *hdiam = hcen + nr * 3, *hworld = hdiam + nhulls, *hverts = hworld + nw * 12, *hplanes = hverts + NV * 3;
+    int *hsteps = (int *)(hcen + nd), *hbeg = hsteps + prog.steps.size(), *hid = hbeg + beg.size(), *htab = hid + nr, *hedges = htab + (size_t)nhulls * 8;
+    int *hpairs = hedges + NE * 4 + (ni_front & 1);  // (int2: 8-byte aligned)
+    for (int h = 0; h < nhulls; h++) {
+        hdiam[h] = diam[h];
+        int *tb = htab + (size_t)h * 8;
+        tb[0] = code[h], tb[1] = vbeg[h], tb[2] = vbeg[h + 1] - vbeg[h], tb[3] = fbeg[h], tb[4] = fbeg[h + 1] - fbeg[h], tb[5] = ebeg[h],
+        tb[6] = ebeg[h + 1] - ebeg[h];
+        if (link[h] >= 0) {
+            const int slot = fill[stepof[link[h]]]++;
+            hid[slot] = code[h];
+            for (int i = 0; i < 3; i++) hcen[(size_t)slot * 3 + i] = offset[3 * h + i];
+        } else {
+            double *w = hworld + (size_t)(-1 - code[h]) * 12;
+            for (int i = 0; i < 9; i++) w[i] = rot[9 * h + i];
+            for (int i = 0; i < 3; i++) w[9 + i] = offset[3 * h + i];
+        }
+    }
+    std::copy(verts, verts + NV * 3, hverts);
+    std::copy(planes, planes + NF * 4, hplanes);
+    std::copy(edges, edges + NE * 4, hedges);
+    std::copy(prog.steps.begin(), prog.steps.end(), hsteps);
+    std::copy(beg.begin(), beg.end(), hbeg);
+    for (size_t k = 0; k < 2 * (size_t)npairs; k++) hpairs[k] = pairs[k];
+    if (int rc = m->hull_tab.ensure(host.size() + 8)) return rc;
+    HIPCHK(hipMemcpy(m->hull_tab.p, host.data(), host.size(), hipMemcpyHostToDevice));
+    const char *base = (const char *)m->hull_tab.p;
+    auto dev = [&](const void *hp) { return base + ((const char *)hp - host.data()); };
+    DevHulls dh;
+    dh.fr = DevBoxes{prog.nsteps, prog.nslots, nrob, 0, 0, offset_in_link_axes ? 1 : 0, (const int *)dev(hsteps), (const int *)dev(hbeg),
+                     (const int *)dev(hid), (const double *)dev(hcen), nullptr, nullptr, nullptr};
+    dh.nhulls = nhulls;
+    dh.npairs = npairs;
+    dh.tab = (const int *)dev(htab);
+    dh.diam = (const double *)dev(hdiam);
+    dh.world = (const double *)dev(hworld);
+    dh.verts = (const double *)dev(hverts);
+    dh.planes = (const double *)dev(hplanes);
+    dh.edges = (const int *)dev(hedges);
+    dh.pairs = (const int2 *)dev(hpairs);
+    m->hulls = dh;
+    return FBR_OK;
+}
+
+extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
+                                            int64_t *idx_out, int32_t out_mem)
+{
+    static const DevBoxes none = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // (a set of world hulls only has no pairs: two world hulls are never paired)
+    const bool have = m && m->hulls.nhulls != 0 && m->hulls.npairs != 0;
+    const long P = m ? m->hulls.npairs : 0;
+    return candidate_frame_distances(m, !m || have ? nullptr : "no hull set with at least one pair (fbr_model_set_hulls)", m ? m->hulls.fr : none, P,
+                                     (P + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
+                                     [&](unsigned grid, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
+                                         hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, m->hulls, tl, b0, nb, fr, pval, pidx);
+                                     });
 }
 
 // ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, csrc/fbr_box_grad.h) --------------------

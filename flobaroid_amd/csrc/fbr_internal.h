@@ -23,6 +23,7 @@
 #include "fbr_capsule_grad.h"
 #include "fbr_box.h"
 #include "fbr_box_grad.h"
+#include "fbr_hull.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -165,6 +166,11 @@ struct fbr_model {
     DevBuf box_tab, box_fr;
     DevBoxGrad boxg = {0, nullptr, nullptr};  // fbr_box_distance_gradients: ancestor masks and per-pair steps / centre slots of the set above
     DevBuf boxg_tab;
+    // convex-hull collision set (fbr_model_set_hulls; csrc/fbr_hull.h), independent of the other two: its tables; the frames of the robot
+    // hulls share the box call's workspace (hulls.fr is the view of the set that fbr_box_frames_kernel takes)
+    DevHulls hulls = {{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, nullptr};
+    DevBuf hull_tab;
     // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its
     // steps on the device, the per-sample records, the results of a host-memory call
     FbrKinIdProgram susp_prog;

@@ -9,7 +9,8 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``candidate_objectives`` -- the whole ``objectiveFunc`` (f, g, soft costs) of many candidates from ``Engine.gram_grouped`` +
   ``Engine.candidate_extrema``: only per-candidate numbers reach the host;
 * ``candidate_collision_constraints`` -- its collision block from ``Engine.candidate_capsule_distances`` (``collisionMode: "capsule"``,
-  pairs of links with capsules) and ``Engine.candidate_box_distances`` (``collisionMode: "box"``, world links, capsule-less links);
+  pairs of links with capsules), ``Engine.candidate_box_distances`` (``collisionMode: "box"``, world links, capsule-less links) and
+  ``Engine.candidate_hull_distances`` (``collisionMode: "convex"``, the reference's default: convex hulls of the links' meshes);
   ``candidate_objectives(..., collision=...)`` appends it to ``g``;
 * ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
   candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``;
@@ -288,7 +289,8 @@ def objectives_from_extrema(neg_log_det, n_observable, ext: dict, limits: dict, 
             "failed": failed, "dopt_scale": dopt_scale, "ag_cache": ag}
 
 
-def candidate_collision_constraints(engine, states: dict, ncand: int, config: dict, margins=None, suspended=None, boxes: bool = False) -> dict:
+def candidate_collision_constraints(engine, states: dict, ncand: int, config: dict, margins=None, suspended=None, boxes: bool = False,
+                                    hulls: bool = False) -> dict:
     """The collision block of ``objectiveFunc`` in capsule mode for ``ncand`` equal candidates stacked in ``states``, for the capsule set of
     the engine (``Engine.set_capsules``; pairs of robot links): per candidate and pair the smallest ``distance - margin`` over
 
@@ -309,14 +311,18 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
 
     ``boxes=True``: the same block for the BOX set of the engine (``Engine.set_boxes``: the pairs the reference sends to its box
     fallback -- ``collisionMode: "box"``, world links, capsule-less links) from ``Engine.candidate_box_distances``; the main trajectory and
-    the transition configurations are walked once per set, each with its set's distance call.  Not covered: the mesh modes ``convex`` and
-    ``full``.
+    the transition configurations are walked once per set, each with its set's distance call.  ``hulls=True``: the same for the HULL set
+    (``Engine.set_hulls``: every pair of ``collisionMode: "convex"``) from ``Engine.candidate_hull_distances``.  Not covered:
+    ``collisionMode: "full"``.
 
     ``suspended``: not None says that ``states`` carry the simulated base motion of the suspended base (``rpy`` and ``base_position`` of
     ``candidate_states(..., suspended=)``); ``floatingBaseAttachment: "suspended"`` is then accepted.  The poses of the main trajectory
     and the seven base poses of the transition configurations are those of ``states``, as in the reference."""
     _check_config(config, suspended)
-    return _collision_constraints(engine, engine.candidate_box_distances if boxes else engine.candidate_capsule_distances, states, ncand, config, margins)
+    if boxes and hulls:
+        raise ValueError("boxes=True and hulls=True: one set per call")
+    distances = engine.candidate_hull_distances if hulls else (engine.candidate_box_distances if boxes else engine.candidate_capsule_distances)
+    return _collision_constraints(engine, distances, states, ncand, config, margins)
 
 
 def _collision_constraints(engine, distances, states, ncand, config, margins):
@@ -391,15 +397,28 @@ def _has_box_pairs(collision) -> bool:
     return collision is not None and len(collision.get("box_pairs", ())) > 0
 
 
+def _has_hull_pairs(collision) -> bool:
+    return collision is not None and len(collision.get("hull_pairs", ())) > 0
+
+
+_NO_HULL_GRADIENT = ("gradients on the device cover capsule and box pairs only: the collision set has hull pairs (collisionMode 'convex'; the "
+                     "reference differentiates those by central differences, which is not built for hulls)")
+
+
 def _collision_block(engine, states, ncand, config, collision, suspended=None):
     """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins``, and for sets with boxes ``boxes``, ``box_pairs``, ``columns``
-    and optionally ``center_in_link_axes`` (``flobaroid_amd.collision.collision_set``).  Both sets are installed, each is walked with its own
-    distance call, and the two (C, P_set) results are merged into the reference's pair order."""
+    and optionally ``center_in_link_axes``, for sets with hulls ``hulls``, ``hull_pairs``, ``columns`` and ``offset_in_link_axes``
+    (``flobaroid_amd.collision.collision_set``).  Every set with pairs is installed and walked with its own distance call, and the
+    (C, P_set) results are merged into the reference's pair order."""
     if collision is None:
         return None
     mode = config.get("collisionMode", "capsule")
-    if mode not in ("capsule", "box"):
-        raise ValueError("collision constraints on the device cover collisionMode 'capsule' and 'box' only (no mesh code: DESIGN 9)")
+    if mode not in ("capsule", "box", "convex"):
+        raise ValueError("collision constraints on the device cover collisionMode 'capsule', 'box' and 'convex' only (no triangle meshes: DESIGN 9)")
+    if mode == "convex" and "hulls" not in collision:
+        raise ValueError("collisionMode 'convex' needs a collision set with hulls (flobaroid_amd.collision.collision_set(..., hulls=))")
+    if mode != "convex" and _has_hull_pairs(collision):
+        raise ValueError(f"collisionMode '{mode}': the collision set was built for convex mode (it has hull pairs)")
     if "columns" not in collision:
         if mode != "capsule":
             raise ValueError("collisionMode 'box' needs a collision set with boxes (flobaroid_amd.collision.collision_set(..., boxes=))")
@@ -411,15 +430,19 @@ def _collision_block(engine, states, ncand, config, collision, suspended=None):
         raise ValueError("collisionMode 'box': the collision set was built for capsule mode (it has capsule pairs)")
     m = np.zeros(P) if collision.get("margins") is None else np.asarray(collision["margins"], dtype=np.float64).reshape(P)
     out = None
-    for which in (0, 1):
+    if mode == "convex" and (cols[:, 0] != 2).any():
+        raise ValueError("collisionMode 'convex': the collision set has capsule or box pairs")
+    for which in (0, 1, 2):
         sel = np.nonzero(cols[:, 0] == which)[0]
         if sel.size == 0:
             continue
         if which == 0:
             engine.set_capsules(collision["capsules"], collision["pairs"])
-        else:
+        elif which == 1:
             engine.set_boxes(collision["boxes"], collision["box_pairs"], center_in_link_axes=bool(collision.get("center_in_link_axes", False)))
-        part = candidate_collision_constraints(engine, states, ncand, config, margins=m[sel], suspended=suspended, boxes=bool(which))
+        else:
+            engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)))
+        part = candidate_collision_constraints(engine, states, ncand, config, margins=m[sel], suspended=suspended, boxes=which == 1, hulls=which == 2)
         if out is None:
             out = {k: np.zeros((np.asarray(v).shape[0], P), dtype=np.asarray(v).dtype) for k, v in part.items()}
         for k, v in part.items():
@@ -680,6 +703,8 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     ``columns`` goes the capsule way unchanged.  Joints off a pair's path are exact zeros where the reference has difference noise."""
     _check_config(config)
     mode = config.get("collisionMode", "capsule")
+    if _has_hull_pairs(collision) and mode in ("capsule", "box"):
+        raise ValueError(_NO_HULL_GRADIENT)
     if not box_gradient:
         if mode != "capsule":
             raise ValueError("the collision gradient on the device covers collisionMode 'capsule' only (no mesh code: DESIGN 9)")
@@ -890,6 +915,8 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     the box distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base, gravity-only models
     (refused), mesh collision modes."""
     _check_config(config)
+    if _has_hull_pairs(collision):
+        raise ValueError(_NO_HULL_GRADIENT)
     if _has_box_pairs(collision) and not box_gradient:
         raise ValueError("gradients on the device cover capsule pairs only: the collision set has box pairs (the reference differentiates those "
                          "by central differences; box_gradient=True does the same on the device)")

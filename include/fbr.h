@@ -88,7 +88,7 @@ typedef struct {
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
- * fbr_box_distance_gradients. */
+ * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -261,6 +261,44 @@ int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *link, const
  */
 int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
                                 int64_t *idx_out, int32_t out_mem);
+
+/*
+ * Convex-hull collision geometry, for fbr_candidate_hull_distances: the reference's default collisionMode "convex", in which every pair of
+ * the collision block goes to fcl.distance on the convex hull of the link's mesh (links without a mesh and all world links: a box, here a
+ * hull of 8 vertices).  Independent of the capsule and the box set.  Host arrays, copied; the tables of hull h are rows
+ * [vbeg[h], vbeg[h + 1]) of verts, [fbeg[h], fbeg[h + 1]) of planes and [ebeg[h], ebeg[h + 1]) of edges:
+ *   link [nhulls]       index of the hull's link among the UNMERGED links, or -1: a world hull, fixed in space
+ *   offset [nhulls][3]  origin of the hull's axes: an offset from the link origin (see offset_in_link_axes), or the world position (link -1)
+ *   rot [nhulls][9]     row-major rotation of a world hull; ignored for a robot hull, which has the axes of its link; may be NULL
+ *                       when there is no world hull
+ *   offset_in_link_axes 0: a robot hull sits at p_link + offset, the offset added in WORLD axes (the reference's Transform(rot, pos + offset));
+ *                       1: at p_link + R_link offset
+ *   verts [][3]         the vertices in the hull's axes (4 to FBR_MAX_HULL_VERTICES a hull: the edge-pair pass of an overlapping pair is
+ *                       E_A E_B arc tests, E <= 3 V - 6, and an uncapped mesh could keep a launch running for minutes)
+ *   planes [][4]        one row per face (coplanar triangles joined): unit outward normal | offset, n . x <= o inside
+ *   edges [][4]         the two end vertices and the two faces that meet at the edge, numbered within the hull
+ *   pairs [npairs][2]   indices into the HULL list; a pair's first hull stays in registers while it does not change
+ * A second call replaces the set; nhulls = 0 clears it.  FBR_E_INVALID: counts above the limits, an index out of range, a hull paired with
+ * itself, a pair of two world hulls, a world hull without rot, non-finite data, a normal that is not unit to 1e-9, a vertex outside one of
+ * its hull's planes by more than 1e-9 x the hull's diameter, an edge whose two faces are the same; the set in place before a refused call stays.
+ */
+#define FBR_MAX_HULLS 4096
+#define FBR_MAX_HULL_PAIRS 262144
+#define FBR_MAX_HULL_VERTICES 128   /* per hull: bounds the worst-case edge-pair loop */
+int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
+                        int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg,
+                        const double *planes, const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs);
+
+/*
+ * Per candidate and hull pair the smallest signed distance over the checked samples and the sample where it is reached: arguments, outputs
+ * and rules of fbr_candidate_box_distances (strict < from 1e10, the first sample wins a tie, a NaN never wins, 1e10 / -1 when no sample
+ * wins, no atomics: the same bits on every run).  Separated hulls: the Euclidean distance (GJK, exact to rounding); touching or
+ * overlapping: minus the minimum translation that separates them.  The reference's FCL returns a GJK/EPA value of tolerance 1e-6, build-
+ * dependent when negative: the sign agrees.
+ * FBR_E_INVALID: no hull set or one without pairs, ncand < 1, step < 1, num_samples 0 or not a multiple of ncand.
+ */
+int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step,
+                                 double *dist_out, int64_t *idx_out, int32_t out_mem);
 
 /*
  * Capsule distance and its derivative with respect to the joint positions at ONE chosen configuration per candidate and pair -- the
