@@ -6,7 +6,17 @@ flobaroid_amd/excitation.py with a stub engine, and the C-ABI.
 Measured here (g++ 11, -ffp-contract=off), in units of eps x the pair's scale |cB - cA| + diam A + diam B: random clouds of 4 .. 40 points
 1.6, scaled to touch (1e-7 apart, 1e-3 deep) 0.24, a tetrahedron against a large hull 0.53, boxes as hulls against the box restatement 2.2; the
 largest number of GJK iterations 7, a ninth of the cap (FBR_HULL_MAX_ITER 64).  The bar of every comparison is the larger of 10 x the
-deviation measured on the same inputs and 32 eps x scale ("Convex-hull collision distances")."""
+deviation measured on the same inputs and 32 eps x scale ("Convex-hull collision distances").
+
+The shapes of tests/hull_shapes.py (the vertex cap of 128, a 64-gon prism, a sphere, a cone whose apex joins 127 faces, a tetrahedron,
+1 mm and 10 m), same units: all 64 ordered pairs of the eight kinds in 12 random poses each 3.46 (the 10 m slab against the cone; 465
+separated, 303 touching or overlapping), 18 iterations at most; flat bottoms on flat tops with exactly parallel faces at five gaps,
+600 cases, 0.00064 (dyadic sizes: next to nothing is rounded), 6 iterations; edge on edge, apex on face, apex on apex, edge on face and a
+prism's side edge on a prism's cap from 1e-2 apart to 1e-3 deep 2.27 (apex on apex, touching), 6 iterations.  World coordinates of
+these cases stay within the pair's scale: the restatement rounds them, so that a 1 mm pair placed 0.3 m from the origin measured the
+restatement's 33 eps x scale, not the routine's.  Four edits of a scratch copy of csrc/fbr_hull.h were each caught by these tests: the
+facet pass without its edge pairs (zoo pairs, contact kinds), the support key (ia << 6) | ib (zoo pairs, parallel stacking), a cap of 8
+iterations (zoo pairs), GJK without its |v|^2 <= floor test (parallel stacking and contact kinds: the facet pass does not run)."""
 import ctypes
 import os
 import re
@@ -18,6 +28,7 @@ import pytest
 
 import box_restatement as br
 import hull_restatement as hr
+import hull_shapes as hs
 from common import GOLDEN, ROOT, load_topo, random_states
 from test_boxes import all_cases, random_rotations
 
@@ -180,6 +191,137 @@ def test_nan_pose_is_a_nan():
     c = np.array([[0.0, 0.0, 0.0], [0.5, np.nan, 0.0]])
     got, _, _ = emul_distance(A, B, R[:1], c[:1], R[1:], c[1:])
     assert np.isnan(got[0]) and np.isnan(hr.hull_distance(R[0], c[0], A.vertices, R[1], c[1], B.vertices))
+
+
+# ---- the vertex cap, round shapes, an apex of 127 faces, exact contacts (tests/hull_shapes.py) ---------------------------------------------------
+GAPS = (1e-2, 1e-6, -1e-6, 1e-9, -1e-9, 1e-12, -1e-12, 0.0, -1e-3)
+
+
+def _rz(a):
+    return np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+
+
+def _family(name, cases):
+    """runs (A, B, RA, cA, RB, cB, tag) through the emulation and the restatement: the file's rule 32 eps x scale, the facet pass exactly
+    when the restatement is <= 0 (or within 64 eps of it), a third of the cases on each side of 0 at least, no more than half the cap of
+    iterations; returns (worst deviation in eps x scale, most iterations, [restatement's value])"""
+    worst, iters, wants, who = 0.0, 0, [], None
+    for A, B, RA, cA, RB, cB, tag in cases:
+        dev, want, it, facet = _deviation(A, B, np.asarray(RA, dtype=np.float64), np.asarray(cA, dtype=np.float64), np.asarray(RB, dtype=np.float64),
+                                          np.asarray(cB, dtype=np.float64))
+        if dev > worst:
+            worst, who = dev, tag
+        iters = max(iters, it)
+        wants.append(want)
+        assert facet == (want <= 0) or abs(want) <= 64 * EPS, (name, tag, want, facet)
+        assert dev <= 32.0, (name, tag, dev, want)
+    wants = np.array(wants)
+    print(f"{name}: worst |emulation - restatement| = {worst:.3g} eps x scale ({who}); most GJK iterations {iters}; {(wants > 0).sum()} separated, "
+          f"{(wants <= 0).sum()} touching or overlapping of {len(wants)}")
+    assert 3 * (wants > 0).sum() >= len(wants) and 3 * (wants <= 0).sum() >= len(wants), name
+    assert 2 * iters <= MAX_ITER, name
+    return worst, iters, wants
+
+
+def _dyadic_shapes():
+    """shapes with dyadic sizes: their tops, bottoms, apexes and ridges have exact z"""
+    from flobaroid_amd.collision import Hull
+
+    z = np.zeros(3)
+    return {"prism128": Hull("a", hs.prism(64, 0.25, 0.5), z), "hexprism": Hull("a", hs.prism(6, 0.25, 0.5), z), "box": Hull("a", hs.box([0.25, 0.125, 0.5]), z),
+            "slab": Hull("a", hs.box([5.0, 5.0, 0.5]), z), "cone128": Hull("a", hs.cone(127, 0.25, 0.5), z), "cube": Hull("a", hs.box([0.25, 0.25, 0.25]), z),
+            "bar": Hull("a", hs.box([0.25, 0.125, 0.125]), z), "ridge_y": Hull("a", hs.wedge(0.25, 0.5, 0.25, "y"), z),
+            "ridge_x": Hull("a", hs.wedge(0.25, 0.5, 0.25, "x"), z)}
+
+
+def _stacked(A, B, RB, xy, gap):
+    """B in the axes RB above A (identity, at the origin): its lowest point ``gap`` above A's highest, shifted by xy"""
+    low = float((B.vertices @ np.asarray(RB).T)[:, 2].min())
+    return A, B, np.eye(3), np.zeros(3), RB, np.array([xy[0], xy[1], (float(A.vertices[:, 2].max()) - low) + gap])
+
+
+def contact_kinds():
+    """{kind: (A, B, rotation of B, shift in x and y)}: B's lowest feature straight above A's highest.  z is exact for all but the box on
+    its edge (a rotation by pi / 4): there the restatement says where the two are."""
+    s = _dyadic_shapes()
+    down, side, quarter = hs.TURNS["apex_down"], hs.TURNS["on_side"], hs.TURNS["quarter"]
+    return {"edge-edge": (s["ridge_y"], s["ridge_x"], down, (0.0625, -0.03125)), "edge-edge, turned": (s["ridge_y"], s["ridge_x"], _rz(0.3) @ down, (0.0625, -0.03125)),
+            "apex-face": (s["cube"], s["cone128"], down, (0.0625, -0.03125)), "apex-apex": (s["cone128"], s["cone128"], down, (0.0, 0.0)),
+            "edge-face": (s["cube"], s["bar"], quarter, (0.03125, 0.0625)), "prism side edge on a prism cap": (s["prism128"], s["prism128"], side, (0.03125, 0.0625))}
+
+
+def test_zoo_tables_at_the_vertex_cap():
+    from flobaroid_amd.collision import FBR_MAX_HULL_VERTICES, Hull
+
+    rng = np.random.default_rng(21)
+    for kind in hs.KINDS:
+        for link in ("l", None):
+            h = hs.zoo(rng, link, kind)
+            _check_tables(h)  # (Euler's V - E + F = 2 among its checks)
+            assert (len(h.vertices), len(h.planes), len(h.edges)) == hs.COUNTS[kind], kind
+            assert (h.rot is None) == (link is not None)
+    assert max(c[0] for c in hs.COUNTS.values()) == FBR_MAX_HULL_VERTICES == 128
+    w = Hull("w", hs.wedge(0.25, 0.5, 0.25, "x"), np.zeros(3))
+    _check_tables(w)
+    assert (len(w.vertices), len(w.planes), len(w.edges)) == (6, 5, 9)
+    for name, h in _dyadic_shapes().items():
+        _check_tables(h)
+        assert len(h.vertices) - len(h.edges) + len(h.planes) == 2, name
+    # the apex of the cone: 127 side faces and 127 edges meet in the last vertex
+    c = _dyadic_shapes()["cone128"]
+    apex = int(np.argmax(c.vertices[:, 2]))
+    assert (c.edges[:, :2] == apex).any(axis=1).sum() == 127
+
+
+def test_zoo_pairs_in_random_poses():
+    """all 64 ordered pairs of the eight kinds (4 to 128 vertices, 1 mm to 10 m), 12 seeded poses each: B's centre along a random direction u
+    at 0.55 .. 1.2 x the sum of the two support widths along u (1: the supporting planes touch)"""
+    rng = np.random.default_rng(22)
+    zoo = {k: hs.zoo(rng, "l", k) for k in hs.KINDS}
+
+    def cases():
+        for ka, A in zoo.items():
+            for kb, B in zoo.items():
+                for i in range(12):
+                    RA, RB = random_rotations(rng, 2)
+                    u = rng.standard_normal(3)
+                    u /= np.linalg.norm(u)
+                    reach = float((A.vertices @ RA.T @ u).max() - (B.vertices @ RB.T @ u).min())
+                    cA = rng.standard_normal(3) * 0.3 * A.diameter  # (the restatement rounds world coordinates: they stay within the pair's scale)
+                    yield A, B, RA, cA, RB, cA + u * reach * rng.uniform(0.55, 1.2), f"{ka} / {kb} pose {i}"
+
+    worst, iters, _ = _family("zoo pairs", cases())
+    assert iters > 7  # (beyond what the random clouds above reach)
+
+
+def test_parallel_stacking():
+    """flat bottoms on flat tops, the faces exactly parallel: B as it is and turned about z by 0.3 and pi / 4, at five gaps"""
+    s = _dyadic_shapes()
+
+    def cases():
+        for ka in ("prism128", "hexprism", "box", "slab"):
+            for kb in ("prism128", "hexprism", "box", "slab", "cone128"):
+                for a in (0.0, 0.3, np.pi / 4):
+                    for xy in ((0.0, 0.0), (0.03125, -0.0625)):
+                        for gap in (1e-3, 1e-9, 0.0, -1e-9, -1e-3):
+                            yield (*_stacked(s[ka], s[kb], _rz(a), xy, gap), f"{kb} on {ka}, turned {a:.2f}, shift {xy}, gap {gap:g}")
+
+    _, _, wants = _family("parallel stacking", cases())
+    gaps = np.tile([1e-3, 1e-9, 0.0, -1e-9, -1e-3], len(wants) // 5)
+    assert np.all(np.abs(wants - gaps) <= 1e-13)  # (the minimum translation of a shallow stack is the vertical one)
+
+
+def test_exact_contacts_by_kind():
+    """edge on edge, apex on face, apex on apex, edge on face, a prism's side edge on a prism's cap: from 1e-2 apart to 1e-3 deep"""
+    def cases():
+        for kind, (A, B, RB, xy) in contact_kinds().items():
+            for gap in GAPS:
+                yield (*_stacked(A, B, RB, xy, gap), f"{kind}, gap {gap:g}")
+
+    _, _, wants = _family("contact kinds", cases())
+    gaps = np.tile(GAPS, len(wants) // len(GAPS))
+    # apart: the gap itself; deep: no deeper than the vertical translation that separates the two
+    assert np.all(np.abs(wants - gaps)[gaps > 0] <= 1e-14) and np.all(wants[gaps <= 0] <= 64 * EPS) and np.all(wants[gaps <= 0] >= gaps[gaps <= 0] - 1e-14)
 
 
 # ---- flobaroid_amd/collision.py ----------------------------------------------------------------------------------------------------------
