@@ -123,6 +123,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_hull_distance_gradients": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -771,8 +776,17 @@ class Engine:
         return self._distance_gradients("fbr_box_distance_gradients", int(getattr(self, "num_box_pairs", 0)), (float(epsilon),), st, ncand, sample,
                                         scale, pose_sample, base_pos, device_out)
 
+    def hull_distance_gradients(self, st: dict, ncand: int, sample, scale=None, pose_sample=None, base_pos=None, epsilon: float = 1e-7,
+                                device_out: bool | None = None) -> dict:
+        """Signed hull distance and its central-difference derivative with respect to the joint positions at one chosen configuration per
+        candidate and hull pair (``fbr_hull_distance_gradients``): ``{"dist": (C, P_hull), "grad_q": (C, P_hull, n)}``, arguments and rules
+        as for ``box_distance_gradients``; a hull's offset follows ``offset_in_link_axes`` of ``set_hulls`` as a box centre follows
+        ``center_in_link_axes``."""
+        return self._distance_gradients("fbr_hull_distance_gradients", int(getattr(self, "num_hull_pairs", 0)), (float(epsilon),), st, ncand, sample,
+                                        scale, pose_sample, base_pos, device_out)
+
     def _distance_gradients(self, entry: str, P: int, extra: tuple, st: dict, ncand: int, sample, scale, pose_sample, base_pos, device_out) -> dict:
-        """the capsule and the box call share their arguments: ``entry`` names the library's function, ``P`` the pairs of its set, ``extra``
+        """the capsule, the box and the hull call share their arguments: ``entry`` names the library's function, ``P`` the pairs of its set, ``extra``
         what the function takes between ``pose_sample`` and the outputs"""
         q = _Ref(st["q"], None, "q")
         if len(q.obj.shape) != 2 or q.obj.shape[1] != self.n:

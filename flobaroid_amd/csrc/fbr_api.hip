@@ -12,7 +12,8 @@ thread_local std::string g_fbr_err;
 // round 5 under 100), option "fused_id"; 102: fbr_gram_lane_info, options "gram_lane" / "gram_force_tiles" / "tsqr_force_group"; 103: fbr_candidate_extrema;
 // 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
 // fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain, fbr_suspended_base_motion,
-// fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances, fbr_box_distance_gradients, fbr_model_set_hulls, fbr_candidate_hull_distances: added symbols change no signature, and _lib.py names a library
+// fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances, fbr_box_distance_gradients, fbr_model_set_hulls, fbr_candidate_hull_distances,
+// fbr_hull_distance_gradients: added symbols change no signature, and _lib.py names a library
 // that lacks one).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
@@ -1510,6 +1511,7 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     HIPCHK(hipStreamSynchronize(m->stream));
     m->hulls = DevHulls{{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
                         nullptr, nullptr};
+    m->hullg = DevHullGrad{0, nullptr, nullptr};
     if (nhulls == 0) return FBR_OK;
     FbrKinIdProgram prog;
     try {
@@ -1573,6 +1575,24 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     dh.planes = (const double *)dev(hplanes);
     dh.edges = (const int *)dev(hedges);
     dh.pairs = (const int2 *)dev(hpairs);
+    // tables of fbr_hull_distance_gradients, in an allocation of their own: per pair the steps of the two members' links (-1: a world hull)
+    // and the slots of their offsets (a world hull: its number) | ancestor masks
+    std::vector<int> stepof2, anc, slotof(nr, 0);
+    fbr_capgrad_ancestors(hm, prog, stepof2, anc);
+    for (int sl = 0; sl < nrob; sl++) slotof[hid[sl]] = sl;
+    std::vector<int> gt((size_t)4 * std::max(npairs, 1) + anc.size(), 0);
+    for (int k = 0; k < npairs; k++)
+        for (int j = 0; j < 2; j++) {
+            const int h = pairs[2 * k + j];
+            gt[4 * (size_t)k + j] = link[h] < 0 ? -1 : stepof[link[h]];
+            gt[4 * (size_t)k + 2 + j] = link[h] < 0 ? -1 - code[h] : slotof[code[h]];
+        }
+    std::copy(anc.begin(), anc.end(), gt.begin() + (size_t)4 * std::max(npairs, 1));
+    if (int rc = m->hullg_tab.ensure(gt.size() * sizeof(int))) return rc;
+    HIPCHK(hipMemcpy(m->hullg_tab.p, gt.data(), gt.size() * sizeof(int), hipMemcpyHostToDevice));
+    m->hullg.W = fbr_capgrad_words(prog.nsteps);
+    m->hullg.pair = (const int4 *)m->hullg_tab.p;
+    m->hullg.anc = m->hullg_tab.as<int>() + (size_t)4 * std::max(npairs, 1);
     m->hulls = dh;
     return FBR_OK;
 }
@@ -1591,8 +1611,8 @@ extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, 
                                      });
 }
 
-// ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, csrc/fbr_box_grad.h) --------------------
-// The capsule and the box call share everything but the set and the kernel: `name` the entry point, P / nslots the pairs and the branch
+// ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, fbr_box_grad.h, fbr_hull_grad.h) -------
+// The capsule, the box and the hull call share everything but the set and the kernel: `name` the entry point, P / nslots the pairs and the branch
 // points of its set, launch(grid, C, T, q, rpy, bpos, sample, scale, pose, dist, grad) the kernel.
 template <class Launch>
 static int distance_gradients(fbr_model *m, const char *name, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
@@ -1706,6 +1726,31 @@ extern "C" int fbr_box_distance_gradients(fbr_model *m, const fbr_states *st, co
                                   const long *dpose, double *ddist, double *dgrad) {
                                   hipLaunchKernelGGL(fbr_box_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->boxes, m->boxg, C, T, dq, drpy,
                                                      dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
+                                                     m->capg_flag.as<int>());
+                              });
+}
+
+extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                           const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                           int32_t out_mem)
+{
+    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
+        set_err("epsilon must be finite and positive");
+        return FBR_E_INVALID;
+    }
+    if (m->hulls.nhulls == 0 || m->hulls.npairs == 0) {
+        set_err("no hull set with at least one pair (fbr_model_set_hulls)");
+        return FBR_E_INVALID;
+    }
+    double se, omc;
+    fbr_boxgrad_trig(epsilon, &se, &omc);
+    return distance_gradients(m, "fbr_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem,
+                              m->hulls.npairs, m->hulls.fr.nslots,
+                              [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
+                                  const long *dpose, double *ddist, double *dgrad) {
+                                  hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->hulls, m->hullg, C, T, dq,
+                                                     drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
                                                      m->capg_flag.as<int>());
                               });
 }

@@ -22,7 +22,8 @@
 // on each and stores the quotient at once.  fbr_box_distance has ONE call site, inside a rolled loop over (centre, +, -): the unmoved
 // distance is the first evaluation of the second walk, at its first step ("box distance gradients").
 //
-// The arithmetic (fbr_boxgrad_move, fbr_boxgrad_item) is HIP-free: tests/emul/box_grad_emul.cpp compiles the same text with g++.
+// The arithmetic (fbr_boxgrad_move, fbr_rigidgrad_item, fbr_boxgrad_item) is HIP-free: tests/emul/box_grad_emul.cpp compiles the same text
+// with g++.  fbr_rigidgrad_item takes the distance routine as a functor: the hulls (fbr_hull_grad.h) instantiate it a second time.
 #pragma once
 #include "fbr_box.h"
 #include "fbr_capsule_grad.h"
@@ -71,14 +72,16 @@ FBR_HD void fbr_boxgrad_turn(double sn, double omc, const double *z, const doubl
     for (int i = 0; i < 3; i++) c[i] += p[i];
 }
 
-// One (pair, configuration).  Member A sits on the link of step ka (ka < 0: a world box), B on that of kb; at most one is a world box.
-// A robot member's `xa` holds its centre offset (3), a world member's R | centre (12); ha, hb: the half extents.  Returns the signed box
-// distance and, through grad(d, v), the central difference over +- eps of every evaluated joint d.  A NaN pose gives NaN in the distance
-// and in the evaluated joints' entries.  mask(k) must leave the bit of a world member clear.
-template <class MaskFn, class QFn, class BaseFn, class SlotSave, class SlotLoad, class ConstFn, class GradFn>
-FBR_HD double fbr_boxgrad_item(int ka, int kb, int cmode, const double *xa, const double *ha, const double *xb, const double *hb, double eps, double se,
-                               double omc, const int *steps, int floating, MaskFn mask, QFn qf, BaseFn basef, SlotSave save, SlotLoad load,
-                               ConstFn consts, GradFn grad)
+// One (pair, configuration) of two rigid bodies placed as boxes are: R_link | p_link + offset (fbr_box_centre).  Member A sits on the link of
+// step ka (ka < 0: a world member), B on that of kb; at most one is a world member.  A robot member's `xa` holds its centre offset (3), a
+// world member's R | centre (12).  distf(X, Y): the signed distance of the two bodies at the frames X, Y [12] (R | centre) -- the boxes'
+// fbr_box_distance, the hulls' fbr_hull_distance (fbr_hull_grad.h); it has ONE call site.  Returns the distance and, through grad(d, v), the
+// central difference over +- eps of every evaluated joint d.  A NaN pose gives NaN in the distance and in the evaluated joints' entries.
+// mask(k) must leave the bit of a world member clear.
+template <class MaskFn, class QFn, class BaseFn, class SlotSave, class SlotLoad, class ConstFn, class GradFn, class DistFn>
+FBR_HD double fbr_rigidgrad_item(int ka, int kb, int cmode, const double *xa, const double *xb, double eps, double se, double omc, const int *steps,
+                                 int floating, MaskFn mask, QFn qf, BaseFn basef, SlotSave save, SlotLoad load, ConstFn consts, GradFn grad,
+                                 DistFn distf)
 {
     const int kend = (ka > kb ? ka : kb) + 1;
     double A[12], pA[3] = {0, 0, 0}, B[12], pB[3] = {0, 0, 0};  // the boxes R | centre (a robot box has its link's R) and the link origins
@@ -130,7 +133,7 @@ FBR_HD double fbr_boxgrad_item(int ka, int kb, int cmode, const double *xa, cons
                                      fbr_boxgrad_turn(-sg * se, omc, z, pB, xb, Y + 9);
                                  }
                              }
-                             const double v = fbr_box_distance(X, X + 9, ha, Y, Y + 9, hb);
+                             const double v = distf(X, Y);
                              if (e == 0)
                                  dist = v;
                              else if (e == 1)
@@ -140,6 +143,16 @@ FBR_HD double fbr_boxgrad_item(int ka, int kb, int cmode, const double *xa, cons
                          }
                      });
     return dist;
+}
+
+// the box pair: ha, hb the half extents of the two members
+template <class MaskFn, class QFn, class BaseFn, class SlotSave, class SlotLoad, class ConstFn, class GradFn>
+FBR_HD double fbr_boxgrad_item(int ka, int kb, int cmode, const double *xa, const double *ha, const double *xb, const double *hb, double eps, double se,
+                               double omc, const int *steps, int floating, MaskFn mask, QFn qf, BaseFn basef, SlotSave save, SlotLoad load,
+                               ConstFn consts, GradFn grad)
+{
+    return fbr_rigidgrad_item(ka, kb, cmode, xa, xb, eps, se, omc, steps, floating, mask, qf, basef, save, load, consts, grad,
+                              [&](const double *X, const double *Y) { return fbr_box_distance(X, X + 9, ha, Y, Y + 9, hb); });
 }
 
 #if defined(__HIPCC__)

@@ -24,6 +24,7 @@
 #include "fbr_box.h"
 #include "fbr_box_grad.h"
 #include "fbr_hull.h"
+#include "fbr_hull_grad.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -171,6 +172,8 @@ struct fbr_model {
     DevHulls hulls = {{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
                       nullptr, nullptr};
     DevBuf hull_tab;
+    DevHullGrad hullg = {0, nullptr, nullptr};  // fbr_hull_distance_gradients: ancestor masks and per-pair steps / offset slots of the set above
+    DevBuf hullg_tab;
     // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its
     // steps on the device, the per-sample records, the results of a host-memory call
     FbrKinIdProgram susp_prog;

@@ -405,6 +405,19 @@ _NO_HULL_GRADIENT = ("gradients on the device cover capsule and box pairs only: 
                      "reference differentiates those by central differences, which is not built for hulls)")
 
 
+def _wants_hull_gradient(config, collision, hull_gradient) -> bool:
+    """True when ``hull_gradient=True`` selects the hull rows: ``collisionMode: "convex"`` and a set of hull pairs only.  Every other
+    combination goes on to the refusals that hold without the keyword."""
+    if not hull_gradient or config.get("collisionMode", "capsule") != "convex":
+        return False
+    if collision is None or "hulls" not in collision or not _has_hull_pairs(collision) or "columns" not in collision:
+        raise ValueError("hull_gradient=True: collisionMode 'convex' needs a collision set with hull pairs "
+                         "(flobaroid_amd.collision.collision_set(..., hulls=))")
+    if (np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)[:, 0] != 2).any():
+        raise ValueError("hull_gradient=True: the collision set of collisionMode 'convex' has capsule or box pairs")
+    return True
+
+
 def _collision_block(engine, states, ncand, config, collision, suspended=None):
     """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins``, and for sets with boxes ``boxes``, ``box_pairs``, ``columns``
     and optionally ``center_in_link_axes``, for sets with hulls ``hulls``, ``hull_pairs``, ``columns`` and ``offset_in_link_axes``
@@ -681,7 +694,8 @@ def _chain_positions(engine, candidates, freq, sample, scale, grad_q, max_bytes)
 
 
 def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: list, freq: float, config: dict, collision: dict,
-                                 constraints: dict | None = None, max_bytes: int = 2**31, box_gradient: bool = False, epsilon=None) -> dict:
+                                 constraints: dict | None = None, max_bytes: int = 2**31, box_gradient: bool = False, epsilon=None,
+                                 hull_gradient: bool = False) -> dict:
     """The collision block ``g = distance - margin`` (C, P) of ``ncand`` equal candidates stacked in ``states`` and its derivative with
     respect to the entries of the candidates' ``fourier_coefficients`` dicts, from which ``states`` were generated at ``freq`` Hz
     (``candidate_states``).  ``collision``: capsules, pairs and optionally margins (``flobaroid_amd.collision.collision_set``);
@@ -700,9 +714,30 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     ``epsilon`` (None: ``config.get("analyticalGradientEpsilon", 1e-7)``) from ``Engine.box_distance_gradients``.  Each of the two sets of
     ``collision["columns"]`` is installed, evaluated at its columns of the constraint block (``constraints``: then the merged block of
     ``candidate_objectives``) and chained; ``g``, ``grad`` and ``grad_q`` come back in the reference's pair order.  A set without
-    ``columns`` goes the capsule way unchanged.  Joints off a pair's path are exact zeros where the reference has difference noise."""
+    ``columns`` goes the capsule way unchanged.  Joints off a pair's path are exact zeros where the reference has difference noise.
+
+    ``hull_gradient=False``: ``collisionMode: "convex"`` and every set with hull pairs raise ``ValueError``.  ``hull_gradient=True`` with
+    ``collisionMode: "convex"`` (the reference's default): the set must have hull pairs and only those; the hull set is installed and the
+    rows are the reference's central differences of the hull distance over ``epsilon`` (as above) from ``Engine.hull_distance_gradients``
+    at the evaluation points of the constraint block, transitions included, in the reference's pair order.  In the modes ``"capsule"`` and
+    ``"box"`` the keyword changes nothing: a set with hull pairs stays refused there."""
     _check_config(config)
     mode = config.get("collisionMode", "capsule")
+    if _wants_hull_gradient(config, collision, hull_gradient):
+        C, n = int(ncand), engine.n
+        bpos = states.get("base_position") if engine.floating else None
+        cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision)
+        eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)
+        cols = np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)
+        sel = np.argsort(cols[:, 1], kind="stable")  # (the set's own pair order)
+        smp, sc, pose = (np.ascontiguousarray(np.asarray(cons[k])[:, sel]) for k in ("eval_sample", "eval_scale", "eval_pose"))
+        engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)))
+        dg = engine.hull_distance_gradients(states, C, smp, scale=sc, pose_sample=pose, base_pos=bpos, epsilon=eps)
+        part, nh = _chain_positions(engine, candidates, freq, smp, sc, dg["grad_q"], max_bytes)
+        out, grad_q = np.zeros((C, cols.shape[0], part.shape[2])), np.zeros((C, cols.shape[0], n))
+        out[:, sel] = part
+        grad_q[:, sel] = _host(dg["grad_q"])
+        return {"g": np.asarray(cons["g"]), "grad": _gradient_dict(out, n, nh), "grad_q": grad_q}
     if _has_hull_pairs(collision) and mode in ("capsule", "box"):
         raise ValueError(_NO_HULL_GRADIENT)
     if not box_gradient:
@@ -751,12 +786,12 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
 
 
 def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
-                                                   max_bytes: int = 2**31, box_gradient: bool = False) -> dict:
+                                                   max_bytes: int = 2**31, box_gradient: bool = False, hull_gradient: bool = False) -> dict:
     """``candidate_collision_gradient`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
-    (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``: as there."""
+    (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``, ``hull_gradient``: as there."""
     st = candidate_states(engine, candidates, int(T), float(freq), device=True)
     return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes,
-                                        box_gradient=box_gradient)
+                                        box_gradient=box_gradient, hull_gradient=hull_gradient)
 
 
 def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
@@ -892,7 +927,7 @@ def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_a
 
 def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict, joint_names,
                                           config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1,
-                                          box_gradient: bool = False) -> dict:
+                                          box_gradient: bool = False, hull_gradient: bool = False) -> dict:
     """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
     and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
     one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
@@ -912,10 +947,13 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     are the clean derivative (no carried-over dq_{n-1} + eps), the Coulomb sign and the Stribeck exponent are held at their baseline;
     a ``failed`` candidate gets the soft-cost gradient only.  ``box_gradient=False``: a ``collision`` set with box pairs (world links,
     capsule-less links, ``collisionMode: "box"``) raises ``ValueError``; ``True``: their rows are the reference's central differences of
-    the box distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base, gravity-only models
-    (refused), mesh collision modes."""
+    the box distance over the same ``epsilon`` (``candidate_collision_gradient``).  ``hull_gradient=False``: a ``collision`` set with hull
+    pairs raises ``ValueError``; ``True`` with ``collisionMode: "convex"``: the rows of the hull pairs are the reference's central
+    differences of the hull distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base,
+    gravity-only models (refused), ``collisionMode: "full"``."""
     _check_config(config)
-    if _has_hull_pairs(collision):
+    hull_rows = collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
+    if _has_hull_pairs(collision) and not hull_rows:
         raise ValueError(_NO_HULL_GRADIENT)
     if _has_box_pairs(collision) and not box_gradient:
         raise ValueError("gradients on the device cover capsule pairs only: the collision set has box pairs (the reference differentiates those "
@@ -947,7 +985,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     con_grad = _gradient_dict(con, n, nh)
     if coll is not None:
         cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll, box_gradient=box_gradient,
-                                          epsilon=eps)["grad"]
+                                          epsilon=eps, hull_gradient=hull_rows)["grad"]
         con_grad = {k: np.concatenate([v, cg[k]], axis=1) for k, v in con_grad.items()}
     return {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
             "layout": lay, "ag_cache": ag, "objectives": obj}

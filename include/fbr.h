@@ -88,7 +88,7 @@ typedef struct {
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
- * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances. */
+ * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -344,6 +344,23 @@ int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st, const dou
 int fbr_box_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
                                int32_t out_mem);
+
+/*
+ * Signed convex-hull distance and its derivative with respect to the joint positions at ONE chosen configuration per candidate and hull
+ * pair -- the collision block of the reference's analytical gradient in its default collisionMode "convex" (central differences with
+ * analyticalGradientEpsilon), for the configurations fbr_candidate_hull_distances found.  Arguments, memory spaces, the zeroing of grad_q_out
+ * and every rule exactly as for fbr_box_distance_gradients; npairs is the hull set's.
+ *   dist_out [ncand][npairs]       the hull distance of fbr_candidate_hull_distances at the configuration
+ *   grad_q_out [ncand][npairs][n]  (dist(q + epsilon e_j) - dist(q - epsilon e_j)) / (2 epsilon), the links below joint j moved rigidly as for
+ *                                  the boxes; a robot hull's offset follows offset_in_link_axes as a box centre follows
+ *                                  center_in_link_axes, and the same entries are exact zeros, never evaluated.  A world hull never moves.
+ * A NaN pose gives NaN in dist_out and in the evaluated joints' entries.  No atomics: the same bits on every run.
+ * FBR_E_INVALID: epsilon not finite or not positive, no hull set or one without pairs, ncand < 1, num_samples 0 or not a multiple of ncand, a
+ * sample or pose_sample outside -1 .. T - 1 (found on the device, which reads such an entry clamped; the outputs are then undefined).
+ */
+int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                int32_t out_mem);
 
 /*
  * tau_out [S][rows] = Y_s . x for an identified-parameter vector x (host, length cols) WITHOUT
