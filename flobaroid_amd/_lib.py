@@ -113,6 +113,7 @@ _SIGNATURES = {
     ),
     "fbr_model_set_hulls": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip, _dp, _ip, _dp, _ip, _ip, ctypes.c_int32,
                                            _ip]),
+    "fbr_model_set_hull_meshes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _ip, _dp]),
     "fbr_candidate_hull_distances": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
@@ -653,12 +654,13 @@ class Engine:
         ``candidate_capsule_distances``.  Separated boxes: the exact Euclidean distance; overlapping: minus the minimum translation."""
         return self._candidate_distances("fbr_candidate_box_distances", int(getattr(self, "num_box_pairs", 0)), st, ncand, step, base_pos, device_out)
 
-    def set_hulls(self, hulls, pairs, offset_in_link_axes: bool = False) -> None:
+    def set_hulls(self, hulls, pairs, offset_in_link_axes: bool = False, meshes=None) -> None:
         """Convex-hull collision set of the handle (``fbr_model_set_hulls``), independent of the capsule and the box set.  ``hulls``: a
         sequence of ``flobaroid_amd.collision.Hull`` (``link_name`` None: a world hull with ``rot``), or of tuples ``(link, offset, rot,
         vertices, planes, edges)`` -- link an index, a name, or None / -1; the tables as ``Hull`` derives them.  ``pairs``: (P, 2) indices
         into that sequence.  ``offset_in_link_axes``: False places a robot hull at ``p_link + offset`` (the reference's sum in world
-        axes), True at ``p_link + R_link offset``.  Replaces the set in place; an empty ``hulls`` clears it."""
+        axes), True at ``p_link + R_link offset``.  Replaces the set in place; an empty ``hulls`` clears it.  ``meshes``: what
+        ``set_hull_meshes`` takes, attached to the new set (None: the new set has no meshes, whatever the one before had)."""
         names = list(self.topo.link_names)
         link, off, rot, V, F, E, any_world = [], [], [], [], [], [], False
         for h in hulls:
@@ -687,12 +689,30 @@ class Engine:
                                              rot.ctypes.data_as(_dp) if any_world else None, int(bool(offset_in_link_axes)), vbeg.ctypes.data_as(_ip),
                                              verts.ctypes.data_as(_dp), fbeg.ctypes.data_as(_ip), planes.ctypes.data_as(_dp), ebeg.ctypes.data_as(_ip),
                                              edges.ctypes.data_as(_ip), int(pr.shape[0]), pr.ctypes.data_as(_ip)), "fbr_model_set_hulls")
-        self.num_hulls, self.num_hull_pairs = int(link.size), int(pr.shape[0])
+        self.num_hulls, self.num_hull_pairs, self.num_hull_meshes = int(link.size), int(pr.shape[0]), 0
+        if meshes:
+            self.set_hull_meshes(meshes)
+
+    def set_hull_meshes(self, meshes) -> None:
+        """Triangle meshes on hulls of the set ``set_hulls`` put in place (``fbr_model_set_hull_meshes``; the reference's ``fullMeshLinks``
+        and ``collisionMode: "full"``).  ``meshes``: ``{hull index: triangles (T, 3, 3)}`` in the hull's axes (``collision_set(...,
+        meshes=)["meshes"]``), or a sequence of such pairs.  ``candidate_hull_distances`` then serves every pair with a meshed hull by the
+        mesh routine: the minimum over the triangles, exactly 0.0 where they touch or intersect, never negative.  An empty ``meshes``
+        clears the attachments, and so does every later ``set_hulls``; ``hull_distance_gradients`` refuses a set with meshes."""
+        items = list(meshes.items()) if hasattr(meshes, "items") else list(meshes or [])
+        tri = [np.asarray(t, dtype=np.float64).reshape(-1, 9) for _, t in items]
+        hull = np.ascontiguousarray([int(h) for h, _ in items], dtype=np.int32)
+        tbeg = np.ascontiguousarray(np.cumsum([0] + [len(t) for t in tri]), dtype=np.int32)
+        tris = np.ascontiguousarray(np.concatenate(tri) if tri else np.zeros((0, 9)))
+        _check(self._lib.fbr_model_set_hull_meshes(self._h, len(items), hull.ctypes.data_as(_ip), tbeg.ctypes.data_as(_ip), tris.ctypes.data_as(_dp)),
+               "fbr_model_set_hull_meshes")
+        self.num_hull_meshes = len(items)
 
     def candidate_hull_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:
         """Per candidate and hull pair, the smallest signed hull distance over every ``step``-th sample of the candidate and the sample
         index where it is reached (``fbr_candidate_hull_distances``): ``{"dist": (C, P), "idx": (C, P) int64}``, arguments and rules as
-        for ``candidate_box_distances``.  Separated hulls: the Euclidean distance; touching or overlapping: minus the minimum translation."""
+        for ``candidate_box_distances``.  Separated hulls: the Euclidean distance; touching or overlapping: minus the minimum translation.
+        Pairs with a meshed hull (``set_hull_meshes``): the mesh distance, 0.0 where they touch or intersect."""
         return self._candidate_distances("fbr_candidate_hull_distances", int(getattr(self, "num_hull_pairs", 0)), st, ncand, step, base_pos, device_out)
 
     def candidate_capsule_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:

@@ -1,6 +1,6 @@
-"""Host side of the collision constraints (the reference's ``collisionMode: "capsule"``, ``"box"`` and ``"convex"``, robot and world links):
-capsules, boxes and convex hulls from the collision geometry of a URDF, the boxes of a world URDF, and the list of link pairs the trajectory
-optimiser checks.  NumPy and ElementTree; the hulls come from ``scipy.spatial.ConvexHull`` and a built-in STL reader (no trimesh, no FCL).
+"""Host side of the collision constraints (the reference's ``collisionMode: "capsule"``, ``"box"``, ``"convex"`` and ``"full"``, and its
+``fullMeshLinks``; robot and world links): capsules, boxes, convex hulls and triangle meshes from the collision geometry of a URDF, the boxes
+of a world URDF, and the list of link pairs the trajectory optimiser checks.  NumPy and ElementTree; the hulls come from ``scipy.spatial.ConvexHull`` and a built-in STL reader (no trimesh, no FCL).
 
 * ``fit_capsules_from_urdf`` -- excitation/capsule.py ``fit_capsules_from_urdf`` for ``cylinder``, ``sphere`` and ``box`` geometry and the
   merge of several primitives of one link.  No capsule is fitted to a mesh: a link whose only collision geometry is a mesh gets no
@@ -14,12 +14,17 @@ optimiser checks.  NumPy and ElementTree; the hulls come from ``scipy.spatial.Co
 * ``read_stl``, ``Hull``, ``hull_from_box``, ``hulls_from_urdf``, ``world_hulls_from_urdf`` -- optimizer.py ``_getLinkCollisionGeometry``
   for ``collisionMode: "convex"``: the convex hull of the link's collision (else visual) mesh times the URDF scale, a box for links
   without a mesh and for all world links.
+* ``Mesh``, ``meshes_from_urdf`` -- ``_getLinkCollisionGeometry`` for ``link_mode == "full"``: the triangles of the same mesh, for the links of
+  ``fullMeshLinks`` (concave shapes such as the cage around WALK-MAN's torso, whose hull is more than 80 % empty space) or, in
+  ``collisionMode: "full"``, for every link that has a mesh.  A mesh distance is the minimum over the triangles, exactly 0.0 where the two
+  touch or intersect and never negative; a geometry wholly inside a closed mesh has a positive distance, as with FCL's BVH.
 * ``collision_set`` -- all of it in the form ``Engine.set_capsules`` / ``Engine.set_boxes`` / ``Engine.set_hulls`` and the ``collision``
   argument of ``excitation.candidate_objectives`` take.
 
 The distances themselves are computed on the device (``Engine.candidate_capsule_distances``, csrc/fbr_capsule.h;
-``Engine.candidate_box_distances``, csrc/fbr_box.h; ``Engine.candidate_hull_distances``, csrc/fbr_hull.h).  Not covered: ``collisionMode:
-"full"`` and ``fullMeshLinks`` (triangle meshes), meshes whose hull has more than ``FBR_MAX_HULL_VERTICES`` vertices, formats other than STL.
+``Engine.candidate_box_distances``, csrc/fbr_box.h; ``Engine.candidate_hull_distances``, csrc/fbr_hull.h and, for pairs with a mesh, csrc/fbr_mesh.h).  Not covered: gradients of mesh pairs;
+meshes whose hull has more than ``FBR_MAX_HULL_VERTICES`` vertices or that have more than ``FBR_MAX_MESH_TRIANGLES`` triangles (no
+simplification, no BVH); formats other than STL; parity with FCL's own numbers.
 """
 from __future__ import annotations
 
@@ -30,6 +35,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 FBR_MAX_HULL_VERTICES = 128  # include/fbr.h
+FBR_MAX_MESH_TRIANGLES = 256  # include/fbr.h
+FBR_MAX_MESH_PAIR_WORK = 32768  # include/fbr.h: triangles x triangles of one pair
 _COPLANAR = 1e-10            # x the hull's diameter: neighbouring triangles this flat against each other are one face
 
 
@@ -131,6 +138,25 @@ class Hull:
         return float(np.linalg.norm(self.vertices[:, None] - self.vertices[None], axis=2).max())
 
 
+@dataclass
+class Mesh:
+    """A triangle mesh of link ``link_name``: ``triangles`` (T, 3, 3) in the axes of the link, relative to ``offset`` -- the axes and the
+    origin of ``hull``, the ``Hull`` of the mesh's vertices, which stays in the hull set (it bounds the mesh).  Zero-area triangles are kept."""
+
+    link_name: str
+    triangles: np.ndarray
+    offset: np.ndarray
+    hull: Hull = field(init=False, repr=False)
+
+    def __post_init__(self):
+        self.triangles = np.ascontiguousarray(np.asarray(self.triangles, dtype=np.float64).reshape(-1, 3, 3))
+        self.offset = np.asarray(self.offset, dtype=np.float64).reshape(3)
+        if len(self.triangles) == 0 or not np.isfinite(self.triangles).all():
+            raise ValueError(f"{self.link_name}: a mesh needs one finite triangle at least")
+        pts = self.triangles.reshape(-1, 3)
+        self.hull = Hull(self.link_name, pts, self.offset, bounds=np.array([pts.min(axis=0), pts.max(axis=0)]))
+
+
 def read_stl(path) -> np.ndarray:
     """The triangles (ntri, 3, 3) float64 of a binary or an ASCII STL file.  Any other mesh format raises ValueError naming the file."""
     with open(path, "rb") as fh:
@@ -206,6 +232,36 @@ def hulls_from_urdf(urdf, link_names, mesh_base_dir: str = "meshes", x_std=None,
             raise ValueError(f"link {name}: the hull of {os.path.basename(path)} has {len(h.vertices)} vertices, more than {max_vertices}")
         found[name] = h
     return {n: found[n] for n in wanted if n in found}, box_links
+
+
+def meshes_from_urdf(urdf, link_names, mesh_base_dir: str = "meshes", max_triangles: int = FBR_MAX_MESH_TRIANGLES) -> dict:
+    """{link: Mesh}: optimizer.py ``_getLinkCollisionGeometry`` for ``link_mode == "full"``, for the links of ``link_names`` only (no other
+    link's file is read).  The collision mesh, else the visual mesh, times the URDF ``scale``; the rotation of the origin is NOT applied and
+    the offset (``visual/origin`` xyz, else ``collision/origin`` xyz) is added in world axes -- the reference's behaviour, exactly as
+    ``hulls_from_urdf`` documents it, so that ``Mesh.hull`` is the hull ``hulls_from_urdf`` gives the link.  Triangle winding is irrelevant to
+    a distance (a negative scale is applied as it is).  A requested link that is not in the URDF or has no STL file that exists raises
+    ValueError naming it; more than ``max_triangles`` triangles: ValueError with link, file and count (no simplification is attempted)."""
+    tree = ET.parse(urdf)
+    wanted = list(link_names)
+    found = {}
+    for link in tree.findall("link"):
+        name = link.attrib["name"]
+        if name not in wanted:
+            continue
+        path, mscale = _mesh_file(urdf, link, mesh_base_dir)
+        if path is None:
+            raise ValueError(f"link {name}: no STL file for its collision or visual mesh (a triangle mesh was asked for)")
+        tri = read_stl(path) * mscale
+        if len(tri) > max_triangles:
+            raise ValueError(f"link {name}: {os.path.basename(path)} has {len(tri)} triangles, more than {max_triangles}")
+        origin = link.find("visual/origin")
+        if origin is None:
+            origin = link.find("collision/origin")
+        found[name] = Mesh(name, tri, _origin(origin)[0])
+    missing = [n for n in wanted if n not in found]
+    if missing:
+        raise ValueError(f"link(s) {missing}: not in {os.path.basename(urdf)}")
+    return {n: found[n] for n in wanted}
 
 
 def world_hulls_from_urdf(world_urdf, placement: str = "reference", cube_size=None) -> dict:
@@ -517,7 +573,7 @@ def world_boxes_from_urdf(world_urdf, placement: str = "reference", cube_size=No
     return out
 
 
-def collision_set(topology, capsules, config: dict, margins=None, boxes=None, world_boxes=None, hulls=None, world_hulls=None) -> dict:
+def collision_set(topology, capsules, config: dict, margins=None, boxes=None, world_boxes=None, hulls=None, world_hulls=None, meshes=None) -> dict:
     """What ``Engine.set_capsules`` / ``Engine.set_boxes`` and the ``collision`` argument of ``excitation.candidate_objectives`` take.
 
     Without ``boxes`` and ``world_boxes``: ``capsules`` (a list, one per link that has one, in link order), ``pairs`` ((P, 2) indices into
@@ -536,14 +592,33 @@ def collision_set(topology, capsules, config: dict, margins=None, boxes=None, wo
     reference's list with the hull links in the role the box links play in box mode, every pair is served by the hull routine
     (``columns[:, 0] == 2``), and there are ``hulls`` (a list: robot hulls in link order, then the world hulls), ``hull_pairs`` ((P, 2)
     into that list, sorted so that a pair's first hull changes rarely; ``columns[:, 1]`` says where a pair of ``pair_names`` went) and
-    ``offset_in_link_axes`` (False: the reference's placement).  Margins default as for boxes.  ``fullMeshLinks`` is refused."""
+    ``offset_in_link_axes`` (False: the reference's placement).  Margins default as for boxes.  Without ``meshes``, ``fullMeshLinks`` and
+    ``collisionMode: "full"`` are refused.
+
+    With ``meshes`` ({robot link: Mesh}, from ``meshes_from_urdf``) beside ``hulls``: ``fullMeshLinks`` is accepted -- every link named
+    there must be in ``meshes`` and is served as its triangle mesh, every other link as its hull -- and so is ``collisionMode: "full"``, in
+    which EVERY robot link in ``meshes`` is a mesh and the others are their hull or box, as in the reference.  A meshed link's hull is
+    ``Mesh.hull`` (it replaces the entry of ``hulls``, if any).  The dict gains ``meshes`` ({hull index: triangles (T, 3, 3)}: what
+    ``Engine.set_hull_meshes`` takes); pair order, ``columns`` and margins are as in convex mode.  A mesh above ``FBR_MAX_MESH_TRIANGLES``
+    or a pair above ``FBR_MAX_MESH_PAIR_WORK`` triangle pairs raises ValueError naming the links and the counts."""
     if hulls is not None:
         mode = config.get("collisionMode", "convex")
-        if config.get("fullMeshLinks") or mode == "full":
+        full = list(config.get("fullMeshLinks", []) or [])
+        if (full or mode == "full") and meshes is None:
             raise ValueError(f"collisionMode 'full' and fullMeshLinks {list(config.get('fullMeshLinks', []))} need triangle meshes: not covered")
-        if mode != "convex":
+        if mode not in ("convex", "full"):
             raise ValueError("hulls serve collisionMode 'convex' (boxes= / world_boxes= serve 'capsule' and 'box')")
         hulls, world_hulls = dict(hulls), dict(world_hulls or {})
+        meshed = {}
+        if meshes is not None:
+            lacking = [n for n in full if n not in meshes]
+            if lacking:
+                raise ValueError(f"fullMeshLinks {lacking}: no mesh given for them (meshes=)")
+            meshed = {n: meshes[n] for n in (meshes if mode == "full" else full) if n in topology.link_names}
+            for n, mm in meshed.items():
+                if len(mm.triangles) > FBR_MAX_MESH_TRIANGLES:
+                    raise ValueError(f"link {n}: {len(mm.triangles)} triangles, more than {FBR_MAX_MESH_TRIANGLES}")
+                hulls[n] = mm.hull
         clash = set(world_hulls) & set(topology.link_names)
         if clash:
             raise ValueError(f"link(s) {sorted(clash)} declared in the model and in the world")
@@ -560,9 +635,16 @@ def collision_set(topology, capsules, config: dict, margins=None, boxes=None, wo
             m = np.array([wm if (a in world_hulls or b in world_hulls) else 0.0 for a, b in pair_names])
         else:
             m = np.asarray(margins, dtype=np.float64).reshape(len(pair_names))
-        return {"capsules": [], "pairs": np.zeros((0, 2), dtype=np.int32), "pair_names": pair_names, "margins": m,
-                "hulls": [hulls[n] if n in hulls else world_hulls[n] for n in hnames],
-                "hull_pairs": np.array([raw[k] for k in order], dtype=np.int32).reshape(-1, 2), "columns": columns, "offset_in_link_axes": False}
+        out = {"capsules": [], "pairs": np.zeros((0, 2), dtype=np.int32), "pair_names": pair_names, "margins": m,
+               "hulls": [hulls[n] if n in hulls else world_hulls[n] for n in hnames],
+               "hull_pairs": np.array([raw[k] for k in order], dtype=np.int32).reshape(-1, 2), "columns": columns, "offset_in_link_axes": False}
+        if meshes is not None:
+            for a, b in pair_names:
+                if a in meshed and b in meshed and len(meshed[a].triangles) * len(meshed[b].triangles) > FBR_MAX_MESH_PAIR_WORK:
+                    raise ValueError(f"pair ({a}, {b}): {len(meshed[a].triangles)} x {len(meshed[b].triangles)} triangle pairs, more than "
+                                     f"{FBR_MAX_MESH_PAIR_WORK}")
+            out["meshes"] = {hpos[n]: meshed[n].triangles for n in hnames if n in meshed}
+        return out
     names = [n for n in topology.link_names if n in capsules]
     pos = {n: i for i, n in enumerate(names)}
     if boxes is None and world_boxes is None:

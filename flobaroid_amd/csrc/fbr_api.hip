@@ -13,7 +13,7 @@ thread_local std::string g_fbr_err;
 // 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
 // fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain, fbr_suspended_base_motion,
 // fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances, fbr_box_distance_gradients, fbr_model_set_hulls, fbr_candidate_hull_distances,
-// fbr_hull_distance_gradients: added symbols change no signature, and _lib.py names a library
+// fbr_hull_distance_gradients, fbr_model_set_hull_meshes: added symbols change no signature, and _lib.py names a library
 // that lacks one).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
@@ -1510,8 +1510,13 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
     HIPCHK(hipStreamSynchronize(m->stream));
     m->hulls = DevHulls{{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr};
+                        nullptr, nullptr, nullptr, 0};
     m->hullg = DevHullGrad{0, nullptr, nullptr};
+    // (the meshes attached to the set before are gone with it: fbr_model_set_hull_meshes)
+    m->hulls_plain = m->hulls;
+    m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    m->has_meshes = false;
+    m->hull_host = {};
     if (nhulls == 0) return FBR_OK;
     FbrKinIdProgram prog;
     try {
@@ -1575,6 +1580,8 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     dh.planes = (const double *)dev(hplanes);
     dh.edges = (const int *)dev(hedges);
     dh.pairs = (const int2 *)dev(hpairs);
+    dh.col = nullptr;
+    dh.ldp = npairs;
     // tables of fbr_hull_distance_gradients, in an allocation of their own: per pair the steps of the two members' links (-1: a world hull)
     // and the slots of their offsets (a world hull: its number) | ancestor masks
     std::vector<int> stepof2, anc, slotof(nr, 0);
@@ -1594,6 +1601,78 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     m->hullg.pair = (const int4 *)m->hullg_tab.p;
     m->hullg.anc = m->hullg_tab.as<int>() + (size_t)4 * std::max(npairs, 1);
     m->hulls = dh;
+    m->hulls_plain = dh;
+    m->hull_host.link.assign(link, link + nhulls);
+    m->hull_host.vbeg.assign(vbeg, vbeg + nhulls + 1);
+    m->hull_host.fbeg.assign(fbeg, fbeg + nhulls + 1);
+    m->hull_host.pairs.assign(pairs, pairs + 2 * (size_t)npairs);
+    m->hull_host.verts.assign(verts, verts + NV * 3);
+    m->hull_host.planes.assign(planes, planes + NF * 4);
+    m->hull_host.diam.assign(diam.begin(), diam.begin() + nhulls);
+    return FBR_OK;
+}
+
+// ---- triangle meshes on hulls of the set (csrc/fbr_mesh.h) ---------------------------------------------------------------------------------
+extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris)
+{
+    if (!m) {
+        set_err("null model");
+        return FBR_E_INVALID;
+    }
+    const auto &hh = m->hull_host;
+    const int nhulls = m->hulls.nhulls, npairs = m->hulls.npairs;
+    const std::string bad = fbr_mesh_validate(nhulls, hh.link.data(), hh.fbeg.data(), hh.planes.data(), hh.diam.data(), npairs, hh.pairs.data(),
+                                              FBR_MAX_MESH_TRIANGLES, FBR_MAX_MESH_PAIR_WORK, nmesh, hull, tbeg, tris);
+    if (!bad.empty()) {
+        set_err(bad);
+        return FBR_E_INVALID;
+    }
+    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (nmesh == 0) {
+        m->hulls_plain = m->hulls;
+        m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        m->has_meshes = false;
+        return FBR_OK;
+    }
+    // the pairs of the set: those with a mesh on either side, the meshed hull first, sorted by it (stable); the others in their order
+    std::vector<int> mtab((size_t)nhulls * 2, 0);
+    for (int i = 0; i < nmesh; i++) mtab[2 * (size_t)hull[i]] = tbeg[i], mtab[2 * (size_t)hull[i] + 1] = tbeg[i + 1] - tbeg[i];
+    std::vector<int> mk, pk;
+    for (int k = 0; k < npairs; k++) (mtab[2 * (size_t)hh.pairs[2 * k] + 1] || mtab[2 * (size_t)hh.pairs[2 * k + 1] + 1] ? mk : pk).push_back(k);
+    auto first = [&](int k) { return mtab[2 * (size_t)hh.pairs[2 * k] + 1] ? hh.pairs[2 * k] : hh.pairs[2 * k + 1]; };
+    std::stable_sort(mk.begin(), mk.end(), [&](int a, int b) { return first(a) < first(b); });
+    const size_t NT = (size_t)tbeg[nmesh], nm = std::max(mk.size(), (size_t)1), np = std::max(pk.size(), (size_t)1);
+    // one allocation, doubles first: sph | tris | aux || mesh pairs | plain pairs | mtab | mesh columns | plain columns
+    const size_t nd = (size_t)nhulls * 4 + NT * 9 + NT * 5, ni = 2 * nm + 2 * np + (size_t)nhulls * 2 + nm + np;
+    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int), 0);
+    double *hsph = (double *)host.data(), *htris = hsph + (size_t)nhulls * 4, *haux = htris + NT * 9;
+    int *hmp = (int *)(hsph + nd), *hpp = hmp + 2 * nm, *hmtab = hpp + 2 * np, *hmc = hmtab + (size_t)nhulls * 2, *hpc = hmc + nm;
+    for (int h = 0; h < nhulls; h++)
+        fbr_mesh_point_sphere(hh.vbeg[h + 1] - hh.vbeg[h], hh.verts.data() + 3 * (size_t)hh.vbeg[h], 3L * mtab[2 * (size_t)h + 1],
+                              tris + 9 * (size_t)mtab[2 * (size_t)h], hsph + 4 * (size_t)h);
+    std::copy(tris, tris + NT * 9, htris);
+    for (size_t t = 0; t < NT; t++) fbr_mesh_triangle_aux(tris + 9 * t, haux + 5 * t);
+    std::copy(mtab.begin(), mtab.end(), hmtab);
+    for (size_t i = 0; i < mk.size(); i++) {
+        const int k = mk[i], a = hh.pairs[2 * k], b = hh.pairs[2 * k + 1], swap = mtab[2 * (size_t)a + 1] == 0;
+        hmp[2 * i] = swap ? b : a, hmp[2 * i + 1] = swap ? a : b, hmc[i] = k;
+    }
+    for (size_t i = 0; i < pk.size(); i++) hpp[2 * i] = hh.pairs[2 * pk[i]], hpp[2 * i + 1] = hh.pairs[2 * pk[i] + 1], hpc[i] = pk[i];
+    // a fresh allocation, swapped in once the copy has succeeded: a call that fails here leaves the attachments in place as well
+    DevBuf fresh;
+    if (int rc = fresh.ensure(host.size() + 8)) return rc;
+    HIPCHK(hipMemcpy(fresh.p, host.data(), host.size(), hipMemcpyHostToDevice));
+    m->mesh_tab = std::move(fresh);
+    m->hulls_plain = m->hulls;
+    const char *base = (const char *)m->mesh_tab.p;
+    auto dev = [&](const void *hp) { return base + ((const char *)hp - host.data()); };
+    m->meshes = DevMeshes{(int)mk.size(), (const int *)dev(hmtab), (const double *)dev(hsph), (const double *)dev(htris), (const double *)dev(haux),
+                          (const int2 *)dev(hmp), (const int *)dev(hmc)};
+    m->hulls_plain.npairs = (int)pk.size();
+    m->hulls_plain.pairs = (const int2 *)dev(hpp);
+    m->hulls_plain.col = (const int *)dev(hpc);
+    m->has_meshes = true;
     return FBR_OK;
 }
 
@@ -1607,7 +1686,18 @@ extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, 
     return candidate_frame_distances(m, !m || have ? nullptr : "no hull set with at least one pair (fbr_model_set_hulls)", m ? m->hulls.fr : none, P,
                                      (P + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
                                      [&](unsigned grid, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
-                                         hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, m->hulls, tl, b0, nb, fr, pval, pidx);
+                                         if (!m->has_meshes) {
+                                             hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, m->hulls, tl, b0, nb, fr, pval, pidx);
+                                             return;
+                                         }
+                                         // a split set: the pairs without a mesh, then those with one, each into its own columns
+                                         const long cap = (long)m->num_cus * 32, ph = m->hulls_plain.npairs, pm = m->meshes.npairs;
+                                         if (ph > 0)
+                                             hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ph + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
+                                                                dim3(64), 0, m->stream, m->hulls_plain, tl, b0, nb, fr, pval, pidx);
+                                         if (pm > 0)
+                                             hipLaunchKernelGGL(fbr_mesh_pairs_kernel, dim3((unsigned)std::min(nb * ((pm + FBR_MESH_BATCH - 1) / FBR_MESH_BATCH), cap)),
+                                                                dim3(64), 0, m->stream, m->hulls, m->meshes, tl, b0, nb, fr, pval, pidx);
                                      });
 }
 
@@ -1742,6 +1832,10 @@ extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, c
     if (m->hulls.nhulls == 0 || m->hulls.npairs == 0) {
         set_err("no hull set with at least one pair (fbr_model_set_hulls)");
         return FBR_E_INVALID;
+    }
+    if (m->has_meshes) {
+        set_err("fbr_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); gradients of mesh pairs are not built");
+        return FBR_E_UNSUPPORTED;
     }
     double se, omc;
     fbr_boxgrad_trig(epsilon, &se, &omc);

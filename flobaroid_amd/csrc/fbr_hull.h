@@ -19,6 +19,7 @@
 //
 // Frames: R_link | p_link + offset per checked sample is what fbr_box_frames_kernel writes for a box centre; the hull set carries a DevBoxes
 // view (steps, slots, offsets) and that kernel is reused.  fbr_hull_pairs_kernel has the structure of fbr_box_pairs_kernel.
+// The GJK loop (fbr_hull_gjk) and the relative pose (fbr_hull_relative) are functions of their own: fbr_mesh.h calls them on triangles.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -154,27 +155,42 @@ FBR_HD double fbr_hull_det(const double *w, const double *x, const double *y, co
         lam[j] = 0.0;                                \
     }
 
-// Signed distance of the hulls A at (RA, cA) and B at (RB, cB): R [9] row-major (orthonormal), c [3] the origin of the hull's axes in the
-// world.  A NaN or an infinity among the poses gives a NaN.  iters (may be null): the GJK iterations taken, + 1000 when the facet pass ran.
-template <class DP, class IP>
-FBR_HD double fbr_hull_distance(const double *RA, const double *cA, const FbrHullT<DP, IP> &A, const double *RB, const double *cB,
-                                const FbrHullT<DP, IP> &B, int *iters)
+// B in the frame of A: C = RA^T RB, t = RA^T (cB - cA); chk - chk is 0.0 for finite poses and a NaN otherwise
+struct FbrHullRel {
+    double t0, t1, t2, C00, C01, C02, C10, C11, C12, C20, C21, C22, chk;
+};
+
+FBR_HD void fbr_hull_relative(const double *RA, const double *cA, const double *RB, const double *cB, FbrHullRel *q)
 {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    // B in the frame of A: C = RA^T RB, t = RA^T (cB - cA)
     const double d0 = cB[0] - cA[0], d1 = cB[1] - cA[1], d2 = cB[2] - cA[2];
-    const double t0 = RA[0] * d0 + RA[3] * d1 + RA[6] * d2, t1 = RA[1] * d0 + RA[4] * d1 + RA[7] * d2, t2 = RA[2] * d0 + RA[5] * d1 + RA[8] * d2;
-    const double C00 = RA[0] * RB[0] + RA[3] * RB[3] + RA[6] * RB[6], C01 = RA[0] * RB[1] + RA[3] * RB[4] + RA[6] * RB[7],
-                 C02 = RA[0] * RB[2] + RA[3] * RB[5] + RA[6] * RB[8];
-    const double C10 = RA[1] * RB[0] + RA[4] * RB[3] + RA[7] * RB[6], C11 = RA[1] * RB[1] + RA[4] * RB[4] + RA[7] * RB[7],
-                 C12 = RA[1] * RB[2] + RA[4] * RB[5] + RA[7] * RB[8];
-    const double C20 = RA[2] * RB[0] + RA[5] * RB[3] + RA[8] * RB[6], C21 = RA[2] * RB[1] + RA[5] * RB[4] + RA[8] * RB[7],
-                 C22 = RA[2] * RB[2] + RA[5] * RB[5] + RA[8] * RB[8];
-    const double chk = (t0 + t1 + t2) + (C00 + C01 + C02) + (C10 + C11 + C12) + (C20 + C21 + C22);
-    double res = chk - chk;            // (a NaN pose never wins a minimum)
-    bool done = !(res == 0.0), touching = false;
+    q->t0 = RA[0] * d0 + RA[3] * d1 + RA[6] * d2, q->t1 = RA[1] * d0 + RA[4] * d1 + RA[7] * d2, q->t2 = RA[2] * d0 + RA[5] * d1 + RA[8] * d2;
+    q->C00 = RA[0] * RB[0] + RA[3] * RB[3] + RA[6] * RB[6], q->C01 = RA[0] * RB[1] + RA[3] * RB[4] + RA[6] * RB[7],
+    q->C02 = RA[0] * RB[2] + RA[3] * RB[5] + RA[6] * RB[8];
+    q->C10 = RA[1] * RB[0] + RA[4] * RB[3] + RA[7] * RB[6], q->C11 = RA[1] * RB[1] + RA[4] * RB[4] + RA[7] * RB[7],
+    q->C12 = RA[1] * RB[2] + RA[4] * RB[5] + RA[7] * RB[8];
+    q->C20 = RA[2] * RB[0] + RA[5] * RB[3] + RA[8] * RB[6], q->C21 = RA[2] * RB[1] + RA[5] * RB[4] + RA[8] * RB[7],
+    q->C22 = RA[2] * RB[2] + RA[5] * RB[5] + RA[8] * RB[8];
+    q->chk = (q->t0 + q->t1 + q->t2) + (q->C00 + q->C01 + q->C02) + (q->C10 + q->C11 + q->C12) + (q->C20 + q->C21 + q->C22);
+}
+
+// GJK on A - (C B + t), shared by fbr_hull_distance and fbr_mesh_distance (csrc/fbr_mesh.h: A or B may be a triangle, nv = 3, whose
+// Minkowski difference with a triangle is flat -- then the tetrahedron never encloses the origin and the exits below carry the case).
+// Returns |v| when the two are apart, a NaN for a NaN pose, and 0.0 with *touching set when the simplex encloses the origin or
+// |v| <= FBR_HULL_NOISE scale.  skip: this lane takes no part (the loop is the wave's); its return value means nothing.
+// *it: the iterations taken.
+template <class DP, class IP>
+FBR_HD double fbr_hull_gjk(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const FbrHullT<DP, IP> &B, bool skip, bool *touch, int *itp)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double t0 = q.t0, t1 = q.t1, t2 = q.t2, C00 = q.C00, C01 = q.C01, C02 = q.C02, C10 = q.C10, C11 = q.C11, C12 = q.C12, C20 = q.C20,
+                 C21 = q.C21, C22 = q.C22;
+    double res = q.chk - q.chk;        // (a NaN pose never wins a minimum)
+    bool done = !(res == 0.0) || skip, touching = false;
     const double scale = sqrt(t0 * t0 + t1 * t1 + t2 * t2) + A.diam + B.diam;
     const double floor2 = (FBR_HULL_NOISE * scale) * (FBR_HULL_NOISE * scale);
 
@@ -284,7 +300,28 @@ FBR_HD double fbr_hull_distance(const double *RA, const double *cA, const FbrHul
             }
         }
     }
+    *touch = touching;
+    *itp = it;
+    return res;
+}
+
+// Signed distance of the hulls A at (RA, cA) and B at (RB, cB): R [9] row-major (orthonormal), c [3] the origin of the hull's axes in the
+// world.  A NaN or an infinity among the poses gives a NaN.  iters (may be null): the GJK iterations taken, + 1000 when the facet pass ran.
+template <class DP, class IP>
+FBR_HD double fbr_hull_distance(const double *RA, const double *cA, const FbrHullT<DP, IP> &A, const double *RB, const double *cB,
+                                const FbrHullT<DP, IP> &B, int *iters)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    FbrHullRel q;
+    fbr_hull_relative(RA, cA, RB, cB, &q);
+    bool touching;
+    int it;
+    double res = fbr_hull_gjk(q, A, B, false, &touching, &it);
     if (iters) *iters = it + (touching ? 1000 : 0);
+    const double t0 = q.t0, t1 = q.t1, t2 = q.t2, C00 = q.C00, C01 = q.C01, C02 = q.C02, C10 = q.C10, C11 = q.C11, C12 = q.C12, C20 = q.C20,
+                 C21 = q.C21, C22 = q.C22;
 
     // ---- touching or overlapping: the largest signed gap over the facets of the Minkowski difference
     if (FBR_HULL_ANY(touching)) {
@@ -428,6 +465,8 @@ struct DevHulls {
     const double *planes; // [][4]
     const int *edges;     // [][4] end vertices and faces, relative to the hull's own tables
     const int2 *pairs;    // [npairs] the caller's hull numbers
+    const int *col;       // [npairs] the column of pval / pidx a pair writes, or null: its own number (a set split by fbr_model_set_hull_meshes)
+    int ldp;              // the columns of pval / pidx: npairs, or all pairs of a split set
 };
 
 #if defined(FBR_KERNELS_CORE)
@@ -498,8 +537,9 @@ __global__ __launch_bounds__(64) void fbr_hull_pairs_kernel(DevHulls hs, DevCapT
                 const double a = sd[lane * 65 + r];
                 if (fbr_capsule_take(a, best)) best = a, ibest = r;
             }
-            pval[b * hs.npairs + k0 + lane] = best;
-            pidx[b * hs.npairs + k0 + lane] = ibest < 0 ? -1 : (i0 + ibest) * tl.step;
+            const int col = hs.col ? hs.col[k0 + lane] : k0 + lane;
+            pval[b * hs.ldp + col] = best;
+            pidx[b * hs.ldp + col] = ibest < 0 ? -1 : (i0 + ibest) * tl.step;
         }
     }
 }

@@ -25,6 +25,7 @@
 #include "fbr_box_grad.h"
 #include "fbr_hull.h"
 #include "fbr_hull_grad.h"
+#include "fbr_mesh.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -170,8 +171,19 @@ struct fbr_model {
     // convex-hull collision set (fbr_model_set_hulls; csrc/fbr_hull.h), independent of the other two: its tables; the frames of the robot
     // hulls share the box call's workspace (hulls.fr is the view of the set that fbr_box_frames_kernel takes)
     DevHulls hulls = {{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr};
+                      nullptr, nullptr, nullptr, 0};
     DevBuf hull_tab;
+    // triangle meshes attached to hulls of that set (fbr_model_set_hull_meshes; csrc/fbr_mesh.h): the host's copy of what the checks and the
+    // bounding spheres need of the hull set, the mesh tables, and the set's pairs split into those without a mesh (hulls_plain: the view
+    // fbr_hull_pairs_kernel takes, its columns in col) and those with one (meshes).  meshes.npairs == 0: nothing attached.
+    struct HostHullSet {
+        std::vector<int32_t> link, vbeg, fbeg, pairs;
+        std::vector<double> verts, planes, diam;
+    } hull_host;
+    DevHulls hulls_plain = hulls;
+    DevMeshes meshes = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool has_meshes = false;
+    DevBuf mesh_tab;
     DevHullGrad hullg = {0, nullptr, nullptr};  // fbr_hull_distance_gradients: ancestor masks and per-pair steps / offset slots of the set above
     DevBuf hullg_tab;
     // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its

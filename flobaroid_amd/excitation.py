@@ -10,7 +10,8 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
   ``Engine.candidate_extrema``: only per-candidate numbers reach the host;
 * ``candidate_collision_constraints`` -- its collision block from ``Engine.candidate_capsule_distances`` (``collisionMode: "capsule"``,
   pairs of links with capsules), ``Engine.candidate_box_distances`` (``collisionMode: "box"``, world links, capsule-less links) and
-  ``Engine.candidate_hull_distances`` (``collisionMode: "convex"``, the reference's default: convex hulls of the links' meshes);
+  ``Engine.candidate_hull_distances`` (``collisionMode: "convex"``, the reference's default: convex hulls of the links' meshes; with
+  ``Engine.set_hull_meshes`` also ``fullMeshLinks`` and ``collisionMode: "full"``: the triangle meshes themselves);
   ``candidate_objectives(..., collision=...)`` appends it to ``g``;
 * ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
   candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``;
@@ -312,8 +313,9 @@ def candidate_collision_constraints(engine, states: dict, ncand: int, config: di
     ``boxes=True``: the same block for the BOX set of the engine (``Engine.set_boxes``: the pairs the reference sends to its box
     fallback -- ``collisionMode: "box"``, world links, capsule-less links) from ``Engine.candidate_box_distances``; the main trajectory and
     the transition configurations are walked once per set, each with its set's distance call.  ``hulls=True``: the same for the HULL set
-    (``Engine.set_hulls``: every pair of ``collisionMode: "convex"``) from ``Engine.candidate_hull_distances``.  Not covered:
-    ``collisionMode: "full"``.
+    (``Engine.set_hulls``: every pair of ``collisionMode: "convex"``) from ``Engine.candidate_hull_distances``; with triangle meshes
+    attached to that set (``Engine.set_hull_meshes``: ``fullMeshLinks``, ``collisionMode: "full"``) the pairs of a meshed link come back as
+    mesh distances, 0.0 where they touch and never negative.
 
     ``suspended``: not None says that ``states`` carry the simulated base motion of the suspended base (``rpy`` and ``base_position`` of
     ``candidate_states(..., suspended=)``); ``floatingBaseAttachment: "suspended"`` is then accepted.  The poses of the main trajectory
@@ -401,6 +403,18 @@ def _has_hull_pairs(collision) -> bool:
     return collision is not None and len(collision.get("hull_pairs", ())) > 0
 
 
+def _has_meshes(collision) -> bool:
+    return collision is not None and bool(collision.get("meshes"))
+
+
+def _refuse_mesh_gradient(collision) -> None:
+    """gradients of mesh pairs are not built: a set with triangle meshes is refused by the names of its meshed links"""
+    if _has_meshes(collision):
+        links = [collision["hulls"][int(h)].link_name for h in collision["meshes"]]
+        raise ValueError(f"gradients on the device do not cover triangle meshes: the collision set has meshes on {links} (fullMeshLinks / "
+                         "collisionMode 'full'); the constraint values are served, their gradients are not built")
+
+
 _NO_HULL_GRADIENT = ("gradients on the device cover capsule and box pairs only: the collision set has hull pairs (collisionMode 'convex'; the "
                      "reference differentiates those by central differences, which is not built for hulls)")
 
@@ -408,6 +422,7 @@ _NO_HULL_GRADIENT = ("gradients on the device cover capsule and box pairs only: 
 def _wants_hull_gradient(config, collision, hull_gradient) -> bool:
     """True when ``hull_gradient=True`` selects the hull rows: ``collisionMode: "convex"`` and a set of hull pairs only.  Every other
     combination goes on to the refusals that hold without the keyword."""
+    _refuse_mesh_gradient(collision)
     if not hull_gradient or config.get("collisionMode", "capsule") != "convex":
         return False
     if collision is None or "hulls" not in collision or not _has_hull_pairs(collision) or "columns" not in collision:
@@ -426,8 +441,15 @@ def _collision_block(engine, states, ncand, config, collision, suspended=None):
     if collision is None:
         return None
     mode = config.get("collisionMode", "capsule")
+    if mode == "full" or config.get("fullMeshLinks"):
+        # triangle meshes ride on the hull set: the pairs, their order and the margins are those of convex mode
+        if not _has_meshes(collision):
+            raise ValueError(f"collisionMode 'full' and fullMeshLinks {list(config.get('fullMeshLinks', []))} need a collision set with triangle "
+                             "meshes (flobaroid_amd.collision.collision_set(..., hulls=, meshes=))")
+        if mode == "full":
+            mode = "convex"
     if mode not in ("capsule", "box", "convex"):
-        raise ValueError("collision constraints on the device cover collisionMode 'capsule', 'box' and 'convex' only (no triangle meshes: DESIGN 9)")
+        raise ValueError("collision constraints on the device cover collisionMode 'capsule', 'box', 'convex' and 'full' only")
     if mode == "convex" and "hulls" not in collision:
         raise ValueError("collisionMode 'convex' needs a collision set with hulls (flobaroid_amd.collision.collision_set(..., hulls=))")
     if mode != "convex" and _has_hull_pairs(collision):
@@ -454,7 +476,8 @@ def _collision_block(engine, states, ncand, config, collision, suspended=None):
         elif which == 1:
             engine.set_boxes(collision["boxes"], collision["box_pairs"], center_in_link_axes=bool(collision.get("center_in_link_axes", False)))
         else:
-            engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)))
+            kw = {"meshes": collision["meshes"]} if _has_meshes(collision) else {}
+            engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)), **kw)
         part = candidate_collision_constraints(engine, states, ncand, config, margins=m[sel], suspended=suspended, boxes=which == 1, hulls=which == 2)
         if out is None:
             out = {k: np.zeros((np.asarray(v).shape[0], P), dtype=np.asarray(v).dtype) for k, v in part.items()}
@@ -720,8 +743,10 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     ``collisionMode: "convex"`` (the reference's default): the set must have hull pairs and only those; the hull set is installed and the
     rows are the reference's central differences of the hull distance over ``epsilon`` (as above) from ``Engine.hull_distance_gradients``
     at the evaluation points of the constraint block, transitions included, in the reference's pair order.  In the modes ``"capsule"`` and
-    ``"box"`` the keyword changes nothing: a set with hull pairs stays refused there."""
+    ``"box"`` the keyword changes nothing: a set with hull pairs stays refused there.  A set with triangle meshes (``fullMeshLinks``,
+    ``collisionMode: "full"``) is refused by the names of its meshed links, whatever the keywords: gradients of mesh pairs are not built."""
     _check_config(config)
+    _refuse_mesh_gradient(collision)
     mode = config.get("collisionMode", "capsule")
     if _wants_hull_gradient(config, collision, hull_gradient):
         C, n = int(ncand), engine.n
@@ -950,8 +975,10 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     the box distance over the same ``epsilon`` (``candidate_collision_gradient``).  ``hull_gradient=False``: a ``collision`` set with hull
     pairs raises ``ValueError``; ``True`` with ``collisionMode: "convex"``: the rows of the hull pairs are the reference's central
     differences of the hull distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base,
-    gravity-only models (refused), ``collisionMode: "full"``."""
+    gravity-only models (refused), gradients of a ``collision`` set with triangle meshes (``fullMeshLinks``, ``collisionMode: "full"``:
+    refused by the names of the meshed links)."""
     _check_config(config)
+    _refuse_mesh_gradient(collision)
     hull_rows = collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
     if _has_hull_pairs(collision) and not hull_rows:
         raise ValueError(_NO_HULL_GRADIENT)

@@ -88,7 +88,7 @@ typedef struct {
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
- * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients. */
+ * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -299,6 +299,30 @@ int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const
  */
 int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step,
                                  double *dist_out, int64_t *idx_out, int32_t out_mem);
+
+/*
+ * Triangle meshes on hulls of the set fbr_model_set_hulls put in place: the reference's fullMeshLinks and collisionMode "full", in which a
+ * link's geometry is the triangle mesh itself (an FCL BVH) instead of its convex hull -- cages and other concave shapes.  Host arrays,
+ * copied; the triangles of mesh i are rows [tbeg[i], tbeg[i + 1]) of tris:
+ *   hull [nmesh]        the hull (index into the hull list) that carries mesh i; its hull stays in the hull tables
+ *   tbeg [nmesh + 1]    starts at 0, ascending
+ *   tris [][9]          three vertices a triangle, in the hull's axes; winding is irrelevant, zero-area triangles are kept
+ * With meshes attached, fbr_candidate_hull_distances serves every pair with a mesh on either side by the mesh routine: the distance of a
+ * mesh to the other hull (a solid), or to the other mesh, is the minimum over its triangles (triangle pairs) of the Euclidean distance,
+ * and EXACTLY 0.0 where they touch or intersect -- never negative; a geometry wholly inside a closed mesh that does not touch its surface
+ * has a positive distance (FCL's BVH behaves the same way).  Pairs without a mesh return the bits they return without any mesh attached.
+ * Brute force over the triangles, culled by bounding spheres without changing a bit (csrc/fbr_mesh.h); the two limits keep a launch from
+ * running for minutes: they admit every pair of the WALK-MAN simple/ collision meshes (170 x 160 = 27 200) and refuse visual meshes.
+ * nmesh = 0 clears the attachments, and so does every later fbr_model_set_hulls.  fbr_hull_distance_gradients returns FBR_E_UNSUPPORTED
+ * while meshes are attached.  FBR_E_INVALID: no hull set, a hull index out of range or given twice, a world hull (the reference never
+ * meshes world links), tbeg not starting at 0 or not ascending, a mesh with no triangle, non-finite data, a triangle vertex outside one
+ * of its hull's planes by more than 1e-9 x the hull's diameter (the culling sphere of a hull is taken over its vertices and its mesh's), a mesh
+ * of more than FBR_MAX_MESH_TRIANGLES triangles, a pair of the set with T_A x T_B above FBR_MAX_MESH_PAIR_WORK; the attachments in place
+ * before a refused call stay, and so they do when the call fails for another reason (an allocation).
+ */
+#define FBR_MAX_MESH_TRIANGLES 256
+#define FBR_MAX_MESH_PAIR_WORK 32768
+int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris);
 
 /*
  * Capsule distance and its derivative with respect to the joint positions at ONE chosen configuration per candidate and pair -- the
