@@ -129,6 +129,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_mesh_distance_gradients": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -698,7 +703,8 @@ class Engine:
         and ``collisionMode: "full"``).  ``meshes``: ``{hull index: triangles (T, 3, 3)}`` in the hull's axes (``collision_set(...,
         meshes=)["meshes"]``), or a sequence of such pairs.  ``candidate_hull_distances`` then serves every pair with a meshed hull by the
         mesh routine: the minimum over the triangles, exactly 0.0 where they touch or intersect, never negative.  An empty ``meshes``
-        clears the attachments, and so does every later ``set_hulls``; ``hull_distance_gradients`` refuses a set with meshes."""
+        clears the attachments, and so does every later ``set_hulls``; ``hull_distance_gradients`` refuses a set with meshes,
+        ``mesh_distance_gradients`` serves it."""
         items = list(meshes.items()) if hasattr(meshes, "items") else list(meshes or [])
         tri = [np.asarray(t, dtype=np.float64).reshape(-1, 9) for _, t in items]
         hull = np.ascontiguousarray([int(h) for h, _ in items], dtype=np.int32)
@@ -805,8 +811,18 @@ class Engine:
         return self._distance_gradients("fbr_hull_distance_gradients", int(getattr(self, "num_hull_pairs", 0)), (float(epsilon),), st, ncand, sample,
                                         scale, pose_sample, base_pos, device_out)
 
+    def mesh_distance_gradients(self, st: dict, ncand: int, sample, scale=None, pose_sample=None, base_pos=None, epsilon: float = 1e-7,
+                                device_out: bool | None = None) -> dict:
+        """``hull_distance_gradients`` for a hull set with triangle meshes attached (``set_hull_meshes``; ``fbr_mesh_distance_gradients``):
+        ``{"dist": (C, P_hull), "grad_q": (C, P_hull, n)}`` over ALL pairs of the set, arguments and rules as there.  A pair without a mesh
+        returns the bytes ``hull_distance_gradients`` gives it from the same set without meshes; a pair with one the mesh distance and its
+        central differences over ``epsilon``.  A mesh distance is exactly 0.0 on contact and never negative, so a pair in intersection has
+        an exactly zero row: a mesh carries no penetration depth.  A set without meshes is refused (``hull_distance_gradients`` serves it)."""
+        return self._distance_gradients("fbr_mesh_distance_gradients", int(getattr(self, "num_hull_pairs", 0)), (float(epsilon),), st, ncand, sample,
+                                        scale, pose_sample, base_pos, device_out)
+
     def _distance_gradients(self, entry: str, P: int, extra: tuple, st: dict, ncand: int, sample, scale, pose_sample, base_pos, device_out) -> dict:
-        """the capsule, the box and the hull call share their arguments: ``entry`` names the library's function, ``P`` the pairs of its set, ``extra``
+        """the capsule, the box, the hull and the mesh call share their arguments: ``entry`` names the library's function, ``P`` the pairs of its set, ``extra``
         what the function takes between ``pose_sample`` and the outputs"""
         q = _Ref(st["q"], None, "q")
         if len(q.obj.shape) != 2 or q.obj.shape[1] != self.n:

@@ -22,7 +22,8 @@ of a world URDF, and the list of link pairs the trajectory optimiser checks.  Nu
   argument of ``excitation.candidate_objectives`` take.
 
 The distances themselves are computed on the device (``Engine.candidate_capsule_distances``, csrc/fbr_capsule.h;
-``Engine.candidate_box_distances``, csrc/fbr_box.h; ``Engine.candidate_hull_distances``, csrc/fbr_hull.h and, for pairs with a mesh, csrc/fbr_mesh.h).  Not covered: gradients of mesh pairs;
+``Engine.candidate_box_distances``, csrc/fbr_box.h; ``Engine.candidate_hull_distances``, csrc/fbr_hull.h and, for pairs with a mesh, csrc/fbr_mesh.h; their
+gradients: ``Engine.mesh_distance_gradients``, csrc/fbr_mesh_grad.h, behind ``mesh_gradient=True`` of ``flobaroid_amd.excitation``).  Not covered:
 meshes whose hull has more than ``FBR_MAX_HULL_VERTICES`` vertices or that have more than ``FBR_MAX_MESH_TRIANGLES`` triangles (no
 simplification, no BVH); formats other than STL; parity with FCL's own numbers.
 """

@@ -13,7 +13,7 @@ thread_local std::string g_fbr_err;
 // 104: fbr_model_set_capsules, fbr_candidate_capsule_distances (and, under the same number, fbr_regressor_weights, fbr_fourier_gradient,
 // fbr_capsule_distance_gradients, fbr_fourier_position_chain, fbr_torque_row_sweep, fbr_fourier_state_chain, fbr_suspended_base_motion,
 // fbr_suspended_records, fbr_model_set_boxes, fbr_candidate_box_distances, fbr_box_distance_gradients, fbr_model_set_hulls, fbr_candidate_hull_distances,
-// fbr_hull_distance_gradients, fbr_model_set_hull_meshes: added symbols change no signature, and _lib.py names a library
+// fbr_hull_distance_gradients, fbr_model_set_hull_meshes, fbr_mesh_distance_gradients: added symbols change no signature, and _lib.py names a library
 // that lacks one).
 // flobaroid_amd/_lib.py refuses a library of another version than the header it was written for.
 extern "C" int fbr_version(void) { return FBR_VERSION; }
@@ -1515,6 +1515,7 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     // (the meshes attached to the set before are gone with it: fbr_model_set_hull_meshes)
     m->hulls_plain = m->hulls;
     m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
     m->has_meshes = false;
     m->hull_host = {};
     if (nhulls == 0) return FBR_OK;
@@ -1632,6 +1633,7 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
     if (nmesh == 0) {
         m->hulls_plain = m->hulls;
         m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
         m->has_meshes = false;
         return FBR_OK;
     }
@@ -1659,11 +1661,45 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
         hmp[2 * i] = swap ? b : a, hmp[2 * i + 1] = swap ? a : b, hmc[i] = k;
     }
     for (size_t i = 0; i < pk.size(); i++) hpp[2 * i] = hh.pairs[2 * pk[i]], hpp[2 * i + 1] = hh.pairs[2 * pk[i] + 1], hpc[i] = pk[i];
-    // a fresh allocation, swapped in once the copy has succeeded: a call that fails here leaves the attachments in place as well
-    DevBuf fresh;
+    // the stencil points of fbr_mesh_distance_gradients (csrc/fbr_mesh_grad.h): per mesh pair the centre, then + eps, - eps of every joint
+    // fbr_rigidgrad_item evaluates, in walk order: sbeg | pair of a point | its joint
+    std::vector<int> gtab(mk.size() + 1, 0), gpair, gjoint;
+    int smax = 0;
+    {
+        FbrKinIdProgram prog;
+        try {
+            fbr_kinid_build(m->hm, prog);
+        } catch (const std::exception &e) {
+            set_err(e.what());
+            return FBR_E_INVALID;
+        }
+        std::vector<int> stepof, anc, joint;
+        fbr_capgrad_ancestors(m->hm, prog, stepof, anc);
+        for (size_t i = 0; i < mk.size(); i++) {
+            const int la = hh.link[hh.pairs[2 * mk[i]]], lb = hh.link[hh.pairs[2 * mk[i] + 1]];
+            fbr_meshgrad_slots(la < 0 ? -1 : stepof[la], lb < 0 ? -1 : stepof[lb], m->hulls.fr.cmode, prog.steps.data(), anc.data(),
+                               fbr_capgrad_words(prog.nsteps), joint);
+            gtab[i + 1] = gtab[i] + (int)joint.size();
+            gpair.insert(gpair.end(), joint.size(), (int)i);
+            gjoint.insert(gjoint.end(), joint.begin(), joint.end());
+            smax = std::max(smax, (int)joint.size());
+        }
+        gtab.insert(gtab.end(), gpair.begin(), gpair.end());
+        gtab.insert(gtab.end(), gjoint.begin(), gjoint.end());
+    }
+    // fresh allocations, swapped in once the copies have succeeded: a call that fails here leaves the attachments in place as well
+    DevBuf fresh, freshg;
     if (int rc = fresh.ensure(host.size() + 8)) return rc;
+    if (int rc = freshg.ensure(gtab.size() * sizeof(int))) return rc;
     HIPCHK(hipMemcpy(fresh.p, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(freshg.p, gtab.data(), gtab.size() * sizeof(int), hipMemcpyHostToDevice));
     m->mesh_tab = std::move(fresh);
+    m->meshg_tab = std::move(freshg);
+    {
+        const int *g = m->meshg_tab.as<int>();
+        const int ni = (int)gpair.size();
+        m->meshg = DevMeshGrad{ni, smax, g, g + mk.size() + 1, g + mk.size() + 1 + ni};
+    }
     m->hulls_plain = m->hulls;
     const char *base = (const char *)m->mesh_tab.p;
     auto dev = [&](const void *hp) { return base + ((const char *)hp - host.data()); };
@@ -1701,9 +1737,11 @@ extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, 
                                      });
 }
 
-// ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, fbr_box_grad.h, fbr_hull_grad.h) -------
-// The capsule, the box and the hull call share everything but the set and the kernel: `name` the entry point, P / nslots the pairs and the branch
-// points of its set, launch(grid, C, T, q, rpy, bpos, sample, scale, pose, dist, grad) the kernel.
+// ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, fbr_box_grad.h, fbr_hull_grad.h,
+// fbr_mesh_grad.h) ----
+// The capsule, the box, the hull and the mesh call share everything but the set and the kernel: `name` the entry point, P / nslots the pairs and
+// the branch points of its set, launch(grid, C, T, q, rpy, bpos, sample, scale, pose, dist, grad) the kernel -- or the kernels of the mesh
+// call; it returns FBR_OK, or the code of a workspace it could not get.
 template <class Launch>
 static int distance_gradients(fbr_model *m, const char *name, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                               const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem, long P, int nslots,
@@ -1747,7 +1785,7 @@ static int distance_gradients(fbr_model *m, const char *name, const fbr_states *
     HIPCHK(hipMemsetAsync(dgrad, 0, items * hm.n * sizeof(double), m->stream));  // (joints off a pair's path: exact zeros, never touched by the kernel)
     {
         ProfScope ps(m, FBR_PROF_KIN);
-        launch(grid, C, T, dq, drpy, dbp, (const long *)dsmp, dscale, (const long *)dpose, ddist, dgrad);
+        if ((rc = launch(grid, C, T, dq, drpy, dbp, (const long *)dsmp, dscale, (const long *)dpose, ddist, dgrad))) return rc;
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(&flag, m->capg_flag.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
@@ -1792,6 +1830,7 @@ extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st
                                   const long *dpose, double *ddist, double *dgrad) {
                                   hipLaunchKernelGGL(fbr_capsule_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->caps, m->capg, C, T, dq,
                                                      drpy, dbp, dsmp, dscale, dpose, ddist, dgrad, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+                                  return FBR_OK;
                               });
 }
 
@@ -1817,6 +1856,7 @@ extern "C" int fbr_box_distance_gradients(fbr_model *m, const fbr_states *st, co
                                   hipLaunchKernelGGL(fbr_box_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->boxes, m->boxg, C, T, dq, drpy,
                                                      dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
                                                      m->capg_flag.as<int>());
+                                  return FBR_OK;
                               });
 }
 
@@ -1846,7 +1886,57 @@ extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, c
                                   hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->hulls, m->hullg, C, T, dq,
                                                      drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
                                                      m->capg_flag.as<int>());
+                                  return FBR_OK;
                               });
+}
+
+// A hull set with triangle meshes attached: the pairs without a mesh through fbr_hull_grad_kernel, into their columns; the pairs with one
+// through the three stages of csrc/fbr_mesh_grad.h.
+extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                           const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                           int32_t out_mem)
+{
+    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
+        set_err("epsilon must be finite and positive");
+        return FBR_E_INVALID;
+    }
+    if (m->hulls.nhulls == 0 || m->hulls.npairs == 0) {
+        set_err("no hull set with at least one pair (fbr_model_set_hulls)");
+        return FBR_E_INVALID;
+    }
+    if (!m->has_meshes) {
+        set_err("fbr_mesh_distance_gradients: the hull set has no triangle meshes attached (fbr_model_set_hull_meshes); fbr_hull_distance_gradients "
+                "serves a set of hulls only");
+        return FBR_E_INVALID;
+    }
+    double se, omc;
+    fbr_boxgrad_trig(epsilon, &se, &omc);
+    return distance_gradients(
+        m, "fbr_mesh_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem, m->hulls.npairs, m->hulls.fr.nslots,
+        [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
+            double *ddist, double *dgrad) -> int {
+            const long tiles = (C + 63) / 64, ph = m->hulls_plain.npairs, pm = m->meshes.npairs, ni = m->meshg.nitems;
+            if (ph > 0)
+                hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)std::min<long>(ph * tiles, grid)), dim3(64), 0, m->stream, m->dm, m->hulls_plain,
+                                   m->hullg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
+                                   m->capg_flag.as<int>());
+            if (pm == 0) return FBR_OK;
+            // the recorded poses [ni][13][C] | the stencil distances [ni][C]
+            if (int rc = m->meshg_work.ensure((size_t)ni * (FBR_MESHGRAD_REL + 1) * (size_t)C * sizeof(double))) return rc;
+            double *rel = m->meshg_work.as<double>(), *dv = rel + (size_t)ni * FBR_MESHGRAD_REL * (size_t)C;
+            hipLaunchKernelGGL(fbr_mesh_grad_frames_kernel, dim3((unsigned)std::min<long>(pm * tiles, grid)), dim3(64), 0, m->stream, m->dm, m->hulls,
+                               m->hullg, m->meshes, m->meshg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(),
+                               m->capg_flag.as<int>());
+            {
+                ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
+                hipLaunchKernelGGL(fbr_mesh_grad_dist_kernel, dim3((unsigned)std::min<long>(ni * tiles, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
+                                   m->hulls, m->meshes, m->meshg, C, (const double *)rel, dv);
+            }
+            hipLaunchKernelGGL(fbr_mesh_grad_quot_kernel, dim3((unsigned)((C * pm + 255) / 256)), dim3(256), 0, m->stream, m->hulls, m->meshes, m->meshg,
+                               (int)m->hm.n, C, T, dsmp, dpose, epsilon, (const double *)dv, ddist, dgrad);
+            return FBR_OK;
+        });
 }
 
 extern "C" int fbr_predict(fbr_model *m, const fbr_states *st, const double *x, double *tau_out, int32_t out_mem)

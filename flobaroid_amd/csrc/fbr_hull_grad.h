@@ -53,7 +53,9 @@ __device__ __forceinline__ void fbr_hullgrad_tables(const DevHulls &hs, int h, F
     H->diam = ((fbr_cdouble_ptr)(unsigned long)hs.diam)[h];
 }
 
-// Work items (pair, tile of 64 candidates), one wave each, pair-major; the arguments as for fbr_box_grad_kernel.
+// Work items (pair, tile of 64 candidates), one wave each, pair-major; the arguments as for fbr_box_grad_kernel.  hs: the set, or the plain
+// pairs of a set with meshes attached (hs.col: their columns among the hs.ldp pairs of the whole set, which sample / scale / pose, dist
+// and grad are laid out by, as hg.pair is; fbr_mesh_grad.h has the other pairs).
 __global__ __launch_bounds__(64) void fbr_hull_grad_kernel(DevModel m, DevHulls hs, DevHullGrad hg, long C, long T, const double *__restrict__ q,
                                                            const double *__restrict__ rpy, const double *__restrict__ bpos,
                                                            const long *__restrict__ sample, const double *__restrict__ scale,
@@ -69,14 +71,15 @@ __global__ __launch_bounds__(64) void fbr_hull_grad_kernel(DevModel m, DevHulls 
         const int valid = (int)min(64L, C - c0);
         const long c = c0 + min(lane, valid - 1);  // lanes behind the last candidate repeat it and store nothing
         const bool live = lane < valid;
-        const long e = c * P + k;
+        const int col = hs.col ? FBR_UNI(hs.col[k]) : (int)k;  // (a set split by fbr_model_set_hull_meshes: the pair's column among all pairs)
+        const long e = c * hs.ldp + col;
         const long s = sample[e], ps0 = pose ? pose[e] : s, ps = ps0 < 0 ? s : ps0;
         const bool bad = s < -1 || s >= T || ps0 < -1 || ps0 >= T;
         if (bad && live) *flag = 1;
         const bool eval = live && s >= 0 && !bad;
         const long sr = c * T + min(max(s, 0L), T - 1), pr = c * T + min(max(ps, 0L), T - 1);
         const double sc = scale ? scale[e] : 1.0;
-        const int4 pt = hg.pair[k];
+        const int4 pt = hg.pair[col];
         const int ka = FBR_UNI(pt.x), kb = FBR_UNI(pt.y), sla = FBR_UNI(pt.z), slb = FBR_UNI(pt.w);
         const int2 ids = hs.pairs[k];
         const int ia = FBR_UNI(ids.x), ib = FBR_UNI(ids.y);

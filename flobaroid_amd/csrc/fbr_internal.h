@@ -26,6 +26,7 @@
 #include "fbr_hull.h"
 #include "fbr_hull_grad.h"
 #include "fbr_mesh.h"
+#include "fbr_mesh_grad.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -186,6 +187,10 @@ struct fbr_model {
     DevBuf mesh_tab;
     DevHullGrad hullg = {0, nullptr, nullptr};  // fbr_hull_distance_gradients: ancestor masks and per-pair steps / offset slots of the set above
     DevBuf hullg_tab;
+    // fbr_mesh_distance_gradients (csrc/fbr_mesh_grad.h): the stencil points of the mesh pairs (built with the attachments) and the call's
+    // workspace, the recorded poses | the stencil distances -- buffers of its own: what fbr_candidate_hull_distances reads never moves
+    DevMeshGrad meshg = {0, 0, nullptr, nullptr, nullptr};
+    DevBuf meshg_tab, meshg_work;
     // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its
     // steps on the device, the per-sample records, the results of a host-memory call
     FbrKinIdProgram susp_prog;

@@ -16,7 +16,8 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
   candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``;
 * ``candidate_collision_gradient`` -- the collision rows of the constraint Jacobian in capsule mode (analyticalGradient.py:955-1027) from
-  ``Engine.capsule_distance_gradients`` + ``Engine.fourier_position_chain``;
+  ``Engine.capsule_distance_gradients`` + ``Engine.fourier_position_chain``; behind keywords the box, hull and triangle-mesh rows
+  (``Engine.box_distance_gradients``, ``Engine.hull_distance_gradients``, ``Engine.mesh_distance_gradients``);
 * ``candidate_gradients_from_coefficients`` -- everything ``IpoptProblem.gradient`` / ``.jacobian`` need of many candidates: the above plus
   the soft-cost gradients and the position, velocity and torque rows of the constraint Jacobian (analyticalGradient.py:764-953) from
   ``Engine.torque_row_sweep`` + ``Engine.fourier_state_chain``.
@@ -408,11 +409,34 @@ def _has_meshes(collision) -> bool:
 
 
 def _refuse_mesh_gradient(collision) -> None:
-    """gradients of mesh pairs are not built: a set with triangle meshes is refused by the names of its meshed links"""
+    """without ``mesh_gradient=True`` a set with triangle meshes is refused by the names of its meshed links (the message is the one from
+    before the mesh gradient was built: callers match it)"""
     if _has_meshes(collision):
         links = [collision["hulls"][int(h)].link_name for h in collision["meshes"]]
         raise ValueError(f"gradients on the device do not cover triangle meshes: the collision set has meshes on {links} (fullMeshLinks / "
                          "collisionMode 'full'); the constraint values are served, their gradients are not built")
+
+
+def _wants_mesh_gradient(config, collision, mesh_gradient) -> bool:
+    """True when ``mesh_gradient=True`` selects the rows of ``Engine.mesh_distance_gradients``: a set with triangle meshes and a
+    configuration that uses them (``collisionMode: "full"``, or ``fullMeshLinks`` in ``"convex"``).  False without the keyword: every
+    refusal of before then holds.  The keyword with anything else raises."""
+    if not mesh_gradient:
+        return False
+    mode = config.get("collisionMode", "capsule")
+    if mode in ("capsule", "box"):
+        raise ValueError(f"mesh_gradient=True: collisionMode '{mode}' has no triangle meshes (they belong to collisionMode 'full' and to "
+                         "fullMeshLinks in collisionMode 'convex')")
+    if not _has_meshes(collision):
+        raise ValueError("mesh_gradient=True: the collision set has no triangle meshes (flobaroid_amd.collision.collision_set(..., hulls=, "
+                         "meshes=)); hull_gradient=True serves a set of hulls only")
+    if mode != "full" and not config.get("fullMeshLinks"):
+        raise ValueError(f"mesh_gradient=True: collisionMode '{mode}' without fullMeshLinks does not use the meshes of the collision set")
+    if "hulls" not in collision or not _has_hull_pairs(collision) or "columns" not in collision:
+        raise ValueError("mesh_gradient=True: the collision set needs hull pairs (flobaroid_amd.collision.collision_set(..., hulls=, meshes=))")
+    if (np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)[:, 0] != 2).any():
+        raise ValueError("mesh_gradient=True: the collision set has capsule or box pairs")
+    return True
 
 
 _NO_HULL_GRADIENT = ("gradients on the device cover capsule and box pairs only: the collision set has hull pairs (collisionMode 'convex'; the "
@@ -718,7 +742,7 @@ def _chain_positions(engine, candidates, freq, sample, scale, grad_q, max_bytes)
 
 def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: list, freq: float, config: dict, collision: dict,
                                  constraints: dict | None = None, max_bytes: int = 2**31, box_gradient: bool = False, epsilon=None,
-                                 hull_gradient: bool = False) -> dict:
+                                 hull_gradient: bool = False, mesh_gradient: bool = False) -> dict:
     """The collision block ``g = distance - margin`` (C, P) of ``ncand`` equal candidates stacked in ``states`` and its derivative with
     respect to the entries of the candidates' ``fourier_coefficients`` dicts, from which ``states`` were generated at ``freq`` Hz
     (``candidate_states``).  ``collision``: capsules, pairs and optionally margins (``flobaroid_amd.collision.collision_set``);
@@ -744,11 +768,20 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     rows are the reference's central differences of the hull distance over ``epsilon`` (as above) from ``Engine.hull_distance_gradients``
     at the evaluation points of the constraint block, transitions included, in the reference's pair order.  In the modes ``"capsule"`` and
     ``"box"`` the keyword changes nothing: a set with hull pairs stays refused there.  A set with triangle meshes (``fullMeshLinks``,
-    ``collisionMode: "full"``) is refused by the names of its meshed links, whatever the keywords: gradients of mesh pairs are not built."""
+    ``collisionMode: "full"``) is refused by the names of its meshed links, whatever the keywords above.
+
+    ``mesh_gradient=True`` serves such a set: it needs triangle meshes in ``collision`` and a configuration that uses them
+    (``collisionMode: "full"``, or ``fullMeshLinks`` in ``"convex"``), installs the hull set with its meshes and takes the rows from
+    ``Engine.mesh_distance_gradients`` exactly as ``hull_gradient=True`` takes them from the hull call: the reference's central
+    differences of the mesh distance, the plain pairs of the set as the hull call returns them.  A pair in intersection has distance 0.0
+    and an exactly zero row (a mesh carries no penetration depth).  The keyword with a set without meshes, or in the modes ``"capsule"``
+    and ``"box"``, raises ``ValueError``."""
     _check_config(config)
-    _refuse_mesh_gradient(collision)
+    mesh_rows = _wants_mesh_gradient(config, collision, mesh_gradient)
+    if not mesh_rows:
+        _refuse_mesh_gradient(collision)
     mode = config.get("collisionMode", "capsule")
-    if _wants_hull_gradient(config, collision, hull_gradient):
+    if mesh_rows or _wants_hull_gradient(config, collision, hull_gradient):
         C, n = int(ncand), engine.n
         bpos = states.get("base_position") if engine.floating else None
         cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision)
@@ -756,8 +789,10 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
         cols = np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)
         sel = np.argsort(cols[:, 1], kind="stable")  # (the set's own pair order)
         smp, sc, pose = (np.ascontiguousarray(np.asarray(cons[k])[:, sel]) for k in ("eval_sample", "eval_scale", "eval_pose"))
-        engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)))
-        dg = engine.hull_distance_gradients(states, C, smp, scale=sc, pose_sample=pose, base_pos=bpos, epsilon=eps)
+        kw = {"meshes": collision["meshes"]} if mesh_rows else {}
+        engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)), **kw)
+        gradients = engine.mesh_distance_gradients if mesh_rows else engine.hull_distance_gradients
+        dg = gradients(states, C, smp, scale=sc, pose_sample=pose, base_pos=bpos, epsilon=eps)
         part, nh = _chain_positions(engine, candidates, freq, smp, sc, dg["grad_q"], max_bytes)
         out, grad_q = np.zeros((C, cols.shape[0], part.shape[2])), np.zeros((C, cols.shape[0], n))
         out[:, sel] = part
@@ -811,12 +846,14 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
 
 
 def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
-                                                   max_bytes: int = 2**31, box_gradient: bool = False, hull_gradient: bool = False) -> dict:
+                                                   max_bytes: int = 2**31, box_gradient: bool = False, hull_gradient: bool = False,
+                                                   mesh_gradient: bool = False) -> dict:
     """``candidate_collision_gradient`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
-    (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``, ``hull_gradient``: as there."""
+    (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``, ``hull_gradient``, ``mesh_gradient``:
+    as there."""
     st = candidate_states(engine, candidates, int(T), float(freq), device=True)
     return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes,
-                                        box_gradient=box_gradient, hull_gradient=hull_gradient)
+                                        box_gradient=box_gradient, hull_gradient=hull_gradient, mesh_gradient=mesh_gradient)
 
 
 def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
@@ -952,7 +989,7 @@ def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_a
 
 def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict, joint_names,
                                           config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1,
-                                          box_gradient: bool = False, hull_gradient: bool = False) -> dict:
+                                          box_gradient: bool = False, hull_gradient: bool = False, mesh_gradient: bool = False) -> dict:
     """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
     and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
     one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
@@ -975,12 +1012,15 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     the box distance over the same ``epsilon`` (``candidate_collision_gradient``).  ``hull_gradient=False``: a ``collision`` set with hull
     pairs raises ``ValueError``; ``True`` with ``collisionMode: "convex"``: the rows of the hull pairs are the reference's central
     differences of the hull distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base,
-    gravity-only models (refused), gradients of a ``collision`` set with triangle meshes (``fullMeshLinks``, ``collisionMode: "full"``:
-    refused by the names of the meshed links)."""
+    gravity-only models (refused).  ``mesh_gradient=False``: a ``collision`` set with triangle meshes (``fullMeshLinks``, ``collisionMode:
+    "full"``) is refused by the names of the meshed links; ``True`` with such a set and configuration: the rows of all its pairs come from
+    ``Engine.mesh_distance_gradients`` (``candidate_collision_gradient``)."""
     _check_config(config)
-    _refuse_mesh_gradient(collision)
-    hull_rows = collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
-    if _has_hull_pairs(collision) and not hull_rows:
+    mesh_rows = collision is not None and _wants_mesh_gradient(config, collision, mesh_gradient)
+    if not mesh_rows:
+        _refuse_mesh_gradient(collision)
+    hull_rows = not mesh_rows and collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
+    if _has_hull_pairs(collision) and not (hull_rows or mesh_rows):
         raise ValueError(_NO_HULL_GRADIENT)
     if _has_box_pairs(collision) and not box_gradient:
         raise ValueError("gradients on the device cover capsule pairs only: the collision set has box pairs (the reference differentiates those "
@@ -1012,7 +1052,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     con_grad = _gradient_dict(con, n, nh)
     if coll is not None:
         cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll, box_gradient=box_gradient,
-                                          epsilon=eps, hull_gradient=hull_rows)["grad"]
+                                          epsilon=eps, hull_gradient=hull_rows, mesh_gradient=mesh_rows)["grad"]
         con_grad = {k: np.concatenate([v, cg[k]], axis=1) for k, v in con_grad.items()}
     return {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
             "layout": lay, "ag_cache": ag, "objectives": obj}

@@ -88,7 +88,8 @@ typedef struct {
  * tests/test_capsule_abi.py pins: two new entry points, no existing signature, struct or array size changed -- fbr_regressor_weights,
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
- * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes. */
+ * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes;
+ * fbr_mesh_distance_gradients. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -314,7 +315,7 @@ int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, const doubl
  * Brute force over the triangles, culled by bounding spheres without changing a bit (csrc/fbr_mesh.h); the two limits keep a launch from
  * running for minutes: they admit every pair of the WALK-MAN simple/ collision meshes (170 x 160 = 27 200) and refuse visual meshes.
  * nmesh = 0 clears the attachments, and so does every later fbr_model_set_hulls.  fbr_hull_distance_gradients returns FBR_E_UNSUPPORTED
- * while meshes are attached.  FBR_E_INVALID: no hull set, a hull index out of range or given twice, a world hull (the reference never
+ * while meshes are attached: fbr_mesh_distance_gradients serves such a set.  FBR_E_INVALID: no hull set, a hull index out of range or given twice, a world hull (the reference never
  * meshes world links), tbeg not starting at 0 or not ascending, a mesh with no triangle, non-finite data, a triangle vertex outside one
  * of its hull's planes by more than 1e-9 x the hull's diameter (the culling sphere of a hull is taken over its vertices and its mesh's), a mesh
  * of more than FBR_MAX_MESH_TRIANGLES triangles, a pair of the set with T_A x T_B above FBR_MAX_MESH_PAIR_WORK; the attachments in place
@@ -383,6 +384,24 @@ int fbr_box_distance_gradients(fbr_model *m, const fbr_states *st, const double 
  * sample or pose_sample outside -1 .. T - 1 (found on the device, which reads such an entry clamped; the outputs are then undefined).
  */
 int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                int32_t out_mem);
+
+/*
+ * The same for a hull set with triangle meshes attached (fbr_model_set_hull_meshes): the gradient half of fullMeshLinks and collisionMode
+ * "full".  The reference has no rule of its own for meshes: the same central differences of whatever distance the link's geometry gives.
+ * Arguments, memory spaces, the zeroing of grad_q_out and every rule exactly as for fbr_hull_distance_gradients; npairs is the hull set's,
+ * ALL its pairs:
+ *   a pair without a mesh   the bytes fbr_hull_distance_gradients returns for it from the same set without meshes
+ *   a pair with a mesh      dist_out the mesh distance of fbr_candidate_hull_distances at the configuration, grad_q_out its central
+ *                           differences, the links moved and the entries left exact zeros as for the hulls
+ * A mesh distance is never negative and exactly 0.0 on contact, so an entry whose two stencil values are both 0.0 is exactly 0.0: a mesh
+ * carries no penetration depth, and a pair in intersection gives the optimiser no direction out of it (FCL's BVH gives the reference the
+ * same zeros).  A NaN pose gives NaN in dist_out and in the evaluated joints' entries only.  No atomics: the same bits on every run.  The
+ * mesh pairs take a workspace of ncand x (stencil points of all mesh pairs) x 14 doubles (csrc/fbr_mesh_grad.h).
+ * FBR_E_INVALID: what fbr_hull_distance_gradients refuses, and a set without meshes attached (that call serves it).
+ */
+int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                 const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
                                 int32_t out_mem);
 
@@ -576,7 +595,8 @@ int fbr_central_diff(fbr_model *m, const double *A, const double *T, double *D, 
 #define FBR_PROF_KIN 0       /* link kinematics kernel */
 #define FBR_PROF_REGRESSOR 1 /* materialising regressor kernel */
 #define FBR_PROF_GRAM 2      /* fused regressor->Gram MFMA kernel; the in-place weight GEMM of fbr_regressor_weights (its writer: REGRESSOR) */
-#define FBR_PROF_REDUCE 3    /* slice reduction / scatter of the Gram partials; chain kernel + finishing pass of fbr_fourier_gradient */
+#define FBR_PROF_REDUCE 3    /* slice reduction / scatter of the Gram partials; chain kernel + finishing pass of fbr_fourier_gradient;
+                                stage B of fbr_mesh_distance_gradients by itself (the whole call, stage B included, is under KIN) */
 #define FBR_PROF_ID 4        /* inverse dynamics / predict kernel */
 #define FBR_PROF_TSQR 5      /* TSQR fold kernels (level 0 per chunk, merge tree) */
 #define FBR_PROF_PACK 6      /* tile-image packing kernel of the fused Gram pass (producer stream) */

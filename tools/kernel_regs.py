@@ -1,7 +1,7 @@
 """Register / spill / LDS figures of every kernel in libfbr.so (code-object notes).  python tools/kernel_regs.py [family | substring] [lib]
 Families: box (csrc/fbr_box.h and the finishing pass it shares), hull (csrc/fbr_hull.h, the frames kernel and the finishing pass it
 shares), hullgrad (csrc/fbr_hull_grad.h), mesh (csrc/fbr_mesh.h and the hull
-pairs kernel it runs beside), capsule; anything else is matched as a substring."""
+pairs kernel it runs beside), meshgrad (csrc/fbr_mesh_grad.h beside the hull gradient kernel and the mesh pairs kernel), capsule; anything else is matched as a substring."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "flobaroid_amd", "libfbr.so")
@@ -23,7 +23,7 @@ with tempfile.TemporaryDirectory() as td:
         notes += subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", f"{td}/co{i}"], text=True)
 pat = re.compile(r"\.agpr_count:\s+(\d+).*?\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.sgpr_spill_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", re.S)
 FAMILIES = {"box": ("fbr_box_", "fbr_capsule_finish_kernel"), "hull": ("fbr_hull_", "fbr_box_frames_kernel", "fbr_capsule_finish_kernel"), "hullgrad": ("fbr_hull_grad_kernel",), "mesh": ("fbr_mesh_", "fbr_hull_pairs_kernel"),
-            "capsule": ("fbr_capsule_",)}
+            "meshgrad": ("fbr_mesh_grad_", "fbr_hull_grad_kernel", "fbr_mesh_pairs_kernel"), "capsule": ("fbr_capsule_",)}
 frag = sys.argv[1] if len(sys.argv) > 1 else ""
 frags = FAMILIES.get(frag, (frag,))
 for m in pat.finditer(notes):
