@@ -25,48 +25,14 @@ extern "C" int fbr_filtfilt(fbr_model *m, const double *b, const double *a, int3
         set_err("fbr_filtfilt: bad arguments (2 <= ncoef <= 12, a[0] != 0, ld >= ncols)");
         return FBR_E_INVALID;
     }
-    const int pad = 3 * ncoef, p = ncoef - 1;
+    const int pad = 3 * ncoef;
     if (S <= pad) {
         set_err("fbr_filtfilt: the signal must be longer than the padding of 3 * ncoef samples");
         return FBR_E_INVALID;
     }
     if (int rc_enter = enter_blocking(m)) return rc_enter;
     FbrIir f;
-    memset(&f, 0, sizeof(f));
-    f.nc = ncoef;
-    for (int i = 0; i < ncoef; i++) {
-        f.b[i] = b[i] / a[0];
-        f.a[i] = a[i] / a[0];
-    }
-    {  // scipy.signal.lfilter_zi: steady state of a unit step
-        double bs = 0.0, as = 0.0;
-        for (int k = 1; k < ncoef; k++) bs += f.b[k] - f.a[k] * f.b[0];
-        for (int k = 0; k < ncoef; k++) as += f.a[k];
-        f.zi[0] = bs / as;
-        double asum = 1.0, csum = 0.0;
-        for (int k = 1; k < p; k++) {
-            asum += f.a[k];
-            csum += f.b[k] - f.a[k] * f.b[0];
-            f.zi[k] = asum * f.zi[0] - csum;
-        }
-    }
-    {  // M^LB of z' = M z + g x (y = z_0 + b_0 x; M[i][0] = -a[i+1], M[i][i+1] = 1): column j = the zero-input recurrence run LB steps
-       // from e_j, i.e. the filter's own arithmetic.  NOT by repeated squaring: the companion matrix of a low cut-off is far from normal
-       // (poles clustered at z = 1: |M^k| grows like k^(p-1) before it decays), the rounding errors of the squarings are relative to
-       // those intermediate norms and do not decay with them -- order 5 at 0.016 of Nyquist (filterLowPass1 = [8 Hz, 5] on a 1 kHz
-       // recording) gave an M^LB with entries far above 1 and NaN / 1e190 outputs from the second block on (found by the randomised
-       // sweep); in the recurrence the errors made at the peak are carried by the same decaying dynamics.
-        for (int j = 0; j < p; j++) {
-            std::vector<double> z((size_t)p, 0.0);
-            z[(size_t)j] = 1.0;
-            for (long t = 0; t < FBR_SIG_LB; t++) {
-                const double y = z[0];
-                for (int i = 0; i + 1 < p; i++) z[(size_t)i] = z[(size_t)i + 1] - y * f.a[i + 1];
-                z[(size_t)p - 1] = -y * f.a[p];
-            }
-            for (int i = 0; i < p; i++) f.Mp[i * p + j] = z[(size_t)i];
-        }
-    }
+    fbr_sig_design(f, b, a, ncoef);
     int rc;
     double *dX = nullptr;
     const size_t xcount = (size_t)(S - 1) * ld + ncols;
