@@ -1,6 +1,6 @@
 // fbr_api.hip -- C-ABI of libfbr (see include/fbr.h): model handle, options, state staging, per-sample entry points.
 // gfx950 only; there is deliberately no CPU path in this library.  The fused Gram lives in fbr_gram_api.hip, the TSQR in
-// fbr_tsqr_api.hip, the signal conditioning in fbr_signal_api.hip.
+// fbr_tsqr_api.hip, the signal conditioning in fbr_signal_api.hip, the collision sets and their calls in fbr_collision_api.hip.
 #define FBR_KERNELS_CORE
 #include "fbr_internal.h"
 #include "fbr_reduce.h"
@@ -1031,912 +1031,6 @@ extern "C" int fbr_suspended_base_motion(fbr_model *m, const fbr_states *st, int
     HIPCHK(hipStreamSynchronize(m->stream));
     prof_collect(m);
     return FBR_OK;
-}
-
-// ---- capsule collision distances (csrc/fbr_capsule.h) --------------------------------------------------------------------------------
-extern "C" int fbr_model_set_capsules(fbr_model *m, int32_t ncaps, const int32_t *link, const double *seg, const double *radius, int32_t npairs,
-                                      const int32_t *pairs)
-{
-    if (!m) {
-        set_err("null model");
-        return FBR_E_INVALID;
-    }
-    if (ncaps < 0 || npairs < 0 || ncaps > FBR_MAX_CAPSULES || npairs > FBR_MAX_CAPSULE_PAIRS) {
-        set_err("capsule set: at most " + std::to_string(FBR_MAX_CAPSULES) + " capsules and " + std::to_string(FBR_MAX_CAPSULE_PAIRS) + " pairs");
-        return FBR_E_INVALID;
-    }
-    if ((ncaps > 0 && (!link || !seg || !radius)) || (npairs > 0 && !pairs)) {
-        set_err("capsule set: null array");
-        return FBR_E_INVALID;
-    }
-    const FbrHostModel &hm = m->hm;
-    for (int c = 0; c < ncaps; c++) {
-        if (link[c] < 0 || link[c] >= hm.L) {
-            set_err("capsule " + std::to_string(c) + ": link index out of range");
-            return FBR_E_INVALID;
-        }
-        if (!(radius[c] >= 0.0) || !std::isfinite(radius[c])) {
-            set_err("capsule " + std::to_string(c) + ": the radius must be finite and not negative");
-            return FBR_E_INVALID;
-        }
-        for (int i = 0; i < 6; i++)
-            if (!std::isfinite(seg[6 * c + i])) {
-                set_err("capsule " + std::to_string(c) + ": non-finite endpoint");
-                return FBR_E_INVALID;
-            }
-    }
-    for (int k = 0; k < npairs; k++) {
-        const int a = pairs[2 * k], b = pairs[2 * k + 1];
-        if (a < 0 || a >= ncaps || b < 0 || b >= ncaps || a == b) {
-            set_err("capsule pair " + std::to_string(k) + ": capsule index out of range, or a capsule paired with itself");
-            return FBR_E_INVALID;
-        }
-    }
-    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->caps = DevCapsules{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (ncaps == 0) return FBR_OK;
-    FbrKinIdProgram prog;
-    try {
-        fbr_kinid_build(hm, prog);
-    } catch (const std::exception &e) {
-        set_err(e.what());
-        return FBR_E_INVALID;
-    }
-    // capsules sorted by the step of their link (stable: the caller's order within a link)
-    std::vector<int> stepof(hm.L, 0), capbeg(prog.nsteps + 1, 0), capid(ncaps);
-    for (int k = 0; k < prog.nsteps; k++) stepof[prog.steps[(size_t)k * FBR_KINID_STEP]] = k;
-    for (int c = 0; c < ncaps; c++) capbeg[stepof[link[c]] + 1]++;
-    for (int k = 0; k < prog.nsteps; k++) capbeg[k + 1] += capbeg[k];
-    std::vector<int> fill(capbeg.begin(), capbeg.end() - 1);
-    std::vector<double> sseg((size_t)ncaps * 6);
-    for (int c = 0; c < ncaps; c++) {
-        const int slot = fill[stepof[link[c]]]++;
-        capid[slot] = c;
-        for (int i = 0; i < 6; i++) sseg[(size_t)slot * 6 + i] = seg[6 * c + i];
-    }
-    // one allocation: seg | radius | steps | capbeg | capid | pairs  (doubles first: every table keeps its alignment)
-    const size_t nd = (size_t)ncaps * 7, ni = prog.steps.size() + capbeg.size() + (size_t)ncaps + 1 + 2 * (size_t)std::max(npairs, 1);  // (+ 1: the padding in front of the pairs)
-    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int));
-    double *hd = (double *)host.data();
-    std::copy(sseg.begin(), sseg.end(), hd);
-    std::copy(radius, radius + ncaps, hd + (size_t)ncaps * 6);
-    int *hi = (int *)(hd + nd), *hsteps = hi, *hcapbeg = hsteps + prog.steps.size(), *hcapid = hcapbeg + capbeg.size();
-    int *hpairs = hcapid + ncaps + ((prog.steps.size() + capbeg.size() + (size_t)ncaps) & 1);  // (int2: 8-byte aligned)
-    std::copy(prog.steps.begin(), prog.steps.end(), hsteps);
-    std::copy(capbeg.begin(), capbeg.end(), hcapbeg);
-    std::copy(capid.begin(), capid.end(), hcapid);
-    std::copy(pairs, pairs + 2 * (size_t)npairs, hpairs);
-    if (int rc = m->cap_tab.ensure(host.size() + 8)) return rc;
-    HIPCHK(hipMemcpy(m->cap_tab.p, host.data(), host.size(), hipMemcpyHostToDevice));
-    const char *base = (const char *)m->cap_tab.p;
-    DevCapsules dc;
-    dc.nsteps = prog.nsteps;
-    dc.nslots = prog.nslots;
-    dc.ncaps = ncaps;
-    dc.npairs = npairs;
-    dc.seg = (const double *)base;
-    dc.radius = dc.seg + (size_t)ncaps * 6;
-    dc.steps = (const int *)(base + ((const char *)hsteps - host.data()));
-    dc.capbeg = (const int *)(base + ((const char *)hcapbeg - host.data()));
-    dc.capid = (const int *)(base + ((const char *)hcapid - host.data()));
-    dc.pairs = (const int2 *)(base + ((const char *)hpairs - host.data()));
-    // tables of fbr_capsule_distance_gradients: per pair the steps of the two links and the slots of the two capsules | ancestor masks
-    std::vector<int> stepof2, anc, slotof(ncaps);
-    fbr_capgrad_ancestors(hm, prog, stepof2, anc);
-    for (int sl = 0; sl < ncaps; sl++) slotof[capid[sl]] = sl;
-    std::vector<int> gt((size_t)4 * std::max(npairs, 1) + anc.size(), 0);
-    for (int k = 0; k < npairs; k++) {
-        const int a = pairs[2 * k], b = pairs[2 * k + 1];
-        gt[4 * (size_t)k] = stepof[link[a]];
-        gt[4 * (size_t)k + 1] = stepof[link[b]];
-        gt[4 * (size_t)k + 2] = slotof[a];
-        gt[4 * (size_t)k + 3] = slotof[b];
-    }
-    std::copy(anc.begin(), anc.end(), gt.begin() + (size_t)4 * std::max(npairs, 1));
-    if (int rc = m->capg_tab.ensure(gt.size() * sizeof(int))) return rc;
-    HIPCHK(hipMemcpy(m->capg_tab.p, gt.data(), gt.size() * sizeof(int), hipMemcpyHostToDevice));
-    m->capg.W = fbr_capgrad_words(prog.nsteps);
-    m->capg.pair = (const int4 *)m->capg_tab.p;
-    m->capg.anc = m->capg_tab.as<int>() + (size_t)4 * std::max(npairs, 1);
-    m->caps = dc;
-    return FBR_OK;
-}
-
-extern "C" int fbr_candidate_capsule_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step,
-                                               double *dist_out, int64_t *idx_out, int32_t out_mem)
-{
-    if (!m || !st || !dist_out || !idx_out) {
-        set_err("null model / states / dist_out / idx_out");
-        return FBR_E_INVALID;
-    }
-    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q) {
-        set_err("bad fbr_states header, or q is NULL");
-        return FBR_E_INVALID;
-    }
-    if (m->caps.ncaps == 0 || m->caps.npairs == 0) {
-        set_err("no capsule set with at least one pair (fbr_model_set_capsules)");
-        return FBR_E_INVALID;
-    }
-    if (ncand < 1 || step < 1) {
-        set_err("ncand and step must be at least 1");
-        return FBR_E_INVALID;
-    }
-    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
-        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
-        return FBR_E_INVALID;
-    }
-    if (int rc = enter_blocking(m)) return rc;
-    const FbrHostModel &hm = m->hm;
-    const DevCapsules &cp = m->caps;
-    const long S = st->num_samples, C = ncand, P = cp.npairs;
-    const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr;
-    int rc;
-    if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
-    if (hm.floating && st->base_rpy) {
-        if ((rc = stage_one(m, m->st_rpy, st->base_rpy, (size_t)S * 3, st->mem, &drpy))) return rc;
-        if ((rc = stage_one(m, m->st_bpos, base_pos, (size_t)S * 3, st->mem, &dbp))) return rc;
-    }
-    DevCapTiles tl;
-    tl.T = S / C;
-    tl.step = step;
-    tl.Tc = (tl.T + step - 1) / step;
-    tl.tiles = (tl.Tc + 63) / 64;
-    tl.nblk = C * tl.tiles;
-    // blocks per launch: the endpoints of the blocks in flight stay below 256 MB, their partials below 64 MB
-    const size_t ep_blk = (size_t)cp.ncaps * 6 * 64 * sizeof(double), part_blk = (size_t)P * (sizeof(double) + sizeof(long));
-    long ch = (long)std::min((size_t)(256u << 20) / ep_blk, (size_t)(64u << 20) / part_blk);
-    if (m->opt.chunk_samples >= 1) ch = (long)m->opt.chunk_samples / 64;  // (tests: the multi-launch path at small sizes)
-    ch = std::max(1L, std::min(ch, tl.nblk));
-    if ((rc = m->cap_ep.ensure((size_t)ch * ep_blk))) return rc;
-    if ((rc = m->cap_part.ensure((size_t)ch * part_blk))) return rc;
-    double *pval = m->cap_part.as<double>();
-    long *pidx = (long *)(pval + (size_t)ch * P);
-    const size_t cnt = (size_t)C * P;
-    double *val = dist_out;
-    long *idx = (long *)idx_out;
-    if (out_mem == FBR_HOST) {
-        if ((rc = m->cap_out.ensure(cnt * (sizeof(double) + sizeof(long))))) return rc;
-        val = m->cap_out.as<double>();
-        idx = (long *)(val + cnt);
-    }
-    const int ldn = std::max(hm.n, 1) | 1;
-    const size_t lds_want = (size_t)64 * ldn * sizeof(double);
-    const int stage = lds_want <= (size_t)64 * 1024;  // up to 127 DOF; beyond, the lanes read their rows from memory
-    const size_t lds = stage ? lds_want : 0;
-    const int pgrid = (int)std::min<long>(ch, (long)m->num_cus * 8);
-    if ((rc = m->cap_scratch.ensure((size_t)pgrid * std::max(cp.nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
-    const long nbatch = (P + FBR_CAPSULE_BATCH - 1) / FBR_CAPSULE_BATCH;
-    if (lds) HIPCHK(hipFuncSetAttribute((const void *)fbr_capsule_points_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    for (long b0 = 0; b0 < tl.nblk; b0 += ch) {
-        const long nb = std::min(ch, tl.nblk - b0);
-        {
-            ProfScope ps(m, FBR_PROF_KIN);
-            hipLaunchKernelGGL(fbr_capsule_points_kernel, dim3((unsigned)std::min<long>(nb, pgrid)), dim3(64), lds, m->stream, m->dm, cp, tl, b0, nb, stage,
-                               ldn, dq, drpy, dbp, m->cap_ep.as<double>(), m->cap_scratch.as<double>());
-            HIPCHK(hipGetLastError());
-        }
-        {
-            ProfScope ps(m, FBR_PROF_REDUCE);
-            hipLaunchKernelGGL(fbr_capsule_pairs_kernel, dim3((unsigned)std::min<long>(nb * nbatch, (long)m->num_cus * 16)), dim3(64), 0, m->stream, cp, tl,
-                               b0, nb, (const double *)m->cap_ep.as<double>(), pval, pidx);
-            HIPCHK(hipGetLastError());
-            const long cands = (b0 + nb - 1) / tl.tiles - b0 / tl.tiles + 1;
-            hipLaunchKernelGGL(fbr_capsule_finish_kernel, dim3((unsigned)((cands * P + 255) / 256)), dim3(256), 0, m->stream, tl, (int)P, b0, nb,
-                               (const double *)pval, (const long *)pidx, val, idx);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    if (out_mem == FBR_HOST) {
-        HIPCHK(hipMemcpyAsync(dist_out, val, cnt * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(idx_out, idx, cnt * sizeof(long), hipMemcpyDeviceToHost, m->stream));
-    }
-    HIPCHK(hipStreamSynchronize(m->stream));
-    prof_collect(m);
-    return FBR_OK;
-}
-
-// ---- box collision distances (csrc/fbr_box.h) ----------------------------------------------------------------------------------------
-extern "C" int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *link, const double *half, const double *center, const double *rot,
-                                   int32_t center_in_link_axes, int32_t npairs, const int32_t *pairs)
-{
-    if (!m) {
-        set_err("null model");
-        return FBR_E_INVALID;
-    }
-    if (nboxes < 0 || npairs < 0 || nboxes > FBR_MAX_BOXES || npairs > FBR_MAX_BOX_PAIRS) {
-        set_err("box set: at most " + std::to_string(FBR_MAX_BOXES) + " boxes and " + std::to_string(FBR_MAX_BOX_PAIRS) + " pairs");
-        return FBR_E_INVALID;
-    }
-    if ((nboxes > 0 && (!link || !half || !center)) || (npairs > 0 && !pairs)) {
-        set_err("box set: null array");
-        return FBR_E_INVALID;
-    }
-    const FbrHostModel &hm = m->hm;
-    int nrob = 0, nworld = 0;
-    std::vector<int> code(nboxes);  // robot-box number, or -1 - (world-box number)
-    for (int c = 0; c < nboxes; c++) {
-        if (link[c] < -1 || link[c] >= hm.L) {
-            set_err("box " + std::to_string(c) + ": link index out of range (-1: a world box)");
-            return FBR_E_INVALID;
-        }
-        for (int i = 0; i < 3; i++) {
-            if (!(half[3 * c + i] > 0.0) || !std::isfinite(half[3 * c + i])) {
-                set_err("box " + std::to_string(c) + ": the half extents must be finite and positive");
-                return FBR_E_INVALID;
-            }
-            if (!std::isfinite(center[3 * c + i])) {
-                set_err("box " + std::to_string(c) + ": non-finite centre");
-                return FBR_E_INVALID;
-            }
-        }
-        if (link[c] < 0) {
-            if (!rot) {
-                set_err("box " + std::to_string(c) + ": a world box needs rot");
-                return FBR_E_INVALID;
-            }
-            for (int i = 0; i < 9; i++)
-                if (!std::isfinite(rot[9 * c + i])) {
-                    set_err("box " + std::to_string(c) + ": non-finite rotation");
-                    return FBR_E_INVALID;
-                }
-            code[c] = -1 - nworld++;
-        } else {
-            code[c] = nrob++;
-        }
-    }
-    for (int k = 0; k < npairs; k++) {
-        const int a = pairs[2 * k], b = pairs[2 * k + 1];
-        if (a < 0 || a >= nboxes || b < 0 || b >= nboxes || a == b) {
-            set_err("box pair " + std::to_string(k) + ": box index out of range, or a box paired with itself");
-            return FBR_E_INVALID;
-        }
-        if (link[a] < 0 && link[b] < 0) {
-            set_err("box pair " + std::to_string(k) + ": two world boxes");
-            return FBR_E_INVALID;
-        }
-    }
-    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->boxes = DevBoxes{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    m->boxg = DevBoxGrad{0, nullptr, nullptr};
-    if (nboxes == 0) return FBR_OK;
-    FbrKinIdProgram prog;
-    try {
-        fbr_kinid_build(hm, prog);
-    } catch (const std::exception &e) {
-        set_err(e.what());
-        return FBR_E_INVALID;
-    }
-    // robot boxes sorted by the step of their link (stable: the caller's order within a link)
-    std::vector<int> stepof(hm.L, 0), boxbeg(prog.nsteps + 1, 0), boxid(std::max(nrob, 1), 0);
-    for (int k = 0; k < prog.nsteps; k++) stepof[prog.steps[(size_t)k * FBR_KINID_STEP]] = k;
-    for (int c = 0; c < nboxes; c++)
-        if (link[c] >= 0) boxbeg[stepof[link[c]] + 1]++;
-    for (int k = 0; k < prog.nsteps; k++) boxbeg[k + 1] += boxbeg[k];
-    std::vector<int> fill(boxbeg.begin(), boxbeg.end() - 1);
-    // one allocation: cen | half | world | steps | boxbeg | boxid | pairs  (doubles first: every table keeps its alignment)
-    const size_t nr = (size_t)std::max(nrob, 1), nw = (size_t)std::max(nworld, 1), nd = nr * 6 + nw * 15;
-    const size_t ni = prog.steps.size() + boxbeg.size() + nr + 1 + 2 * (size_t)std::max(npairs, 1);  // (+ 1: the padding in front of the pairs)
-    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int), 0);
-    double *hcen = (double *)host.data(), *hhalf = hcen + nr * 3, *hworld = hhalf + nr * 3;
-    for (int c = 0; c < nboxes; c++) {
-        if (link[c] >= 0) {
-            const int slot = fill[stepof[link[c]]]++;
-            boxid[slot] = code[c];
-            for (int i = 0; i < 3; i++) {
-                hcen[(size_t)slot * 3 + i] = center[3 * c + i];
-                hhalf[(size_t)code[c] * 3 + i] = half[3 * c + i];
-            }
-        } else {
-            double *w = hworld + (size_t)(-1 - code[c]) * 15;
-            for (int i = 0; i < 9; i++) w[i] = rot[9 * c + i];
-            for (int i = 0; i < 3; i++) {
-                w[9 + i] = center[3 * c + i];
-                w[12 + i] = half[3 * c + i];
-            }
-        }
-    }
-    int *hi = (int *)(hcen + nd), *hsteps = hi, *hboxbeg = hsteps + prog.steps.size(), *hboxid = hboxbeg + boxbeg.size();
-    int *hpairs = hboxid + nr + ((prog.steps.size() + boxbeg.size() + nr) & 1);  // (int2: 8-byte aligned)
-    std::copy(prog.steps.begin(), prog.steps.end(), hsteps);
-    std::copy(boxbeg.begin(), boxbeg.end(), hboxbeg);
-    std::copy(boxid.begin(), boxid.end(), hboxid);
-    for (size_t k = 0; k < 2 * (size_t)npairs; k++) hpairs[k] = code[pairs[k]];
-    if (int rc = m->box_tab.ensure(host.size() + 8)) return rc;
-    HIPCHK(hipMemcpy(m->box_tab.p, host.data(), host.size(), hipMemcpyHostToDevice));
-    const char *base = (const char *)m->box_tab.p;
-    DevBoxes db;
-    db.nsteps = prog.nsteps;
-    db.nslots = prog.nslots;
-    db.nrob = nrob;
-    db.nworld = nworld;
-    db.npairs = npairs;
-    db.cmode = center_in_link_axes ? 1 : 0;
-    db.cen = (const double *)base;
-    db.half = db.cen + nr * 3;
-    db.world = db.half + nr * 3;
-    db.steps = (const int *)(base + ((const char *)hsteps - host.data()));
-    db.boxbeg = (const int *)(base + ((const char *)hboxbeg - host.data()));
-    db.boxid = (const int *)(base + ((const char *)hboxid - host.data()));
-    db.pairs = (const int2 *)(base + ((const char *)hpairs - host.data()));
-    // tables of fbr_box_distance_gradients, in an allocation of their own: per pair the steps of the two members' links (-1: a world box)
-    // and the slots of their centres (a world box: its number) | ancestor masks
-    std::vector<int> stepof2, anc, slotof(nr, 0);
-    fbr_capgrad_ancestors(hm, prog, stepof2, anc);
-    for (int sl = 0; sl < nrob; sl++) slotof[boxid[sl]] = sl;
-    std::vector<int> gt((size_t)4 * std::max(npairs, 1) + anc.size(), 0);
-    for (int k = 0; k < npairs; k++)
-        for (int j = 0; j < 2; j++) {
-            const int c = pairs[2 * k + j];
-            gt[4 * (size_t)k + j] = link[c] < 0 ? -1 : stepof[link[c]];
-            gt[4 * (size_t)k + 2 + j] = link[c] < 0 ? -1 - code[c] : slotof[code[c]];
-        }
-    std::copy(anc.begin(), anc.end(), gt.begin() + (size_t)4 * std::max(npairs, 1));
-    if (int rc = m->boxg_tab.ensure(gt.size() * sizeof(int))) return rc;
-    HIPCHK(hipMemcpy(m->boxg_tab.p, gt.data(), gt.size() * sizeof(int), hipMemcpyHostToDevice));
-    m->boxg.W = fbr_capgrad_words(prog.nsteps);
-    m->boxg.pair = (const int4 *)m->boxg_tab.p;
-    m->boxg.anc = m->boxg_tab.as<int>() + (size_t)4 * std::max(npairs, 1);
-    m->boxes = db;
-    return FBR_OK;
-}
-
-// The box and the hull call share everything but the set and the pairs kernel: bx the frames (for the hulls: the DevBoxes view of the set),
-// P the pairs, nbatch the batches of pairs a block of samples is cut into, launch_pairs(grid, tl, b0, nb, frames, pval, pidx) the kernel;
-// missing: the message when there is no set (null: there is one).
-template <class LaunchPairs>
-static int candidate_frame_distances(fbr_model *m, const char *missing, const DevBoxes &bx, long P, long nbatch, const fbr_states *st,
-                                     const double *base_pos, int32_t ncand, int32_t step, double *dist_out, int64_t *idx_out, int32_t out_mem,
-                                     LaunchPairs launch_pairs)
-{
-    if (!m || !st || !dist_out || !idx_out) {
-        set_err("null model / states / dist_out / idx_out");
-        return FBR_E_INVALID;
-    }
-    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q) {
-        set_err("bad fbr_states header, or q is NULL");
-        return FBR_E_INVALID;
-    }
-    if (missing) {
-        set_err(missing);
-        return FBR_E_INVALID;
-    }
-    if (ncand < 1 || step < 1) {
-        set_err("ncand and step must be at least 1");
-        return FBR_E_INVALID;
-    }
-    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
-        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
-        return FBR_E_INVALID;
-    }
-    if (int rc = enter_blocking(m)) return rc;
-    const FbrHostModel &hm = m->hm;
-    const long S = st->num_samples, C = ncand;
-    const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr;
-    int rc;
-    if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
-    if (hm.floating && st->base_rpy) {
-        if ((rc = stage_one(m, m->st_rpy, st->base_rpy, (size_t)S * 3, st->mem, &drpy))) return rc;
-        if ((rc = stage_one(m, m->st_bpos, base_pos, (size_t)S * 3, st->mem, &dbp))) return rc;
-    }
-    DevCapTiles tl;
-    tl.T = S / C;
-    tl.step = step;
-    tl.Tc = (tl.T + step - 1) / step;
-    tl.tiles = (tl.Tc + 63) / 64;
-    tl.nblk = C * tl.tiles;
-    // blocks per launch: the frames of the blocks in flight stay below 256 MB, their partials below 64 MB
-    const size_t fr_blk = (size_t)bx.nrob * 12 * 64 * sizeof(double), part_blk = (size_t)P * (sizeof(double) + sizeof(long));
-    long ch = (long)std::min((size_t)(256u << 20) / fr_blk, (size_t)(64u << 20) / part_blk);
-    if (m->opt.chunk_samples >= 1) ch = (long)m->opt.chunk_samples / 64;  // (tests: the multi-launch path at small sizes)
-    ch = std::max(1L, std::min(ch, tl.nblk));
-    if ((rc = m->box_fr.ensure((size_t)ch * fr_blk))) return rc;
-    if ((rc = m->cap_part.ensure((size_t)ch * part_blk))) return rc;
-    double *pval = m->cap_part.as<double>();
-    long *pidx = (long *)(pval + (size_t)ch * P);
-    const size_t cnt = (size_t)C * P;
-    double *val = dist_out;
-    long *idx = (long *)idx_out;
-    if (out_mem == FBR_HOST) {
-        if ((rc = m->cap_out.ensure(cnt * (sizeof(double) + sizeof(long))))) return rc;
-        val = m->cap_out.as<double>();
-        idx = (long *)(val + cnt);
-    }
-    const int ldn = std::max(hm.n, 1) | 1;
-    const size_t lds_want = (size_t)64 * ldn * sizeof(double);
-    const int stage = lds_want <= (size_t)64 * 1024;  // up to 127 DOF; beyond, the lanes read their rows from memory
-    const size_t lds = stage ? lds_want : 0;
-    const int pgrid = (int)std::min<long>(ch, (long)m->num_cus * 8);
-    if ((rc = m->cap_scratch.ensure((size_t)pgrid * std::max(bx.nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
-    if (lds) HIPCHK(hipFuncSetAttribute((const void *)fbr_box_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    for (long b0 = 0; b0 < tl.nblk; b0 += ch) {
-        const long nb = std::min(ch, tl.nblk - b0);
-        {
-            ProfScope ps(m, FBR_PROF_KIN);
-            hipLaunchKernelGGL(fbr_box_frames_kernel, dim3((unsigned)std::min<long>(nb, pgrid)), dim3(64), lds, m->stream, m->dm, bx, tl, b0, nb, stage, ldn,
-                               dq, drpy, dbp, m->box_fr.as<double>(), m->cap_scratch.as<double>());
-            HIPCHK(hipGetLastError());
-        }
-        {
-            ProfScope ps(m, FBR_PROF_REDUCE);
-            launch_pairs((unsigned)std::min<long>(nb * nbatch, (long)m->num_cus * 32), tl, b0, nb, (const double *)m->box_fr.as<double>(), pval, pidx);
-            HIPCHK(hipGetLastError());
-            const long cands = (b0 + nb - 1) / tl.tiles - b0 / tl.tiles + 1;
-            hipLaunchKernelGGL(fbr_capsule_finish_kernel, dim3((unsigned)((cands * P + 255) / 256)), dim3(256), 0, m->stream, tl, (int)P, b0, nb,
-                               (const double *)pval, (const long *)pidx, val, idx);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    if (out_mem == FBR_HOST) {
-        HIPCHK(hipMemcpyAsync(dist_out, val, cnt * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(idx_out, idx, cnt * sizeof(long), hipMemcpyDeviceToHost, m->stream));
-    }
-    HIPCHK(hipStreamSynchronize(m->stream));
-    prof_collect(m);
-    return FBR_OK;
-}
-
-extern "C" int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
-                                           int64_t *idx_out, int32_t out_mem)
-{
-    static const DevBoxes none = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const bool have = m && m->boxes.nrob != 0 && m->boxes.npairs != 0;
-    const DevBoxes &bx = m ? m->boxes : none;
-    return candidate_frame_distances(m, !m || have ? nullptr : "no box set with at least one pair (fbr_model_set_boxes)", bx, bx.npairs,
-                                     (bx.npairs + FBR_BOX_BATCH - 1) / FBR_BOX_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
-                                     [&](unsigned grid, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
-                                         hipLaunchKernelGGL(fbr_box_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, bx, tl, b0, nb, fr, pval, pidx);
-                                     });
-}
-
-// ---- convex-hull collision distances (csrc/fbr_hull.h) -------------------------------------------------------------------------------------
-extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
-                                   int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg, const double *planes,
-                                   const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs)
-{
-    if (!m) {
-        set_err("null model");
-        return FBR_E_INVALID;
-    }
-    const FbrHostModel &hm = m->hm;
-    std::vector<double> diam((size_t)std::max(std::min(nhulls, FBR_MAX_HULLS), 1), 0.0);
-    const std::string bad = fbr_hull_validate(hm.L, FBR_MAX_HULLS, FBR_MAX_HULL_PAIRS, FBR_MAX_HULL_VERTICES, nhulls, link, offset, rot, vbeg, verts, fbeg,
-                                              planes, ebeg, edges, npairs, pairs, diam.data());
-    if (!bad.empty()) {
-        set_err(bad);
-        return FBR_E_INVALID;
-    }
-    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->hulls = DevHulls{{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, 0};
-    m->hullg = DevHullGrad{0, nullptr, nullptr};
-    // (the meshes attached to the set before are gone with it: fbr_model_set_hull_meshes)
-    m->hulls_plain = m->hulls;
-    m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
-    m->has_meshes = false;
-    m->hull_host = {};
-    if (nhulls == 0) return FBR_OK;
-    FbrKinIdProgram prog;
-    try {
-        fbr_kinid_build(hm, prog);
-    } catch (const std::exception &e) {
-        set_err(e.what());
-        return FBR_E_INVALID;
-    }
-    // robot hulls sorted by the step of their link (stable), as the robot boxes are: the frames kernel walks them by slot
-    int nrob = 0, nworld = 0;
-    std::vector<int> code(nhulls), stepof(hm.L, 0), beg(prog.nsteps + 1, 0);
-    for (int h = 0; h < nhulls; h++) code[h] = link[h] < 0 ? -1 - nworld++ : nrob++;
-    for (int k = 0; k < prog.nsteps; k++) stepof[prog.steps[(size_t)k * FBR_KINID_STEP]] = k;
-    for (int h = 0; h < nhulls; h++)
-        if (link[h] >= 0) beg[stepof[link[h]] + 1]++;
-    for (int k = 0; k < prog.nsteps; k++) beg[k + 1] += beg[k];
-    std::vector<int> fill(beg.begin(), beg.end() - 1);
-    // one allocation, doubles first: cen | diam | world | verts | planes || steps | beg | slot ids | tab | edges | (padding) pairs
-    const size_t nr = (size_t)std::max(nrob, 1), nw = (size_t)std::max(nworld, 1), NV = (size_t)vbeg[nhulls], NF = (size_t)fbeg[nhulls], NE = (size_t)ebeg[nhulls];
-    const size_t nd = nr * 3 + (size_t)nhulls + nw * 12 + NV * 3 + NF * 4;
-    const size_t ni_front = prog.steps.size() + beg.size() + nr + (size_t)nhulls * 8 + NE * 4;
-    const size_t ni = ni_front + 1 + 2 * (size_t)std::max(npairs, 1);
-    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int), 0);
-    double *hcen = (double *)host.data(), *hdiam = hcen + nr * 3, *hworld = hdiam + nhulls, *hverts = hworld + nw * 12, *hplanes = hverts + NV * 3;
-    int *hsteps = (int *)(hcen + nd), *hbeg = hsteps + prog.steps.size(), *hid = hbeg + beg.size(), *htab = hid + nr, *hedges = htab + (size_t)nhulls * 8;
-    int *hpairs = hedges + NE * 4 + (ni_front & 1);  // (int2: 8-byte aligned)
-    for (int h = 0; h < nhulls; h++) {
-        hdiam[h] = diam[h];
-        int *tb = htab + (size_t)h * 8;
-        tb[0] = code[h], tb[1] = vbeg[h], tb[2] = vbeg[h + 1] - vbeg[h], tb[3] = fbeg[h], tb[4] = fbeg[h + 1] - fbeg[h], tb[5] = ebeg[h],
-        tb[6] = ebeg[h + 1] - ebeg[h];
-        if (link[h] >= 0) {
-            const int slot = fill[stepof[link[h]]]++;
-            hid[slot] = code[h];
-            for (int i = 0; i < 3; i++) hcen[(size_t)slot * 3 + i] = offset[3 * h + i];
-        } else {
-            double *w = hworld + (size_t)(-1 - code[h]) * 12;
-            for (int i = 0; i < 9; i++) w[i] = rot[9 * h + i];
-            for (int i = 0; i < 3; i++) w[9 + i] = offset[3 * h + i];
-        }
-    }
-    std::copy(verts, verts + NV * 3, hverts);
-    std::copy(planes, planes + NF * 4, hplanes);
-    std::copy(edges, edges + NE * 4, hedges);
-    std::copy(prog.steps.begin(), prog.steps.end(), hsteps);
-    std::copy(beg.begin(), beg.end(), hbeg);
-    for (size_t k = 0; k < 2 * (size_t)npairs; k++) hpairs[k] = pairs[k];
-    if (int rc = m->hull_tab.ensure(host.size() + 8)) return rc;
-    HIPCHK(hipMemcpy(m->hull_tab.p, host.data(), host.size(), hipMemcpyHostToDevice));
-    const char *base = (const char *)m->hull_tab.p;
-    auto dev = [&](const void *hp) { return base + ((const char *)hp - host.data()); };
-    DevHulls dh;
-    dh.fr = DevBoxes{prog.nsteps, prog.nslots, nrob, 0, 0, offset_in_link_axes ? 1 : 0, (const int *)dev(hsteps), (const int *)dev(hbeg),
-                     (const int *)dev(hid), (const double *)dev(hcen), nullptr, nullptr, nullptr};
-    dh.nhulls = nhulls;
-    dh.npairs = npairs;
-    dh.tab = (const int *)dev(htab);
-    dh.diam = (const double *)dev(hdiam);
-    dh.world = (const double *)dev(hworld);
-    dh.verts = (const double *)dev(hverts);
-    dh.planes = (const double *)dev(hplanes);
-    dh.edges = (const int *)dev(hedges);
-    dh.pairs = (const int2 *)dev(hpairs);
-    dh.col = nullptr;
-    dh.ldp = npairs;
-    // tables of fbr_hull_distance_gradients, in an allocation of their own: per pair the steps of the two members' links (-1: a world hull)
-    // and the slots of their offsets (a world hull: its number) | ancestor masks
-    std::vector<int> stepof2, anc, slotof(nr, 0);
-    fbr_capgrad_ancestors(hm, prog, stepof2, anc);
-    for (int sl = 0; sl < nrob; sl++) slotof[hid[sl]] = sl;
-    std::vector<int> gt((size_t)4 * std::max(npairs, 1) + anc.size(), 0);
-    for (int k = 0; k < npairs; k++)
-        for (int j = 0; j < 2; j++) {
-            const int h = pairs[2 * k + j];
-            gt[4 * (size_t)k + j] = link[h] < 0 ? -1 : stepof[link[h]];
-            gt[4 * (size_t)k + 2 + j] = link[h] < 0 ? -1 - code[h] : slotof[code[h]];
-        }
-    std::copy(anc.begin(), anc.end(), gt.begin() + (size_t)4 * std::max(npairs, 1));
-    if (int rc = m->hullg_tab.ensure(gt.size() * sizeof(int))) return rc;
-    HIPCHK(hipMemcpy(m->hullg_tab.p, gt.data(), gt.size() * sizeof(int), hipMemcpyHostToDevice));
-    m->hullg.W = fbr_capgrad_words(prog.nsteps);
-    m->hullg.pair = (const int4 *)m->hullg_tab.p;
-    m->hullg.anc = m->hullg_tab.as<int>() + (size_t)4 * std::max(npairs, 1);
-    m->hulls = dh;
-    m->hulls_plain = dh;
-    m->hull_host.link.assign(link, link + nhulls);
-    m->hull_host.vbeg.assign(vbeg, vbeg + nhulls + 1);
-    m->hull_host.fbeg.assign(fbeg, fbeg + nhulls + 1);
-    m->hull_host.pairs.assign(pairs, pairs + 2 * (size_t)npairs);
-    m->hull_host.verts.assign(verts, verts + NV * 3);
-    m->hull_host.planes.assign(planes, planes + NF * 4);
-    m->hull_host.diam.assign(diam.begin(), diam.begin() + nhulls);
-    return FBR_OK;
-}
-
-// ---- triangle meshes on hulls of the set (csrc/fbr_mesh.h) ---------------------------------------------------------------------------------
-extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris)
-{
-    if (!m) {
-        set_err("null model");
-        return FBR_E_INVALID;
-    }
-    const auto &hh = m->hull_host;
-    const int nhulls = m->hulls.nhulls, npairs = m->hulls.npairs;
-    const std::string bad = fbr_mesh_validate(nhulls, hh.link.data(), hh.fbeg.data(), hh.planes.data(), hh.diam.data(), npairs, hh.pairs.data(),
-                                              FBR_MAX_MESH_TRIANGLES, FBR_MAX_MESH_PAIR_WORK, nmesh, hull, tbeg, tris);
-    if (!bad.empty()) {
-        set_err(bad);
-        return FBR_E_INVALID;
-    }
-    if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
-    HIPCHK(hipStreamSynchronize(m->stream));
-    if (nmesh == 0) {
-        m->hulls_plain = m->hulls;
-        m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
-        m->has_meshes = false;
-        return FBR_OK;
-    }
-    // the pairs of the set: those with a mesh on either side, the meshed hull first, sorted by it (stable); the others in their order
-    std::vector<int> mtab((size_t)nhulls * 2, 0);
-    for (int i = 0; i < nmesh; i++) mtab[2 * (size_t)hull[i]] = tbeg[i], mtab[2 * (size_t)hull[i] + 1] = tbeg[i + 1] - tbeg[i];
-    std::vector<int> mk, pk;
-    for (int k = 0; k < npairs; k++) (mtab[2 * (size_t)hh.pairs[2 * k] + 1] || mtab[2 * (size_t)hh.pairs[2 * k + 1] + 1] ? mk : pk).push_back(k);
-    auto first = [&](int k) { return mtab[2 * (size_t)hh.pairs[2 * k] + 1] ? hh.pairs[2 * k] : hh.pairs[2 * k + 1]; };
-    std::stable_sort(mk.begin(), mk.end(), [&](int a, int b) { return first(a) < first(b); });
-    const size_t NT = (size_t)tbeg[nmesh], nm = std::max(mk.size(), (size_t)1), np = std::max(pk.size(), (size_t)1);
-    // one allocation, doubles first: sph | tris | aux || mesh pairs | plain pairs | mtab | mesh columns | plain columns
-    const size_t nd = (size_t)nhulls * 4 + NT * 9 + NT * 5, ni = 2 * nm + 2 * np + (size_t)nhulls * 2 + nm + np;
-    std::vector<char> host(nd * sizeof(double) + ni * sizeof(int), 0);
-    double *hsph = (double *)host.data(), *htris = hsph + (size_t)nhulls * 4, *haux = htris + NT * 9;
-    int *hmp = (int *)(hsph + nd), *hpp = hmp + 2 * nm, *hmtab = hpp + 2 * np, *hmc = hmtab + (size_t)nhulls * 2, *hpc = hmc + nm;
-    for (int h = 0; h < nhulls; h++)
-        fbr_mesh_point_sphere(hh.vbeg[h + 1] - hh.vbeg[h], hh.verts.data() + 3 * (size_t)hh.vbeg[h], 3L * mtab[2 * (size_t)h + 1],
-                              tris + 9 * (size_t)mtab[2 * (size_t)h], hsph + 4 * (size_t)h);
-    std::copy(tris, tris + NT * 9, htris);
-    for (size_t t = 0; t < NT; t++) fbr_mesh_triangle_aux(tris + 9 * t, haux + 5 * t);
-    std::copy(mtab.begin(), mtab.end(), hmtab);
-    for (size_t i = 0; i < mk.size(); i++) {
-        const int k = mk[i], a = hh.pairs[2 * k], b = hh.pairs[2 * k + 1], swap = mtab[2 * (size_t)a + 1] == 0;
-        hmp[2 * i] = swap ? b : a, hmp[2 * i + 1] = swap ? a : b, hmc[i] = k;
-    }
-    for (size_t i = 0; i < pk.size(); i++) hpp[2 * i] = hh.pairs[2 * pk[i]], hpp[2 * i + 1] = hh.pairs[2 * pk[i] + 1], hpc[i] = pk[i];
-    // the stencil points of fbr_mesh_distance_gradients (csrc/fbr_mesh_grad.h): per mesh pair the centre, then + eps, - eps of every joint
-    // fbr_rigidgrad_item evaluates, in walk order: sbeg | pair of a point | its joint
-    std::vector<int> gtab(mk.size() + 1, 0), gpair, gjoint;
-    int smax = 0;
-    {
-        FbrKinIdProgram prog;
-        try {
-            fbr_kinid_build(m->hm, prog);
-        } catch (const std::exception &e) {
-            set_err(e.what());
-            return FBR_E_INVALID;
-        }
-        std::vector<int> stepof, anc, joint;
-        fbr_capgrad_ancestors(m->hm, prog, stepof, anc);
-        for (size_t i = 0; i < mk.size(); i++) {
-            const int la = hh.link[hh.pairs[2 * mk[i]]], lb = hh.link[hh.pairs[2 * mk[i] + 1]];
-            fbr_meshgrad_slots(la < 0 ? -1 : stepof[la], lb < 0 ? -1 : stepof[lb], m->hulls.fr.cmode, prog.steps.data(), anc.data(),
-                               fbr_capgrad_words(prog.nsteps), joint);
-            gtab[i + 1] = gtab[i] + (int)joint.size();
-            gpair.insert(gpair.end(), joint.size(), (int)i);
-            gjoint.insert(gjoint.end(), joint.begin(), joint.end());
-            smax = std::max(smax, (int)joint.size());
-        }
-        gtab.insert(gtab.end(), gpair.begin(), gpair.end());
-        gtab.insert(gtab.end(), gjoint.begin(), gjoint.end());
-    }
-    // fresh allocations, swapped in once the copies have succeeded: a call that fails here leaves the attachments in place as well
-    DevBuf fresh, freshg;
-    if (int rc = fresh.ensure(host.size() + 8)) return rc;
-    if (int rc = freshg.ensure(gtab.size() * sizeof(int))) return rc;
-    HIPCHK(hipMemcpy(fresh.p, host.data(), host.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(freshg.p, gtab.data(), gtab.size() * sizeof(int), hipMemcpyHostToDevice));
-    m->mesh_tab = std::move(fresh);
-    m->meshg_tab = std::move(freshg);
-    {
-        const int *g = m->meshg_tab.as<int>();
-        const int ni = (int)gpair.size();
-        m->meshg = DevMeshGrad{ni, smax, g, g + mk.size() + 1, g + mk.size() + 1 + ni};
-    }
-    m->hulls_plain = m->hulls;
-    const char *base = (const char *)m->mesh_tab.p;
-    auto dev = [&](const void *hp) { return base + ((const char *)hp - host.data()); };
-    m->meshes = DevMeshes{(int)mk.size(), (const int *)dev(hmtab), (const double *)dev(hsph), (const double *)dev(htris), (const double *)dev(haux),
-                          (const int2 *)dev(hmp), (const int *)dev(hmc)};
-    m->hulls_plain.npairs = (int)pk.size();
-    m->hulls_plain.pairs = (const int2 *)dev(hpp);
-    m->hulls_plain.col = (const int *)dev(hpc);
-    m->has_meshes = true;
-    return FBR_OK;
-}
-
-extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, int32_t step, double *dist_out,
-                                            int64_t *idx_out, int32_t out_mem)
-{
-    static const DevBoxes none = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // (a set of world hulls only has no pairs: two world hulls are never paired)
-    const bool have = m && m->hulls.nhulls != 0 && m->hulls.npairs != 0;
-    const long P = m ? m->hulls.npairs : 0;
-    return candidate_frame_distances(m, !m || have ? nullptr : "no hull set with at least one pair (fbr_model_set_hulls)", m ? m->hulls.fr : none, P,
-                                     (P + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
-                                     [&](unsigned grid, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
-                                         if (!m->has_meshes) {
-                                             hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, m->hulls, tl, b0, nb, fr, pval, pidx);
-                                             return;
-                                         }
-                                         // a split set: the pairs without a mesh, then those with one, each into its own columns
-                                         const long cap = (long)m->num_cus * 32, ph = m->hulls_plain.npairs, pm = m->meshes.npairs;
-                                         if (ph > 0)
-                                             hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ph + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
-                                                                dim3(64), 0, m->stream, m->hulls_plain, tl, b0, nb, fr, pval, pidx);
-                                         if (pm > 0)
-                                             hipLaunchKernelGGL(fbr_mesh_pairs_kernel, dim3((unsigned)std::min(nb * ((pm + FBR_MESH_BATCH - 1) / FBR_MESH_BATCH), cap)),
-                                                                dim3(64), 0, m->stream, m->hulls, m->meshes, tl, b0, nb, fr, pval, pidx);
-                                     });
-}
-
-// ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, fbr_box_grad.h, fbr_hull_grad.h,
-// fbr_mesh_grad.h) ----
-// The capsule, the box, the hull and the mesh call share everything but the set and the kernel: `name` the entry point, P / nslots the pairs and
-// the branch points of its set, launch(grid, C, T, q, rpy, bpos, sample, scale, pose, dist, grad) the kernel -- or the kernels of the mesh
-// call; it returns FBR_OK, or the code of a workspace it could not get.
-template <class Launch>
-static int distance_gradients(fbr_model *m, const char *name, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
-                              const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem, long P, int nslots,
-                              Launch launch)
-{
-    if (ncand < 1) {
-        set_err("ncand must be at least 1");
-        return FBR_E_INVALID;
-    }
-    if (st->num_samples <= 0 || st->num_samples % ncand != 0) {
-        set_err("num_samples must be a positive multiple of ncand (equal candidates of consecutive samples)");
-        return FBR_E_INVALID;
-    }
-    if (int rc = enter_blocking(m)) return rc;
-    const FbrHostModel &hm = m->hm;
-    const long S = st->num_samples, C = ncand, T = S / C;
-    const size_t items = (size_t)C * P;
-    const double *dq = nullptr, *drpy = nullptr, *dbp = nullptr, *dsmp = nullptr, *dscale = nullptr, *dpose = nullptr;
-    int rc;
-    if ((rc = stage_one(m, m->st_q, st->q, (size_t)S * hm.n, st->mem, &dq))) return rc;
-    if (hm.floating && st->base_rpy) {
-        if ((rc = stage_one(m, m->st_rpy, st->base_rpy, (size_t)S * 3, st->mem, &drpy))) return rc;
-        if ((rc = stage_one(m, m->st_bpos, base_pos, (size_t)S * 3, st->mem, &dbp))) return rc;
-    }
-    // (the index arrays are 8 bytes an entry, like the doubles the staging helper copies)
-    if ((rc = stage_one(m, m->st_dq, (const double *)sample, items, st->mem, &dsmp))) return rc;
-    if ((rc = stage_one(m, m->st_ddq, (const double *)pose_sample, items, st->mem, &dpose))) return rc;
-    if ((rc = stage_one(m, m->st_aux, scale, items, st->mem, &dscale))) return rc;
-    double *ddist = dist_out, *dgrad = grad_q_out;
-    if (out_mem == FBR_HOST) {
-        if ((rc = m->cap_out.ensure(items * (1 + (size_t)hm.n) * sizeof(double)))) return rc;
-        ddist = m->cap_out.as<double>();
-        dgrad = ddist + items;
-    }
-    const long tiles = (C + 63) / 64;
-    const int grid = (int)std::min<long>(P * tiles, (long)m->num_cus * 8);
-    if ((rc = m->cap_scratch.ensure((size_t)grid * std::max(nslots, 1) * 12 * 64 * sizeof(double)))) return rc;
-    if ((rc = m->capg_flag.ensure(sizeof(int)))) return rc;
-    int flag = 0;
-    HIPCHK(hipMemsetAsync(m->capg_flag.p, 0, sizeof(int), m->stream));
-    HIPCHK(hipMemsetAsync(dgrad, 0, items * hm.n * sizeof(double), m->stream));  // (joints off a pair's path: exact zeros, never touched by the kernel)
-    {
-        ProfScope ps(m, FBR_PROF_KIN);
-        if ((rc = launch(grid, C, T, dq, drpy, dbp, (const long *)dsmp, dscale, (const long *)dpose, ddist, dgrad))) return rc;
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(&flag, m->capg_flag.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    if (out_mem == FBR_HOST) {
-        HIPCHK(hipMemcpyAsync(dist_out, ddist, items * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(grad_q_out, dgrad, items * hm.n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    }
-    HIPCHK(hipStreamSynchronize(m->stream));
-    prof_collect(m);
-    if (flag) {
-        set_err(std::string(name) + ": a sample or pose_sample index lies outside -1 .. T - 1");
-        return FBR_E_INVALID;
-    }
-    return FBR_OK;
-}
-
-static bool distance_gradient_args(const fbr_model *m, const fbr_states *st, const int64_t *sample, const double *dist_out, const double *grad_q_out,
-                                   int32_t out_mem)
-{
-    if (!m || !st || !sample || !dist_out || !grad_q_out) {
-        set_err("null model / states / sample / dist_out / grad_q_out");
-        return false;
-    }
-    if (st->num_samples < 0 || (st->mem != FBR_HOST && st->mem != FBR_DEVICE) || !st->q || (out_mem != FBR_HOST && out_mem != FBR_DEVICE)) {
-        set_err("bad fbr_states header or memory space, or q is NULL");
-        return false;
-    }
-    return true;
-}
-
-extern "C" int fbr_capsule_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
-                                              const double *scale, const int64_t *pose_sample, double *dist_out, double *grad_q_out, int32_t out_mem)
-{
-    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
-    if (m->caps.ncaps == 0 || m->caps.npairs == 0) {
-        set_err("no capsule set with at least one pair (fbr_model_set_capsules)");
-        return FBR_E_INVALID;
-    }
-    return distance_gradients(m, "fbr_capsule_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem,
-                              m->caps.npairs, m->caps.nslots,
-                              [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
-                                  const long *dpose, double *ddist, double *dgrad) {
-                                  hipLaunchKernelGGL(fbr_capsule_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->caps, m->capg, C, T, dq,
-                                                     drpy, dbp, dsmp, dscale, dpose, ddist, dgrad, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
-                                  return FBR_OK;
-                              });
-}
-
-extern "C" int fbr_box_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
-                                          const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
-                                          int32_t out_mem)
-{
-    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
-    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
-        set_err("epsilon must be finite and positive");
-        return FBR_E_INVALID;
-    }
-    if (m->boxes.nrob == 0 || m->boxes.npairs == 0) {
-        set_err("no box set with at least one pair (fbr_model_set_boxes)");
-        return FBR_E_INVALID;
-    }
-    double se, omc;
-    fbr_boxgrad_trig(epsilon, &se, &omc);
-    return distance_gradients(m, "fbr_box_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem,
-                              m->boxes.npairs, m->boxes.nslots,
-                              [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
-                                  const long *dpose, double *ddist, double *dgrad) {
-                                  hipLaunchKernelGGL(fbr_box_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->boxes, m->boxg, C, T, dq, drpy,
-                                                     dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
-                                                     m->capg_flag.as<int>());
-                                  return FBR_OK;
-                              });
-}
-
-extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
-                                           const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
-                                           int32_t out_mem)
-{
-    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
-    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
-        set_err("epsilon must be finite and positive");
-        return FBR_E_INVALID;
-    }
-    if (m->hulls.nhulls == 0 || m->hulls.npairs == 0) {
-        set_err("no hull set with at least one pair (fbr_model_set_hulls)");
-        return FBR_E_INVALID;
-    }
-    if (m->has_meshes) {
-        set_err("fbr_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); gradients of mesh pairs are not built");
-        return FBR_E_UNSUPPORTED;
-    }
-    double se, omc;
-    fbr_boxgrad_trig(epsilon, &se, &omc);
-    return distance_gradients(m, "fbr_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem,
-                              m->hulls.npairs, m->hulls.fr.nslots,
-                              [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
-                                  const long *dpose, double *ddist, double *dgrad) {
-                                  hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->hulls, m->hullg, C, T, dq,
-                                                     drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
-                                                     m->capg_flag.as<int>());
-                                  return FBR_OK;
-                              });
-}
-
-// A hull set with triangle meshes attached: the pairs without a mesh through fbr_hull_grad_kernel, into their columns; the pairs with one
-// through the three stages of csrc/fbr_mesh_grad.h.
-extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
-                                           const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
-                                           int32_t out_mem)
-{
-    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
-    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
-        set_err("epsilon must be finite and positive");
-        return FBR_E_INVALID;
-    }
-    if (m->hulls.nhulls == 0 || m->hulls.npairs == 0) {
-        set_err("no hull set with at least one pair (fbr_model_set_hulls)");
-        return FBR_E_INVALID;
-    }
-    if (!m->has_meshes) {
-        set_err("fbr_mesh_distance_gradients: the hull set has no triangle meshes attached (fbr_model_set_hull_meshes); fbr_hull_distance_gradients "
-                "serves a set of hulls only");
-        return FBR_E_INVALID;
-    }
-    double se, omc;
-    fbr_boxgrad_trig(epsilon, &se, &omc);
-    return distance_gradients(
-        m, "fbr_mesh_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem, m->hulls.npairs, m->hulls.fr.nslots,
-        [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
-            double *ddist, double *dgrad) -> int {
-            const long tiles = (C + 63) / 64, ph = m->hulls_plain.npairs, pm = m->meshes.npairs, ni = m->meshg.nitems;
-            if (ph > 0)
-                hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)std::min<long>(ph * tiles, grid)), dim3(64), 0, m->stream, m->dm, m->hulls_plain,
-                                   m->hullg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
-                                   m->capg_flag.as<int>());
-            if (pm == 0) return FBR_OK;
-            // the recorded poses [ni][13][C] | the stencil distances [ni][C]
-            if (int rc = m->meshg_work.ensure((size_t)ni * (FBR_MESHGRAD_REL + 1) * (size_t)C * sizeof(double))) return rc;
-            double *rel = m->meshg_work.as<double>(), *dv = rel + (size_t)ni * FBR_MESHGRAD_REL * (size_t)C;
-            hipLaunchKernelGGL(fbr_mesh_grad_frames_kernel, dim3((unsigned)std::min<long>(pm * tiles, grid)), dim3(64), 0, m->stream, m->dm, m->hulls,
-                               m->hullg, m->meshes, m->meshg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(),
-                               m->capg_flag.as<int>());
-            {
-                ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
-                hipLaunchKernelGGL(fbr_mesh_grad_dist_kernel, dim3((unsigned)std::min<long>(ni * tiles, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
-                                   m->hulls, m->meshes, m->meshg, C, (const double *)rel, dv);
-            }
-            hipLaunchKernelGGL(fbr_mesh_grad_quot_kernel, dim3((unsigned)((C * pm + 255) / 256)), dim3(256), 0, m->stream, m->hulls, m->meshes, m->meshg,
-                               (int)m->hm.n, C, T, dsmp, dpose, epsilon, (const double *)dv, ddist, dgrad);
-            return FBR_OK;
-        });
 }
 
 extern "C" int fbr_predict(fbr_model *m, const fbr_states *st, const double *x, double *tau_out, int32_t out_mem)

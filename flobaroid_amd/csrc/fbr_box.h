@@ -175,8 +175,10 @@ struct DevBoxes {
     const int2 *pairs;    // [npairs] each entry: a robot-box number, or -1 - (world-box number)
 };
 
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
 // blocks [blk0, blk0 + nb) of the tiling; fr [nb][nrob][12][64]: R (row-major) | centre; the other arguments as for fbr_capsule_points_kernel
+// (The walk is fbr_capsule_points_kernel's, written out a second time: on a shared body this kernel measured 2 % slower on a 9-link
+// robot on an MI355X -- DESIGN.md, "collision layout".)
 __global__ __launch_bounds__(64) void fbr_box_frames_kernel(DevModel m, DevBoxes bx, DevCapTiles tl, long blk0, long nb, int stage, int ldn,
                                                             const double *__restrict__ q, const double *__restrict__ rpy,
                                                             const double *__restrict__ bpos, double *__restrict__ fr, double *__restrict__ scratch)
@@ -255,15 +257,12 @@ __device__ __forceinline__ void fbr_box_fetch(const DevBoxes &bx, int id, const 
 __global__ __launch_bounds__(64) void fbr_box_pairs_kernel(DevBoxes bx, DevCapTiles tl, long blk0, long nb, const double *__restrict__ fr,
                                                            double *__restrict__ pval, long *__restrict__ pidx)
 {
-    __shared__ double sd[FBR_BOX_BATCH * 65];  // [pair of the batch][sample], rows 65 apart: the scan's lanes hit different banks
+    __shared__ double sd[FBR_BOX_BATCH * 65];
     const int lane = threadIdx.x;
     const long nbatch = (bx.npairs + FBR_BOX_BATCH - 1) / FBR_BOX_BATCH, items = nb * nbatch;
     for (long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long b = it / nbatch;
-        const int k0 = (int)(it - b * nbatch) * FBR_BOX_BATCH, cnt = min(FBR_BOX_BATCH, bx.npairs - k0);
-        const long blk = blk0 + b, c = blk / tl.tiles, i0 = (blk - c * tl.tiles) << 6;
-        const int valid = (int)min(64L, tl.Tc - i0);
-        const double *f = fr + b * (long)bx.nrob * 12 * 64 + lane;  // (lanes behind the last checked sample read what an earlier call left: never scanned)
+        const FbrPairItem w = fbr_pair_item(it, nbatch, FBR_BOX_BATCH, bx.npairs, tl, blk0);
+        const double *f = fr + w.b * (long)bx.nrob * 12 * 64 + lane;  // (lanes behind the last checked sample read what an earlier call left: never scanned)
         int cura = 0;
         bool have = false;
         double RA[9], cA[3], hA[3];
@@ -271,8 +270,8 @@ __global__ __launch_bounds__(64) void fbr_box_pairs_kernel(DevBoxes bx, DevCapTi
         for (int i = 0; i < 3; i++) cA[i] = hA[i] = 0.0;
         __syncthreads();  // (the item before has been scanned)
 #pragma unroll 1
-        for (int j = 0; j < cnt; j++) {
-            const fbr_cint_ptr pr = (fbr_cint_ptr)(unsigned long)(bx.pairs + k0 + j);
+        for (int j = 0; j < w.cnt; j++) {
+            const fbr_cint_ptr pr = (fbr_cint_ptr)(unsigned long)(bx.pairs + w.k0 + j);
             const int ia = FBR_UNI(pr[0]), ib = FBR_UNI(pr[1]);
             if (!have || ia != cura) {  // (pair lists come sorted by their first box: it stays in registers)
                 fbr_box_fetch(bx, ia, f, RA, cA, hA);
@@ -284,17 +283,8 @@ __global__ __launch_bounds__(64) void fbr_box_pairs_kernel(DevBoxes bx, DevCapTi
             sd[j * 65 + lane] = fbr_box_distance(RA, cA, hA, RB, cB, hB);
         }
         __syncthreads();
-        if (lane < cnt) {
-            double best = FBR_CAPSULE_NONE;
-            int ibest = -1;
-            for (int r = 0; r < valid; r++) {
-                const double a = sd[lane * 65 + r];
-                if (fbr_capsule_take(a, best)) best = a, ibest = r;
-            }
-            pval[b * bx.npairs + k0 + lane] = best;
-            pidx[b * bx.npairs + k0 + lane] = ibest < 0 ? -1 : (i0 + ibest) * tl.step;
-        }
+        fbr_pair_scan_store(sd, w, lane, tl, bx.npairs, [](int k) { return k; }, pval, pidx);
     }
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__

@@ -156,17 +156,13 @@ FBR_HD double fbr_boxgrad_item(int ka, int kb, int cmode, const double *xa, cons
 }
 
 #if defined(__HIPCC__)
-struct DevBoxGrad {
-    int W;             // words per row of anc
-    const int *anc;    // [nsteps][W] (fbr_capgrad_ancestors)
-    const int4 *pair;  // [npairs] step of the first member's link (-1: a world box), of the second's, slot of the first member's centre
-                       // (DevBoxes.cen; a world box: its number), of the second's
-};
-
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
+// (This kernel and fbr_hull_grad_kernel keep their item preamble and their callbacks written out: with the shared helpers of
+// fbr_capsule.h / fbr_capsule_grad.h their code came out a little different and 1 to 2 % slower on an MI355X -- DESIGN.md, "collision
+// layout".)
 // Work items (pair, tile of 64 candidates), one wave each, pair-major; the arguments as for fbr_capsule_grad_kernel.  eps, se, omc: the
 // stencil step and fbr_boxgrad_trig of it.
-__global__ __launch_bounds__(64) void fbr_box_grad_kernel(DevModel m, DevBoxes bx, DevBoxGrad bg, long C, long T, const double *__restrict__ q,
+__global__ __launch_bounds__(64) void fbr_box_grad_kernel(DevModel m, DevBoxes bx, DevPairGrad bg, long C, long T, const double *__restrict__ q,
                                                           const double *__restrict__ rpy, const double *__restrict__ bpos,
                                                           const long *__restrict__ sample, const double *__restrict__ scale,
                                                           const long *__restrict__ pose, double eps, double se, double omc,
@@ -246,5 +242,5 @@ __global__ __launch_bounds__(64) void fbr_box_grad_kernel(DevModel m, DevBoxes b
         if (live) dist[e] = eval ? dd : FBR_CAPSULE_NONE;
     }
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__

@@ -204,7 +204,44 @@ struct DevCapTiles {
     long T, step, Tc, tiles, nblk;
 };
 
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
+// ---- what fbr_capsule_pairs_kernel, fbr_box_pairs_kernel and fbr_mesh_pairs_kernel share ("collision layout") ------------------
+// Work item `it` of a pairs kernel, one wave: block b of the launch (its first checked sample i0 inside the candidate, `valid` of them) and
+// the batch of cnt pairs from k0.
+struct FbrPairItem {
+    long b, i0;
+    int k0, cnt, valid;
+};
+__device__ __forceinline__ FbrPairItem fbr_pair_item(long it, long nbatch, int batch, int npairs, const DevCapTiles &tl, long blk0)
+{
+    FbrPairItem w;
+    w.b = it / nbatch;
+    w.k0 = (int)(it - w.b * nbatch) * batch;
+    w.cnt = min(batch, npairs - w.k0);
+    const long blk = blk0 + w.b, c = blk / tl.tiles;
+    w.i0 = (blk - c * tl.tiles) << 6;
+    w.valid = (int)min(64L, tl.Tc - w.i0);
+    return w;
+}
+// The tail of a pairs kernel: sd [pair of the batch][sample], rows 65 apart (the scan's lanes hit different banks); one lane per pair scans
+// the item's samples in order (strict <: the first sample wins a tie, a NaN never wins) and writes the block's partial into column
+// col(pair) of pval / pidx [nb][ldp] (FBR_CAPSULE_NONE / -1: no sample won).
+template <class ColFn>
+__device__ __forceinline__ void fbr_pair_scan_store(const double *sd, const FbrPairItem &w, int lane, const DevCapTiles &tl, long ldp, ColFn col,
+                                                    double *pval, long *pidx)
+{
+    if (lane >= w.cnt) return;
+    double best = FBR_CAPSULE_NONE;
+    int ibest = -1;
+    for (int r = 0; r < w.valid; r++) {
+        const double a = sd[lane * 65 + r];
+        if (fbr_capsule_take(a, best)) best = a, ibest = r;
+    }
+    const long o = w.b * ldp + col(w.k0 + lane);
+    pval[o] = best;
+    pidx[o] = ibest < 0 ? -1 : (w.i0 + ibest) * tl.step;
+}
+
 // blocks [blk0, blk0 + nb) of the tiling; ep [nb][ncaps][6][64]; dynamic LDS (stage != 0): the q rows of the block's samples, [64][ldn];
 // scratch [gridDim.x][nslots][12][64]
 __global__ __launch_bounds__(64) void fbr_capsule_points_kernel(DevModel m, DevCapsules cp, DevCapTiles tl, long blk0, long nb, int stage, int ldn,
@@ -266,24 +303,21 @@ __global__ __launch_bounds__(64) void fbr_capsule_points_kernel(DevModel m, DevC
 }
 
 // work items (block, batch of FBR_CAPSULE_BATCH pairs), one wave each; pval / pidx [nb][npairs]: the block's minimum of every pair and the
-// sample index inside the candidate where it is reached (FBR_CAPSULE_NONE / -1: no sample won)
+// sample index inside the candidate where it is reached
 __global__ __launch_bounds__(64) void fbr_capsule_pairs_kernel(DevCapsules cp, DevCapTiles tl, long blk0, long nb, const double *__restrict__ ep,
                                                                double *__restrict__ pval, long *__restrict__ pidx)
 {
-    __shared__ double sd[FBR_CAPSULE_BATCH * 65];  // [pair of the batch][sample], rows 65 apart: the scan's lanes hit different banks
+    __shared__ double sd[FBR_CAPSULE_BATCH * 65];
     const int lane = threadIdx.x;
     const long nbatch = (cp.npairs + FBR_CAPSULE_BATCH - 1) / FBR_CAPSULE_BATCH, items = nb * nbatch;
     for (long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long b = it / nbatch;
-        const int k0 = (int)(it - b * nbatch) * FBR_CAPSULE_BATCH, cnt = min(FBR_CAPSULE_BATCH, cp.npairs - k0);
-        const long blk = blk0 + b, c = blk / tl.tiles, i0 = (blk - c * tl.tiles) << 6;
-        const int valid = (int)min(64L, tl.Tc - i0);
-        const double *e = ep + b * (long)cp.ncaps * 6 * 64 + lane;  // (lanes behind the last checked sample read what an earlier call left: never scanned)
+        const FbrPairItem w = fbr_pair_item(it, nbatch, FBR_CAPSULE_BATCH, cp.npairs, tl, blk0);
+        const double *e = ep + w.b * (long)cp.ncaps * 6 * 64 + lane;  // (lanes behind the last checked sample read what an earlier call left: never scanned)
         int cura = -1;
         double a0[3] = {0, 0, 0}, a1[3] = {0, 0, 0}, ra = 0.0;
         __syncthreads();  // (the item before has been scanned)
-        for (int j = 0; j < cnt; j++) {
-            const fbr_cint_ptr pr = (fbr_cint_ptr)(unsigned long)(cp.pairs + k0 + j);
+        for (int j = 0; j < w.cnt; j++) {
+            const fbr_cint_ptr pr = (fbr_cint_ptr)(unsigned long)(cp.pairs + w.k0 + j);
             const int ia = FBR_UNI(pr[0]), ib = FBR_UNI(pr[1]);
             if (ia != cura) {  // (pair lists come sorted by their first capsule: its endpoints stay in registers)
                 for (int i = 0; i < 3; i++) {
@@ -302,16 +336,7 @@ __global__ __launch_bounds__(64) void fbr_capsule_pairs_kernel(DevCapsules cp, D
             sd[j * 65 + lane] = fbr_segment_distance(a0, a1, b0, b1, &s, &t) - ra - rb;
         }
         __syncthreads();
-        if (lane < cnt) {
-            double best = FBR_CAPSULE_NONE;
-            int ibest = -1;
-            for (int r = 0; r < valid; r++) {
-                const double a = sd[lane * 65 + r];
-                if (fbr_capsule_take(a, best)) best = a, ibest = r;
-            }
-            pval[b * cp.npairs + k0 + lane] = best;
-            pidx[b * cp.npairs + k0 + lane] = ibest < 0 ? -1 : (i0 + ibest) * tl.step;
-        }
+        fbr_pair_scan_store(sd, w, lane, tl, cp.npairs, [](int k) { return k; }, pval, pidx);
     }
 }
 
@@ -337,5 +362,5 @@ __global__ __launch_bounds__(256) void fbr_capsule_finish_kernel(DevCapTiles tl,
     val[c * npairs + k] = best;
     idx[c * npairs + k] = ibest;
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__

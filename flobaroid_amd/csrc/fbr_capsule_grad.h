@@ -134,17 +134,121 @@ FBR_HD int fbr_capgrad_mask(const int *anc, int W, int ka, int kb, int k)
 }
 
 #if defined(__HIPCC__)
-struct DevCapGrad {
+// The table of a set's gradient call (fbr_collision_grad_table), the same for capsules, boxes and hulls.
+struct DevPairGrad {
     int W;             // words per row of anc
-    const int *anc;    // [nsteps][W]
-    const int4 *pair;  // [npairs] step of the first capsule's link, of the second's, slot of the first capsule (DevCapsules.seg), of the second
+    const int *anc;    // [nsteps][W] (fbr_capgrad_ancestors)
+    const int4 *pair;  // [npairs] step of the first member's link (-1: a world member), of the second's, slot of the first member (DevCapsules.seg,
+                       // DevBoxes.cen, DevHulls.fr.cen; a world member: its number), of the second
 };
 
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
+// ---- what fbr_capsule_grad_kernel and fbr_mesh_grad_frames_kernel share ("collision layout"; the box and the hull gradient
+// kernel have the same things written out) --------------------------------------------------------------------------------------------
+// The callbacks that the gradient items (fbr_capgrad_item, fbr_meshgrad_frames_item) take besides the kernel's own.  qf: the joint
+// positions of the lane's configuration, row q, times the item's scale; basef: the base pose inputs of row s; save / load: the lane's
+// column of the branch-point scratch; consts: the constants of link l (l is wave-uniform: scalar loads through the constant address space).
+struct FbrLaneQ {
+    const double *q;
+    double sc;
+    __device__ __forceinline__ double operator()(int d) const { return sc * q[d]; }
+};
+struct FbrLaneBase {
+    const double *rpy, *bpos;
+    long s;
+    __device__ __forceinline__ void operator()(double *e3, double *b3) const
+    {
+        for (int i = 0; i < 3; i++) {
+            e3[i] = rpy ? rpy[s * 3 + i] : 0.0;
+            b3[i] = bpos ? bpos[s * 3 + i] : 0.0;
+        }
+    }
+};
+struct FbrLaneSave {
+    double *scr;
+    __device__ __forceinline__ void operator()(int sl, int i, double v) const { scr[(sl * 12 + i) * 64] = v; }
+};
+struct FbrLaneLoad {
+    const double *scr;
+    __device__ __forceinline__ double operator()(int sl, int i) const { return scr[(sl * 12 + i) * 64]; }
+};
+struct FbrLaneConsts {
+    fbr_cdouble_ptr cR, cq, ca;
+    __device__ __forceinline__ void operator()(int l, double *rR, double *rp, double *ax) const
+    {
+        for (int i = 0; i < 9; i++) rR[i] = cR[9 * l + i];
+        for (int i = 0; i < 3; i++) {
+            rp[i] = cq[3 * l + i];
+            ax[i] = ca[3 * l + i];
+        }
+    }
+};
+struct FbrLaneIO {
+    FbrLaneQ qf;
+    FbrLaneBase basef;
+    FbrLaneSave save;
+    FbrLaneLoad load;
+    FbrLaneConsts consts;
+};
+// scr: the lane's column of the wave's scratch [nslots][12][64]
+__device__ __forceinline__ FbrLaneIO fbr_lane_io(const DevModel &m, const double *qrow, double sc, const double *rpy, const double *bpos, long s,
+                                                 double *scr)
+{
+    return {{qrow, sc},
+            {rpy, bpos, s},
+            {scr},
+            {scr},
+            {(fbr_cdouble_ptr)(unsigned long)m.restR, (fbr_cdouble_ptr)(unsigned long)m.restp, (fbr_cdouble_ptr)(unsigned long)m.axis}};
+}
+
+// The head of work item `it` = (pair k of the launch, tile of 64 candidates), pair-major, one lane per candidate.  sample / scale / pose
+// [C][ld] (scale, pose may be NULL), the pair's column col(k) among the ld; pair: the set's table, by column.  Lanes behind the last
+// candidate repeat it and store nothing (live); a sample or pose index outside -1 .. T - 1 sets *flag and is read clamped (nothing
+// faults); eval: the lane has a sample to evaluate.
+struct FbrGradItem {
+    long k, c, e;        // pair of the launch, candidate, entry c * ld + col
+    int col;             // the pair's column
+    long sr, pr;         // rows of q and of the base pose
+    bool live, eval;
+    double sc;
+    int ka, kb, sla, slb;  // the pair's record: steps of the two members' links (-1: a world member), their slots (a world member: its number)
+};
+template <class ColFn>
+__device__ __forceinline__ FbrGradItem fbr_grad_item_head(long it, long tiles, long C, long T, long ld, ColFn col, const long *sample, const double *scale,
+                                                          const long *pose, const int4 *pair, int *flag)
+{
+    FbrGradItem w;
+    const int lane = threadIdx.x;
+    w.k = it / tiles;
+    const long c0 = (it - w.k * tiles) << 6;
+    const int valid = (int)min(64L, C - c0);
+    w.col = col(w.k);
+    w.c = c0 + min(lane, valid - 1);
+    w.live = lane < valid;
+    w.e = w.c * ld + w.col;
+    const long s = sample[w.e], ps0 = pose ? pose[w.e] : s, ps = ps0 < 0 ? s : ps0;
+    const bool bad = s < -1 || s >= T || ps0 < -1 || ps0 >= T;
+    if (bad && w.live) *flag = 1;
+    w.eval = w.live && s >= 0 && !bad;
+    w.sr = w.c * T + min(max(s, 0L), T - 1);
+    w.pr = w.c * T + min(max(ps, 0L), T - 1);
+    w.sc = scale ? scale[w.e] : 1.0;
+    const int4 pt = pair[w.col];
+    w.ka = FBR_UNI(pt.x), w.kb = FBR_UNI(pt.y), w.sla = FBR_UNI(pt.z), w.slb = FBR_UNI(pt.w);
+    return w;
+}
+// which of a pair's two members step st lies above (fbr_capgrad_mask), cut to `keep`: 3 for capsules, less in fbr_mesh_grad_frames_kernel
+// where a world member owns no step
+struct FbrGradMask {
+    const int *anc;
+    int W, ka, kb, keep;
+    __device__ __forceinline__ int operator()(int st) const { return fbr_capgrad_mask(anc, W, ka, kb, st) & keep; }
+};
+
 // Work items (pair, tile of 64 candidates), one wave each, pair-major; C candidates of T samples; sample / scale / pose [C][npairs] (scale,
 // pose may be NULL).  dist [C][npairs]; grad [C][npairs][n], ZEROED by the caller: only the path joints of evaluated items are stored.
 // scratch [gridDim.x][nslots][12][64].  flag: set when a sample or pose index lies outside -1 .. T - 1 (read clamped: nothing faults).
-__global__ __launch_bounds__(64) void fbr_capsule_grad_kernel(DevModel m, DevCapsules cp, DevCapGrad cg, long C, long T, const double *__restrict__ q,
+__global__ __launch_bounds__(64) void fbr_capsule_grad_kernel(DevModel m, DevCapsules cp, DevPairGrad cg, long C, long T, const double *__restrict__ q,
                                                               const double *__restrict__ rpy, const double *__restrict__ bpos,
                                                               const long *__restrict__ sample, const double *__restrict__ scale,
                                                               const long *__restrict__ pose, double *__restrict__ dist, double *__restrict__ grad,
@@ -154,54 +258,24 @@ __global__ __launch_bounds__(64) void fbr_capsule_grad_kernel(DevModel m, DevCap
     const long P = cp.npairs, tiles = (C + 63) >> 6, items = P * tiles;
     double *scr = scratch + (long)blockIdx.x * cp.nslots * 12 * 64 + lane;
     for (long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long k = it / tiles, c0 = (it - k * tiles) << 6;
-        const int valid = (int)min(64L, C - c0);
-        const long c = c0 + min(lane, valid - 1);  // lanes behind the last candidate repeat it and store nothing
-        const bool live = lane < valid;
-        const long e = c * P + k;
-        const long s = sample[e], ps0 = pose ? pose[e] : s, ps = ps0 < 0 ? s : ps0;
-        const bool bad = s < -1 || s >= T || ps0 < -1 || ps0 >= T;
-        if (bad && live) *flag = 1;
-        const bool eval = live && s >= 0 && !bad;
-        const long sr = c * T + min(max(s, 0L), T - 1), pr = c * T + min(max(ps, 0L), T - 1);
-        const double sc = scale ? scale[e] : 1.0;
-        const int4 pt = cg.pair[k];
-        const int ka = FBR_UNI(pt.x), kb = FBR_UNI(pt.y), sla = FBR_UNI(pt.z), slb = FBR_UNI(pt.w);
-        const int2 ids = cp.pairs[k];
+        const FbrGradItem w = fbr_grad_item_head(it, tiles, C, T, P, [](long k) { return (int)k; }, sample, scale, pose, cg.pair, flag);
+        // (the capsules' own: both members sit on links, and their constants are the segments by slot and the radii by number)
+        const int2 ids = cp.pairs[w.k];
         const fbr_cdouble_ptr crad = (fbr_cdouble_ptr)(unsigned long)cp.radius, cseg = (fbr_cdouble_ptr)(unsigned long)cp.seg;
         const double ra = crad[FBR_UNI(ids.x)], rb = crad[FBR_UNI(ids.y)];
         double sa[6], sb[6];
         for (int i = 0; i < 6; i++) {
-            sa[i] = cseg[6 * sla + i];
-            sb[i] = cseg[6 * slb + i];
+            sa[i] = cseg[6 * w.sla + i];
+            sb[i] = cseg[6 * w.slb + i];
         }
-        const double *myq = q + sr * n;
-        double *g = grad + e * n;
-        auto mask = [&](int st) { return fbr_capgrad_mask(cg.anc, cg.W, ka, kb, st); };
-        auto qf = [&](int d) { return sc * myq[d]; };
-        auto basef = [&](double *e3, double *b3) {
-            for (int i = 0; i < 3; i++) {
-                e3[i] = rpy ? rpy[pr * 3 + i] : 0.0;
-                b3[i] = bpos ? bpos[pr * 3 + i] : 0.0;
-            }
-        };
-        auto save = [&](int sl, int i, double v) { scr[(sl * 12 + i) * 64] = v; };
-        auto load = [&](int sl, int i) { return scr[(sl * 12 + i) * 64]; };
-        auto consts = [&](int l, double *rR, double *rp, double *ax) {  // (l is wave-uniform: scalar loads through the constant address space)
-            const fbr_cdouble_ptr cR = (fbr_cdouble_ptr)(unsigned long)m.restR, cq = (fbr_cdouble_ptr)(unsigned long)m.restp,
-                                  ca = (fbr_cdouble_ptr)(unsigned long)m.axis;
-            for (int i = 0; i < 9; i++) rR[i] = cR[9 * l + i];
-            for (int i = 0; i < 3; i++) {
-                rp[i] = cq[3 * l + i];
-                ax[i] = ca[3 * l + i];
-            }
-        };
-        auto gst = [&](int d, double v) {
+        const FbrLaneIO io = fbr_lane_io(m, q + w.sr * n, w.sc, rpy, bpos, w.pr, scr);
+        auto gst = [g = grad + w.e * n, eval = w.eval](int d, double v) {
             if (eval) g[d] = v;
         };
-        const double dd = fbr_capgrad_item(ka, kb, sa, sb, cp.steps, m.floating && rpy != nullptr, mask, qf, basef, save, load, consts, gst);
-        if (live) dist[e] = eval ? dd - ra - rb : FBR_CAPSULE_NONE;
+        const double dd = fbr_capgrad_item(w.ka, w.kb, sa, sb, cp.steps, m.floating && rpy != nullptr, FbrGradMask{cg.anc, cg.W, w.ka, w.kb, 3}, io.qf, io.basef,
+                                           io.save, io.load, io.consts, gst);
+        if (w.live) dist[w.e] = w.eval ? dd - ra - rb : FBR_CAPSULE_NONE;
     }
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__

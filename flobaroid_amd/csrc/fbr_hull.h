@@ -469,7 +469,7 @@ struct DevHulls {
     int ldp;              // the columns of pval / pidx: npairs, or all pairs of a split set
 };
 
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
 typedef FbrHullT<fbr_cdouble_ptr, fbr_cint_ptr> FbrDevHull;
 
 // the frame and the tables of hull h (wave-uniform) for this lane's sample
@@ -495,6 +495,8 @@ __device__ __forceinline__ void fbr_hull_fetch(const DevHulls &hs, int h, const 
 }
 
 // work items (block, batch of FBR_HULL_BATCH pairs), one wave each; pval / pidx [nb][npairs] as for fbr_box_pairs_kernel
+// (The decode and the scan tail are fbr_pair_item and fbr_pair_scan_store of fbr_capsule.h written out: on the helpers this kernel
+// measured 1 to 2 % slower on an MI355X -- DESIGN.md, "collision layout".)
 __global__ __launch_bounds__(64) void fbr_hull_pairs_kernel(DevHulls hs, DevCapTiles tl, long blk0, long nb, const double *__restrict__ fr,
                                                             double *__restrict__ pval, long *__restrict__ pidx)
 {
@@ -543,5 +545,5 @@ __global__ __launch_bounds__(64) void fbr_hull_pairs_kernel(DevHulls hs, DevCapT
         }
     }
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__

@@ -32,14 +32,7 @@ FBR_HD double fbr_hullgrad_item(int ka, int kb, int cmode, const double *xa, con
 }
 
 #if defined(__HIPCC__)
-struct DevHullGrad {
-    int W;             // words per row of anc
-    const int *anc;    // [nsteps][W] (fbr_capgrad_ancestors)
-    const int4 *pair;  // [npairs] step of the first member's link (-1: a world hull), of the second's, slot of the first member's offset
-                       // (DevHulls.fr.cen; a world hull: its number in DevHulls.world), of the second's
-};
-
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
 // the tables of hull h (wave-uniform), as fbr_hull_fetch reads them
 __device__ __forceinline__ void fbr_hullgrad_tables(const DevHulls &hs, int h, FbrDevHull *H)
 {
@@ -56,7 +49,7 @@ __device__ __forceinline__ void fbr_hullgrad_tables(const DevHulls &hs, int h, F
 // Work items (pair, tile of 64 candidates), one wave each, pair-major; the arguments as for fbr_box_grad_kernel.  hs: the set, or the plain
 // pairs of a set with meshes attached (hs.col: their columns among the hs.ldp pairs of the whole set, which sample / scale / pose, dist
 // and grad are laid out by, as hg.pair is; fbr_mesh_grad.h has the other pairs).
-__global__ __launch_bounds__(64) void fbr_hull_grad_kernel(DevModel m, DevHulls hs, DevHullGrad hg, long C, long T, const double *__restrict__ q,
+__global__ __launch_bounds__(64) void fbr_hull_grad_kernel(DevModel m, DevHulls hs, DevPairGrad hg, long C, long T, const double *__restrict__ q,
                                                            const double *__restrict__ rpy, const double *__restrict__ bpos,
                                                            const long *__restrict__ sample, const double *__restrict__ scale,
                                                            const long *__restrict__ pose, double eps, double se, double omc,
@@ -131,5 +124,5 @@ __global__ __launch_bounds__(64) void fbr_hull_grad_kernel(DevModel m, DevHulls 
         if (live) dist[e] = eval ? dd : FBR_CAPSULE_NONE;
     }
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__

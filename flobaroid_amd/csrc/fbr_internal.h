@@ -161,13 +161,13 @@ struct fbr_model {
     // partials of the blocks in flight, the branch-point poses of the waves in flight, the results of a host-memory call
     DevCapsules caps = {0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     DevBuf cap_tab, cap_ep, cap_part, cap_scratch, cap_out, st_bpos;
-    DevCapGrad capg = {0, nullptr, nullptr};  // fbr_capsule_distance_gradients: ancestor masks and per-pair steps / slots of the set above
+    DevPairGrad capg = {0, nullptr, nullptr};  // fbr_capsule_distance_gradients: ancestor masks and per-pair steps / slots of the set above
     DevBuf capg_tab, capg_flag;
     // box collision set (fbr_model_set_boxes; csrc/fbr_box.h), independent of the capsule set: its tables and the frames of the robot boxes
     // of the blocks in flight; the partials, the branch-point poses and the host results share the capsule call's workspaces
     DevBoxes boxes = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     DevBuf box_tab, box_fr;
-    DevBoxGrad boxg = {0, nullptr, nullptr};  // fbr_box_distance_gradients: ancestor masks and per-pair steps / centre slots of the set above
+    DevPairGrad boxg = {0, nullptr, nullptr};  // fbr_box_distance_gradients: ancestor masks and per-pair steps / centre slots of the set above
     DevBuf boxg_tab;
     // convex-hull collision set (fbr_model_set_hulls; csrc/fbr_hull.h), independent of the other two: its tables; the frames of the robot
     // hulls share the box call's workspace (hulls.fr is the view of the set that fbr_box_frames_kernel takes)
@@ -185,7 +185,7 @@ struct fbr_model {
     DevMeshes meshes = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool has_meshes = false;
     DevBuf mesh_tab;
-    DevHullGrad hullg = {0, nullptr, nullptr};  // fbr_hull_distance_gradients: ancestor masks and per-pair steps / offset slots of the set above
+    DevPairGrad hullg = {0, nullptr, nullptr};  // fbr_hull_distance_gradients: ancestor masks and per-pair steps / offset slots of the set above
     DevBuf hullg_tab;
     // fbr_mesh_distance_gradients (csrc/fbr_mesh_grad.h): the stencil points of the mesh pairs (built with the attachments) and the call's
     // workspace, the recorded poses | the stencil distances -- buffers of its own: what fbr_candidate_hull_distances reads never moves

@@ -1,5 +1,6 @@
 // fbr_kernels.h -- device tables and HIP kernels of libfbr (gfx950).  Every translation unit of the library includes it with the
-// section(s) it launches switched on (FBR_KERNELS_CORE / _GROUPS / _GRAM): a __global__ function is defined in exactly one unit.
+// section(s) it launches switched on (FBR_KERNELS_CORE / _GROUPS / _GRAM here; FBR_KERNELS_COLLISION, of fbr_collision_api.hip, gates the
+// kernels of fbr_capsule.h, fbr_box.h, fbr_hull.h, fbr_mesh.h and their *_grad.h siblings): a __global__ function is defined in exactly one unit.
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>

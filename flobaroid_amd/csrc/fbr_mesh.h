@@ -203,7 +203,7 @@ struct DevMeshes {
     const int *col;      // [npairs] the pair's column among the caller's pairs
 };
 
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
 // work items (block, batch of FBR_MESH_BATCH mesh pairs), one wave each; pval / pidx [nb][hs.ldp]: the columns of ALL pairs of the set (hs: the whole set)
 __global__ __launch_bounds__(64) void fbr_mesh_pairs_kernel(DevHulls hs, DevMeshes ms, DevCapTiles tl, long blk0, long nb, const double *__restrict__ fr,
                                                             double *__restrict__ pval, long *__restrict__ pidx)
@@ -212,12 +212,9 @@ __global__ __launch_bounds__(64) void fbr_mesh_pairs_kernel(DevHulls hs, DevMesh
     const int lane = threadIdx.x;
     const long nbatch = (ms.npairs + FBR_MESH_BATCH - 1) / FBR_MESH_BATCH, items = nb * nbatch;
     for (long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long b = it / nbatch;
-        const int k0 = (int)(it - b * nbatch) * FBR_MESH_BATCH, cnt = min(FBR_MESH_BATCH, ms.npairs - k0);
-        const long blk = blk0 + b, c = blk / tl.tiles, i0 = (blk - c * tl.tiles) << 6;
-        const int valid = (int)min(64L, tl.Tc - i0);
-        // lanes behind the last checked sample repeat it: they take its path through the loops below and are never scanned
-        const double *f = fr + b * (long)hs.fr.nrob * 12 * 64 + min(lane, valid - 1);
+        const FbrPairItem w = fbr_pair_item(it, nbatch, FBR_MESH_BATCH, ms.npairs, tl, blk0);
+        // lanes behind the last checked sample repeat it, as in fbr_hull_pairs_kernel
+        const double *f = fr + w.b * (long)hs.fr.nrob * 12 * 64 + min(lane, w.valid - 1);
         int cura = 0;
         bool have = false;
         double RA[9], cA[3];
@@ -226,8 +223,8 @@ __global__ __launch_bounds__(64) void fbr_mesh_pairs_kernel(DevHulls hs, DevMesh
         for (int i = 0; i < 3; i++) cA[i] = 0.0;
         __syncthreads();  // (the item before has been scanned)
 #pragma unroll 1
-        for (int j = 0; j < cnt; j++) {
-            const fbr_cint_ptr pr = (fbr_cint_ptr)(unsigned long)(ms.pairs + k0 + j);
+        for (int j = 0; j < w.cnt; j++) {
+            const fbr_cint_ptr pr = (fbr_cint_ptr)(unsigned long)(ms.pairs + w.k0 + j);
             const int ia = FBR_UNI(pr[0]), ib = FBR_UNI(pr[1]);
             if (!have || ia != cura) {
                 fbr_hull_fetch(hs, ia, f, RA, cA, &HA);
@@ -246,18 +243,8 @@ __global__ __launch_bounds__(64) void fbr_mesh_pairs_kernel(DevHulls hs, DevMesh
             sd[j * 65 + lane] = fbr_mesh_distance_oriented<true>(q, HA, MA, HB, MB, (fbr_cdouble_ptr)(unsigned long)(ms.sph + 4 * (long)ib), (FbrMeshStats *)nullptr);
         }
         __syncthreads();
-        if (lane < cnt) {
-            double best = FBR_CAPSULE_NONE;
-            int ibest = -1;
-            for (int r = 0; r < valid; r++) {
-                const double a = sd[lane * 65 + r];
-                if (fbr_capsule_take(a, best)) best = a, ibest = r;
-            }
-            const int col = ms.col[k0 + lane];
-            pval[b * hs.ldp + col] = best;
-            pidx[b * hs.ldp + col] = ibest < 0 ? -1 : (i0 + ibest) * tl.step;
-        }
+        fbr_pair_scan_store(sd, w, lane, tl, hs.ldp, [&](int k) { return ms.col[k]; }, pval, pidx);
     }
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__

@@ -92,10 +92,10 @@ struct DevMeshGrad {
     const int *sjoint;  // [nitems] the joint it moves (-1: the centre)
 };
 
-#if defined(FBR_KERNELS_CORE)
+#if defined(FBR_KERNELS_COLLISION)
 // Stage A.  Work items (mesh pair, tile of 64 candidates), one wave each, pair-major; hs: the WHOLE set (sample / scale / pose
 // [C][hs.npairs], the pair's column from ms.col); the other arguments as for fbr_hull_grad_kernel.  rel [mg.nitems][13][C].
-__global__ __launch_bounds__(64) void fbr_mesh_grad_frames_kernel(DevModel m, DevHulls hs, DevHullGrad hg, DevMeshes ms, DevMeshGrad mg, long C, long T,
+__global__ __launch_bounds__(64) void fbr_mesh_grad_frames_kernel(DevModel m, DevHulls hs, DevPairGrad hg, DevMeshes ms, DevMeshGrad mg, long C, long T,
                                                                   const double *__restrict__ q, const double *__restrict__ rpy,
                                                                   const double *__restrict__ bpos, const long *__restrict__ sample,
                                                                   const double *__restrict__ scale, const long *__restrict__ pose, double eps, double se,
@@ -106,65 +106,37 @@ __global__ __launch_bounds__(64) void fbr_mesh_grad_frames_kernel(DevModel m, De
     const long P = hs.npairs, tiles = (C + 63) >> 6, items = ms.npairs * tiles;
     double *scr = scratch + (long)blockIdx.x * hs.fr.nslots * 12 * 64 + lane;
     for (long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long k = it / tiles, c0 = (it - k * tiles) << 6;
-        const int valid = (int)min(64L, C - c0);
-        const long c = c0 + min(lane, valid - 1);  // lanes behind the last candidate repeat it and store nothing
-        const bool live = lane < valid;
-        const int col = FBR_UNI(((fbr_cint_ptr)(unsigned long)ms.col)[k]);
-        const fbr_cint_ptr sb = (fbr_cint_ptr)(unsigned long)(mg.sbeg + k);
+        const FbrGradItem w = fbr_grad_item_head(it, tiles, C, T, P, [&](long k) { return FBR_UNI(((fbr_cint_ptr)(unsigned long)ms.col)[k]); }, sample, scale,
+                                                 pose, hg.pair, flag);
+        const fbr_cint_ptr sb = (fbr_cint_ptr)(unsigned long)(mg.sbeg + w.k);
         const int s0 = FBR_UNI(sb[0]), sk = FBR_UNI(sb[1]) - s0;
-        const long e = c * P + col;
-        const long s = sample[e], ps0 = pose ? pose[e] : s, ps = ps0 < 0 ? s : ps0;
-        const bool bad = s < -1 || s >= T || ps0 < -1 || ps0 >= T;
-        if (bad && live) *flag = 1;
-        const long sr = c * T + min(max(s, 0L), T - 1), pr = c * T + min(max(ps, 0L), T - 1);
-        const double sc = scale ? scale[e] : 1.0;
-        const int4 pt = hg.pair[col];
-        const int ka = FBR_UNI(pt.x), kb = FBR_UNI(pt.y), sla = FBR_UNI(pt.z), slb = FBR_UNI(pt.w);
-        const int ia = FBR_UNI(((fbr_cint_ptr)(unsigned long)hs.pairs)[2 * (long)col]);
+        const int ia = FBR_UNI(((fbr_cint_ptr)(unsigned long)hs.pairs)[2 * (long)w.col]);
         const bool swap = FBR_UNI(((fbr_cint_ptr)(unsigned long)ms.mtab)[2 * (long)ia + 1]) == 0;  // (the mesh is the second member's)
+        // the constants of the two hulls (wave-uniform loads): a robot hull's offset by slot, a world hull's R | position
         const fbr_cdouble_ptr ccen = (fbr_cdouble_ptr)(unsigned long)hs.fr.cen, cworld = (fbr_cdouble_ptr)(unsigned long)hs.world;
         double xa[12], xb[12];
         for (int i = 0; i < 12; i++) xa[i] = xb[i] = 0.0;
-        if (ka >= 0) {
-            for (int i = 0; i < 3; i++) xa[i] = ccen[3 * sla + i];
+        if (w.ka >= 0) {
+            for (int i = 0; i < 3; i++) xa[i] = ccen[3 * w.sla + i];
         } else {
-            for (int i = 0; i < 12; i++) xa[i] = cworld[12 * sla + i];
+            for (int i = 0; i < 12; i++) xa[i] = cworld[12 * w.sla + i];
         }
-        if (kb >= 0) {
-            for (int i = 0; i < 3; i++) xb[i] = ccen[3 * slb + i];
+        if (w.kb >= 0) {
+            for (int i = 0; i < 3; i++) xb[i] = ccen[3 * w.slb + i];
         } else {
-            for (int i = 0; i < 12; i++) xb[i] = cworld[12 * slb + i];
+            for (int i = 0; i < 12; i++) xb[i] = cworld[12 * w.slb + i];
         }
-        const double *myq = q + sr * n;
-        const int kam = ka < 0 ? 0 : ka, kbm = kb < 0 ? 0 : kb, keep = (ka < 0 ? 0 : 1) | (kb < 0 ? 0 : 2);
-        auto mask = [&](int st) { return fbr_capgrad_mask(hg.anc, hg.W, kam, kbm, st) & keep; };  // (a world member owns no step)
-        auto qf = [&](int d) { return sc * myq[d]; };
-        auto basef = [&](double *e3, double *b3) {
-            for (int i = 0; i < 3; i++) {
-                e3[i] = rpy ? rpy[pr * 3 + i] : 0.0;
-                b3[i] = bpos ? bpos[pr * 3 + i] : 0.0;
-            }
-        };
-        auto save = [&](int sl, int i, double v) { scr[(sl * 12 + i) * 64] = v; };
-        auto load = [&](int sl, int i) { return scr[(sl * 12 + i) * 64]; };
-        auto consts = [&](int l, double *rR, double *rp, double *ax) {  // (l is wave-uniform: scalar loads through the constant address space)
-            const fbr_cdouble_ptr cR = (fbr_cdouble_ptr)(unsigned long)m.restR, cq = (fbr_cdouble_ptr)(unsigned long)m.restp,
-                                  ca = (fbr_cdouble_ptr)(unsigned long)m.axis;
-            for (int i = 0; i < 9; i++) rR[i] = cR[9 * l + i];
-            for (int i = 0; i < 3; i++) {
-                rp[i] = cq[3 * l + i];
-                ax[i] = ca[3 * l + i];
-            }
-        };
+        // (a world member, step -1, owns no step)
+        const FbrGradMask mask = {hg.anc, hg.W, w.ka < 0 ? 0 : w.ka, w.kb < 0 ? 0 : w.kb, (w.ka < 0 ? 0 : 1) | (w.kb < 0 ? 0 : 2)};
+        const FbrLaneIO io = fbr_lane_io(m, q + w.sr * n, w.sc, rpy, bpos, w.pr, scr);
         auto rec = [&](int sp, const FbrHullRel &r) {
-            if (!live || sp >= sk) return;  // (the host's table has the walk's count: nothing is stored past the pair's slots)
-            double *w = rel + (long)(s0 + sp) * FBR_MESHGRAD_REL * C + c;
+            if (!w.live || sp >= sk) return;  // (the host's table has the walk's count: nothing is stored past the pair's slots)
+            double *o = rel + (long)(s0 + sp) * FBR_MESHGRAD_REL * C + w.c;
             const double v[FBR_MESHGRAD_REL] = {r.t0, r.t1, r.t2, r.C00, r.C01, r.C02, r.C10, r.C11, r.C12, r.C20, r.C21, r.C22, r.chk};
-            for (int i = 0; i < FBR_MESHGRAD_REL; i++) w[i * C] = v[i];
+            for (int i = 0; i < FBR_MESHGRAD_REL; i++) o[i * C] = v[i];
         };
-        fbr_meshgrad_frames_item(ka, kb, hs.fr.cmode, xa, xb, swap, eps, se, omc, hs.fr.steps, m.floating && rpy != nullptr, mask, qf, basef, save, load,
-                                 consts, rec);
+        fbr_meshgrad_frames_item(w.ka, w.kb, hs.fr.cmode, xa, xb, swap, eps, se, omc, hs.fr.steps, m.floating && rpy != nullptr, mask, io.qf,
+                                 io.basef, io.save, io.load, io.consts, rec);
     }
 }
 
@@ -215,5 +187,5 @@ __global__ __launch_bounds__(256) void fbr_mesh_grad_quot_kernel(DevHulls hs, De
     dist[e] = fbr_meshgrad_quotients(
         sk, [&](int sp) { return mg.sjoint[s0 + sp]; }, [&](int sp) { return d[(long)(s0 + sp) * C + c]; }, eps, [&](int j, double v) { g[j] = v; });
 }
-#endif  // FBR_KERNELS_CORE
+#endif  // FBR_KERNELS_COLLISION
 #endif  // __HIPCC__
