@@ -113,6 +113,8 @@ _SIGNATURES = {
     ),
     "fbr_model_set_hulls": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip, _dp, _ip, _dp, _ip, _ip, ctypes.c_int32,
                                            _ip]),
+    "fbr_model_set_large_hulls": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip, _dp, _ip, _dp, _ip, _ip,
+                                                 ctypes.c_int32, _ip]),
     "fbr_model_set_hull_meshes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _ip, _dp]),
     "fbr_candidate_hull_distances": (
         ctypes.c_int,
@@ -224,6 +226,8 @@ _SIGNATURES = {
 # the ``options`` argument of the constructor.  A plain Python dict: the library itself never reads the process environment.  The test
 # suite uses it to run whole modules with the column reductions forced / switched off (tests/conftest.py: reduction_mode).
 FBR_VERSION = 104  # include/fbr.h FBR_VERSION: the C-ABI these ctypes signatures describe
+FBR_MAX_HULL_VERTICES = 128  # include/fbr.h: a hull of Engine.set_hulls
+FBR_MAX_LARGE_HULL_VERTICES = 1024  # include/fbr.h: a hull of Engine.set_hulls(..., large=True)
 DEFAULT_OPTIONS: dict = {}
 
 
@@ -659,13 +663,18 @@ class Engine:
         ``candidate_capsule_distances``.  Separated boxes: the exact Euclidean distance; overlapping: minus the minimum translation."""
         return self._candidate_distances("fbr_candidate_box_distances", int(getattr(self, "num_box_pairs", 0)), st, ncand, step, base_pos, device_out)
 
-    def set_hulls(self, hulls, pairs, offset_in_link_axes: bool = False, meshes=None) -> None:
+    def set_hulls(self, hulls, pairs, offset_in_link_axes: bool = False, meshes=None, large: bool = False) -> None:
         """Convex-hull collision set of the handle (``fbr_model_set_hulls``), independent of the capsule and the box set.  ``hulls``: a
         sequence of ``flobaroid_amd.collision.Hull`` (``link_name`` None: a world hull with ``rot``), or of tuples ``(link, offset, rot,
         vertices, planes, edges)`` -- link an index, a name, or None / -1; the tables as ``Hull`` derives them.  ``pairs``: (P, 2) indices
         into that sequence.  ``offset_in_link_axes``: False places a robot hull at ``p_link + offset`` (the reference's sum in world
         axes), True at ``p_link + R_link offset``.  Replaces the set in place; an empty ``hulls`` clears it.  ``meshes``: what
-        ``set_hull_meshes`` takes, attached to the new set (None: the new set has no meshes, whatever the one before had)."""
+        ``set_hull_meshes`` takes, attached to the new set (None: the new set has no meshes, whatever the one before had).  ``large``: False
+        is ``fbr_model_set_hulls``, at most ``FBR_MAX_HULL_VERTICES`` (128) vertices a hull; True is ``fbr_model_set_large_hulls``, up to
+        ``FBR_MAX_LARGE_HULL_VERTICES`` (1024): distances only -- no ``meshes`` (ValueError), and the gradient calls refuse the set while
+        one of its hulls has more than 128 vertices."""
+        if large and meshes:
+            raise ValueError("set_hulls(large=True): triangle meshes on a set of large hulls are not built (meshes= needs large=False)")
         names = list(self.topo.link_names)
         link, off, rot, V, F, E, any_world = [], [], [], [], [], [], False
         for h in hulls:
@@ -690,10 +699,11 @@ class Engine:
         verts, planes, edges = cat(V, 3, np.float64), cat(F, 4, np.float64), cat(E, 4, np.int32)
         vbeg, fbeg, ebeg = beg(V), beg(F), beg(E)
         pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
-        _check(self._lib.fbr_model_set_hulls(self._h, int(link.size), link.ctypes.data_as(_ip), off.ctypes.data_as(_dp),
-                                             rot.ctypes.data_as(_dp) if any_world else None, int(bool(offset_in_link_axes)), vbeg.ctypes.data_as(_ip),
-                                             verts.ctypes.data_as(_dp), fbeg.ctypes.data_as(_ip), planes.ctypes.data_as(_dp), ebeg.ctypes.data_as(_ip),
-                                             edges.ctypes.data_as(_ip), int(pr.shape[0]), pr.ctypes.data_as(_ip)), "fbr_model_set_hulls")
+        entry = "fbr_model_set_large_hulls" if large else "fbr_model_set_hulls"
+        _check(getattr(self._lib, entry)(self._h, int(link.size), link.ctypes.data_as(_ip), off.ctypes.data_as(_dp),
+                                         rot.ctypes.data_as(_dp) if any_world else None, int(bool(offset_in_link_axes)), vbeg.ctypes.data_as(_ip),
+                                         verts.ctypes.data_as(_dp), fbeg.ctypes.data_as(_ip), planes.ctypes.data_as(_dp), ebeg.ctypes.data_as(_ip),
+                                         edges.ctypes.data_as(_ip), int(pr.shape[0]), pr.ctypes.data_as(_ip)), entry)
         self.num_hulls, self.num_hull_pairs, self.num_hull_meshes = int(link.size), int(pr.shape[0]), 0
         if meshes:
             self.set_hull_meshes(meshes)

@@ -23,9 +23,11 @@ of a world URDF, and the list of link pairs the trajectory optimiser checks.  Nu
 
 The distances themselves are computed on the device (``Engine.candidate_capsule_distances``, csrc/fbr_capsule.h;
 ``Engine.candidate_box_distances``, csrc/fbr_box.h; ``Engine.candidate_hull_distances``, csrc/fbr_hull.h and, for pairs with a mesh, csrc/fbr_mesh.h; their
-gradients: ``Engine.mesh_distance_gradients``, csrc/fbr_mesh_grad.h, behind ``mesh_gradient=True`` of ``flobaroid_amd.excitation``).  Not covered:
-meshes whose hull has more than ``FBR_MAX_HULL_VERTICES`` vertices or that have more than ``FBR_MAX_MESH_TRIANGLES`` triangles (no
-simplification, no BVH); formats other than STL; parity with FCL's own numbers.
+gradients: ``Engine.mesh_distance_gradients``, csrc/fbr_mesh_grad.h, behind ``mesh_gradient=True`` of ``flobaroid_amd.excitation``).  Hulls of
+``FBR_MAX_HULL_VERTICES`` + 1 to ``FBR_MAX_LARGE_HULL_VERTICES`` vertices (KUKA LWR4: the hulls of its visual meshes) are served for
+distances only: ``hulls_from_urdf(..., max_vertices=FBR_MAX_LARGE_HULL_VERTICES)`` and ``Engine.set_hulls(..., large=True)``,
+csrc/fbr_hull_large.h.  Not covered: gradients of such hulls and meshes attached to them; meshes whose hull has more than
+``FBR_MAX_LARGE_HULL_VERTICES`` vertices or that have more than ``FBR_MAX_MESH_TRIANGLES`` triangles (no simplification, no BVH); formats other than STL; parity with FCL's own numbers.
 """
 from __future__ import annotations
 
@@ -35,7 +37,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-FBR_MAX_HULL_VERTICES = 128  # include/fbr.h
+FBR_MAX_HULL_VERTICES = 128  # include/fbr.h: Engine.set_hulls
+FBR_MAX_LARGE_HULL_VERTICES = 1024  # include/fbr.h: Engine.set_hulls(..., large=True), distances only
 FBR_MAX_MESH_TRIANGLES = 256  # include/fbr.h
 FBR_MAX_MESH_PAIR_WORK = 32768  # include/fbr.h: triangles x triangles of one pair
 _COPLANAR = 1e-10            # x the hull's diameter: neighbouring triangles this flat against each other are one face
@@ -209,7 +212,8 @@ def hulls_from_urdf(urdf, link_names, mesh_base_dir: str = "meshes", x_std=None,
     that origin is NOT applied to the vertices, as in the reference.  ``Hull.bounds`` is ``mesh.bounding_box.bounds * scale``.  Every
     other link (no mesh, or the file is missing) is listed in ``box_links`` and gets the box of ``boxes_from_urdf`` (``x_std``,
     ``cube_size``, ``scale`` = ``scaleCollisionHull`` as there) through ``hull_from_box``; a link without any geometry gets nothing.  A
-    hull with more than ``max_vertices`` vertices raises ValueError naming the link and its count: no simplification is attempted."""
+    hull with more than ``max_vertices`` vertices raises ValueError naming the link and its count: no simplification is attempted.  A
+    robot with visual meshes only (KUKA LWR4) passes ``max_vertices=FBR_MAX_LARGE_HULL_VERTICES``."""
     tree = ET.parse(urdf)
     wanted = list(link_names)
     boxes, _ = boxes_from_urdf(urdf, wanted, x_std=x_std, cube_size=cube_size, scale=scale)

@@ -198,9 +198,10 @@ extern "C" int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *
 }
 
 // ---- convex-hull collision set (csrc/fbr_hull.h) -----------------------------------------------------------------------------------------
-extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
-                                   int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg, const double *planes,
-                                   const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs)
+// fbr_model_set_hulls (max_vertices FBR_MAX_HULL_VERTICES) and fbr_model_set_large_hulls (FBR_MAX_LARGE_HULL_VERTICES, large): one set, two caps
+static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
+                         int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg, const double *planes,
+                         const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs)
 {
     if (!m) {
         set_err("null model");
@@ -208,8 +209,8 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     }
     const FbrHostModel &hm = m->hm;
     std::vector<double> diam((size_t)std::max(std::min(nhulls, FBR_MAX_HULLS), 1), 0.0);
-    const std::string bad = fbr_hull_validate(hm.L, FBR_MAX_HULLS, FBR_MAX_HULL_PAIRS, FBR_MAX_HULL_VERTICES, nhulls, link, offset, rot, vbeg, verts, fbeg,
-                                              planes, ebeg, edges, npairs, pairs, diam.data());
+    const std::string bad = fbr_hull_validate(hm.L, FBR_MAX_HULLS, FBR_MAX_HULL_PAIRS, max_vertices, nhulls, link, offset, rot, vbeg, verts, fbeg, planes, ebeg,
+                                              edges, npairs, pairs, diam.data());
     if (!bad.empty()) {
         set_err(bad);
         return FBR_E_INVALID;
@@ -224,6 +225,10 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
     m->has_meshes = false;
     m->hull_host = {};
+    m->hulls_small = m->hulls_big = m->hulls;
+    m->hull_big = -1;
+    m->hull_big_nv = 0;
+    m->hull_large_set = false;
     if (nhulls == 0) return FBR_OK;
     FbrKinIdProgram prog;
     if (int rc = collision_program(m, prog)) return rc;
@@ -268,8 +273,36 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     dh.col = nullptr;
     dh.ldp = npairs;
     if (int rc = upload_grad_table(m->hullg_tab, srt, link, npairs, pairs, &m->hullg)) return rc;
+    // a hull above the small cap: the pairs of two small hulls, in their order, and the others, in theirs, each with its columns
+    int big = -1;
+    for (int h = 0; h < nhulls && big < 0; h++)
+        if (vbeg[h + 1] - vbeg[h] > FBR_MAX_HULL_VERTICES) big = h;
+    DevHulls small = dh, rest = dh;
+    if (big >= 0) {
+        std::vector<int> sk, bk;
+        for (int k = 0; k < npairs; k++) {
+            const int a = pairs[2 * k], b = pairs[2 * k + 1];
+            (vbeg[a + 1] - vbeg[a] > FBR_MAX_HULL_VERTICES || vbeg[b + 1] - vbeg[b] > FBR_MAX_HULL_VERTICES ? bk : sk).push_back(k);
+        }
+        const size_t ns = std::max(sk.size(), (size_t)1), nl = std::max(bk.size(), (size_t)1);
+        FbrBlob split;  // small pairs | large pairs | small columns | large columns
+        const size_t osp = split.add<int>(2 * ns, sizeof(int2)), olp = split.add<int>(2 * nl, sizeof(int2)), osc = split.add<int>(ns), olc = split.add<int>(nl);
+        for (size_t i = 0; i < sk.size(); i++)
+            split.at<int>(osp)[2 * i] = pairs[2 * sk[i]], split.at<int>(osp)[2 * i + 1] = pairs[2 * sk[i] + 1], split.at<int>(osc)[i] = sk[i];
+        for (size_t i = 0; i < bk.size(); i++)
+            split.at<int>(olp)[2 * i] = pairs[2 * bk[i]], split.at<int>(olp)[2 * i + 1] = pairs[2 * bk[i] + 1], split.at<int>(olc)[i] = bk[i];
+        if (int rc = upload_blob(m->hull_split_tab, split)) return rc;
+        const char *sb = (const char *)m->hull_split_tab.p;
+        small.npairs = (int)sk.size(), small.pairs = (const int2 *)(sb + osp), small.col = (const int *)(sb + osc);
+        rest.npairs = (int)bk.size(), rest.pairs = (const int2 *)(sb + olp), rest.col = (const int *)(sb + olc);
+    }
     m->hulls = dh;
     m->hulls_plain = dh;
+    m->hulls_small = small;
+    m->hulls_big = rest;
+    m->hull_big = big;
+    m->hull_big_nv = big < 0 ? 0 : vbeg[big + 1] - vbeg[big];
+    m->hull_large_set = large;
     m->hull_host.link.assign(link, link + nhulls);
     m->hull_host.vbeg.assign(vbeg, vbeg + nhulls + 1);
     m->hull_host.fbeg.assign(fbeg, fbeg + nhulls + 1);
@@ -280,6 +313,30 @@ extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *
     return FBR_OK;
 }
 
+extern "C" int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
+                                   int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg, const double *planes,
+                                   const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs)
+{
+    return install_hulls(m, FBR_MAX_HULL_VERTICES, false, nhulls, link, offset, rot, offset_in_link_axes, vbeg, verts, fbeg, planes, ebeg, edges, npairs, pairs);
+}
+
+extern "C" int fbr_model_set_large_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
+                                         int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg,
+                                         const double *planes, const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs)
+{
+    return install_hulls(m, FBR_MAX_LARGE_HULL_VERTICES, true, nhulls, link, offset, rot, offset_in_link_axes, vbeg, verts, fbeg, planes, ebeg, edges, npairs,
+                         pairs);
+}
+
+// the hull set has a hull above FBR_MAX_HULL_VERTICES vertices: what `who` does is not built for it
+static bool refuse_large_hulls(const fbr_model *m, const char *who)
+{
+    if (m->hull_big < 0) return false;
+    set_err(std::string(who) + ": hull " + std::to_string(m->hull_big) + " of the set has " + std::to_string(m->hull_big_nv) + " vertices, more than " +
+            std::to_string(FBR_MAX_HULL_VERTICES) + " (a set of fbr_model_set_large_hulls: distances only, no meshes and no gradients)");
+    return true;
+}
+
 // ---- triangle meshes on hulls of the set (csrc/fbr_mesh.h) ---------------------------------------------------------------------------------
 extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris)
 {
@@ -287,6 +344,7 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
         set_err("null model");
         return FBR_E_INVALID;
     }
+    if (refuse_large_hulls(m, "fbr_model_set_hull_meshes")) return FBR_E_INVALID;
     const auto &hh = m->hull_host;
     const int nhulls = m->hulls.nhulls, npairs = m->hulls.npairs;
     const std::string bad = fbr_mesh_validate(nhulls, hh.link.data(), hh.fbeg.data(), hh.planes.data(), hh.diam.data(), npairs, hh.pairs.data(),
@@ -526,12 +584,31 @@ extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, 
     return candidate_frame_distances(m, !m || have ? nullptr : "no hull set with at least one pair (fbr_model_set_hulls)", m ? m->hulls.fr : kNoBoxes, P,
                                      (P + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
                                      [&](unsigned grid, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
+                                         const long cap = (long)m->num_cus * 32;
+                                         const auto large = [&](const DevHulls &hs) {
+                                             const long items = nb * ((hs.npairs + FBR_HULL_LARGE_BATCH - 1) / FBR_HULL_LARGE_BATCH);
+                                             hipLaunchKernelGGL(fbr_hull_large_pairs_kernel, dim3((unsigned)std::min(items, cap)), dim3(64), 0, m->stream, hs, tl,
+                                                                b0, nb, fr, pval, pidx);
+                                         };
+                                         if (!m->has_meshes && m->hull_large_set && m->opt.hull_large_all != 0) {
+                                             large(m->hulls);  // (every pair, in the caller's columns)
+                                             return;
+                                         }
+                                         if (!m->has_meshes && m->hull_big >= 0) {
+                                             // a set with large hulls: the pairs of two small hulls, then the others, each into its own columns
+                                             const long ps = m->hulls_small.npairs;
+                                             if (ps > 0)
+                                                 hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ps + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
+                                                                    dim3(64), 0, m->stream, m->hulls_small, tl, b0, nb, fr, pval, pidx);
+                                             if (m->hulls_big.npairs > 0) large(m->hulls_big);
+                                             return;
+                                         }
                                          if (!m->has_meshes) {
                                              hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, m->hulls, tl, b0, nb, fr, pval, pidx);
                                              return;
                                          }
                                          // a split set: the pairs without a mesh, then those with one, each into its own columns
-                                         const long cap = (long)m->num_cus * 32, ph = m->hulls_plain.npairs, pm = m->meshes.npairs;
+                                         const long ph = m->hulls_plain.npairs, pm = m->meshes.npairs;
                                          if (ph > 0)
                                              hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ph + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
                                                                 dim3(64), 0, m->stream, m->hulls_plain, tl, b0, nb, fr, pval, pidx);
@@ -677,6 +754,7 @@ extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, c
         set_err("no hull set with at least one pair (fbr_model_set_hulls)");
         return FBR_E_INVALID;
     }
+    if (refuse_large_hulls(m, "fbr_hull_distance_gradients")) return FBR_E_INVALID;
     if (m->has_meshes) {
         set_err("fbr_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); gradients of mesh pairs are not built");
         return FBR_E_UNSUPPORTED;
@@ -709,6 +787,7 @@ extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, c
         set_err("no hull set with at least one pair (fbr_model_set_hulls)");
         return FBR_E_INVALID;
     }
+    if (refuse_large_hulls(m, "fbr_mesh_distance_gradients")) return FBR_E_INVALID;
     if (!m->has_meshes) {
         set_err("fbr_mesh_distance_gradients: the hull set has no triangle meshes attached (fbr_model_set_hull_meshes); fbr_hull_distance_gradients "
                 "serves a set of hulls only");

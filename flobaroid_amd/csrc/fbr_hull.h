@@ -20,6 +20,8 @@
 // Frames: R_link | p_link + offset per checked sample is what fbr_box_frames_kernel writes for a box centre; the hull set carries a DevBoxes
 // view (steps, slots, offsets) and that kernel is reused.  fbr_hull_pairs_kernel has the structure of fbr_box_pairs_kernel.
 // The GJK loop (fbr_hull_gjk) and the relative pose (fbr_hull_relative) are functions of their own: fbr_mesh.h calls them on triangles.
+// So is the facet pass (fbr_hull_facets), over every facet or over one part of them: fbr_hull_large.h deals the parts to the lanes of a wave
+// for hulls of 129 to FBR_MAX_LARGE_HULL_VERTICES vertices (fbr_model_set_large_hulls).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -33,6 +35,9 @@
 #define FBR_HULL_GAP_REL 1e-15                   // duality gap relative to |v|^2
 #define FBR_HULL_NOISE (8.0 * 2.220446049250313e-16)  // x scale: below this |v| counts as touching; x |v| scale: the roundings of v.w
 #define FBR_HULL_FLAT 1e-12                      // x scale^3: a tetrahedron of smaller volume (x 6) encloses nothing
+#ifndef FBR_HULL_KEY_BITS                        // (tests/test_hulls_large.py builds the emulation once more with 8, the width of before)
+#define FBR_HULL_KEY_BITS 10                     // a support pair's key is (ia << 10) | ib: unique up to FBR_MAX_LARGE_HULL_VERTICES = 1 << 10
+#endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define FBR_HULL_ANY(p) (__builtin_amdgcn_ballot_w64(p) != 0)  // the wave's vote: the loops below are wave-uniform
@@ -215,7 +220,7 @@ FBR_HD double fbr_hull_gjk(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const
                 const int ia = fbr_hull_support(A.nv, A.verts, -v0, -v1, -v2, pa);
                 const int ib = fbr_hull_support(B.nv, B.verts, C00 * v0 + C10 * v1 + C20 * v2, C01 * v0 + C11 * v1 + C21 * v2,
                                                 C02 * v0 + C12 * v1 + C22 * v2, pb);
-                const int key = (ia << 8) | ib;
+                const int key = (ia << FBR_HULL_KEY_BITS) | ib;
                 P[3][0] = pa[0] - ((C00 * pb[0] + C01 * pb[1] + C02 * pb[2]) + t0);
                 P[3][1] = pa[1] - ((C10 * pb[0] + C11 * pb[1] + C12 * pb[2]) + t1);
                 P[3][2] = pa[2] - ((C20 * pb[0] + C21 * pb[1] + C22 * pb[2]) + t2);
@@ -305,6 +310,83 @@ FBR_HD double fbr_hull_gjk(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const
     return res;
 }
 
+// The facet pass of a touching or overlapping pair: the largest signed gap over those facets of the Minkowski difference A - (C B + t) whose
+// index is `part` modulo `nparts` -- the faces of A, the faces of B, and the edges of B, each against every edge of A (the inner loop stays
+// whole).  (0, 1): all of them, what fbr_hull_distance returns for a touching pair.  A maximum: the parts may be taken in any order and
+// joined with the same rule (g > gap: a NaN is never taken); only the sign of a zero may depend on the order.  -1e300 for an empty part.
+// (csrc/fbr_hull_large.h shares one pass among the 64 lanes of a wave.)
+template <class DP, class IP>
+FBR_HD double fbr_hull_facets(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const FbrHullT<DP, IP> &B, int part, int nparts)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double t0 = q.t0, t1 = q.t1, t2 = q.t2, C00 = q.C00, C01 = q.C01, C02 = q.C02, C10 = q.C10, C11 = q.C11, C12 = q.C12, C20 = q.C20,
+                 C21 = q.C21, C22 = q.C22;
+    double gap = -1e300;
+#pragma unroll 1
+    for (int f = part; f < A.nf; f += nparts) {  // the faces of A: n . t - o + min over B of (C^T n) . v
+        const double n0 = A.planes[4 * f], n1 = A.planes[4 * f + 1], n2 = A.planes[4 * f + 2], o = A.planes[4 * f + 3];
+        const double low = fbr_hull_low(B.nv, B.verts, C00 * n0 + C10 * n1 + C20 * n2, C01 * n0 + C11 * n1 + C21 * n2,
+                                        C02 * n0 + C12 * n1 + C22 * n2);
+        const double g = ((n0 * t0 + n1 * t1 + n2 * t2) - o) + low;
+        gap = g > gap ? g : gap;
+    }
+#pragma unroll 1
+    for (int f = part; f < B.nf; f += nparts) {  // the faces of B, their normals C n in A's axes: min over A of (C n) . v - (C n) . t - o
+        const double m0 = B.planes[4 * f], m1 = B.planes[4 * f + 1], m2 = B.planes[4 * f + 2], o = B.planes[4 * f + 3];
+        const double n0 = C00 * m0 + C01 * m1 + C02 * m2, n1 = C10 * m0 + C11 * m1 + C12 * m2, n2 = C20 * m0 + C21 * m1 + C22 * m2;
+        const double g = (fbr_hull_low(A.nv, A.verts, n0, n1, n2) - (n0 * t0 + n1 * t1 + n2 * t2)) - o;
+        gap = g > gap ? g : gap;
+    }
+    // The edge pairs that form a face of the Minkowski difference: on the Gauss map the arc between the normals a, b of the two
+    // faces at A's edge crosses the arc between the negated normals c, d at B's edge (Gregorius, "The Separating Axis Test between
+    // Convex Polyhedra", GDC 2013).  The axis: the normalised cross product of the edges, turned out of A.
+#pragma unroll 1
+    for (int eb = part; eb < B.ne; eb += nparts) {
+        const int bv0 = B.edges[4 * eb], bv1 = B.edges[4 * eb + 1], bf0 = B.edges[4 * eb + 2], bf1 = B.edges[4 * eb + 3];
+        double c0, c1, c2, e0, e1, e2, q0, q1, q2, u0, u1, u2;
+        {
+            const double m0 = B.planes[4 * bf0], m1 = B.planes[4 * bf0 + 1], m2 = B.planes[4 * bf0 + 2];
+            c0 = -(C00 * m0 + C01 * m1 + C02 * m2), c1 = -(C10 * m0 + C11 * m1 + C12 * m2), c2 = -(C20 * m0 + C21 * m1 + C22 * m2);
+        }
+        {
+            const double m0 = B.planes[4 * bf1], m1 = B.planes[4 * bf1 + 1], m2 = B.planes[4 * bf1 + 2];
+            e0 = -(C00 * m0 + C01 * m1 + C02 * m2), e1 = -(C10 * m0 + C11 * m1 + C12 * m2), e2 = -(C20 * m0 + C21 * m1 + C22 * m2);
+        }
+        {
+            const double x = B.verts[3 * bv0], y = B.verts[3 * bv0 + 1], z = B.verts[3 * bv0 + 2];
+            q0 = (C00 * x + C01 * y + C02 * z) + t0, q1 = (C10 * x + C11 * y + C12 * z) + t1, q2 = (C20 * x + C21 * y + C22 * z) + t2;
+            const double dx = B.verts[3 * bv1] - x, dy = B.verts[3 * bv1 + 1] - y, dz = B.verts[3 * bv1 + 2] - z;
+            u0 = C00 * dx + C01 * dy + C02 * dz, u1 = C10 * dx + C11 * dy + C12 * dz, u2 = C20 * dx + C21 * dy + C22 * dz;
+        }
+        const double x0 = e1 * c2 - e2 * c1, x1 = e2 * c0 - e0 * c2, x2 = e0 * c1 - e1 * c0;  // d x c
+        const double uu = u0 * u0 + u1 * u1 + u2 * u2;
+#pragma unroll 1
+        for (int ea = 0; ea < A.ne; ea++) {
+            const int af0 = A.edges[4 * ea + 2], af1 = A.edges[4 * ea + 3];
+            const double a0 = A.planes[4 * af0], a1 = A.planes[4 * af0 + 1], a2 = A.planes[4 * af0 + 2];
+            const double b0 = A.planes[4 * af1], b1 = A.planes[4 * af1 + 1], b2 = A.planes[4 * af1 + 2];
+            const double y0 = b1 * a2 - b2 * a1, y1 = b2 * a0 - b0 * a2, y2 = b0 * a1 - b1 * a0;  // b x a
+            const double cba = c0 * y0 + c1 * y1 + c2 * y2, dba = e0 * y0 + e1 * y1 + e2 * y2;
+            const double adc = a0 * x0 + a1 * x1 + a2 * x2, bdc = b0 * x0 + b1 * x1 + b2 * x2;
+            if (cba * dba < 0.0 && adc * bdc < 0.0 && cba * bdc > 0.0) {
+                const int av0 = A.edges[4 * ea], av1 = A.edges[4 * ea + 1];
+                const double p0 = A.verts[3 * av0], p1 = A.verts[3 * av0 + 1], p2 = A.verts[3 * av0 + 2];
+                const double w0 = A.verts[3 * av1] - p0, w1 = A.verts[3 * av1 + 1] - p1, w2 = A.verts[3 * av1 + 2] - p2;
+                double n0 = w1 * u2 - w2 * u1, n1 = w2 * u0 - w0 * u2, n2 = w0 * u1 - w1 * u0;
+                const double len2 = n0 * n0 + n1 * n1 + n2 * n2;
+                if (len2 >= FBR_BOX_PARALLEL * ((w0 * w0 + w1 * w1 + w2 * w2) * uu)) {
+                    const double s = (n0 * (a0 + b0) + n1 * (a1 + b1) + n2 * (a2 + b2) < 0.0 ? -1.0 : 1.0) / sqrt(len2);
+                    const double g = s * (n0 * (q0 - p0) + n1 * (q1 - p1) + n2 * (q2 - p2));
+                    gap = g > gap ? g : gap;
+                }
+            }
+        }
+    }
+    return gap;
+}
+
 // Signed distance of the hulls A at (RA, cA) and B at (RB, cB): R [9] row-major (orthonormal), c [3] the origin of the hull's axes in the
 // world.  A NaN or an infinity among the poses gives a NaN.  iters (may be null): the GJK iterations taken, + 1000 when the facet pass ran.
 template <class DP, class IP>
@@ -320,75 +402,9 @@ FBR_HD double fbr_hull_distance(const double *RA, const double *cA, const FbrHul
     int it;
     double res = fbr_hull_gjk(q, A, B, false, &touching, &it);
     if (iters) *iters = it + (touching ? 1000 : 0);
-    const double t0 = q.t0, t1 = q.t1, t2 = q.t2, C00 = q.C00, C01 = q.C01, C02 = q.C02, C10 = q.C10, C11 = q.C11, C12 = q.C12, C20 = q.C20,
-                 C21 = q.C21, C22 = q.C22;
-
     // ---- touching or overlapping: the largest signed gap over the facets of the Minkowski difference
     if (FBR_HULL_ANY(touching)) {
-        if (touching) {
-            double gap = -1e300;
-#pragma unroll 1
-            for (int f = 0; f < A.nf; f++) {  // the faces of A: n . t - o + min over B of (C^T n) . v
-                const double n0 = A.planes[4 * f], n1 = A.planes[4 * f + 1], n2 = A.planes[4 * f + 2], o = A.planes[4 * f + 3];
-                const double low = fbr_hull_low(B.nv, B.verts, C00 * n0 + C10 * n1 + C20 * n2, C01 * n0 + C11 * n1 + C21 * n2,
-                                                C02 * n0 + C12 * n1 + C22 * n2);
-                const double g = ((n0 * t0 + n1 * t1 + n2 * t2) - o) + low;
-                gap = g > gap ? g : gap;
-            }
-#pragma unroll 1
-            for (int f = 0; f < B.nf; f++) {  // the faces of B, their normals C n in A's axes: min over A of (C n) . v - (C n) . t - o
-                const double m0 = B.planes[4 * f], m1 = B.planes[4 * f + 1], m2 = B.planes[4 * f + 2], o = B.planes[4 * f + 3];
-                const double n0 = C00 * m0 + C01 * m1 + C02 * m2, n1 = C10 * m0 + C11 * m1 + C12 * m2, n2 = C20 * m0 + C21 * m1 + C22 * m2;
-                const double g = (fbr_hull_low(A.nv, A.verts, n0, n1, n2) - (n0 * t0 + n1 * t1 + n2 * t2)) - o;
-                gap = g > gap ? g : gap;
-            }
-            // The edge pairs that form a face of the Minkowski difference: on the Gauss map the arc between the normals a, b of the two
-            // faces at A's edge crosses the arc between the negated normals c, d at B's edge (Gregorius, "The Separating Axis Test between
-            // Convex Polyhedra", GDC 2013).  The axis: the normalised cross product of the edges, turned out of A.
-#pragma unroll 1
-            for (int eb = 0; eb < B.ne; eb++) {
-                const int bv0 = B.edges[4 * eb], bv1 = B.edges[4 * eb + 1], bf0 = B.edges[4 * eb + 2], bf1 = B.edges[4 * eb + 3];
-                double c0, c1, c2, e0, e1, e2, q0, q1, q2, u0, u1, u2;
-                {
-                    const double m0 = B.planes[4 * bf0], m1 = B.planes[4 * bf0 + 1], m2 = B.planes[4 * bf0 + 2];
-                    c0 = -(C00 * m0 + C01 * m1 + C02 * m2), c1 = -(C10 * m0 + C11 * m1 + C12 * m2), c2 = -(C20 * m0 + C21 * m1 + C22 * m2);
-                }
-                {
-                    const double m0 = B.planes[4 * bf1], m1 = B.planes[4 * bf1 + 1], m2 = B.planes[4 * bf1 + 2];
-                    e0 = -(C00 * m0 + C01 * m1 + C02 * m2), e1 = -(C10 * m0 + C11 * m1 + C12 * m2), e2 = -(C20 * m0 + C21 * m1 + C22 * m2);
-                }
-                {
-                    const double x = B.verts[3 * bv0], y = B.verts[3 * bv0 + 1], z = B.verts[3 * bv0 + 2];
-                    q0 = (C00 * x + C01 * y + C02 * z) + t0, q1 = (C10 * x + C11 * y + C12 * z) + t1, q2 = (C20 * x + C21 * y + C22 * z) + t2;
-                    const double dx = B.verts[3 * bv1] - x, dy = B.verts[3 * bv1 + 1] - y, dz = B.verts[3 * bv1 + 2] - z;
-                    u0 = C00 * dx + C01 * dy + C02 * dz, u1 = C10 * dx + C11 * dy + C12 * dz, u2 = C20 * dx + C21 * dy + C22 * dz;
-                }
-                const double x0 = e1 * c2 - e2 * c1, x1 = e2 * c0 - e0 * c2, x2 = e0 * c1 - e1 * c0;  // d x c
-                const double uu = u0 * u0 + u1 * u1 + u2 * u2;
-#pragma unroll 1
-                for (int ea = 0; ea < A.ne; ea++) {
-                    const int af0 = A.edges[4 * ea + 2], af1 = A.edges[4 * ea + 3];
-                    const double a0 = A.planes[4 * af0], a1 = A.planes[4 * af0 + 1], a2 = A.planes[4 * af0 + 2];
-                    const double b0 = A.planes[4 * af1], b1 = A.planes[4 * af1 + 1], b2 = A.planes[4 * af1 + 2];
-                    const double y0 = b1 * a2 - b2 * a1, y1 = b2 * a0 - b0 * a2, y2 = b0 * a1 - b1 * a0;  // b x a
-                    const double cba = c0 * y0 + c1 * y1 + c2 * y2, dba = e0 * y0 + e1 * y1 + e2 * y2;
-                    const double adc = a0 * x0 + a1 * x1 + a2 * x2, bdc = b0 * x0 + b1 * x1 + b2 * x2;
-                    if (cba * dba < 0.0 && adc * bdc < 0.0 && cba * bdc > 0.0) {
-                        const int av0 = A.edges[4 * ea], av1 = A.edges[4 * ea + 1];
-                        const double p0 = A.verts[3 * av0], p1 = A.verts[3 * av0 + 1], p2 = A.verts[3 * av0 + 2];
-                        const double w0 = A.verts[3 * av1] - p0, w1 = A.verts[3 * av1 + 1] - p1, w2 = A.verts[3 * av1 + 2] - p2;
-                        double n0 = w1 * u2 - w2 * u1, n1 = w2 * u0 - w0 * u2, n2 = w0 * u1 - w1 * u0;
-                        const double len2 = n0 * n0 + n1 * n1 + n2 * n2;
-                        if (len2 >= FBR_BOX_PARALLEL * ((w0 * w0 + w1 * w1 + w2 * w2) * uu)) {
-                            const double s = (n0 * (a0 + b0) + n1 * (a1 + b1) + n2 * (a2 + b2) < 0.0 ? -1.0 : 1.0) / sqrt(len2);
-                            const double g = s * (n0 * (q0 - p0) + n1 * (q1 - p1) + n2 * (q2 - p2));
-                            gap = g > gap ? g : gap;
-                        }
-                    }
-                }
-            }
-            res = gap;
-        }
+        if (touching) res = fbr_hull_facets(q, A, B, 0, 1);
     }
     return res;
 }

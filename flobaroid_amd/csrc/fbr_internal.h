@@ -25,6 +25,7 @@
 #include "fbr_box_grad.h"
 #include "fbr_hull.h"
 #include "fbr_hull_grad.h"
+#include "fbr_hull_large.h"
 #include "fbr_mesh.h"
 #include "fbr_mesh_grad.h"
 #include "fbr_gram64.h"
@@ -174,6 +175,14 @@ struct fbr_model {
     DevHulls hulls = {{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
                       nullptr, nullptr, nullptr, 0};
     DevBuf hull_tab;
+    // a set with a hull above FBR_MAX_HULL_VERTICES vertices (fbr_model_set_large_hulls; csrc/fbr_hull_large.h): its pairs split into those
+    // of two small hulls (hulls_small: the view fbr_hull_pairs_kernel takes, its columns in col) and the others (hulls_big: the view
+    // fbr_hull_large_pairs_kernel takes); hull_big: the first hull above the cap, -1: none (then the views are not used); hull_large_set:
+    // fbr_model_set_large_hulls installed the set (option hull_large_all applies)
+    DevHulls hulls_small = hulls, hulls_big = hulls;
+    DevBuf hull_split_tab;
+    int hull_big = -1, hull_big_nv = 0;
+    bool hull_large_set = false;
     // triangle meshes attached to hulls of that set (fbr_model_set_hull_meshes; csrc/fbr_mesh.h): the host's copy of what the checks and the
     // bounding spheres need of the hull set, the mesh tables, and the set's pairs split into those without a mesh (hulls_plain: the view
     // fbr_hull_pairs_kernel takes, its columns in col) and those with one (meshes).  meshes.npairs == 0: nothing attached.

@@ -16,6 +16,8 @@ struct FbrOptions {
     double h2d_chunked = 1;                 // pinned host inputs are staged chunk by chunk on a copy stream
     // ---- per-sample entry points
     double fused_id = 1;                    // fbr_predict / fbr_inverse_dynamics_batch: kinematics + torques in one kernel, no records in HBM (0: two kernels)
+    // ---- collision
+    double hull_large_all = 0;              // fbr_candidate_hull_distances on a set of fbr_model_set_large_hulls: 1: every pair through fbr_hull_large_pairs_kernel
     // ---- fused Gram program
     double gram_lane_waves = 8;             // gram_lane, models of the one-workgroup-per-CU shape: 8 waves of 18 accumulators (16: 16 waves of 10; measured slower)
     double gram_force_tiles = 1;            // gram_lane: the force rows of the base wrench run on tiles of the columns that have a force (fbr_gram64.h)
@@ -62,6 +64,7 @@ static inline const FbrOptionKey *fbr_option_keys(int *count)
         {"min_chunks", &FbrOptions::min_chunks, false},
         {"h2d_chunked", &FbrOptions::h2d_chunked, false},
         {"fused_id", &FbrOptions::fused_id, false},
+        {"hull_large_all", &FbrOptions::hull_large_all, false},  // (read at every call: both pair lists are built with the set)
         {"gram_lane", &FbrOptions::gram_lane, false},
         {"gram_force_tiles", &FbrOptions::gram_force_tiles, true},   // (these three shape the program of the sample-contiguous pass, get_gram64)
         {"gram_lane_waves", &FbrOptions::gram_lane_waves, true},

@@ -457,6 +457,33 @@ def _wants_hull_gradient(config, collision, hull_gradient) -> bool:
     return True
 
 
+def _large_hulls(collision) -> list:
+    """[(link or world name, vertices)] of the hulls of the set above ``FBR_MAX_HULL_VERTICES`` vertices, which ``Engine.set_hulls`` takes
+    with ``large=True`` only"""
+    from .collision import FBR_MAX_HULL_VERTICES
+
+    if collision is None or "hulls" not in collision:
+        return []
+    out = []
+    for h in collision["hulls"]:
+        if not hasattr(h, "vertices") and not (isinstance(h, (tuple, list)) and len(h) >= 4):
+            continue  # (not a hull as Engine.set_hulls takes it: that call says so)
+        v = h.vertices if hasattr(h, "vertices") else h[3]
+        if len(v) > FBR_MAX_HULL_VERTICES:
+            out.append(((h.link_name or h.name) if hasattr(h, "vertices") else h[0], len(v)))
+    return out
+
+
+def _refuse_large_hull_gradient(collision) -> None:
+    """hulls above ``FBR_MAX_HULL_VERTICES`` vertices are served for distances only: every gradient entry point refuses the set by the
+    names and counts of those hulls, whatever its ``*_gradient`` keywords say"""
+    big = _large_hulls(collision)
+    if big and _has_hull_pairs(collision):
+        raise ValueError("gradients on the device do not cover hulls of more than 128 vertices: the collision set has "
+                         + ", ".join(f"{name} ({nv} vertices)" for name, nv in big)
+                         + "; the constraint values are served (Engine.set_hulls(..., large=True)), their gradients are not built")
+
+
 def _collision_block(engine, states, ncand, config, collision, suspended=None):
     """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins``, and for sets with boxes ``boxes``, ``box_pairs``, ``columns``
     and optionally ``center_in_link_axes``, for sets with hulls ``hulls``, ``hull_pairs``, ``columns`` and ``offset_in_link_axes``
@@ -501,6 +528,8 @@ def _collision_block(engine, states, ncand, config, collision, suspended=None):
             engine.set_boxes(collision["boxes"], collision["box_pairs"], center_in_link_axes=bool(collision.get("center_in_link_axes", False)))
         else:
             kw = {"meshes": collision["meshes"]} if _has_meshes(collision) else {}
+            if _large_hulls(collision):  # (the keyword only then: engines of before know nothing of it)
+                kw["large"] = True
             engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)), **kw)
         part = candidate_collision_constraints(engine, states, ncand, config, margins=m[sel], suspended=suspended, boxes=which == 1, hulls=which == 2)
         if out is None:
@@ -777,6 +806,7 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     and an exactly zero row (a mesh carries no penetration depth).  The keyword with a set without meshes, or in the modes ``"capsule"``
     and ``"box"``, raises ``ValueError``."""
     _check_config(config)
+    _refuse_large_hull_gradient(collision)
     mesh_rows = _wants_mesh_gradient(config, collision, mesh_gradient)
     if not mesh_rows:
         _refuse_mesh_gradient(collision)
@@ -1016,6 +1046,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     "full"``) is refused by the names of the meshed links; ``True`` with such a set and configuration: the rows of all its pairs come from
     ``Engine.mesh_distance_gradients`` (``candidate_collision_gradient``)."""
     _check_config(config)
+    _refuse_large_hull_gradient(collision)
     mesh_rows = collision is not None and _wants_mesh_gradient(config, collision, mesh_gradient)
     if not mesh_rows:
         _refuse_mesh_gradient(collision)

@@ -89,7 +89,7 @@ typedef struct {
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
  * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes;
- * fbr_mesh_distance_gradients. */
+ * fbr_mesh_distance_gradients; fbr_model_set_large_hulls, option "hull_large_all". */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -285,10 +285,30 @@ int fbr_candidate_box_distances(fbr_model *m, const fbr_states *st, const double
  */
 #define FBR_MAX_HULLS 4096
 #define FBR_MAX_HULL_PAIRS 262144
-#define FBR_MAX_HULL_VERTICES 128   /* per hull: bounds the worst-case edge-pair loop */
+#define FBR_MAX_HULL_VERTICES 128   /* per hull, fbr_model_set_hulls: bounds the edge-pair loop that ONE LANE walks for a touching pair
+                                     * (E_A E_B <= 378^2 arc tests).  Larger hulls: fbr_model_set_large_hulls below */
 int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
                         int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg,
                         const double *planes, const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs);
+
+/*
+ * The same set with hulls of up to FBR_MAX_LARGE_HULL_VERTICES vertices: the hulls of visual meshes (KUKA LWR4 has no collision meshes; its
+ * eight hulls have 158 to 793 vertices).  Arguments, checks and rules of fbr_model_set_hulls, which keeps refusing 129 vertices; the call
+ * replaces the hull set in place, whichever of the two calls installed it, and either call replaces a set this one installed.
+ * fbr_candidate_hull_distances serves such a set pair by pair: a pair whose two hulls both have at most FBR_MAX_HULL_VERTICES vertices goes
+ * to the kernel of fbr_model_set_hulls and returns the bits it returns from that call; every other pair goes to
+ * fbr_hull_large_pairs_kernel (csrc/fbr_hull_large.h), where the 64 lanes of a wave share the facet pass of a touching sample -- the same
+ * value (the maximum over the same facets; the sign of a zero gap may differ), the same bits on every run.  Option "hull_large_all" = 1
+ * sends every pair of a set installed by THIS call to that kernel (not while triangle meshes are attached to it, which needs a set
+ * of small hulls only: then fbr_model_set_hull_meshes' split of the pairs holds).
+ * While a hull of the set has more than FBR_MAX_HULL_VERTICES vertices, fbr_model_set_hull_meshes, fbr_hull_distance_gradients and
+ * fbr_mesh_distance_gradients return FBR_E_INVALID with the hull's number and its vertex count in the message: meshes on, and gradients of,
+ * large hulls are not built.
+ */
+#define FBR_MAX_LARGE_HULL_VERTICES 1024   /* per hull, fbr_model_set_large_hulls: E_A E_B <= 3066^2 arc tests, shared by 64 lanes */
+int fbr_model_set_large_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
+                              int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg,
+                              const double *planes, const int32_t *ebeg, const int32_t *edges, int32_t npairs, const int32_t *pairs);
 
 /*
  * Per candidate and hull pair the smallest signed distance over the checked samples and the sample where it is reached: arguments, outputs
@@ -717,6 +737,9 @@ int fbr_suspended_records(fbr_model *m, const fbr_states *st, const double *x_st
  *                                      fold is half as long and a 125 k-sample call is 0.45 ms shorter this way)
  *   "tsqr_prologue_overlap"      1     a submission's kinematics / first writer beside the merge trees of the one before
  *   "tsqr_short_call_factors"    1     fewer private factors (shallower merge trees) for calls too short to amortise them
+ *   "hull_large_all"             0     fbr_candidate_hull_distances, a set installed by fbr_model_set_large_hulls: 1 sends every pair to
+ *                                      fbr_hull_large_pairs_kernel, also those of two hulls of at most FBR_MAX_HULL_VERTICES vertices (tests:
+ *                                      the two kernels on the same pairs).  Read by every call: a later change is never ignored
  *   "gram_serial", "gram_timing", "tsqr_timing"  0   diagnostics (producer on the main stream; cycle counters printed to stderr)
  * fbr_model_option_name enumerates the keys (index 0 .. until it fails).
  */

@@ -50,6 +50,10 @@ npz) and writes small derived fixtures; no reference source code is copied.
                                               numerics (those stay unpinned).  Same for
                                               Model.getRandomRegressor (model.py:634-830) and the D-optimality gradient worker
                                               _dopt_gradient_worker_func (excitation/analyticalGradient.py:46-185).
+  tests/golden/kuka_hulls.npz                 the vertices of the convex hulls of model/meshes/kuka/*.STL (the visual meshes of KUKA LWR4, which
+                                              has no collision meshes) as the files' own float32, 158 to 793 a hull, with the link names and
+                                              the offsets flobaroid_amd.collision.hulls_from_urdf gives them (visual/origin xyz): data only,
+                                              about 50 KB; the STL files, 55 to 220 KB each, stay out
 """
 import json
 import os
@@ -1062,7 +1066,34 @@ def reference_capsules(golden):
     print("ref_capsules.npz:", len(out), "arrays")
 
 
+def kuka_hulls(golden):
+    """tests/golden/kuka_hulls.npz (see the module docstring): link [8], mesh [8] names, vbeg [9], verts [sum V][3] float32, offset [8][3]"""
+    import shutil
+    import tempfile
+
+    from flobaroid_amd.collision import FBR_MAX_LARGE_HULL_VERTICES, hulls_from_urdf
+
+    links = ["lwr_base_link"] + [f"lwr_{i}_link" for i in range(1, 8)]
+    with tempfile.TemporaryDirectory() as td:  # (the URDF names its meshes relative to its own directory)
+        shutil.copy(os.path.join(REF, "model", "kuka_lwr4.urdf"), td)
+        shutil.copytree(os.path.join(REF, "model", "meshes"), os.path.join(td, "meshes"))
+        hulls, box_links = hulls_from_urdf(os.path.join(td, "kuka_lwr4.urdf"), links, max_vertices=FBR_MAX_LARGE_HULL_VERTICES)
+    assert not box_links and list(hulls) == links
+    verts = [hulls[n].vertices.astype(np.float32) for n in links]
+    for n, v in zip(links, verts):
+        assert np.array_equal(v.astype(np.float64), hulls[n].vertices), n  # (unscaled STL coordinates: float32 holds them exactly)
+        print(f"  {n}: {len(hulls[n].vertices)} vertices, {len(hulls[n].planes)} faces, {len(hulls[n].edges)} edges")
+    mesh = ["base"] + [f"link_{i}" for i in range(1, 8)]
+    np.savez_compressed(os.path.join(golden, "kuka_hulls.npz"), link=np.array(links), mesh=np.array(mesh),
+                        vbeg=np.cumsum([0] + [len(v) for v in verts]).astype(np.int32), verts=np.concatenate(verts),
+                        offset=np.array([hulls[n].offset for n in links]))
+    print("kuka_hulls.npz:", sum(len(v) for v in verts), "vertices")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "kuka_hulls":
+        kuka_hulls(os.path.join(REPO, "tests", "golden"))
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "capsules":
         reference_capsules(os.path.join(REPO, "tests", "golden"))
         sys.exit(0)
@@ -1083,3 +1114,4 @@ if __name__ == "__main__":
     reference_identification_fb(os.path.join(REPO, "tests", "golden"))
     reference_trajectories(os.path.join(REPO, "tests", "golden"))
     reference_capsules(os.path.join(REPO, "tests", "golden"))
+    kuka_hulls(os.path.join(REPO, "tests", "golden"))
