@@ -136,6 +136,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_large_hull_distance_gradients": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -830,6 +835,16 @@ class Engine:
         an exactly zero row: a mesh carries no penetration depth.  A set without meshes is refused (``hull_distance_gradients`` serves it)."""
         return self._distance_gradients("fbr_mesh_distance_gradients", int(getattr(self, "num_hull_pairs", 0)), (float(epsilon),), st, ncand, sample,
                                         scale, pose_sample, base_pos, device_out)
+
+    def large_hull_distance_gradients(self, st: dict, ncand: int, sample, scale=None, pose_sample=None, base_pos=None, epsilon: float = 1e-7,
+                                      device_out: bool | None = None) -> dict:
+        """``hull_distance_gradients`` for a hull set installed with ``set_hulls(..., large=True)`` (``fbr_large_hull_distance_gradients``):
+        ``{"dist": (C, P_hull), "grad_q": (C, P_hull, n)}`` over ALL pairs of the set, arguments and rules as there.  A pair of two hulls
+        of at most ``FBR_MAX_HULL_VERTICES`` vertices returns the bytes ``hull_distance_gradients`` gives it from a set without large
+        hulls; every other pair (every pair with option ``hull_large_all`` = 1) the same central differences with the facet pass of a
+        touching stencil point shared by a wave.  A set installed without ``large=True`` is refused."""
+        return self._distance_gradients("fbr_large_hull_distance_gradients", int(getattr(self, "num_hull_pairs", 0)), (float(epsilon),), st, ncand,
+                                        sample, scale, pose_sample, base_pos, device_out)
 
     def _distance_gradients(self, entry: str, P: int, extra: tuple, st: dict, ncand: int, sample, scale, pose_sample, base_pos, device_out) -> dict:
         """the capsule, the box, the hull and the mesh call share their arguments: ``entry`` names the library's function, ``P`` the pairs of its set, ``extra``

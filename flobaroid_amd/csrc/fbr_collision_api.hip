@@ -5,6 +5,7 @@
 #define FBR_KERNELS_COLLISION
 #include "fbr_internal.h"
 #include "fbr_collision_tables.h"
+#include "fbr_hull_large_grad.h"
 
 // ---- what the three sets share -------------------------------------------------------------------------------------------------------
 static int collision_program(const fbr_model *m, FbrKinIdProgram &prog)
@@ -229,6 +230,10 @@ static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhu
     m->hull_big = -1;
     m->hull_big_nv = 0;
     m->hull_large_set = false;
+    for (int i = 0; i < 2; i++) {
+        m->hull_lgrad[i] = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
+        m->hull_lgrad_sbeg[i].clear();
+    }
     if (nhulls == 0) return FBR_OK;
     FbrKinIdProgram prog;
     if (int rc = collision_program(m, prog)) return rc;
@@ -295,6 +300,47 @@ static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhu
         const char *sb = (const char *)m->hull_split_tab.p;
         small.npairs = (int)sk.size(), small.pairs = (const int2 *)(sb + osp), small.col = (const int *)(sb + osc);
         rest.npairs = (int)bk.size(), rest.pairs = (const int2 *)(sb + olp), rest.col = (const int *)(sb + olc);
+    }
+    // the stencil points of fbr_large_hull_distance_gradients (csrc/fbr_hull_large_grad.h): per large pair the centre, then + eps, - eps of
+    // every joint fbr_rigidgrad_item evaluates, in walk order -- for the pairs of `rest` and for every pair (option hull_large_all, read by
+    // every call): sbeg | pair of a point | its joint, twice
+    DevMeshGrad lgrad[2] = {{0, 0, nullptr, nullptr, nullptr}, {0, 0, nullptr, nullptr, nullptr}};
+    std::vector<int> lsbeg[2];
+    if (large && npairs > 0) {
+        std::vector<int> stepof, anc, joint, gtab;
+        fbr_capgrad_ancestors(hm, prog, stepof, anc);
+        const auto isbig = [&](int h) { return vbeg[h + 1] - vbeg[h] > FBR_MAX_HULL_VERTICES; };
+        size_t off[2], np[2];
+        for (int arr = 0; arr < 2; arr++) {
+            std::vector<int> gpair, gjoint;
+            lsbeg[arr].assign(1, 0);
+            int smax = 0;
+            for (int k = 0; k < npairs; k++) {
+                const int a = pairs[2 * k], b = pairs[2 * k + 1];
+                if (arr == 0 && big >= 0 && !isbig(a) && !isbig(b)) continue;  // (no hull above the cap: `rest` is the whole set)
+                fbr_meshgrad_slots(link[a] < 0 ? -1 : stepof[link[a]], link[b] < 0 ? -1 : stepof[link[b]], offset_in_link_axes ? 1 : 0, prog.steps.data(),
+                                   anc.data(), fbr_capgrad_words(prog.nsteps), joint);
+                gpair.insert(gpair.end(), joint.size(), (int)lsbeg[arr].size() - 1);
+                gjoint.insert(gjoint.end(), joint.begin(), joint.end());
+                lsbeg[arr].push_back(lsbeg[arr].back() + (int)joint.size());
+                smax = std::max(smax, (int)joint.size());
+            }
+            off[arr] = gtab.size(), np[arr] = lsbeg[arr].size() - 1;
+            lgrad[arr].nitems = (int)gpair.size(), lgrad[arr].smax = smax;
+            gtab.insert(gtab.end(), lsbeg[arr].begin(), lsbeg[arr].end());
+            gtab.insert(gtab.end(), gpair.begin(), gpair.end());
+            gtab.insert(gtab.end(), gjoint.begin(), gjoint.end());
+        }
+        if (int rc = m->hull_lgrad_tab.ensure(gtab.size() * sizeof(int))) return rc;
+        HIPCHK(hipMemcpy(m->hull_lgrad_tab.p, gtab.data(), gtab.size() * sizeof(int), hipMemcpyHostToDevice));
+        for (int arr = 0; arr < 2; arr++) {
+            const int *g = m->hull_lgrad_tab.as<int>() + off[arr];
+            lgrad[arr].sbeg = g, lgrad[arr].spair = g + np[arr] + 1, lgrad[arr].sjoint = g + np[arr] + 1 + lgrad[arr].nitems;
+        }
+    }
+    for (int i = 0; i < 2; i++) {
+        m->hull_lgrad[i] = lgrad[i];
+        m->hull_lgrad_sbeg[i] = lsbeg[i];
     }
     m->hulls = dh;
     m->hulls_plain = dh;
@@ -818,6 +864,79 @@ extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, c
             }
             hipLaunchKernelGGL(fbr_mesh_grad_quot_kernel, dim3((unsigned)((C * pm + 255) / 256)), dim3(256), 0, m->stream, m->hulls, m->meshes, m->meshg,
                                (int)m->hm.n, C, T, dsmp, dpose, epsilon, (const double *)dv, ddist, dgrad);
+            return FBR_OK;
+        });
+}
+
+// A hull set installed by fbr_model_set_large_hulls: the pairs of two hulls of at most FBR_MAX_HULL_VERTICES vertices through
+// fbr_hull_grad_kernel, into their columns; the large pairs -- every pair with option hull_large_all -- through the three stages of
+// csrc/fbr_hull_large_grad.h.
+extern "C" int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                                 const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out,
+                                                 double *grad_q_out, int32_t out_mem)
+{
+    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
+        set_err("fbr_large_hull_distance_gradients: epsilon must be finite and positive");
+        return FBR_E_INVALID;
+    }
+    if (m->hulls.nhulls == 0 || !m->hull_large_set) {
+        set_err("fbr_large_hull_distance_gradients: no hull set installed by fbr_model_set_large_hulls (fbr_hull_distance_gradients serves a set of "
+                "fbr_model_set_hulls)");
+        return FBR_E_INVALID;
+    }
+    if (m->hulls.npairs == 0) {
+        set_err("fbr_large_hull_distance_gradients: the hull set has no pair");
+        return FBR_E_INVALID;
+    }
+    if (m->has_meshes) {  // (only a set without a hull above the cap can have them: fbr_model_set_hull_meshes)
+        set_err("fbr_large_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); "
+                "fbr_mesh_distance_gradients serves such a set");
+        return FBR_E_UNSUPPORTED;
+    }
+    const double wopt = m->opt.hull_grad_tile;
+    if (!(wopt == 0 || wopt == 1 || wopt == 2 || wopt == 4 || wopt == 8 || wopt == 16 || wopt == 32 || wopt == 64)) {
+        set_err("fbr_large_hull_distance_gradients: option hull_grad_tile must be 0 or a power of two from 1 to 64");
+        return FBR_E_INVALID;
+    }
+    const bool all = m->opt.hull_large_all != 0;
+    const int arr = all ? 1 : 0;
+    const DevHulls none = DevHulls{kNoBoxes, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    const DevHulls hsmall = all ? none : (m->hull_big >= 0 ? m->hulls_small : m->hulls), hbig = all ? m->hulls : (m->hull_big >= 0 ? m->hulls_big : none);
+    const DevMeshGrad lg = m->hull_lgrad[arr];
+    const std::vector<int> &sbeg = m->hull_lgrad_sbeg[arr];
+    double se, omc;
+    fbr_boxgrad_trig(epsilon, &se, &omc);
+    return distance_gradients(
+        m, "fbr_large_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem, m->hulls.npairs,
+        m->hulls.fr.nslots,
+        [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
+            double *ddist, double *dgrad) -> int {
+            const long tiles = (C + 63) / 64, ps = hsmall.npairs, pl = hbig.npairs, ni = lg.nitems;
+            if (ps > 0)
+                hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)std::min<long>(ps * tiles, grid)), dim3(64), 0, m->stream, m->dm, hsmall, m->hullg, C,
+                                   T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
+                                   m->capg_flag.as<int>());
+            if (pl == 0) return FBR_OK;
+            if ((long)sbeg.size() != pl + 1) {
+                set_err("fbr_large_hull_distance_gradients: the stencil tables do not match the set");
+                return FBR_E_INVALID;
+            }
+            // the recorded poses [ni][13][C] | the stencil distances [ni][C]
+            if (int rc = m->hull_lgrad_work.ensure((size_t)ni * (FBR_MESHGRAD_REL + 1) * (size_t)C * sizeof(double))) return rc;
+            double *rel = m->hull_lgrad_work.as<double>(), *dv = rel + (size_t)ni * FBR_MESHGRAD_REL * (size_t)C;
+            hipLaunchKernelGGL(fbr_hull_large_grad_frames_kernel, dim3((unsigned)std::min<long>(pl * tiles, grid)), dim3(64), 0, m->stream, m->dm, hbig,
+                               m->hullg, lg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(),
+                               m->capg_flag.as<int>());
+            const int width = wopt != 0 ? (int)wopt : fbr_hull_large_grad_width(sbeg.data(), (int)pl, C, (long)FBR_HULL_LARGE_GRAD_WAVES_PER_CU * m->num_cus);
+            const long tpp = ((long)lg.smax * C + width - 1) / width;
+            {
+                ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
+                hipLaunchKernelGGL(fbr_hull_large_grad_dist_kernel, dim3((unsigned)std::min<long>(pl * tpp, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
+                                   hbig, lg, C, width, tpp, (const double *)rel, dv);
+            }
+            hipLaunchKernelGGL(fbr_hull_large_grad_quot_kernel, dim3((unsigned)((C * pl + 255) / 256)), dim3(256), 0, m->stream, hbig, lg, (int)m->hm.n, C, T,
+                               dsmp, dpose, epsilon, (const double *)dv, ddist, dgrad);
             return FBR_OK;
         });
 }

@@ -183,6 +183,13 @@ struct fbr_model {
     DevBuf hull_split_tab;
     int hull_big = -1, hull_big_nv = 0;
     bool hull_large_set = false;
+    // fbr_large_hull_distance_gradients (csrc/fbr_hull_large_grad.h): the stencil points of the large pairs, built with a set of
+    // fbr_model_set_large_hulls for both arrangements of option hull_large_all -- [0] the pairs of hulls_big, [1] every pair of the set --,
+    // the host's copy of their sbeg (the tile width of stage B is chosen from it) and the call's workspace, the recorded poses | the
+    // stencil distances
+    DevMeshGrad hull_lgrad[2] = {{0, 0, nullptr, nullptr, nullptr}, {0, 0, nullptr, nullptr, nullptr}};
+    std::vector<int> hull_lgrad_sbeg[2];
+    DevBuf hull_lgrad_tab, hull_lgrad_work;
     // triangle meshes attached to hulls of that set (fbr_model_set_hull_meshes; csrc/fbr_mesh.h): the host's copy of what the checks and the
     // bounding spheres need of the hull set, the mesh tables, and the set's pairs split into those without a mesh (hulls_plain: the view
     // fbr_hull_pairs_kernel takes, its columns in col) and those with one (meshes).  meshes.npairs == 0: nothing attached.

@@ -484,6 +484,29 @@ def _refuse_large_hull_gradient(collision) -> None:
                          + "; the constraint values are served (Engine.set_hulls(..., large=True)), their gradients are not built")
 
 
+def _wants_large_hull_gradient(config, collision, large_hull_gradient) -> bool:
+    """True when ``large_hull_gradient=True`` selects the rows of ``Engine.large_hull_distance_gradients``: ``collisionMode: "convex"``, a set
+    of hull pairs only, at least one hull above ``FBR_MAX_HULL_VERTICES`` vertices and no triangle meshes.  False without the keyword:
+    every refusal of before then holds.  The keyword with anything else raises and says which condition fails."""
+    if not large_hull_gradient:
+        return False
+    mode = config.get("collisionMode", "capsule")
+    if mode != "convex":
+        raise ValueError(f"large_hull_gradient=True: collisionMode '{mode}' is not 'convex', the only mode whose pairs are hulls of more than 128 "
+                         "vertices")
+    if _has_meshes(collision) or config.get("fullMeshLinks"):
+        raise ValueError("large_hull_gradient=True: the collision set has triangle meshes or the configuration names fullMeshLinks (meshes on large "
+                         "hulls are not built; mesh_gradient=True serves a set of small hulls with meshes)")
+    if collision is None or "hulls" not in collision or not _has_hull_pairs(collision) or "columns" not in collision:
+        raise ValueError("large_hull_gradient=True: collisionMode 'convex' needs a collision set with hull pairs "
+                         "(flobaroid_amd.collision.collision_set(..., hulls=))")
+    if (np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)[:, 0] != 2).any():
+        raise ValueError("large_hull_gradient=True: the collision set has capsule or box pairs")
+    if not _large_hulls(collision):
+        raise ValueError("large_hull_gradient=True: the collision set has no hull above 128 vertices; hull_gradient=True serves such a set")
+    return True
+
+
 def _collision_block(engine, states, ncand, config, collision, suspended=None):
     """``collision``: dict with ``capsules``, ``pairs`` and optionally ``margins``, and for sets with boxes ``boxes``, ``box_pairs``, ``columns``
     and optionally ``center_in_link_axes``, for sets with hulls ``hulls``, ``hull_pairs``, ``columns`` and ``offset_in_link_axes``
@@ -771,7 +794,7 @@ def _chain_positions(engine, candidates, freq, sample, scale, grad_q, max_bytes)
 
 def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: list, freq: float, config: dict, collision: dict,
                                  constraints: dict | None = None, max_bytes: int = 2**31, box_gradient: bool = False, epsilon=None,
-                                 hull_gradient: bool = False, mesh_gradient: bool = False) -> dict:
+                                 hull_gradient: bool = False, mesh_gradient: bool = False, large_hull_gradient: bool = False) -> dict:
     """The collision block ``g = distance - margin`` (C, P) of ``ncand`` equal candidates stacked in ``states`` and its derivative with
     respect to the entries of the candidates' ``fourier_coefficients`` dicts, from which ``states`` were generated at ``freq`` Hz
     (``candidate_states``).  ``collision``: capsules, pairs and optionally margins (``flobaroid_amd.collision.collision_set``);
@@ -804,14 +827,22 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     ``Engine.mesh_distance_gradients`` exactly as ``hull_gradient=True`` takes them from the hull call: the reference's central
     differences of the mesh distance, the plain pairs of the set as the hull call returns them.  A pair in intersection has distance 0.0
     and an exactly zero row (a mesh carries no penetration depth).  The keyword with a set without meshes, or in the modes ``"capsule"``
-    and ``"box"``, raises ``ValueError``."""
+    and ``"box"``, raises ``ValueError``.
+
+    ``large_hull_gradient=False``: a set with a hull above 128 vertices (KUKA LWR4's hulls of visual meshes) is refused by the names and
+    vertex counts of those hulls, whatever the keywords above.  ``True`` serves it: ``collisionMode: "convex"``, a set of hull pairs only
+    with at least one such hull and no triangle meshes; the hull set is installed with ``large=True`` and the rows of ALL its pairs come
+    from ``Engine.large_hull_distance_gradients`` exactly as ``hull_gradient=True`` takes them from the hull call (``hull_gradient`` may
+    then be either value).  The keyword with anything else raises ``ValueError`` and says which condition fails."""
     _check_config(config)
-    _refuse_large_hull_gradient(collision)
-    mesh_rows = _wants_mesh_gradient(config, collision, mesh_gradient)
+    large_rows = _wants_large_hull_gradient(config, collision, large_hull_gradient)
+    if not large_rows:
+        _refuse_large_hull_gradient(collision)
+    mesh_rows = not large_rows and _wants_mesh_gradient(config, collision, mesh_gradient)
     if not mesh_rows:
         _refuse_mesh_gradient(collision)
     mode = config.get("collisionMode", "capsule")
-    if mesh_rows or _wants_hull_gradient(config, collision, hull_gradient):
+    if large_rows or mesh_rows or _wants_hull_gradient(config, collision, hull_gradient):
         C, n = int(ncand), engine.n
         bpos = states.get("base_position") if engine.floating else None
         cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision)
@@ -819,9 +850,10 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
         cols = np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)
         sel = np.argsort(cols[:, 1], kind="stable")  # (the set's own pair order)
         smp, sc, pose = (np.ascontiguousarray(np.asarray(cons[k])[:, sel]) for k in ("eval_sample", "eval_scale", "eval_pose"))
-        kw = {"meshes": collision["meshes"]} if mesh_rows else {}
+        kw = {"meshes": collision["meshes"]} if mesh_rows else ({"large": True} if large_rows else {})
         engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)), **kw)
-        gradients = engine.mesh_distance_gradients if mesh_rows else engine.hull_distance_gradients
+        gradients = (engine.large_hull_distance_gradients if large_rows else
+                     engine.mesh_distance_gradients if mesh_rows else engine.hull_distance_gradients)
         dg = gradients(states, C, smp, scale=sc, pose_sample=pose, base_pos=bpos, epsilon=eps)
         part, nh = _chain_positions(engine, candidates, freq, smp, sc, dg["grad_q"], max_bytes)
         out, grad_q = np.zeros((C, cols.shape[0], part.shape[2])), np.zeros((C, cols.shape[0], n))
@@ -877,13 +909,14 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
 
 def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
                                                    max_bytes: int = 2**31, box_gradient: bool = False, hull_gradient: bool = False,
-                                                   mesh_gradient: bool = False) -> dict:
+                                                   mesh_gradient: bool = False, large_hull_gradient: bool = False) -> dict:
     """``candidate_collision_gradient`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
-    (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``, ``hull_gradient``, ``mesh_gradient``:
-    as there."""
+    (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``, ``hull_gradient``, ``mesh_gradient``,
+    ``large_hull_gradient``: as there."""
     st = candidate_states(engine, candidates, int(T), float(freq), device=True)
     return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes,
-                                        box_gradient=box_gradient, hull_gradient=hull_gradient, mesh_gradient=mesh_gradient)
+                                        box_gradient=box_gradient, hull_gradient=hull_gradient, mesh_gradient=mesh_gradient,
+                                        large_hull_gradient=large_hull_gradient)
 
 
 def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
@@ -1019,7 +1052,8 @@ def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_a
 
 def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict, joint_names,
                                           config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1,
-                                          box_gradient: bool = False, hull_gradient: bool = False, mesh_gradient: bool = False) -> dict:
+                                          box_gradient: bool = False, hull_gradient: bool = False, mesh_gradient: bool = False,
+                                          large_hull_gradient: bool = False) -> dict:
     """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
     and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
     one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
@@ -1044,14 +1078,20 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     differences of the hull distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base,
     gravity-only models (refused).  ``mesh_gradient=False``: a ``collision`` set with triangle meshes (``fullMeshLinks``, ``collisionMode:
     "full"``) is refused by the names of the meshed links; ``True`` with such a set and configuration: the rows of all its pairs come from
-    ``Engine.mesh_distance_gradients`` (``candidate_collision_gradient``)."""
+    ``Engine.mesh_distance_gradients`` (``candidate_collision_gradient``).  ``large_hull_gradient=False``: a ``collision`` set with a hull
+    above 128 vertices is refused by the names and vertex counts of those hulls; ``True`` with ``collisionMode: "convex"``, hull pairs only
+    and no meshes: the rows of all its pairs come from ``Engine.large_hull_distance_gradients`` (``candidate_collision_gradient``)."""
     _check_config(config)
-    _refuse_large_hull_gradient(collision)
-    mesh_rows = collision is not None and _wants_mesh_gradient(config, collision, mesh_gradient)
+    large_rows = collision is not None and _wants_large_hull_gradient(config, collision, large_hull_gradient)
+    if large_hull_gradient and collision is None:
+        raise ValueError("large_hull_gradient=True: no collision set (collision=)")
+    if not large_rows:
+        _refuse_large_hull_gradient(collision)
+    mesh_rows = not large_rows and collision is not None and _wants_mesh_gradient(config, collision, mesh_gradient)
     if not mesh_rows:
         _refuse_mesh_gradient(collision)
-    hull_rows = not mesh_rows and collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
-    if _has_hull_pairs(collision) and not (hull_rows or mesh_rows):
+    hull_rows = not (mesh_rows or large_rows) and collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
+    if _has_hull_pairs(collision) and not (hull_rows or mesh_rows or large_rows):
         raise ValueError(_NO_HULL_GRADIENT)
     if _has_box_pairs(collision) and not box_gradient:
         raise ValueError("gradients on the device cover capsule pairs only: the collision set has box pairs (the reference differentiates those "
@@ -1083,7 +1123,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     con_grad = _gradient_dict(con, n, nh)
     if coll is not None:
         cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll, box_gradient=box_gradient,
-                                          epsilon=eps, hull_gradient=hull_rows, mesh_gradient=mesh_rows)["grad"]
+                                          epsilon=eps, hull_gradient=hull_rows, mesh_gradient=mesh_rows, large_hull_gradient=large_rows)["grad"]
         con_grad = {k: np.concatenate([v, cg[k]], axis=1) for k, v in con_grad.items()}
     return {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
             "layout": lay, "ag_cache": ag, "objectives": obj}

@@ -89,7 +89,8 @@ typedef struct {
  * fbr_fourier_gradient; and, in the same way, fbr_capsule_distance_gradients, fbr_fourier_position_chain; fbr_torque_row_sweep,
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
  * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes;
- * fbr_mesh_distance_gradients; fbr_model_set_large_hulls, option "hull_large_all". */
+ * fbr_mesh_distance_gradients; fbr_model_set_large_hulls, option "hull_large_all"; fbr_large_hull_distance_gradients, option
+ * "hull_grad_tile". */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -302,8 +303,9 @@ int fbr_model_set_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const
  * sends every pair of a set installed by THIS call to that kernel (not while triangle meshes are attached to it, which needs a set
  * of small hulls only: then fbr_model_set_hull_meshes' split of the pairs holds).
  * While a hull of the set has more than FBR_MAX_HULL_VERTICES vertices, fbr_model_set_hull_meshes, fbr_hull_distance_gradients and
- * fbr_mesh_distance_gradients return FBR_E_INVALID with the hull's number and its vertex count in the message: meshes on, and gradients of,
- * large hulls are not built.
+ * fbr_mesh_distance_gradients return FBR_E_INVALID with the hull's number and its vertex count in the message: meshes on large hulls are
+ * not built, and the gradients of such a set have an entry point of their own, fbr_large_hull_distance_gradients below.  The option
+ * "hull_large_all" applies to that call as well.
  */
 #define FBR_MAX_LARGE_HULL_VERTICES 1024   /* per hull, fbr_model_set_large_hulls: E_A E_B <= 3066^2 arc tests, shared by 64 lanes */
 int fbr_model_set_large_hulls(fbr_model *m, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
@@ -424,6 +426,28 @@ int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double
 int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                 const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
                                 int32_t out_mem);
+
+/*
+ * fbr_hull_distance_gradients for a hull set installed by fbr_model_set_large_hulls: hulls of up to FBR_MAX_LARGE_HULL_VERTICES vertices --
+ * KUKA LWR4 in the reference's default collisionMode "convex", whose hulls all have more than FBR_MAX_HULL_VERTICES vertices.  It replaces
+ * the same call site: the `else` branch of the collision block of excitation/analyticalGradient.py, per joint two whole-robot forward
+ * kinematics and two fcl.distance calls at q +- analyticalGradientEpsilon e_j.  Arguments, layouts, memory spaces, the zeroing of
+ * grad_q_out, the exact zeros and the error rules are those of fbr_hull_distance_gradients; npairs is the hull set's.
+ * A pair of two hulls of at most FBR_MAX_HULL_VERTICES vertices goes through the kernel of fbr_hull_distance_gradients and returns the bits
+ * that call returns for it from a set of fbr_model_set_hulls.  Every other pair -- every pair with option "hull_large_all" = 1 -- goes
+ * through three stages (csrc/fbr_hull_large_grad.h): the relative poses of the 1 + 2 J stencil points are recorded, one distance per
+ * recorded pose is evaluated with the facet pass of a touching entry shared by the 64 lanes of a wave as in fbr_candidate_hull_distances,
+ * and the quotients (d+ - d-) / (2 epsilon) are formed.  The values are those of the one-lane routine (a maximum over the same facets; the
+ * sign of a zero gap may differ).  Option "hull_grad_tile": the live lanes of a work item of the distance stage; a value never depends on
+ * it.  No atomics: the same bits on every run.
+ * FBR_E_INVALID, by name: a set not installed by fbr_model_set_large_hulls, a set with no pair, epsilon not finite or not positive, option
+ * "hull_grad_tile" neither 0 nor a power of two from 1 to 64; and what fbr_hull_distance_gradients refuses.  FBR_E_UNSUPPORTED: triangle
+ * meshes attached (possible only while no hull of the set is above FBR_MAX_HULL_VERTICES).  fbr_hull_distance_gradients and
+ * fbr_mesh_distance_gradients keep refusing a set with a hull above FBR_MAX_HULL_VERTICES vertices.
+ */
+int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                      const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                      int32_t out_mem);
 
 /*
  * tau_out [S][rows] = Y_s . x for an identified-parameter vector x (host, length cols) WITHOUT
@@ -740,6 +764,9 @@ int fbr_suspended_records(fbr_model *m, const fbr_states *st, const double *x_st
  *   "hull_large_all"             0     fbr_candidate_hull_distances, a set installed by fbr_model_set_large_hulls: 1 sends every pair to
  *                                      fbr_hull_large_pairs_kernel, also those of two hulls of at most FBR_MAX_HULL_VERTICES vertices (tests:
  *                                      the two kernels on the same pairs).  Read by every call: a later change is never ignored
+ *   "hull_grad_tile"             0     fbr_large_hull_distance_gradients: the live lanes of a work item of its distance stage, a power of two from
+ *                                      1 to 64 (anything else: the call returns FBR_E_INVALID); 0: the widest that leaves 12 items a CU, the waves a CU holds.  The
+ *                                      touching entries of an item run their facet passes one after the other.  Read by every call
  *   "gram_serial", "gram_timing", "tsqr_timing"  0   diagnostics (producer on the main stream; cycle counters printed to stderr)
  * fbr_model_option_name enumerates the keys (index 0 .. until it fails).
  */
