@@ -116,6 +116,7 @@ _SIGNATURES = {
     "fbr_model_set_large_hulls": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip, _dp, _ip, _dp, _ip, _ip,
                                                  ctypes.c_int32, _ip]),
     "fbr_model_set_hull_meshes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _ip, _dp]),
+    "fbr_model_set_large_hull_meshes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _ip, _ip, _dp]),
     "fbr_candidate_hull_distances": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
@@ -233,6 +234,7 @@ _SIGNATURES = {
 FBR_VERSION = 104  # include/fbr.h FBR_VERSION: the C-ABI these ctypes signatures describe
 FBR_MAX_HULL_VERTICES = 128  # include/fbr.h: a hull of Engine.set_hulls
 FBR_MAX_LARGE_HULL_VERTICES = 1024  # include/fbr.h: a hull of Engine.set_hulls(..., large=True)
+FBR_MAX_LARGE_MESH_TRIANGLES = 8192  # include/fbr.h: a mesh of Engine.set_large_hull_meshes / set_hulls(..., large_meshes=True)
 DEFAULT_OPTIONS: dict = {}
 
 
@@ -668,7 +670,7 @@ class Engine:
         ``candidate_capsule_distances``.  Separated boxes: the exact Euclidean distance; overlapping: minus the minimum translation."""
         return self._candidate_distances("fbr_candidate_box_distances", int(getattr(self, "num_box_pairs", 0)), st, ncand, step, base_pos, device_out)
 
-    def set_hulls(self, hulls, pairs, offset_in_link_axes: bool = False, meshes=None, large: bool = False) -> None:
+    def set_hulls(self, hulls, pairs, offset_in_link_axes: bool = False, meshes=None, large: bool = False, large_meshes: bool = False) -> None:
         """Convex-hull collision set of the handle (``fbr_model_set_hulls``), independent of the capsule and the box set.  ``hulls``: a
         sequence of ``flobaroid_amd.collision.Hull`` (``link_name`` None: a world hull with ``rot``), or of tuples ``(link, offset, rot,
         vertices, planes, edges)`` -- link an index, a name, or None / -1; the tables as ``Hull`` derives them.  ``pairs``: (P, 2) indices
@@ -676,9 +678,10 @@ class Engine:
         axes), True at ``p_link + R_link offset``.  Replaces the set in place; an empty ``hulls`` clears it.  ``meshes``: what
         ``set_hull_meshes`` takes, attached to the new set (None: the new set has no meshes, whatever the one before had).  ``large``: False
         is ``fbr_model_set_hulls``, at most ``FBR_MAX_HULL_VERTICES`` (128) vertices a hull; True is ``fbr_model_set_large_hulls``, up to
-        ``FBR_MAX_LARGE_HULL_VERTICES`` (1024): distances only -- no ``meshes`` (ValueError), and the gradient calls refuse the set while
-        one of its hulls has more than 128 vertices."""
-        if large and meshes:
+        ``FBR_MAX_LARGE_HULL_VERTICES`` (1024): distances only -- no ``meshes`` (ValueError) unless ``large_meshes``, and the gradient
+        calls refuse the set while one of its hulls has more than 128 vertices.  ``large_meshes``: attach ``meshes`` through
+        ``set_large_hull_meshes`` (up to ``FBR_MAX_LARGE_MESH_TRIANGLES`` triangles a mesh, on small or large hulls; distances only)."""
+        if large and meshes and not large_meshes:
             raise ValueError("set_hulls(large=True): triangle meshes on a set of large hulls are not built (meshes= needs large=False)")
         names = list(self.topo.link_names)
         link, off, rot, V, F, E, any_world = [], [], [], [], [], [], False
@@ -711,7 +714,15 @@ class Engine:
                                          edges.ctypes.data_as(_ip), int(pr.shape[0]), pr.ctypes.data_as(_ip)), entry)
         self.num_hulls, self.num_hull_pairs, self.num_hull_meshes = int(link.size), int(pr.shape[0]), 0
         if meshes:
-            self.set_hull_meshes(meshes)
+            (self.set_large_hull_meshes if large_meshes else self.set_hull_meshes)(meshes)
+
+    def set_large_hull_meshes(self, meshes) -> None:
+        """``set_hull_meshes`` for meshes of up to ``FBR_MAX_LARGE_MESH_TRIANGLES`` (8192) triangles, on a set of ``set_hulls`` with or
+        without ``large=True`` (``fbr_model_set_large_hull_meshes``): KUKA LWR4's visual meshes, ``collisionMode: "full"`` on a robot
+        without collision meshes.  The library builds a bounding-sphere tree per mesh and ``candidate_hull_distances`` walks the two
+        trees of a pair for the 64 samples of a wave together; the values have the bits of the brute force over all triangle pairs.  No
+        cap on the triangle pairs of a pair.  Distances only: every gradient call refuses the set while such meshes are attached."""
+        self._set_meshes("fbr_model_set_large_hull_meshes", meshes)
 
     def set_hull_meshes(self, meshes) -> None:
         """Triangle meshes on hulls of the set ``set_hulls`` put in place (``fbr_model_set_hull_meshes``; the reference's ``fullMeshLinks``
@@ -720,13 +731,15 @@ class Engine:
         mesh routine: the minimum over the triangles, exactly 0.0 where they touch or intersect, never negative.  An empty ``meshes``
         clears the attachments, and so does every later ``set_hulls``; ``hull_distance_gradients`` refuses a set with meshes,
         ``mesh_distance_gradients`` serves it."""
+        self._set_meshes("fbr_model_set_hull_meshes", meshes)
+
+    def _set_meshes(self, entry: str, meshes) -> None:
         items = list(meshes.items()) if hasattr(meshes, "items") else list(meshes or [])
         tri = [np.asarray(t, dtype=np.float64).reshape(-1, 9) for _, t in items]
         hull = np.ascontiguousarray([int(h) for h, _ in items], dtype=np.int32)
         tbeg = np.ascontiguousarray(np.cumsum([0] + [len(t) for t in tri]), dtype=np.int32)
         tris = np.ascontiguousarray(np.concatenate(tri) if tri else np.zeros((0, 9)))
-        _check(self._lib.fbr_model_set_hull_meshes(self._h, len(items), hull.ctypes.data_as(_ip), tbeg.ctypes.data_as(_ip), tris.ctypes.data_as(_dp)),
-               "fbr_model_set_hull_meshes")
+        _check(getattr(self._lib, entry)(self._h, len(items), hull.ctypes.data_as(_ip), tbeg.ctypes.data_as(_ip), tris.ctypes.data_as(_dp)), entry)
         self.num_hull_meshes = len(items)
 
     def candidate_hull_distances(self, st: dict, ncand: int, step: int = 3, base_pos=None, device_out: bool | None = None) -> dict:

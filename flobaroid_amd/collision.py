@@ -26,8 +26,12 @@ The distances themselves are computed on the device (``Engine.candidate_capsule_
 gradients: ``Engine.mesh_distance_gradients``, csrc/fbr_mesh_grad.h, behind ``mesh_gradient=True`` of ``flobaroid_amd.excitation``).  Hulls of
 ``FBR_MAX_HULL_VERTICES`` + 1 to ``FBR_MAX_LARGE_HULL_VERTICES`` vertices (KUKA LWR4: the hulls of its visual meshes) are served for
 distances only: ``hulls_from_urdf(..., max_vertices=FBR_MAX_LARGE_HULL_VERTICES)`` and ``Engine.set_hulls(..., large=True)``,
-csrc/fbr_hull_large.h.  Not covered: gradients of such hulls and meshes attached to them; meshes whose hull has more than
-``FBR_MAX_LARGE_HULL_VERTICES`` vertices or that have more than ``FBR_MAX_MESH_TRIANGLES`` triangles (no simplification, no BVH); formats other than STL; parity with FCL's own numbers.
+csrc/fbr_hull_large.h.  Meshes of ``FBR_MAX_MESH_TRIANGLES`` + 1 to ``FBR_MAX_LARGE_MESH_TRIANGLES`` triangles, mesh pairs above
+``FBR_MAX_MESH_PAIR_WORK`` and meshes on such hulls (KUKA LWR4 in ``collisionMode: "full"``) are served for distances only, through a
+bounding-sphere tree per mesh: ``meshes_from_urdf(..., max_triangles=FBR_MAX_LARGE_MESH_TRIANGLES)``, ``collision_set(...,
+large_meshes=True)`` and ``Engine.set_large_hull_meshes``, csrc/fbr_mesh_bvh.h.  Not covered: gradients of meshes attached that way;
+meshes whose hull has more than ``FBR_MAX_LARGE_HULL_VERTICES`` vertices or that have more than ``FBR_MAX_LARGE_MESH_TRIANGLES``
+triangles (no simplification); formats other than STL; parity with FCL's own numbers.
 """
 from __future__ import annotations
 
@@ -40,6 +44,7 @@ import numpy as np
 FBR_MAX_HULL_VERTICES = 128  # include/fbr.h: Engine.set_hulls
 FBR_MAX_LARGE_HULL_VERTICES = 1024  # include/fbr.h: Engine.set_hulls(..., large=True), distances only
 FBR_MAX_MESH_TRIANGLES = 256  # include/fbr.h
+FBR_MAX_LARGE_MESH_TRIANGLES = 8192  # include/fbr.h: Engine.set_large_hull_meshes, collision_set(..., large_meshes=True), distances only
 FBR_MAX_MESH_PAIR_WORK = 32768  # include/fbr.h: triangles x triangles of one pair
 _COPLANAR = 1e-10            # x the hull's diameter: neighbouring triangles this flat against each other are one face
 
@@ -578,7 +583,8 @@ def world_boxes_from_urdf(world_urdf, placement: str = "reference", cube_size=No
     return out
 
 
-def collision_set(topology, capsules, config: dict, margins=None, boxes=None, world_boxes=None, hulls=None, world_hulls=None, meshes=None) -> dict:
+def collision_set(topology, capsules, config: dict, margins=None, boxes=None, world_boxes=None, hulls=None, world_hulls=None, meshes=None,
+                  large_meshes: bool = False) -> dict:
     """What ``Engine.set_capsules`` / ``Engine.set_boxes`` and the ``collision`` argument of ``excitation.candidate_objectives`` take.
 
     Without ``boxes`` and ``world_boxes``: ``capsules`` (a list, one per link that has one, in link order), ``pairs`` ((P, 2) indices into
@@ -605,7 +611,11 @@ def collision_set(topology, capsules, config: dict, margins=None, boxes=None, wo
     which EVERY robot link in ``meshes`` is a mesh and the others are their hull or box, as in the reference.  A meshed link's hull is
     ``Mesh.hull`` (it replaces the entry of ``hulls``, if any).  The dict gains ``meshes`` ({hull index: triangles (T, 3, 3)}: what
     ``Engine.set_hull_meshes`` takes); pair order, ``columns`` and margins are as in convex mode.  A mesh above ``FBR_MAX_MESH_TRIANGLES``
-    or a pair above ``FBR_MAX_MESH_PAIR_WORK`` triangle pairs raises ValueError naming the links and the counts."""
+    or a pair above ``FBR_MAX_MESH_PAIR_WORK`` triangle pairs raises ValueError naming the links and the counts.
+
+    ``large_meshes=True`` (with ``meshes``): the meshes go to ``Engine.set_large_hull_meshes`` -- the cap of a mesh is
+    ``FBR_MAX_LARGE_MESH_TRIANGLES``, a pair has no cap, the hulls may have up to ``FBR_MAX_LARGE_HULL_VERTICES`` vertices, and the dict
+    carries ``"large_meshes": True`` (KUKA LWR4 in ``collisionMode: "full"``).  Distances only: the gradient entry points refuse the set."""
     if hulls is not None:
         mode = config.get("collisionMode", "convex")
         full = list(config.get("fullMeshLinks", []) or [])
@@ -621,8 +631,9 @@ def collision_set(topology, capsules, config: dict, margins=None, boxes=None, wo
                 raise ValueError(f"fullMeshLinks {lacking}: no mesh given for them (meshes=)")
             meshed = {n: meshes[n] for n in (meshes if mode == "full" else full) if n in topology.link_names}
             for n, mm in meshed.items():
-                if len(mm.triangles) > FBR_MAX_MESH_TRIANGLES:
-                    raise ValueError(f"link {n}: {len(mm.triangles)} triangles, more than {FBR_MAX_MESH_TRIANGLES}")
+                cap = FBR_MAX_LARGE_MESH_TRIANGLES if large_meshes else FBR_MAX_MESH_TRIANGLES
+                if len(mm.triangles) > cap:
+                    raise ValueError(f"link {n}: {len(mm.triangles)} triangles, more than {cap}")
                 hulls[n] = mm.hull
         clash = set(world_hulls) & set(topology.link_names)
         if clash:
@@ -645,10 +656,14 @@ def collision_set(topology, capsules, config: dict, margins=None, boxes=None, wo
                "hull_pairs": np.array([raw[k] for k in order], dtype=np.int32).reshape(-1, 2), "columns": columns, "offset_in_link_axes": False}
         if meshes is not None:
             for a, b in pair_names:
+                if large_meshes:
+                    break  # (the trees bound the work of a pair)
                 if a in meshed and b in meshed and len(meshed[a].triangles) * len(meshed[b].triangles) > FBR_MAX_MESH_PAIR_WORK:
                     raise ValueError(f"pair ({a}, {b}): {len(meshed[a].triangles)} x {len(meshed[b].triangles)} triangle pairs, more than "
                                      f"{FBR_MAX_MESH_PAIR_WORK}")
             out["meshes"] = {hpos[n]: meshed[n].triangles for n in hnames if n in meshed}
+            if large_meshes:
+                out["large_meshes"] = True
         return out
     names = [n for n in topology.link_names if n in capsules]
     pos = {n: i for i, n in enumerate(names)}

@@ -6,6 +6,7 @@
 #include "fbr_internal.h"
 #include "fbr_collision_tables.h"
 #include "fbr_hull_large_grad.h"
+#include <limits>
 
 // ---- what the three sets share -------------------------------------------------------------------------------------------------------
 static int collision_program(const fbr_model *m, FbrKinIdProgram &prog)
@@ -225,6 +226,9 @@ static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhu
     m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
     m->has_meshes = false;
+    m->mesh_large = false;
+    m->mesh_bvh = DevMeshBvh{nullptr, nullptr, nullptr};
+    m->hulls_plain_big = m->hulls;
     m->hull_host = {};
     m->hulls_small = m->hulls_big = m->hulls;
     m->hull_big = -1;
@@ -384,20 +388,33 @@ static bool refuse_large_hulls(const fbr_model *m, const char *who)
 }
 
 // ---- triangle meshes on hulls of the set (csrc/fbr_mesh.h) ---------------------------------------------------------------------------------
-extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris)
+// fbr_model_set_hull_meshes (large false: the caps of the brute-force kernel, small hulls only) and fbr_model_set_large_hull_meshes (large:
+// the cap of the trees of csrc/fbr_mesh_bvh.h, no cap on a pair's work, any hull set): one attachment, two kernels
+static int attach_meshes(fbr_model *m, bool large, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris)
 {
     if (!m) {
         set_err("null model");
         return FBR_E_INVALID;
     }
-    if (refuse_large_hulls(m, "fbr_model_set_hull_meshes")) return FBR_E_INVALID;
+    if (!large && refuse_large_hulls(m, "fbr_model_set_hull_meshes")) return FBR_E_INVALID;
     const auto &hh = m->hull_host;
     const int nhulls = m->hulls.nhulls, npairs = m->hulls.npairs;
     const std::string bad = fbr_mesh_validate(nhulls, hh.link.data(), hh.fbeg.data(), hh.planes.data(), hh.diam.data(), npairs, hh.pairs.data(),
-                                              FBR_MAX_MESH_TRIANGLES, FBR_MAX_MESH_PAIR_WORK, nmesh, hull, tbeg, tris);
+                                              large ? FBR_MAX_LARGE_MESH_TRIANGLES : FBR_MAX_MESH_TRIANGLES,
+                                              large ? std::numeric_limits<long>::max() : (long)FBR_MAX_MESH_PAIR_WORK, nmesh, hull, tbeg, tris);
     if (!bad.empty()) {
         set_err(bad);
         return FBR_E_INVALID;
+    }
+    // the trees, and the triangles in their order: what the tables below hold of a large attachment
+    FbrMeshBvhSet bvh;
+    if (large && nmesh > 0) {
+        const std::string deep = fbr_mesh_bvh_set(nmesh, tbeg, tris, bvh);
+        if (!deep.empty()) {
+            set_err("hull meshes: " + deep);
+            return FBR_E_INVALID;
+        }
+        tris = bvh.tris.data();
     }
     if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -406,13 +423,22 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
         m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
         m->has_meshes = false;
+        m->mesh_large = false;
+        m->mesh_bvh = DevMeshBvh{nullptr, nullptr, nullptr};
+        m->hulls_plain_big = m->hulls;
         return FBR_OK;
     }
     // the pairs of the set: those with a mesh on either side, the meshed hull first, sorted by it (stable); the others in their order
     std::vector<int> mtab((size_t)nhulls * 2, 0);
     for (int i = 0; i < nmesh; i++) mtab[2 * (size_t)hull[i]] = tbeg[i], mtab[2 * (size_t)hull[i] + 1] = tbeg[i + 1] - tbeg[i];
-    std::vector<int> mk, pk;
-    for (int k = 0; k < npairs; k++) (mtab[2 * (size_t)hh.pairs[2 * k] + 1] || mtab[2 * (size_t)hh.pairs[2 * k + 1] + 1] ? mk : pk).push_back(k);
+    // (a large attachment: the plain pairs of two hulls of at most FBR_MAX_HULL_VERTICES vertices in pk, the other plain pairs in bk --
+    // the kernels they go to without meshes)
+    std::vector<int> mk, pk, bk;
+    const auto bighull = [&](int h) { return large && hh.vbeg[h + 1] - hh.vbeg[h] > FBR_MAX_HULL_VERTICES; };
+    for (int k = 0; k < npairs; k++) {
+        const int a = hh.pairs[2 * k], b = hh.pairs[2 * k + 1];
+        (mtab[2 * (size_t)a + 1] || mtab[2 * (size_t)b + 1] ? mk : (bighull(a) || bighull(b) ? bk : pk)).push_back(k);
+    }
     auto first = [&](int k) { return mtab[2 * (size_t)hh.pairs[2 * k] + 1] ? hh.pairs[2 * k] : hh.pairs[2 * k + 1]; };
     std::stable_sort(mk.begin(), mk.end(), [&](int a, int b) { return first(a) < first(b); });
     const size_t NT = (size_t)tbeg[nmesh], nm = std::max(mk.size(), (size_t)1), np = std::max(pk.size(), (size_t)1);
@@ -421,10 +447,19 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
     const size_t osph = blob.add<double>((size_t)nhulls * 4), otris = blob.add<double>(tris, tris + NT * 9), oaux = blob.add<double>(NT * 5);
     const size_t omp = blob.add<int>(2 * nm), opp = blob.add<int>(2 * np), omtab = blob.add<int>(mtab.begin(), mtab.end());
     const size_t omc = blob.add<int>(nm), opc = blob.add<int>(np);
+    // (a large attachment: | big plain pairs | their columns | first node of a hull's tree | nodes | node spheres)
+    const size_t nbp = std::max(bk.size(), (size_t)1);
+    const size_t obp = blob.add<int>(2 * nbp), obc = blob.add<int>(nbp), onbeg = blob.add<int>((size_t)nhulls);
+    const size_t onode = blob.add<int>(bvh.node.begin(), bvh.node.end()), ovol = blob.add<double>(bvh.vol.begin(), bvh.vol.end());
+    for (size_t i = 0; i < bk.size(); i++)
+        blob.at<int>(obp)[2 * i] = hh.pairs[2 * bk[i]], blob.at<int>(obp)[2 * i + 1] = hh.pairs[2 * bk[i] + 1], blob.at<int>(obc)[i] = bk[i];
+    std::fill(blob.at<int>(onbeg), blob.at<int>(onbeg) + nhulls, 0);
+    if (large)
+        for (int i = 0; i < nmesh; i++) blob.at<int>(onbeg)[hull[i]] = bvh.nbeg[i];
     for (int h = 0; h < nhulls; h++)
         fbr_mesh_point_sphere(hh.vbeg[h + 1] - hh.vbeg[h], hh.verts.data() + 3 * (size_t)hh.vbeg[h], 3L * mtab[2 * (size_t)h + 1],
                               tris + 9 * (size_t)mtab[2 * (size_t)h], blob.at<double>(osph) + 4 * (size_t)h);
-    for (size_t t = 0; t < NT; t++) fbr_mesh_triangle_aux(tris + 9 * t, blob.at<double>(oaux) + 5 * t);
+    for (size_t t = 0; t < NT; t++) fbr_mesh_triangle_aux(tris + 9 * t, blob.at<double>(oaux) + 5 * t);  // (large: what bvh.aux holds)
     int *hmp = blob.at<int>(omp), *hpp = blob.at<int>(opp), *hmc = blob.at<int>(omc), *hpc = blob.at<int>(opc);
     for (size_t i = 0; i < mk.size(); i++) {
         const int k = mk[i], a = hh.pairs[2 * k], b = hh.pairs[2 * k + 1], swap = mtab[2 * (size_t)a + 1] == 0;
@@ -435,7 +470,7 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
     // fbr_rigidgrad_item evaluates, in walk order: sbeg | pair of a point | its joint
     std::vector<int> gtab(mk.size() + 1, 0), gpair, gjoint;
     int smax = 0;
-    {
+    if (!large) {  // (a large attachment has distances only)
         FbrKinIdProgram prog;
         if (int rc = collision_program(m, prog)) return rc;
         std::vector<int> stepof, anc, joint;
@@ -451,6 +486,8 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
         }
         gtab.insert(gtab.end(), gpair.begin(), gpair.end());
         gtab.insert(gtab.end(), gjoint.begin(), gjoint.end());
+    } else {
+        gtab.assign(1, 0);
     }
     // Unlike the three setters above, which reuse their buffers (they have cleared their set before they build), this one builds into fresh
     // allocations and swaps them in once the copies have succeeded: a call that fails here leaves the attachments in place as well.
@@ -463,7 +500,7 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
     {
         const int *g = m->meshg_tab.as<int>();
         const int ni = (int)gpair.size();
-        m->meshg = DevMeshGrad{ni, smax, g, g + mk.size() + 1, g + mk.size() + 1 + ni};
+        m->meshg = large ? DevMeshGrad{0, 0, nullptr, nullptr, nullptr} : DevMeshGrad{ni, smax, g, g + mk.size() + 1, g + mk.size() + 1 + ni};
     }
     m->hulls_plain = m->hulls;
     const char *base = (const char *)m->mesh_tab.p;
@@ -472,8 +509,33 @@ extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int3
     m->hulls_plain.npairs = (int)pk.size();
     m->hulls_plain.pairs = (const int2 *)(base + opp);
     m->hulls_plain.col = (const int *)(base + opc);
+    m->hulls_plain_big = m->hulls;
+    m->hulls_plain_big.npairs = (int)bk.size();
+    m->hulls_plain_big.pairs = (const int2 *)(base + obp);
+    m->hulls_plain_big.col = (const int *)(base + obc);
+    m->mesh_bvh = DevMeshBvh{(const int *)(base + onbeg), (const int *)(base + onode), (const double *)(base + ovol)};
+    m->mesh_large = large;
     m->has_meshes = true;
     return FBR_OK;
+}
+
+extern "C" int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris)
+{
+    return attach_meshes(m, false, nmesh, hull, tbeg, tris);
+}
+
+extern "C" int fbr_model_set_large_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris)
+{
+    return attach_meshes(m, true, nmesh, hull, tbeg, tris);
+}
+
+// attachments of fbr_model_set_large_hull_meshes are in place: distances only, `who` has no gradients of them
+static bool refuse_large_meshes(const fbr_model *m, const char *who)
+{
+    if (!(m->has_meshes && m->mesh_large)) return false;
+    set_err(std::string(who) + ": the hull set has triangle meshes attached by fbr_model_set_large_hull_meshes: distances only "
+                               "(fbr_candidate_hull_distances), gradients of such a set are not built");
+    return true;
 }
 
 // ---- candidate distances -------------------------------------------------------------------------------------------------------------
@@ -636,6 +698,21 @@ extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, 
                                              hipLaunchKernelGGL(fbr_hull_large_pairs_kernel, dim3((unsigned)std::min(items, cap)), dim3(64), 0, m->stream, hs, tl,
                                                                 b0, nb, fr, pval, pidx);
                                          };
+                                         if (m->has_meshes && m->mesh_large) {
+                                             // attachments of fbr_model_set_large_hull_meshes: the pairs without a mesh to the kernels they go
+                                             // to without any mesh, the others to the tree kernel, each into its own columns
+                                             const long ps = m->hulls_plain.npairs, pb = m->hulls_plain_big.npairs, pm = m->meshes.npairs;
+                                             const bool all = m->hull_large_set && m->opt.hull_large_all != 0;
+                                             if (ps > 0 && all) large(m->hulls_plain);
+                                             if (ps > 0 && !all)
+                                                 hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ps + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
+                                                                    dim3(64), 0, m->stream, m->hulls_plain, tl, b0, nb, fr, pval, pidx);
+                                             if (pb > 0) large(m->hulls_plain_big);
+                                             if (pm > 0)
+                                                 hipLaunchKernelGGL(fbr_mesh_bvh_pairs_kernel, dim3((unsigned)std::min(nb * pm, cap)), dim3(64), 0, m->stream,
+                                                                    m->hulls, m->meshes, m->mesh_bvh, tl, b0, nb, fr, pval, pidx);
+                                             return;
+                                         }
                                          if (!m->has_meshes && m->hull_large_set && m->opt.hull_large_all != 0) {
                                              large(m->hulls);  // (every pair, in the caller's columns)
                                              return;
@@ -800,6 +877,7 @@ extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, c
         set_err("no hull set with at least one pair (fbr_model_set_hulls)");
         return FBR_E_INVALID;
     }
+    if (refuse_large_meshes(m, "fbr_hull_distance_gradients")) return FBR_E_UNSUPPORTED;
     if (refuse_large_hulls(m, "fbr_hull_distance_gradients")) return FBR_E_INVALID;
     if (m->has_meshes) {
         set_err("fbr_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); gradients of mesh pairs are not built");
@@ -833,6 +911,7 @@ extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, c
         set_err("no hull set with at least one pair (fbr_model_set_hulls)");
         return FBR_E_INVALID;
     }
+    if (refuse_large_meshes(m, "fbr_mesh_distance_gradients")) return FBR_E_UNSUPPORTED;
     if (refuse_large_hulls(m, "fbr_mesh_distance_gradients")) return FBR_E_INVALID;
     if (!m->has_meshes) {
         set_err("fbr_mesh_distance_gradients: the hull set has no triangle meshes attached (fbr_model_set_hull_meshes); fbr_hull_distance_gradients "
@@ -889,7 +968,8 @@ extern "C" int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states 
         set_err("fbr_large_hull_distance_gradients: the hull set has no pair");
         return FBR_E_INVALID;
     }
-    if (m->has_meshes) {  // (only a set without a hull above the cap can have them: fbr_model_set_hull_meshes)
+    if (refuse_large_meshes(m, "fbr_large_hull_distance_gradients")) return FBR_E_UNSUPPORTED;
+    if (m->has_meshes) {  // (fbr_model_set_hull_meshes: only a set without a hull above the cap can have them)
         set_err("fbr_large_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); "
                 "fbr_mesh_distance_gradients serves such a set");
         return FBR_E_UNSUPPORTED;

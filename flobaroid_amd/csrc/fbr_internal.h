@@ -27,6 +27,7 @@
 #include "fbr_hull_grad.h"
 #include "fbr_hull_large.h"
 #include "fbr_mesh.h"
+#include "fbr_mesh_bvh.h"
 #include "fbr_mesh_grad.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
@@ -201,6 +202,11 @@ struct fbr_model {
     DevMeshes meshes = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool has_meshes = false;
     DevBuf mesh_tab;
+    // attachments of fbr_model_set_large_hull_meshes (csrc/fbr_mesh_bvh.h): meshes holds the triangles in tree order, mesh_bvh the trees;
+    // the pairs without a mesh are hulls_plain (two hulls of at most FBR_MAX_HULL_VERTICES vertices) and hulls_plain_big (the others)
+    bool mesh_large = false;
+    DevMeshBvh mesh_bvh = {nullptr, nullptr, nullptr};
+    DevHulls hulls_plain_big = hulls;
     DevPairGrad hullg = {0, nullptr, nullptr};  // fbr_hull_distance_gradients: ancestor masks and per-pair steps / offset slots of the set above
     DevBuf hullg_tab;
     // fbr_mesh_distance_gradients (csrc/fbr_mesh_grad.h): the stencil points of the mesh pairs (built with the attachments) and the call's

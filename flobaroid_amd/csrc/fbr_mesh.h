@@ -73,23 +73,21 @@ inline void fbr_mesh_point_sphere(long nv, const double *v, long ne, const doubl
     sph[3] = r * (1.0 + 4.0 * FBR_MESH_EPS);
 }
 
-// Distance of the mesh MA (in the axes of hull A; MA.nt >= 1) to B: to the triangles of MB when MB.nt >= 1, else to the solid hull B.
-// q: B relative to A (fbr_hull_relative); sphB [4]: the bounding sphere of hull B in its axes.  A NaN pose gives a NaN.
+// The triangles of MA (in the axes of hull A; MA.nt >= 1) against B -- the triangles of MB when MB.nt >= 1, else the solid hull B -- folded
+// into *best: the body of fbr_mesh_distance_oriented, and of a leaf pair of csrc/fbr_mesh_bvh.h, where MA and MB are the leaves' ranges.
+// q: B relative to A; (hb0, hb1, hb2 | hbr): a sphere, in the axes of A, that holds everything of B the call looks at; off: this lane takes
+// no part (a NaN pose, or a lane of the wave that does not want this range); slack: the deflation of the bounds.
 template <bool CULL, class DP, class IP>
-FBR_HD double fbr_mesh_distance_oriented(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const FbrMeshT<DP> &MA, const FbrHullT<DP, IP> &B,
-                                         const FbrMeshT<DP> &MB, DP sphB, FbrMeshStats *stats)
+FBR_HD void fbr_mesh_range_oriented(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const FbrMeshT<DP> &MA, const FbrHullT<DP, IP> &B,
+                                    const FbrMeshT<DP> &MB, double hb0, double hb1, double hb2, double hbr, double slack, bool off, double *bestp,
+                                    FbrMeshStats *stats)
 {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    const double nan0 = q.chk - q.chk;
-    const bool dead = !(nan0 == 0.0);
-    double best = FBR_CAPSULE_NONE;
-    const double slack = (FBR_MESH_CULL_K * FBR_MESH_EPS) * (sqrt(q.t0 * q.t0 + q.t1 * q.t1 + q.t2 * q.t2) + A.diam + B.diam);
+    const bool dead = off;
+    double best = *bestp;
     const int nb = MB.nt > 0 ? MB.nt : 1;
-    // the sphere of hull B in the axes of A
-    const double hb0 = (q.C00 * sphB[0] + q.C01 * sphB[1] + q.C02 * sphB[2]) + q.t0, hb1 = (q.C10 * sphB[0] + q.C11 * sphB[1] + q.C12 * sphB[2]) + q.t1,
-                 hb2 = (q.C20 * sphB[0] + q.C21 * sphB[1] + q.C22 * sphB[2]) + q.t2, hbr = sphB[3];
 #pragma unroll 1
     for (int ta = 0; ta < MA.nt; ta++) {
         if (!FBR_HULL_ANY(!dead && best != 0.0)) break;
@@ -132,6 +130,36 @@ FBR_HD double fbr_mesh_distance_oriented(const FbrHullRel &q, const FbrHullT<DP,
             if (want && d < best) best = d;  // (touching: the GJK returns 0.0)
         }
     }
+    *bestp = best;
+}
+
+// the deflation of a sphere bound of the pose q between the hulls A and B: FBR_MESH_CULL_K eps x scale
+template <class DP, class IP>
+FBR_HD double fbr_mesh_slack(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const FbrHullT<DP, IP> &B)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return (FBR_MESH_CULL_K * FBR_MESH_EPS) * (sqrt(q.t0 * q.t0 + q.t1 * q.t1 + q.t2 * q.t2) + A.diam + B.diam);
+}
+
+// Distance of the mesh MA (in the axes of hull A; MA.nt >= 1) to B: to the triangles of MB when MB.nt >= 1, else to the solid hull B.
+// q: B relative to A (fbr_hull_relative); sphB [4]: the bounding sphere of hull B in its axes.  A NaN pose gives a NaN.
+template <bool CULL, class DP, class IP>
+FBR_HD double fbr_mesh_distance_oriented(const FbrHullRel &q, const FbrHullT<DP, IP> &A, const FbrMeshT<DP> &MA, const FbrHullT<DP, IP> &B,
+                                         const FbrMeshT<DP> &MB, DP sphB, FbrMeshStats *stats)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double nan0 = q.chk - q.chk;
+    const bool dead = !(nan0 == 0.0);
+    double best = FBR_CAPSULE_NONE;
+    const double slack = fbr_mesh_slack(q, A, B);
+    // the sphere of hull B in the axes of A
+    const double hb0 = (q.C00 * sphB[0] + q.C01 * sphB[1] + q.C02 * sphB[2]) + q.t0, hb1 = (q.C10 * sphB[0] + q.C11 * sphB[1] + q.C12 * sphB[2]) + q.t1,
+                 hb2 = (q.C20 * sphB[0] + q.C21 * sphB[1] + q.C22 * sphB[2]) + q.t2, hbr = sphB[3];
+    fbr_mesh_range_oriented<CULL>(q, A, MA, B, MB, hb0, hb1, hb2, hbr, slack, dead, &best, stats);
     return dead ? nan0 : best;
 }
 

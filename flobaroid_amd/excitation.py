@@ -11,7 +11,8 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``candidate_collision_constraints`` -- its collision block from ``Engine.candidate_capsule_distances`` (``collisionMode: "capsule"``,
   pairs of links with capsules), ``Engine.candidate_box_distances`` (``collisionMode: "box"``, world links, capsule-less links) and
   ``Engine.candidate_hull_distances`` (``collisionMode: "convex"``, the reference's default: convex hulls of the links' meshes; with
-  ``Engine.set_hull_meshes`` also ``fullMeshLinks`` and ``collisionMode: "full"``: the triangle meshes themselves);
+  ``Engine.set_hull_meshes`` also ``fullMeshLinks`` and ``collisionMode: "full"``: the triangle meshes themselves, through
+  ``Engine.set_large_hull_meshes`` up to 8192 triangles a mesh on hulls of up to 1024 vertices -- KUKA LWR4's ``"full"`` mode);
   ``candidate_objectives(..., collision=...)`` appends it to ``g``;
 * ``candidate_dopt_gradient_from_coefficients`` -- the D-optimality term's gradient with respect to the Fourier coefficients of many
   candidates (analyticalGradient.py:538-762) from ``Engine.regressor_weights`` + ``Engine.fd_scores`` + ``Engine.fourier_gradient``;
@@ -408,6 +409,25 @@ def _has_meshes(collision) -> bool:
     return collision is not None and bool(collision.get("meshes"))
 
 
+def _refuse_large_mesh_gradient(collision) -> None:
+    """a set built with ``collision_set(..., large_meshes=True)`` is served for distances only (``Engine.set_large_hull_meshes``): every
+    gradient entry point refuses it, whatever its ``*_gradient`` keywords say, by the names and triangle counts of its meshes above
+    ``FBR_MAX_MESH_TRIANGLES`` triangles or on hulls above ``FBR_MAX_HULL_VERTICES`` vertices"""
+    from .collision import FBR_MAX_HULL_VERTICES, FBR_MAX_MESH_TRIANGLES
+
+    if not (_has_meshes(collision) and collision.get("large_meshes")):
+        return
+    why = []
+    for h, t in collision["meshes"].items():
+        hull = collision["hulls"][int(h)]
+        nt, nv = len(np.asarray(t).reshape(-1, 9)), len(hull.vertices)
+        if nt > FBR_MAX_MESH_TRIANGLES or nv > FBR_MAX_HULL_VERTICES:
+            why.append(f"{hull.link_name} ({nt} triangles on a hull of {nv} vertices)")
+    raise ValueError("gradients on the device do not cover triangle meshes of more than 256 triangles or on hulls of more than 128 vertices: "
+                     "the collision set was built with large_meshes=True and has " + (", ".join(why) if why else "no such mesh")
+                     + "; the constraint values are served (Engine.set_large_hull_meshes), their gradients are not built")
+
+
 def _refuse_mesh_gradient(collision) -> None:
     """without ``mesh_gradient=True`` a set with triangle meshes is refused by the names of its meshed links (the message is the one from
     before the mesh gradient was built: callers match it)"""
@@ -553,6 +573,8 @@ def _collision_block(engine, states, ncand, config, collision, suspended=None):
             kw = {"meshes": collision["meshes"]} if _has_meshes(collision) else {}
             if _large_hulls(collision):  # (the keyword only then: engines of before know nothing of it)
                 kw["large"] = True
+            if kw.get("meshes") and collision.get("large_meshes"):  # (Engine.set_large_hull_meshes: the same rule)
+                kw["large_meshes"] = True
             engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)), **kw)
         part = candidate_collision_constraints(engine, states, ncand, config, margins=m[sel], suspended=suspended, boxes=which == 1, hulls=which == 2)
         if out is None:
@@ -835,6 +857,7 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     from ``Engine.large_hull_distance_gradients`` exactly as ``hull_gradient=True`` takes them from the hull call (``hull_gradient`` may
     then be either value).  The keyword with anything else raises ``ValueError`` and says which condition fails."""
     _check_config(config)
+    _refuse_large_mesh_gradient(collision)
     large_rows = _wants_large_hull_gradient(config, collision, large_hull_gradient)
     if not large_rows:
         _refuse_large_hull_gradient(collision)
@@ -1082,6 +1105,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     above 128 vertices is refused by the names and vertex counts of those hulls; ``True`` with ``collisionMode: "convex"``, hull pairs only
     and no meshes: the rows of all its pairs come from ``Engine.large_hull_distance_gradients`` (``candidate_collision_gradient``)."""
     _check_config(config)
+    _refuse_large_mesh_gradient(collision)
     large_rows = collision is not None and _wants_large_hull_gradient(config, collision, large_hull_gradient)
     if large_hull_gradient and collision is None:
         raise ValueError("large_hull_gradient=True: no collision set (collision=)")

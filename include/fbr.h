@@ -90,7 +90,7 @@ typedef struct {
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
  * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes;
  * fbr_mesh_distance_gradients; fbr_model_set_large_hulls, option "hull_large_all"; fbr_large_hull_distance_gradients, option
- * "hull_grad_tile". */
+ * "hull_grad_tile"; fbr_model_set_large_hull_meshes. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -346,6 +346,23 @@ int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, const doubl
 #define FBR_MAX_MESH_TRIANGLES 256
 #define FBR_MAX_MESH_PAIR_WORK 32768
 int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris);
+
+/*
+ * The same attachment for meshes of up to FBR_MAX_LARGE_MESH_TRIANGLES triangles, on a hull set of fbr_model_set_hulls OR of
+ * fbr_model_set_large_hulls: the visual meshes of KUKA LWR4 (1098 to 4434 triangles on hulls of 158 to 793 vertices), collisionMode "full"
+ * on robots without collision meshes.  Arguments, attachment rules (in place; nmesh = 0 clears; a later fbr_model_set_hulls /
+ * fbr_model_set_large_hulls clears; a refused or failed call leaves what was there) and every check as for fbr_model_set_hull_meshes, but
+ * for the cap on the triangles of a mesh, and no cap on a pair's T_A x T_B: at set time a bounding-sphere tree is built per mesh (median
+ * splits, leaves of 8 triangles; the triangles are reordered inside the library), and fbr_candidate_hull_distances sends every pair with a
+ * meshed hull to a kernel that walks the two trees for the 64 samples of a wave together (csrc/fbr_mesh_bvh.h).  The value is the one
+ * fbr_model_set_hull_meshes defines -- the minimum over triangles (triangle pairs), exactly 0.0 on contact, never negative -- with the
+ * bits the brute force gives on the same poses: the tree only skips what could not have won.  Pairs without a mesh go to the kernels
+ * they go to without any mesh attached and return the same bytes.  Distances only: fbr_hull_distance_gradients,
+ * fbr_mesh_distance_gradients and fbr_large_hull_distance_gradients return FBR_E_UNSUPPORTED while such attachments are in place.
+ * FBR_E_INVALID in addition: a tree deeper than the traversal's stack holds (median splits of 8192 triangles cannot produce one).
+ */
+#define FBR_MAX_LARGE_MESH_TRIANGLES 8192
+int fbr_model_set_large_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, const int32_t *tbeg, const double *tris);
 
 /*
  * Capsule distance and its derivative with respect to the joint positions at ONE chosen configuration per candidate and pair -- the

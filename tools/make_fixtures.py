@@ -53,7 +53,9 @@ npz) and writes small derived fixtures; no reference source code is copied.
   tests/golden/kuka_hulls.npz                 the vertices of the convex hulls of model/meshes/kuka/*.STL (the visual meshes of KUKA LWR4, which
                                               has no collision meshes) as the files' own float32, 158 to 793 a hull, with the link names and
                                               the offsets flobaroid_amd.collision.hulls_from_urdf gives them (visual/origin xyz): data only,
-                                              about 50 KB; the STL files, 55 to 220 KB each, stay out
+                                              about 50 KB (written before the STL files themselves were fixtures)
+  tests/golden/urdf/meshes/kuka/*.STL         the eight visual meshes of KUKA LWR4, copied as they are (data only, 1.15 MB): collisionMode
+                                              "full" on KUKA, tests/test_meshes_large.py and tests/test_gpu_meshes_large.py
 """
 import json
 import os
@@ -1090,7 +1092,24 @@ def kuka_hulls(golden):
     print("kuka_hulls.npz:", sum(len(v) for v in verts), "vertices")
 
 
+def kuka_meshes(golden):
+    """tests/golden/urdf/meshes/kuka/*.STL: the eight visual meshes of KUKA LWR4 (1098 to 4434 triangles, 55 to 222 KB a file, 1.15 MB in
+    all) as the reference ships them, data only -- what collisionMode "full" on KUKA reads through flobaroid_amd.collision.meshes_from_urdf"""
+    import shutil
+
+    src, dst = os.path.join(REF, "model", "meshes", "kuka"), os.path.join(golden, "urdf", "meshes", "kuka")
+    os.makedirs(dst, exist_ok=True)
+    names = sorted(f for f in os.listdir(src) if f.endswith(".STL"))
+    assert len(names) == 8, names
+    for f in names:
+        shutil.copyfile(os.path.join(src, f), os.path.join(dst, f))
+    print("kuka meshes:", names)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "kuka_meshes":
+        kuka_meshes(os.path.join(REPO, "tests", "golden"))
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "kuka_hulls":
         kuka_hulls(os.path.join(REPO, "tests", "golden"))
         sys.exit(0)
@@ -1115,3 +1134,4 @@ if __name__ == "__main__":
     reference_trajectories(os.path.join(REPO, "tests", "golden"))
     reference_capsules(os.path.join(REPO, "tests", "golden"))
     kuka_hulls(os.path.join(REPO, "tests", "golden"))
+    kuka_meshes(os.path.join(REPO, "tests", "golden"))
