@@ -4,7 +4,6 @@
 // fbr_collision_tables.h.  DESIGN.md, "collision layout".
 #define FBR_KERNELS_COLLISION
 #include "fbr_internal.h"
-#include "fbr_collision_tables.h"
 #include "fbr_hull_large_grad.h"
 #include <limits>
 
@@ -39,8 +38,6 @@ static int upload_grad_table(DevBuf &buf, const FbrCollisionSort &srt, const int
     out->anc = buf.as<int>() + (size_t)4 * std::max(npairs, 1);
     return FBR_OK;
 }
-
-static const DevBoxes kNoBoxes = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 // ---- capsule collision set (csrc/fbr_capsule.h) ------------------------------------------------------------------------------------------
 extern "C" int fbr_model_set_capsules(fbr_model *m, int32_t ncaps, const int32_t *link, const double *seg, const double *radius, int32_t npairs,
@@ -200,6 +197,58 @@ extern "C" int fbr_model_set_boxes(fbr_model *m, int32_t nboxes, const int32_t *
 }
 
 // ---- convex-hull collision set (csrc/fbr_hull.h) -----------------------------------------------------------------------------------------
+// The class views and the stencil tables of a hull set (fbr_hull_pair_classes, fbr_stencil_table of fbr_collision_tables.h) from the host's
+// copy of the set and the mesh table (null: no meshes), into an allocation of their own: both setters build `out` beside what is installed
+// and move it in once nothing can fail any more.
+static int build_hull_views(const fbr_model *m, const DevHulls &set, const FbrHullSet::Host &hh, bool large_set, const int *mtab, int meshes,
+                            FbrHullViews &out)
+{
+    const int npairs = set.npairs;
+    const FbrPairClasses pc = fbr_hull_pair_classes(set.nhulls, hh.vbeg.data(), mtab, npairs, hh.pairs.data());
+    // the stencil tables and the columns they cover: the MESH view (small meshes: the others have distances only), the BIG view and every
+    // pair (fbr_large_hull_distance_gradients: a set of fbr_model_set_large_hulls without meshes)
+    std::vector<int> every((size_t)npairs);
+    std::iota(every.begin(), every.end(), 0);
+    const bool lgrad = large_set && meshes == FBR_MESHES_NONE && npairs > 0;
+    const std::vector<int> *cols[3] = {meshes == FBR_MESHES_SMALL ? &pc.col[FBR_PAIR_MESH] : nullptr,
+                                       lgrad && !pc.col[FBR_PAIR_BIG].empty() ? &pc.col[FBR_PAIR_BIG] : nullptr, lgrad ? &every : nullptr};
+    FbrStencilTable st[3];
+    if (cols[0] || cols[1] || cols[2]) {
+        FbrKinIdProgram prog;
+        if (int rc = collision_program(m, prog)) return rc;
+        std::vector<int> stepof, anc;
+        fbr_capgrad_ancestors(m->hm, prog, stepof, anc);
+        for (int i = 0; i < 3; i++)
+            if (cols[i])
+                st[i] = fbr_stencil_table(*cols[i], hh.link.data(), stepof.data(), anc.data(), fbr_capgrad_words(prog.nsteps), set.fr.cmode,
+                                          prog.steps.data(), hh.pairs.data());
+    }
+    // one allocation: the pairs of the classes | their columns | the stencil tables
+    FbrBlob blob;
+    size_t op[FBR_PAIR_CLASSES], oc[FBR_PAIR_CLASSES], os[3];
+    for (int c = 0; c < FBR_PAIR_CLASSES; c++) op[c] = blob.add<int>(pc.pairs[c].begin(), pc.pairs[c].end(), sizeof(int2));
+    for (int c = 0; c < FBR_PAIR_CLASSES; c++) oc[c] = blob.add<int>(pc.col[c].begin(), pc.col[c].end());
+    for (int i = 0; i < 3; i++) os[i] = blob.add<int>(st[i].tab.begin(), st[i].tab.end());
+    if (int rc = upload_blob(out.tab, blob)) return rc;
+    const char *base = (const char *)out.tab.p;
+    for (int c = 0; c < FBR_PAIR_CLASSES; c++) {
+        const int cnt = (int)pc.col[c].size();
+        // (a class that covers every pair of a set without meshes is the whole set, in the caller's columns)
+        const bool whole = mtab == nullptr && cnt == npairs;
+        out.view[c].npairs = cnt;
+        out.view[c].pairs = whole ? set.pairs : (const int2 *)(base + op[c]);
+        out.view[c].col = whole ? nullptr : (const int *)(base + oc[c]);
+    }
+    FbrStencil *dst[3] = {&out.mesh, &out.big, &out.all};
+    for (int i = 0; i < 3; i++) {
+        const int *g = (const int *)(base + os[i]);
+        if (!cols[i]) continue;  // (out is the caller's fresh one: an empty table)
+        dst[i]->dev = DevMeshGrad{st[i].nitems, st[i].smax, g, g + st[i].npairs + 1, g + st[i].npairs + 1 + st[i].nitems};
+        dst[i]->sbeg.assign(st[i].tab.begin(), st[i].tab.begin() + st[i].npairs + 1);
+    }
+    return FBR_OK;
+}
+
 // fbr_model_set_hulls (max_vertices FBR_MAX_HULL_VERTICES) and fbr_model_set_large_hulls (FBR_MAX_LARGE_HULL_VERTICES, large): one set, two caps
 static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhulls, const int32_t *link, const double *offset, const double *rot,
                          int32_t offset_in_link_axes, const int32_t *vbeg, const double *verts, const int32_t *fbeg, const double *planes,
@@ -219,25 +268,7 @@ static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhu
     }
     if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
     HIPCHK(hipStreamSynchronize(m->stream));
-    m->hulls = DevHulls{kNoBoxes, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    m->hullg = DevPairGrad{0, nullptr, nullptr};
-    // (the meshes attached to the set before are gone with it: fbr_model_set_hull_meshes)
-    m->hulls_plain = m->hulls;
-    m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
-    m->has_meshes = false;
-    m->mesh_large = false;
-    m->mesh_bvh = DevMeshBvh{nullptr, nullptr, nullptr};
-    m->hulls_plain_big = m->hulls;
-    m->hull_host = {};
-    m->hulls_small = m->hulls_big = m->hulls;
-    m->hull_big = -1;
-    m->hull_big_nv = 0;
-    m->hull_large_set = false;
-    for (int i = 0; i < 2; i++) {
-        m->hull_lgrad[i] = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
-        m->hull_lgrad_sbeg[i].clear();
-    }
+    m->hs.clear();  // (the meshes attached to the set before are gone with it: fbr_model_set_hull_meshes)
     if (nhulls == 0) return FBR_OK;
     FbrKinIdProgram prog;
     if (int rc = collision_program(m, prog)) return rc;
@@ -265,8 +296,8 @@ static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhu
         }
     }
     std::copy(pairs, pairs + 2 * (size_t)npairs, blob.at<int>(opairs));
-    if (int rc = upload_blob(m->hull_tab, blob)) return rc;
-    const char *base = (const char *)m->hull_tab.p;
+    if (int rc = upload_blob(m->hs.set_tab, blob)) return rc;
+    const char *base = (const char *)m->hs.set_tab.p;
     DevHulls dh;
     dh.fr = DevBoxes{prog.nsteps, prog.nslots, srt.nrob, 0, 0, offset_in_link_axes ? 1 : 0, (const int *)(base + osteps), (const int *)(base + obeg),
                      (const int *)(base + oid), (const double *)(base + ocen), nullptr, nullptr, nullptr};
@@ -281,85 +312,28 @@ static int install_hulls(fbr_model *m, int max_vertices, bool large, int32_t nhu
     dh.pairs = (const int2 *)(base + opairs);
     dh.col = nullptr;
     dh.ldp = npairs;
-    if (int rc = upload_grad_table(m->hullg_tab, srt, link, npairs, pairs, &m->hullg)) return rc;
-    // a hull above the small cap: the pairs of two small hulls, in their order, and the others, in theirs, each with its columns
+    DevPairGrad dg;
+    if (int rc = upload_grad_table(m->hs.grad_tab, srt, link, npairs, pairs, &dg)) return rc;
+    FbrHullSet::Host hh;
+    hh.link.assign(link, link + nhulls);
+    hh.vbeg.assign(vbeg, vbeg + nhulls + 1);
+    hh.fbeg.assign(fbeg, fbeg + nhulls + 1);
+    hh.pairs.assign(pairs, pairs + 2 * (size_t)npairs);
+    hh.verts.assign(verts, verts + NV * 3);
+    hh.planes.assign(planes, planes + NF * 4);
+    hh.diam.assign(diam.begin(), diam.begin() + nhulls);
+    FbrHullViews views;
+    if (int rc = build_hull_views(m, dh, hh, large, nullptr, FBR_MESHES_NONE, views)) return rc;
     int big = -1;
     for (int h = 0; h < nhulls && big < 0; h++)
         if (vbeg[h + 1] - vbeg[h] > FBR_MAX_HULL_VERTICES) big = h;
-    DevHulls small = dh, rest = dh;
-    if (big >= 0) {
-        std::vector<int> sk, bk;
-        for (int k = 0; k < npairs; k++) {
-            const int a = pairs[2 * k], b = pairs[2 * k + 1];
-            (vbeg[a + 1] - vbeg[a] > FBR_MAX_HULL_VERTICES || vbeg[b + 1] - vbeg[b] > FBR_MAX_HULL_VERTICES ? bk : sk).push_back(k);
-        }
-        const size_t ns = std::max(sk.size(), (size_t)1), nl = std::max(bk.size(), (size_t)1);
-        FbrBlob split;  // small pairs | large pairs | small columns | large columns
-        const size_t osp = split.add<int>(2 * ns, sizeof(int2)), olp = split.add<int>(2 * nl, sizeof(int2)), osc = split.add<int>(ns), olc = split.add<int>(nl);
-        for (size_t i = 0; i < sk.size(); i++)
-            split.at<int>(osp)[2 * i] = pairs[2 * sk[i]], split.at<int>(osp)[2 * i + 1] = pairs[2 * sk[i] + 1], split.at<int>(osc)[i] = sk[i];
-        for (size_t i = 0; i < bk.size(); i++)
-            split.at<int>(olp)[2 * i] = pairs[2 * bk[i]], split.at<int>(olp)[2 * i + 1] = pairs[2 * bk[i] + 1], split.at<int>(olc)[i] = bk[i];
-        if (int rc = upload_blob(m->hull_split_tab, split)) return rc;
-        const char *sb = (const char *)m->hull_split_tab.p;
-        small.npairs = (int)sk.size(), small.pairs = (const int2 *)(sb + osp), small.col = (const int *)(sb + osc);
-        rest.npairs = (int)bk.size(), rest.pairs = (const int2 *)(sb + olp), rest.col = (const int *)(sb + olc);
-    }
-    // the stencil points of fbr_large_hull_distance_gradients (csrc/fbr_hull_large_grad.h): per large pair the centre, then + eps, - eps of
-    // every joint fbr_rigidgrad_item evaluates, in walk order -- for the pairs of `rest` and for every pair (option hull_large_all, read by
-    // every call): sbeg | pair of a point | its joint, twice
-    DevMeshGrad lgrad[2] = {{0, 0, nullptr, nullptr, nullptr}, {0, 0, nullptr, nullptr, nullptr}};
-    std::vector<int> lsbeg[2];
-    if (large && npairs > 0) {
-        std::vector<int> stepof, anc, joint, gtab;
-        fbr_capgrad_ancestors(hm, prog, stepof, anc);
-        const auto isbig = [&](int h) { return vbeg[h + 1] - vbeg[h] > FBR_MAX_HULL_VERTICES; };
-        size_t off[2], np[2];
-        for (int arr = 0; arr < 2; arr++) {
-            std::vector<int> gpair, gjoint;
-            lsbeg[arr].assign(1, 0);
-            int smax = 0;
-            for (int k = 0; k < npairs; k++) {
-                const int a = pairs[2 * k], b = pairs[2 * k + 1];
-                if (arr == 0 && big >= 0 && !isbig(a) && !isbig(b)) continue;  // (no hull above the cap: `rest` is the whole set)
-                fbr_meshgrad_slots(link[a] < 0 ? -1 : stepof[link[a]], link[b] < 0 ? -1 : stepof[link[b]], offset_in_link_axes ? 1 : 0, prog.steps.data(),
-                                   anc.data(), fbr_capgrad_words(prog.nsteps), joint);
-                gpair.insert(gpair.end(), joint.size(), (int)lsbeg[arr].size() - 1);
-                gjoint.insert(gjoint.end(), joint.begin(), joint.end());
-                lsbeg[arr].push_back(lsbeg[arr].back() + (int)joint.size());
-                smax = std::max(smax, (int)joint.size());
-            }
-            off[arr] = gtab.size(), np[arr] = lsbeg[arr].size() - 1;
-            lgrad[arr].nitems = (int)gpair.size(), lgrad[arr].smax = smax;
-            gtab.insert(gtab.end(), lsbeg[arr].begin(), lsbeg[arr].end());
-            gtab.insert(gtab.end(), gpair.begin(), gpair.end());
-            gtab.insert(gtab.end(), gjoint.begin(), gjoint.end());
-        }
-        if (int rc = m->hull_lgrad_tab.ensure(gtab.size() * sizeof(int))) return rc;
-        HIPCHK(hipMemcpy(m->hull_lgrad_tab.p, gtab.data(), gtab.size() * sizeof(int), hipMemcpyHostToDevice));
-        for (int arr = 0; arr < 2; arr++) {
-            const int *g = m->hull_lgrad_tab.as<int>() + off[arr];
-            lgrad[arr].sbeg = g, lgrad[arr].spair = g + np[arr] + 1, lgrad[arr].sjoint = g + np[arr] + 1 + lgrad[arr].nitems;
-        }
-    }
-    for (int i = 0; i < 2; i++) {
-        m->hull_lgrad[i] = lgrad[i];
-        m->hull_lgrad_sbeg[i] = lsbeg[i];
-    }
-    m->hulls = dh;
-    m->hulls_plain = dh;
-    m->hulls_small = small;
-    m->hulls_big = rest;
-    m->hull_big = big;
-    m->hull_big_nv = big < 0 ? 0 : vbeg[big + 1] - vbeg[big];
-    m->hull_large_set = large;
-    m->hull_host.link.assign(link, link + nhulls);
-    m->hull_host.vbeg.assign(vbeg, vbeg + nhulls + 1);
-    m->hull_host.fbeg.assign(fbeg, fbeg + nhulls + 1);
-    m->hull_host.pairs.assign(pairs, pairs + 2 * (size_t)npairs);
-    m->hull_host.verts.assign(verts, verts + NV * 3);
-    m->hull_host.planes.assign(planes, planes + NF * 4);
-    m->hull_host.diam.assign(diam.begin(), diam.begin() + nhulls);
+    m->hs.set = dh;
+    m->hs.grad = dg;
+    m->hs.host = std::move(hh);
+    m->hs.large_set = large;
+    m->hs.big = big;
+    m->hs.big_nv = big < 0 ? 0 : vbeg[big + 1] - vbeg[big];
+    m->hs.views = std::move(views);
     return FBR_OK;
 }
 
@@ -381,8 +355,8 @@ extern "C" int fbr_model_set_large_hulls(fbr_model *m, int32_t nhulls, const int
 // the hull set has a hull above FBR_MAX_HULL_VERTICES vertices: what `who` does is not built for it
 static bool refuse_large_hulls(const fbr_model *m, const char *who)
 {
-    if (m->hull_big < 0) return false;
-    set_err(std::string(who) + ": hull " + std::to_string(m->hull_big) + " of the set has " + std::to_string(m->hull_big_nv) + " vertices, more than " +
+    if (m->hs.big < 0) return false;
+    set_err(std::string(who) + ": hull " + std::to_string(m->hs.big) + " of the set has " + std::to_string(m->hs.big_nv) + " vertices, more than " +
             std::to_string(FBR_MAX_HULL_VERTICES) + " (a set of fbr_model_set_large_hulls: distances only, no meshes and no gradients)");
     return true;
 }
@@ -397,8 +371,9 @@ static int attach_meshes(fbr_model *m, bool large, int32_t nmesh, const int32_t 
         return FBR_E_INVALID;
     }
     if (!large && refuse_large_hulls(m, "fbr_model_set_hull_meshes")) return FBR_E_INVALID;
-    const auto &hh = m->hull_host;
-    const int nhulls = m->hulls.nhulls, npairs = m->hulls.npairs;
+    FbrHullSet &H = m->hs;
+    const auto &hh = H.host;
+    const int nhulls = H.set.nhulls, npairs = H.set.npairs;
     const std::string bad = fbr_mesh_validate(nhulls, hh.link.data(), hh.fbeg.data(), hh.planes.data(), hh.diam.data(), npairs, hh.pairs.data(),
                                               large ? FBR_MAX_LARGE_MESH_TRIANGLES : FBR_MAX_MESH_TRIANGLES,
                                               large ? std::numeric_limits<long>::max() : (long)FBR_MAX_MESH_PAIR_WORK, nmesh, hull, tbeg, tris);
@@ -418,104 +393,40 @@ static int attach_meshes(fbr_model *m, bool large, int32_t nmesh, const int32_t 
     }
     if (int rc = enter_blocking(m)) return rc;  // (no launch that reads the tables replaced below is in flight)
     HIPCHK(hipStreamSynchronize(m->stream));
+    // Unlike the three setters above, which reuse their buffers (they have cleared their set before they build), this one builds into fresh
+    // allocations and swaps them in once the copies have succeeded: a call that fails here leaves the attachments in place as well.
+    FbrHullViews views;
     if (nmesh == 0) {
-        m->hulls_plain = m->hulls;
-        m->meshes = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        m->meshg = DevMeshGrad{0, 0, nullptr, nullptr, nullptr};
-        m->has_meshes = false;
-        m->mesh_large = false;
-        m->mesh_bvh = DevMeshBvh{nullptr, nullptr, nullptr};
-        m->hulls_plain_big = m->hulls;
+        if (int rc = build_hull_views(m, H.set, hh, H.large_set, nullptr, FBR_MESHES_NONE, views)) return rc;
+        H.clear_meshes();
+        H.views = std::move(views);
         return FBR_OK;
     }
-    // the pairs of the set: those with a mesh on either side, the meshed hull first, sorted by it (stable); the others in their order
     std::vector<int> mtab((size_t)nhulls * 2, 0);
     for (int i = 0; i < nmesh; i++) mtab[2 * (size_t)hull[i]] = tbeg[i], mtab[2 * (size_t)hull[i] + 1] = tbeg[i + 1] - tbeg[i];
-    // (a large attachment: the plain pairs of two hulls of at most FBR_MAX_HULL_VERTICES vertices in pk, the other plain pairs in bk --
-    // the kernels they go to without meshes)
-    std::vector<int> mk, pk, bk;
-    const auto bighull = [&](int h) { return large && hh.vbeg[h + 1] - hh.vbeg[h] > FBR_MAX_HULL_VERTICES; };
-    for (int k = 0; k < npairs; k++) {
-        const int a = hh.pairs[2 * k], b = hh.pairs[2 * k + 1];
-        (mtab[2 * (size_t)a + 1] || mtab[2 * (size_t)b + 1] ? mk : (bighull(a) || bighull(b) ? bk : pk)).push_back(k);
-    }
-    auto first = [&](int k) { return mtab[2 * (size_t)hh.pairs[2 * k] + 1] ? hh.pairs[2 * k] : hh.pairs[2 * k + 1]; };
-    std::stable_sort(mk.begin(), mk.end(), [&](int a, int b) { return first(a) < first(b); });
-    const size_t NT = (size_t)tbeg[nmesh], nm = std::max(mk.size(), (size_t)1), np = std::max(pk.size(), (size_t)1);
-    // one allocation: sph | tris | aux | mesh pairs | plain pairs | mtab | mesh columns | plain columns
+    const int kind = large ? FBR_MESHES_TREE : FBR_MESHES_SMALL;
+    if (int rc = build_hull_views(m, H.set, hh, H.large_set, mtab.data(), kind, views)) return rc;
+    // one allocation: sph | tris | aux | mtab | first node of a hull's tree | nodes | node spheres (the last three: a large attachment)
+    const size_t NT = (size_t)tbeg[nmesh];
     FbrBlob blob;
     const size_t osph = blob.add<double>((size_t)nhulls * 4), otris = blob.add<double>(tris, tris + NT * 9), oaux = blob.add<double>(NT * 5);
-    const size_t omp = blob.add<int>(2 * nm), opp = blob.add<int>(2 * np), omtab = blob.add<int>(mtab.begin(), mtab.end());
-    const size_t omc = blob.add<int>(nm), opc = blob.add<int>(np);
-    // (a large attachment: | big plain pairs | their columns | first node of a hull's tree | nodes | node spheres)
-    const size_t nbp = std::max(bk.size(), (size_t)1);
-    const size_t obp = blob.add<int>(2 * nbp), obc = blob.add<int>(nbp), onbeg = blob.add<int>((size_t)nhulls);
-    const size_t onode = blob.add<int>(bvh.node.begin(), bvh.node.end()), ovol = blob.add<double>(bvh.vol.begin(), bvh.vol.end());
-    for (size_t i = 0; i < bk.size(); i++)
-        blob.at<int>(obp)[2 * i] = hh.pairs[2 * bk[i]], blob.at<int>(obp)[2 * i + 1] = hh.pairs[2 * bk[i] + 1], blob.at<int>(obc)[i] = bk[i];
-    std::fill(blob.at<int>(onbeg), blob.at<int>(onbeg) + nhulls, 0);
+    const size_t ovol = blob.add<double>(bvh.vol.begin(), bvh.vol.end()), omtab = blob.add<int>(mtab.begin(), mtab.end());
+    const size_t onbeg = blob.add<int>((size_t)nhulls), onode = blob.add<int>(bvh.node.begin(), bvh.node.end());
     if (large)
         for (int i = 0; i < nmesh; i++) blob.at<int>(onbeg)[hull[i]] = bvh.nbeg[i];
     for (int h = 0; h < nhulls; h++)
         fbr_mesh_point_sphere(hh.vbeg[h + 1] - hh.vbeg[h], hh.verts.data() + 3 * (size_t)hh.vbeg[h], 3L * mtab[2 * (size_t)h + 1],
                               tris + 9 * (size_t)mtab[2 * (size_t)h], blob.at<double>(osph) + 4 * (size_t)h);
     for (size_t t = 0; t < NT; t++) fbr_mesh_triangle_aux(tris + 9 * t, blob.at<double>(oaux) + 5 * t);  // (large: what bvh.aux holds)
-    int *hmp = blob.at<int>(omp), *hpp = blob.at<int>(opp), *hmc = blob.at<int>(omc), *hpc = blob.at<int>(opc);
-    for (size_t i = 0; i < mk.size(); i++) {
-        const int k = mk[i], a = hh.pairs[2 * k], b = hh.pairs[2 * k + 1], swap = mtab[2 * (size_t)a + 1] == 0;
-        hmp[2 * i] = swap ? b : a, hmp[2 * i + 1] = swap ? a : b, hmc[i] = k;
-    }
-    for (size_t i = 0; i < pk.size(); i++) hpp[2 * i] = hh.pairs[2 * pk[i]], hpp[2 * i + 1] = hh.pairs[2 * pk[i] + 1], hpc[i] = pk[i];
-    // the stencil points of fbr_mesh_distance_gradients (csrc/fbr_mesh_grad.h): per mesh pair the centre, then + eps, - eps of every joint
-    // fbr_rigidgrad_item evaluates, in walk order: sbeg | pair of a point | its joint
-    std::vector<int> gtab(mk.size() + 1, 0), gpair, gjoint;
-    int smax = 0;
-    if (!large) {  // (a large attachment has distances only)
-        FbrKinIdProgram prog;
-        if (int rc = collision_program(m, prog)) return rc;
-        std::vector<int> stepof, anc, joint;
-        fbr_capgrad_ancestors(m->hm, prog, stepof, anc);
-        for (size_t i = 0; i < mk.size(); i++) {
-            const int la = hh.link[hh.pairs[2 * mk[i]]], lb = hh.link[hh.pairs[2 * mk[i] + 1]];
-            fbr_meshgrad_slots(la < 0 ? -1 : stepof[la], lb < 0 ? -1 : stepof[lb], m->hulls.fr.cmode, prog.steps.data(), anc.data(),
-                               fbr_capgrad_words(prog.nsteps), joint);
-            gtab[i + 1] = gtab[i] + (int)joint.size();
-            gpair.insert(gpair.end(), joint.size(), (int)i);
-            gjoint.insert(gjoint.end(), joint.begin(), joint.end());
-            smax = std::max(smax, (int)joint.size());
-        }
-        gtab.insert(gtab.end(), gpair.begin(), gpair.end());
-        gtab.insert(gtab.end(), gjoint.begin(), gjoint.end());
-    } else {
-        gtab.assign(1, 0);
-    }
-    // Unlike the three setters above, which reuse their buffers (they have cleared their set before they build), this one builds into fresh
-    // allocations and swaps them in once the copies have succeeded: a call that fails here leaves the attachments in place as well.
-    DevBuf fresh, freshg;
+    DevBuf fresh;
     if (int rc = upload_blob(fresh, blob)) return rc;
-    if (int rc = freshg.ensure(gtab.size() * sizeof(int))) return rc;
-    HIPCHK(hipMemcpy(freshg.p, gtab.data(), gtab.size() * sizeof(int), hipMemcpyHostToDevice));
-    m->mesh_tab = std::move(fresh);
-    m->meshg_tab = std::move(freshg);
-    {
-        const int *g = m->meshg_tab.as<int>();
-        const int ni = (int)gpair.size();
-        m->meshg = large ? DevMeshGrad{0, 0, nullptr, nullptr, nullptr} : DevMeshGrad{ni, smax, g, g + mk.size() + 1, g + mk.size() + 1 + ni};
-    }
-    m->hulls_plain = m->hulls;
-    const char *base = (const char *)m->mesh_tab.p;
-    m->meshes = DevMeshes{(int)mk.size(), (const int *)(base + omtab), (const double *)(base + osph), (const double *)(base + otris),
-                          (const double *)(base + oaux), (const int2 *)(base + omp), (const int *)(base + omc)};
-    m->hulls_plain.npairs = (int)pk.size();
-    m->hulls_plain.pairs = (const int2 *)(base + opp);
-    m->hulls_plain.col = (const int *)(base + opc);
-    m->hulls_plain_big = m->hulls;
-    m->hulls_plain_big.npairs = (int)bk.size();
-    m->hulls_plain_big.pairs = (const int2 *)(base + obp);
-    m->hulls_plain_big.col = (const int *)(base + obc);
-    m->mesh_bvh = DevMeshBvh{(const int *)(base + onbeg), (const int *)(base + onode), (const double *)(base + ovol)};
-    m->mesh_large = large;
-    m->has_meshes = true;
+    H.mesh_tab = std::move(fresh);
+    H.views = std::move(views);
+    const char *base = (const char *)H.mesh_tab.p;
+    H.geo = DevMeshes{0, (const int *)(base + omtab), (const double *)(base + osph), (const double *)(base + otris), (const double *)(base + oaux),
+                      nullptr, nullptr};
+    H.bvh = DevMeshBvh{(const int *)(base + onbeg), (const int *)(base + onode), (const double *)(base + ovol)};
+    H.meshes = kind;
     return FBR_OK;
 }
 
@@ -532,7 +443,7 @@ extern "C" int fbr_model_set_large_hull_meshes(fbr_model *m, int32_t nmesh, cons
 // attachments of fbr_model_set_large_hull_meshes are in place: distances only, `who` has no gradients of them
 static bool refuse_large_meshes(const fbr_model *m, const char *who)
 {
-    if (!(m->has_meshes && m->mesh_large)) return false;
+    if (m->hs.meshes != FBR_MESHES_TREE) return false;
     set_err(std::string(who) + ": the hull set has triangle meshes attached by fbr_model_set_large_hull_meshes: distances only "
                                "(fbr_candidate_hull_distances), gradients of such a set are not built");
     return true;
@@ -687,58 +598,39 @@ extern "C" int fbr_candidate_hull_distances(fbr_model *m, const fbr_states *st, 
                                             int64_t *idx_out, int32_t out_mem)
 {
     // (a set of world hulls only has no pairs: two world hulls are never paired)
-    const bool have = m && m->hulls.nhulls != 0 && m->hulls.npairs != 0;
-    const long P = m ? m->hulls.npairs : 0;
-    return candidate_frame_distances(m, !m || have ? nullptr : "no hull set with at least one pair (fbr_model_set_hulls)", m ? m->hulls.fr : kNoBoxes, P,
-                                     (P + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
-                                     [&](unsigned grid, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
-                                         const long cap = (long)m->num_cus * 32;
-                                         const auto large = [&](const DevHulls &hs) {
-                                             const long items = nb * ((hs.npairs + FBR_HULL_LARGE_BATCH - 1) / FBR_HULL_LARGE_BATCH);
-                                             hipLaunchKernelGGL(fbr_hull_large_pairs_kernel, dim3((unsigned)std::min(items, cap)), dim3(64), 0, m->stream, hs, tl,
-                                                                b0, nb, fr, pval, pidx);
-                                         };
-                                         if (m->has_meshes && m->mesh_large) {
-                                             // attachments of fbr_model_set_large_hull_meshes: the pairs without a mesh to the kernels they go
-                                             // to without any mesh, the others to the tree kernel, each into its own columns
-                                             const long ps = m->hulls_plain.npairs, pb = m->hulls_plain_big.npairs, pm = m->meshes.npairs;
-                                             const bool all = m->hull_large_set && m->opt.hull_large_all != 0;
-                                             if (ps > 0 && all) large(m->hulls_plain);
-                                             if (ps > 0 && !all)
-                                                 hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ps + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
-                                                                    dim3(64), 0, m->stream, m->hulls_plain, tl, b0, nb, fr, pval, pidx);
-                                             if (pb > 0) large(m->hulls_plain_big);
-                                             if (pm > 0)
-                                                 hipLaunchKernelGGL(fbr_mesh_bvh_pairs_kernel, dim3((unsigned)std::min(nb * pm, cap)), dim3(64), 0, m->stream,
-                                                                    m->hulls, m->meshes, m->mesh_bvh, tl, b0, nb, fr, pval, pidx);
-                                             return;
-                                         }
-                                         if (!m->has_meshes && m->hull_large_set && m->opt.hull_large_all != 0) {
-                                             large(m->hulls);  // (every pair, in the caller's columns)
-                                             return;
-                                         }
-                                         if (!m->has_meshes && m->hull_big >= 0) {
-                                             // a set with large hulls: the pairs of two small hulls, then the others, each into its own columns
-                                             const long ps = m->hulls_small.npairs;
-                                             if (ps > 0)
-                                                 hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ps + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
-                                                                    dim3(64), 0, m->stream, m->hulls_small, tl, b0, nb, fr, pval, pidx);
-                                             if (m->hulls_big.npairs > 0) large(m->hulls_big);
-                                             return;
-                                         }
-                                         if (!m->has_meshes) {
-                                             hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3(grid), dim3(64), 0, m->stream, m->hulls, tl, b0, nb, fr, pval, pidx);
-                                             return;
-                                         }
-                                         // a split set: the pairs without a mesh, then those with one, each into its own columns
-                                         const long ph = m->hulls_plain.npairs, pm = m->meshes.npairs;
-                                         if (ph > 0)
-                                             hipLaunchKernelGGL(fbr_hull_pairs_kernel, dim3((unsigned)std::min(nb * ((ph + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH), cap)),
-                                                                dim3(64), 0, m->stream, m->hulls_plain, tl, b0, nb, fr, pval, pidx);
-                                         if (pm > 0)
-                                             hipLaunchKernelGGL(fbr_mesh_pairs_kernel, dim3((unsigned)std::min(nb * ((pm + FBR_MESH_BATCH - 1) / FBR_MESH_BATCH), cap)),
-                                                                dim3(64), 0, m->stream, m->hulls, m->meshes, tl, b0, nb, fr, pval, pidx);
-                                     });
+    const bool have = m && m->hs.set.nhulls != 0 && m->hs.set.npairs != 0;
+    const long P = m ? m->hs.set.npairs : 0;
+    return candidate_frame_distances(
+        m, !m || have ? nullptr : "no hull set with at least one pair (fbr_model_set_hulls)", m ? m->hs.set.fr : kNoBoxes, P,
+        (P + FBR_HULL_BATCH - 1) / FBR_HULL_BATCH, st, base_pos, ncand, step, dist_out, idx_out, out_mem,
+        [&](unsigned, const DevCapTiles &tl, long b0, long nb, const double *fr, double *pval, long *pidx) {
+            const FbrHullSet &H = m->hs;
+            // the pairs of a class (sets...: the view, or the whole set and what the mesh kernels take besides) on `kernel`, `batch` pairs an
+            // item, into their own columns; a class without a pair launches nothing
+            const auto launch = [&](long pairs, int batch, auto kernel, auto... sets) {
+                if (pairs == 0) return;
+                hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(nb * ((pairs + batch - 1) / batch), (long)m->num_cus * 32)), dim3(64), 0, m->stream,
+                                   sets..., tl, b0, nb, fr, pval, pidx);
+            };
+            // class   kernel
+            // SMALL   fbr_hull_pairs_kernel -- fbr_hull_large_pairs_kernel on a set of fbr_model_set_large_hulls with option hull_large_all
+            //         (not beside small meshes: DESIGN.md)
+            // BIG     fbr_hull_large_pairs_kernel
+            // MESH    fbr_mesh_pairs_kernel (small meshes), fbr_mesh_bvh_pairs_kernel (tree meshes)
+            const bool all = H.large_set && m->opt.hull_large_all != 0 && H.meshes != FBR_MESHES_SMALL;
+            if (all && H.meshes == FBR_MESHES_NONE) return launch(P, FBR_HULL_LARGE_BATCH, fbr_hull_large_pairs_kernel, H.set);  // (one launch)
+            const DevHulls small = H.of(FBR_PAIR_SMALL), big = H.of(FBR_PAIR_BIG);
+            const DevMeshes ms = H.mesh_pairs();
+            if (all)
+                launch(small.npairs, FBR_HULL_LARGE_BATCH, fbr_hull_large_pairs_kernel, small);
+            else
+                launch(small.npairs, FBR_HULL_BATCH, fbr_hull_pairs_kernel, small);
+            launch(big.npairs, FBR_HULL_LARGE_BATCH, fbr_hull_large_pairs_kernel, big);
+            if (H.meshes == FBR_MESHES_TREE)
+                launch(ms.npairs, 1, fbr_mesh_bvh_pairs_kernel, H.set, ms, H.bvh);
+            else
+                launch(ms.npairs, FBR_MESH_BATCH, fbr_mesh_pairs_kernel, H.set, ms);
+        });
 }
 
 // ---- distance and its joint-position gradient at chosen configurations (csrc/fbr_capsule_grad.h, fbr_box_grad.h, fbr_hull_grad.h,
@@ -873,31 +765,70 @@ extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, c
         set_err("epsilon must be finite and positive");
         return FBR_E_INVALID;
     }
-    if (m->hulls.nhulls == 0 || m->hulls.npairs == 0) {
+    if (m->hs.set.nhulls == 0 || m->hs.set.npairs == 0) {
         set_err("no hull set with at least one pair (fbr_model_set_hulls)");
         return FBR_E_INVALID;
     }
     if (refuse_large_meshes(m, "fbr_hull_distance_gradients")) return FBR_E_UNSUPPORTED;
     if (refuse_large_hulls(m, "fbr_hull_distance_gradients")) return FBR_E_INVALID;
-    if (m->has_meshes) {
+    if (m->hs.meshes != FBR_MESHES_NONE) {
         set_err("fbr_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); gradients of mesh pairs are not built");
         return FBR_E_UNSUPPORTED;
     }
     double se, omc;
     fbr_boxgrad_trig(epsilon, &se, &omc);
     return distance_gradients(m, "fbr_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem,
-                              m->hulls.npairs, m->hulls.fr.nslots,
+                              m->hs.set.npairs, m->hs.set.fr.nslots,
                               [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
                                   const long *dpose, double *ddist, double *dgrad) {
-                                  hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->hulls, m->hullg, C, T, dq,
+                                  hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)grid), dim3(64), 0, m->stream, m->dm, m->hs.set, m->hs.grad, C, T, dq,
                                                      drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
                                                      m->capg_flag.as<int>());
                                   return FBR_OK;
                               });
 }
 
-// A hull set with triangle meshes attached: the pairs without a mesh through fbr_hull_grad_kernel, into their columns; the pairs with one
-// through the three stages of csrc/fbr_mesh_grad.h.
+// The two staged gradient calls: the pairs of `small` through fbr_hull_grad_kernel, into their columns; the pl pairs of the staged view (sg
+// its stencil table) through three stages (csrc/fbr_mesh_grad.h) -- launch_A(grid, C, T, q, rpy, bpos, sample, scale, pose, se, omc, rel) records the
+// relative pose of every stencil point, launch_B(C, tiles, rel, dv) measures them, launch_C(grid, C, T, sample, pose, dv, dist, grad) forms
+// the quotients.  The stages' kernels are each call's own: as one kernel for both they missed the register and timing rule.
+template <class LaunchA, class LaunchB, class LaunchC>
+static int staged_distance_gradients(fbr_model *m, const char *name, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                     const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                     int32_t out_mem, const DevHulls &small, long pl, const FbrStencil &sg, LaunchA launch_A, LaunchB launch_B,
+                                     LaunchC launch_C)
+{
+    double se, omc;
+    fbr_boxgrad_trig(epsilon, &se, &omc);
+    const FbrHullSet &H = m->hs;
+    return distance_gradients(
+        m, name, st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem, H.set.npairs, H.set.fr.nslots,
+        [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
+            double *ddist, double *dgrad) -> int {
+            const long tiles = (C + 63) / 64, ps = small.npairs, ni = sg.dev.nitems;
+            if (ps > 0)
+                hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)std::min<long>(ps * tiles, grid)), dim3(64), 0, m->stream, m->dm, small, H.grad, C, T,
+                                   dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
+                                   m->capg_flag.as<int>());
+            if (pl == 0) return FBR_OK;
+            if ((long)sg.sbeg.size() != pl + 1) {
+                set_err(std::string(name) + ": the stencil tables do not match the set");
+                return FBR_E_INVALID;
+            }
+            // the recorded poses [ni][13][C] | the stencil distances [ni][C]
+            if (int rc = m->hs.work.ensure((size_t)ni * (FBR_MESHGRAD_REL + 1) * (size_t)C * sizeof(double))) return rc;
+            double *rel = m->hs.work.as<double>(), *dv = rel + (size_t)ni * FBR_MESHGRAD_REL * (size_t)C;
+            launch_A((unsigned)std::min<long>(pl * tiles, grid), C, T, dq, drpy, dbp, dsmp, dscale, dpose, se, omc, rel);
+            {
+                ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
+                launch_B(C, tiles, (const double *)rel, dv);
+            }
+            launch_C((unsigned)((C * pl + 255) / 256), C, T, dsmp, dpose, (const double *)dv, ddist, dgrad);
+            return FBR_OK;
+        });
+}
+
+// A hull set with triangle meshes attached (fbr_model_set_hull_meshes): the SMALL pairs directly, the MESH pairs staged.
 extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                            const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
                                            int32_t out_mem)
@@ -907,49 +838,40 @@ extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, c
         set_err("epsilon must be finite and positive");
         return FBR_E_INVALID;
     }
-    if (m->hulls.nhulls == 0 || m->hulls.npairs == 0) {
+    if (m->hs.set.nhulls == 0 || m->hs.set.npairs == 0) {
         set_err("no hull set with at least one pair (fbr_model_set_hulls)");
         return FBR_E_INVALID;
     }
     if (refuse_large_meshes(m, "fbr_mesh_distance_gradients")) return FBR_E_UNSUPPORTED;
     if (refuse_large_hulls(m, "fbr_mesh_distance_gradients")) return FBR_E_INVALID;
-    if (!m->has_meshes) {
+    if (m->hs.meshes == FBR_MESHES_NONE) {
         set_err("fbr_mesh_distance_gradients: the hull set has no triangle meshes attached (fbr_model_set_hull_meshes); fbr_hull_distance_gradients "
                 "serves a set of hulls only");
         return FBR_E_INVALID;
     }
-    double se, omc;
-    fbr_boxgrad_trig(epsilon, &se, &omc);
-    return distance_gradients(
-        m, "fbr_mesh_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem, m->hulls.npairs, m->hulls.fr.nslots,
-        [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
-            double *ddist, double *dgrad) -> int {
-            const long tiles = (C + 63) / 64, ph = m->hulls_plain.npairs, pm = m->meshes.npairs, ni = m->meshg.nitems;
-            if (ph > 0)
-                hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)std::min<long>(ph * tiles, grid)), dim3(64), 0, m->stream, m->dm, m->hulls_plain,
-                                   m->hullg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
-                                   m->capg_flag.as<int>());
-            if (pm == 0) return FBR_OK;
-            // the recorded poses [ni][13][C] | the stencil distances [ni][C]
-            if (int rc = m->meshg_work.ensure((size_t)ni * (FBR_MESHGRAD_REL + 1) * (size_t)C * sizeof(double))) return rc;
-            double *rel = m->meshg_work.as<double>(), *dv = rel + (size_t)ni * FBR_MESHGRAD_REL * (size_t)C;
-            hipLaunchKernelGGL(fbr_mesh_grad_frames_kernel, dim3((unsigned)std::min<long>(pm * tiles, grid)), dim3(64), 0, m->stream, m->dm, m->hulls,
-                               m->hullg, m->meshes, m->meshg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(),
-                               m->capg_flag.as<int>());
-            {
-                ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
-                hipLaunchKernelGGL(fbr_mesh_grad_dist_kernel, dim3((unsigned)std::min<long>(ni * tiles, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
-                                   m->hulls, m->meshes, m->meshg, C, (const double *)rel, dv);
-            }
-            hipLaunchKernelGGL(fbr_mesh_grad_quot_kernel, dim3((unsigned)((C * pm + 255) / 256)), dim3(256), 0, m->stream, m->hulls, m->meshes, m->meshg,
-                               (int)m->hm.n, C, T, dsmp, dpose, epsilon, (const double *)dv, ddist, dgrad);
-            return FBR_OK;
+    const FbrHullSet &H = m->hs;
+    const DevMeshes ms = H.mesh_pairs();
+    const DevMeshGrad mg = H.views.mesh.dev;
+    return staged_distance_gradients(
+        m, "fbr_mesh_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, epsilon, dist_out, grad_q_out, out_mem, H.of(FBR_PAIR_SMALL),
+        ms.npairs, H.views.mesh,
+        [&](unsigned grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
+            double se, double omc, double *rel) {
+            hipLaunchKernelGGL(fbr_mesh_grad_frames_kernel, dim3(grid), dim3(64), 0, m->stream, m->dm, H.set, H.grad, ms, mg, C, T, dq, drpy, dbp, dsmp, dscale,
+                               dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+        },
+        [&](long C, long tiles, const double *rel, double *dv) {
+            hipLaunchKernelGGL(fbr_mesh_grad_dist_kernel, dim3((unsigned)std::min<long>(mg.nitems * tiles, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
+                               H.set, ms, mg, C, rel, dv);
+        },
+        [&](unsigned grid, long C, long T, const long *dsmp, const long *dpose, const double *dv, double *ddist, double *dgrad) {
+            hipLaunchKernelGGL(fbr_mesh_grad_quot_kernel, dim3(grid), dim3(256), 0, m->stream, H.set, ms, mg, (int)m->hm.n, C, T, dsmp, dpose, epsilon, dv,
+                               ddist, dgrad);
         });
 }
 
-// A hull set installed by fbr_model_set_large_hulls: the pairs of two hulls of at most FBR_MAX_HULL_VERTICES vertices through
-// fbr_hull_grad_kernel, into their columns; the large pairs -- every pair with option hull_large_all -- through the three stages of
-// csrc/fbr_hull_large_grad.h.
+// A hull set installed by fbr_model_set_large_hulls: the SMALL pairs directly, the BIG pairs -- every pair with option hull_large_all --
+// staged (csrc/fbr_hull_large_grad.h).
 extern "C" int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                                  const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out,
                                                  double *grad_q_out, int32_t out_mem)
@@ -959,17 +881,17 @@ extern "C" int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states 
         set_err("fbr_large_hull_distance_gradients: epsilon must be finite and positive");
         return FBR_E_INVALID;
     }
-    if (m->hulls.nhulls == 0 || !m->hull_large_set) {
+    if (m->hs.set.nhulls == 0 || !m->hs.large_set) {
         set_err("fbr_large_hull_distance_gradients: no hull set installed by fbr_model_set_large_hulls (fbr_hull_distance_gradients serves a set of "
                 "fbr_model_set_hulls)");
         return FBR_E_INVALID;
     }
-    if (m->hulls.npairs == 0) {
+    if (m->hs.set.npairs == 0) {
         set_err("fbr_large_hull_distance_gradients: the hull set has no pair");
         return FBR_E_INVALID;
     }
     if (refuse_large_meshes(m, "fbr_large_hull_distance_gradients")) return FBR_E_UNSUPPORTED;
-    if (m->has_meshes) {  // (fbr_model_set_hull_meshes: only a set without a hull above the cap can have them)
+    if (m->hs.meshes != FBR_MESHES_NONE) {  // (fbr_model_set_hull_meshes: only a set without a hull above the cap can have them)
         set_err("fbr_large_hull_distance_gradients: the hull set has triangle meshes attached (fbr_model_set_hull_meshes); "
                 "fbr_mesh_distance_gradients serves such a set");
         return FBR_E_UNSUPPORTED;
@@ -979,44 +901,28 @@ extern "C" int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states 
         set_err("fbr_large_hull_distance_gradients: option hull_grad_tile must be 0 or a power of two from 1 to 64");
         return FBR_E_INVALID;
     }
+    const FbrHullSet &H = m->hs;
     const bool all = m->opt.hull_large_all != 0;
-    const int arr = all ? 1 : 0;
-    const DevHulls none = DevHulls{kNoBoxes, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    const DevHulls hsmall = all ? none : (m->hull_big >= 0 ? m->hulls_small : m->hulls), hbig = all ? m->hulls : (m->hull_big >= 0 ? m->hulls_big : none);
-    const DevMeshGrad lg = m->hull_lgrad[arr];
-    const std::vector<int> &sbeg = m->hull_lgrad_sbeg[arr];
-    double se, omc;
-    fbr_boxgrad_trig(epsilon, &se, &omc);
-    return distance_gradients(
-        m, "fbr_large_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem, m->hulls.npairs,
-        m->hulls.fr.nslots,
-        [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
-            double *ddist, double *dgrad) -> int {
-            const long tiles = (C + 63) / 64, ps = hsmall.npairs, pl = hbig.npairs, ni = lg.nitems;
-            if (ps > 0)
-                hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)std::min<long>(ps * tiles, grid)), dim3(64), 0, m->stream, m->dm, hsmall, m->hullg, C,
-                                   T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
-                                   m->capg_flag.as<int>());
-            if (pl == 0) return FBR_OK;
-            if ((long)sbeg.size() != pl + 1) {
-                set_err("fbr_large_hull_distance_gradients: the stencil tables do not match the set");
-                return FBR_E_INVALID;
-            }
-            // the recorded poses [ni][13][C] | the stencil distances [ni][C]
-            if (int rc = m->hull_lgrad_work.ensure((size_t)ni * (FBR_MESHGRAD_REL + 1) * (size_t)C * sizeof(double))) return rc;
-            double *rel = m->hull_lgrad_work.as<double>(), *dv = rel + (size_t)ni * FBR_MESHGRAD_REL * (size_t)C;
-            hipLaunchKernelGGL(fbr_hull_large_grad_frames_kernel, dim3((unsigned)std::min<long>(pl * tiles, grid)), dim3(64), 0, m->stream, m->dm, hbig,
-                               m->hullg, lg, C, T, dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(),
-                               m->capg_flag.as<int>());
-            const int width = wopt != 0 ? (int)wopt : fbr_hull_large_grad_width(sbeg.data(), (int)pl, C, (long)FBR_HULL_LARGE_GRAD_WAVES_PER_CU * m->num_cus);
-            const long tpp = ((long)lg.smax * C + width - 1) / width;
-            {
-                ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
-                hipLaunchKernelGGL(fbr_hull_large_grad_dist_kernel, dim3((unsigned)std::min<long>(pl * tpp, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
-                                   hbig, lg, C, width, tpp, (const double *)rel, dv);
-            }
-            hipLaunchKernelGGL(fbr_hull_large_grad_quot_kernel, dim3((unsigned)((C * pl + 255) / 256)), dim3(256), 0, m->stream, hbig, lg, (int)m->hm.n, C, T,
-                               dsmp, dpose, epsilon, (const double *)dv, ddist, dgrad);
-            return FBR_OK;
+    const DevHulls small = all ? kNoHulls : H.of(FBR_PAIR_SMALL), staged = all ? H.set : H.of(FBR_PAIR_BIG);
+    const FbrStencil &sg = all ? H.views.all : H.views.big;
+    return staged_distance_gradients(
+        m, "fbr_large_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, epsilon, dist_out, grad_q_out, out_mem, small, staged.npairs,
+        sg,
+        [&](unsigned grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
+            double se, double omc, double *rel) {
+            hipLaunchKernelGGL(fbr_hull_large_grad_frames_kernel, dim3(grid), dim3(64), 0, m->stream, m->dm, staged, H.grad, sg.dev, C, T, dq, drpy, dbp, dsmp,
+                               dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+        },
+        [&](long C, long, const double *rel, double *dv) {
+            const long pl = staged.npairs;
+            const int width =
+                wopt != 0 ? (int)wopt : fbr_hull_large_grad_width(sg.sbeg.data(), (int)pl, C, (long)FBR_HULL_LARGE_GRAD_WAVES_PER_CU * m->num_cus);
+            const long tpp = ((long)sg.dev.smax * C + width - 1) / width;
+            hipLaunchKernelGGL(fbr_hull_large_grad_dist_kernel, dim3((unsigned)std::min<long>(pl * tpp, (long)m->num_cus * 32)), dim3(64), 0, m->stream, staged,
+                               sg.dev, C, width, tpp, rel, dv);
+        },
+        [&](unsigned grid, long C, long T, const long *dsmp, const long *dpose, const double *dv, double *ddist, double *dgrad) {
+            hipLaunchKernelGGL(fbr_hull_large_grad_quot_kernel, dim3(grid), dim3(256), 0, m->stream, staged, sg.dev, (int)m->hm.n, C, T, dsmp, dpose, epsilon, dv,
+                               ddist, dgrad);
         });
 }

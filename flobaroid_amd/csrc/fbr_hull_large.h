@@ -55,6 +55,34 @@ __device__ __forceinline__ double fbr_lane_value(double x, int s)
     return __longlong_as_double((long)(((unsigned long)hi << 32) | lo));
 }
 
+// The facet pass of the touching lanes `todo` (wave-uniform) of a wave whose lanes hold the poses q of one pair of hulls, one lane after
+// the other in ascending order: the pose of lane s broadcast exactly, lane l on fbr_hull_facets(q_s, A, B, l, 64), the 64 partial maxima
+// joined in lane order with g > gap.  Returns d, in a touching lane the gap of its pose.
+__device__ __forceinline__ double fbr_hull_large_touching(unsigned long todo, const FbrHullRel &q, const FbrDevHull &HA, const FbrDevHull &HB, int lane,
+                                                          double d)
+{
+#pragma unroll 1
+    while (todo != 0) {
+        const int s = (int)__builtin_ctzl(todo);
+        todo &= todo - 1;
+        FbrHullRel qs;
+        qs.t0 = fbr_lane_value(q.t0, s), qs.t1 = fbr_lane_value(q.t1, s), qs.t2 = fbr_lane_value(q.t2, s);
+        qs.C00 = fbr_lane_value(q.C00, s), qs.C01 = fbr_lane_value(q.C01, s), qs.C02 = fbr_lane_value(q.C02, s);
+        qs.C10 = fbr_lane_value(q.C10, s), qs.C11 = fbr_lane_value(q.C11, s), qs.C12 = fbr_lane_value(q.C12, s);
+        qs.C20 = fbr_lane_value(q.C20, s), qs.C21 = fbr_lane_value(q.C21, s), qs.C22 = fbr_lane_value(q.C22, s);
+        qs.chk = fbr_lane_value(q.chk, s);
+        const double g = fbr_hull_facets(qs, HA, HB, lane, FBR_HULL_LARGE_PARTS);
+        double gap = -1e300;
+#pragma unroll
+        for (int l = 0; l < FBR_HULL_LARGE_PARTS; l++) {
+            const double x = fbr_lane_value(g, l);
+            gap = x > gap ? x : gap;
+        }
+        if (lane == s) d = gap;
+    }
+    return d;
+}
+
 // work items (block, batch of FBR_HULL_LARGE_BATCH pairs), one wave each, one lane per checked sample; pval / pidx [nb][hs.ldp], the
 // pair's column hs.col[pair] (null: its own number), as for fbr_hull_pairs_kernel.  Every loop is bounded by the hull tables, the 64 bits
 // of the ballot and FBR_HULL_MAX_ITER.
@@ -93,26 +121,8 @@ __global__ __launch_bounds__(64) void fbr_hull_large_pairs_kernel(DevHulls hs, D
             int iters;
             double d = fbr_hull_gjk(q, HA, HB, false, &touching, &iters);
             // the touching samples, one after the other (the repeats behind the last checked sample are not counted)
-            unsigned long todo = __builtin_amdgcn_ballot_w64(touching && lane < w.valid);
-#pragma unroll 1
-            while (todo != 0) {
-                const int s = (int)__builtin_ctzl(todo);
-                todo &= todo - 1;
-                FbrHullRel qs;
-                qs.t0 = fbr_lane_value(q.t0, s), qs.t1 = fbr_lane_value(q.t1, s), qs.t2 = fbr_lane_value(q.t2, s);
-                qs.C00 = fbr_lane_value(q.C00, s), qs.C01 = fbr_lane_value(q.C01, s), qs.C02 = fbr_lane_value(q.C02, s);
-                qs.C10 = fbr_lane_value(q.C10, s), qs.C11 = fbr_lane_value(q.C11, s), qs.C12 = fbr_lane_value(q.C12, s);
-                qs.C20 = fbr_lane_value(q.C20, s), qs.C21 = fbr_lane_value(q.C21, s), qs.C22 = fbr_lane_value(q.C22, s);
-                qs.chk = fbr_lane_value(q.chk, s);
-                const double g = fbr_hull_facets(qs, HA, HB, lane, FBR_HULL_LARGE_PARTS);
-                double gap = -1e300;
-#pragma unroll
-                for (int l = 0; l < FBR_HULL_LARGE_PARTS; l++) {
-                    const double x = fbr_lane_value(g, l);
-                    gap = x > gap ? x : gap;
-                }
-                if (lane == s) d = gap;
-            }
+            const unsigned long todo = __builtin_amdgcn_ballot_w64(touching && lane < w.valid);
+            d = fbr_hull_large_touching(todo, q, HA, HB, lane, d);
             sd[j * 65 + lane] = d;
         }
         __syncthreads();

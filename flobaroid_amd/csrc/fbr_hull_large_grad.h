@@ -10,7 +10,7 @@
 // every pair with option hull_large_all = 1; the others go through fbr_hull_grad_kernel into their own columns:
 //   A  fbr_hull_large_grad_frames_kernel: (large pair, tile of 64 candidates), one wave each.  fbr_rigidgrad_item with the recording functor
 //      of fbr_meshgrad_frames_item: slot 0 the centre, then + eps, - eps of every evaluated joint in walk order.  The members keep the pair's
-//      own order (no swap).  The slot tables (fbr_meshgrad_slots: sbeg, spair, sjoint) are built with the set, for both arrangements of
+//      own order (no swap).  The slot tables (fbr_stencil_table: sbeg, spair, sjoint) are built with the set, for both arrangements of
 //      hull_large_all.
 //   B  fbr_hull_large_grad_dist_kernel: work items belong to one large pair; their lanes are the flattened (stencil point, candidate)
 //      entries of that pair, [sbeg[k] C, sbeg[k + 1] C) in the [nitems][C] layout of the stencil distances, `width` live lanes an item
@@ -161,26 +161,8 @@ __global__ __launch_bounds__(64) void fbr_hull_large_grad_dist_kernel(DevHulls h
         int iters;
         double dd = fbr_hull_gjk(q, HA, HB, false, &touching, &iters);
         // the touching entries, one after the other (the repeats behind the last entry are not counted)
-        unsigned long todo = __builtin_amdgcn_ballot_w64(touching && lane < valid);
-#pragma unroll 1
-        while (todo != 0) {
-            const int sl = (int)__builtin_ctzl(todo);
-            todo &= todo - 1;
-            FbrHullRel qs;
-            qs.t0 = fbr_lane_value(q.t0, sl), qs.t1 = fbr_lane_value(q.t1, sl), qs.t2 = fbr_lane_value(q.t2, sl);
-            qs.C00 = fbr_lane_value(q.C00, sl), qs.C01 = fbr_lane_value(q.C01, sl), qs.C02 = fbr_lane_value(q.C02, sl);
-            qs.C10 = fbr_lane_value(q.C10, sl), qs.C11 = fbr_lane_value(q.C11, sl), qs.C12 = fbr_lane_value(q.C12, sl);
-            qs.C20 = fbr_lane_value(q.C20, sl), qs.C21 = fbr_lane_value(q.C21, sl), qs.C22 = fbr_lane_value(q.C22, sl);
-            qs.chk = fbr_lane_value(q.chk, sl);
-            const double g = fbr_hull_facets(qs, HA, HB, lane, FBR_HULL_LARGE_PARTS);
-            double gap = -1e300;
-#pragma unroll
-            for (int l = 0; l < FBR_HULL_LARGE_PARTS; l++) {
-                const double x = fbr_lane_value(g, l);
-                gap = x > gap ? x : gap;
-            }
-            if (lane == sl) dd = gap;
-        }
+        const unsigned long todo = __builtin_amdgcn_ballot_w64(touching && lane < valid);
+        dd = fbr_hull_large_touching(todo, q, HA, HB, lane, dd);
         if (lane < valid) d[f] = dd;
     }
 }

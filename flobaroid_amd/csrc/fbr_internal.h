@@ -29,6 +29,7 @@
 #include "fbr_mesh.h"
 #include "fbr_mesh_bvh.h"
 #include "fbr_mesh_grad.h"
+#include "fbr_collision_tables.h"
 #include "fbr_gram64.h"
 #include "fbr_tsqr_work.h"
 #include "fbr_weights.h"
@@ -103,6 +104,76 @@ template <class T> static inline int upload(std::vector<DevBuf> &pool, const std
     return FBR_OK;
 }
 
+// ---- the hull set of a model: fbr_model_set_hulls / fbr_model_set_large_hulls and the triangle meshes attached to it (fbr_collision_api.hip;
+// DESIGN.md, "Hull set: classes, views, stencils") ---------------------------------------------------------------------------------------
+static const DevBoxes kNoBoxes = {0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+static const DevHulls kNoHulls = {kNoBoxes, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+
+// a stencil table (fbr_stencil_table) on the device, and the host's copy of its sbeg (the tile width of stage B is chosen from it)
+struct FbrStencil {
+    DevMeshGrad dev = {0, 0, nullptr, nullptr, nullptr};
+    std::vector<int> sbeg;
+};
+
+// What fbr_hull_pair_classes and fbr_stencil_table say of a set and its mesh table, in one allocation (build_hull_views): replaced as a
+// whole when the set or its meshes change.
+struct FbrHullViews {
+    struct View {  // the pairs of a class: what a kernel puts in the place of the whole set's npairs / pairs / col
+        int npairs = 0;
+        const int2 *pairs = nullptr;
+        const int *col = nullptr;  // null: the class is the whole set (a set without meshes), a pair's column is its number
+    } view[FBR_PAIR_CLASSES];
+    FbrStencil mesh, big, all;  // of the MESH view (small meshes), of the BIG view (a set with a big hull), of every pair (hull_large_all)
+    DevBuf tab;
+};
+
+enum { FBR_MESHES_NONE = 0, FBR_MESHES_SMALL = 1, FBR_MESHES_TREE = 2 };  // fbr_model_set_hull_meshes, fbr_model_set_large_hull_meshes
+
+struct FbrHullSet {
+    DevHulls set = kNoHulls;    // the whole set; set.fr is the view fbr_box_frames_kernel takes
+    DevPairGrad grad = {0, nullptr, nullptr};  // ancestor masks and per-pair steps / offset slots (fbr_collision_grad_table)
+    struct Host {               // the host's copy of what the checks, the bounding spheres and the views need of the set
+        std::vector<int32_t> link, vbeg, fbeg, pairs;
+        std::vector<double> verts, planes, diam;
+    } host;
+    bool large_set = false;     // fbr_model_set_large_hulls installed the set (option hull_large_all applies)
+    int big = -1, big_nv = 0;   // the first hull above FBR_MAX_HULL_VERTICES vertices (-1: none) and its vertices, for the refusals
+    int meshes = FBR_MESHES_NONE;
+    DevMeshes geo = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // the meshes' geometry: npairs / pairs / col come from the MESH view
+    DevMeshBvh bvh = {nullptr, nullptr, nullptr};
+    FbrHullViews views;
+    DevBuf set_tab, grad_tab, mesh_tab;  // the set's arrays, its gradient table, the meshes' geometry
+    DevBuf work;                // the staged gradient calls: the recorded poses | the stencil distances
+
+    DevHulls of(int cls) const
+    {
+        DevHulls v = set;
+        v.npairs = views.view[cls].npairs, v.pairs = views.view[cls].pairs, v.col = views.view[cls].col;
+        return v;
+    }
+    DevMeshes mesh_pairs() const
+    {
+        const FbrHullViews::View &v = views.view[FBR_PAIR_MESH];
+        return DevMeshes{v.npairs, geo.mtab, geo.sph, geo.tris, geo.aux, v.pairs, v.col};
+    }
+    void clear_meshes()  // (the views are the caller's to rebuild: they still name the mesh pairs)
+    {
+        meshes = FBR_MESHES_NONE;
+        geo = DevMeshes{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        bvh = DevMeshBvh{nullptr, nullptr, nullptr};
+    }
+    void clear()
+    {
+        clear_meshes();
+        set = kNoHulls;
+        grad = DevPairGrad{0, nullptr, nullptr};
+        host = {};
+        large_set = false;
+        big = -1, big_nv = 0;
+        views = FbrHullViews{};
+    }
+};
+
 struct GramHolder {
     FbrGramProgram prog;
     DevGram dev;
@@ -171,48 +242,9 @@ struct fbr_model {
     DevBuf box_tab, box_fr;
     DevPairGrad boxg = {0, nullptr, nullptr};  // fbr_box_distance_gradients: ancestor masks and per-pair steps / centre slots of the set above
     DevBuf boxg_tab;
-    // convex-hull collision set (fbr_model_set_hulls; csrc/fbr_hull.h), independent of the other two: its tables; the frames of the robot
-    // hulls share the box call's workspace (hulls.fr is the view of the set that fbr_box_frames_kernel takes)
-    DevHulls hulls = {{0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, 0};
-    DevBuf hull_tab;
-    // a set with a hull above FBR_MAX_HULL_VERTICES vertices (fbr_model_set_large_hulls; csrc/fbr_hull_large.h): its pairs split into those
-    // of two small hulls (hulls_small: the view fbr_hull_pairs_kernel takes, its columns in col) and the others (hulls_big: the view
-    // fbr_hull_large_pairs_kernel takes); hull_big: the first hull above the cap, -1: none (then the views are not used); hull_large_set:
-    // fbr_model_set_large_hulls installed the set (option hull_large_all applies)
-    DevHulls hulls_small = hulls, hulls_big = hulls;
-    DevBuf hull_split_tab;
-    int hull_big = -1, hull_big_nv = 0;
-    bool hull_large_set = false;
-    // fbr_large_hull_distance_gradients (csrc/fbr_hull_large_grad.h): the stencil points of the large pairs, built with a set of
-    // fbr_model_set_large_hulls for both arrangements of option hull_large_all -- [0] the pairs of hulls_big, [1] every pair of the set --,
-    // the host's copy of their sbeg (the tile width of stage B is chosen from it) and the call's workspace, the recorded poses | the
-    // stencil distances
-    DevMeshGrad hull_lgrad[2] = {{0, 0, nullptr, nullptr, nullptr}, {0, 0, nullptr, nullptr, nullptr}};
-    std::vector<int> hull_lgrad_sbeg[2];
-    DevBuf hull_lgrad_tab, hull_lgrad_work;
-    // triangle meshes attached to hulls of that set (fbr_model_set_hull_meshes; csrc/fbr_mesh.h): the host's copy of what the checks and the
-    // bounding spheres need of the hull set, the mesh tables, and the set's pairs split into those without a mesh (hulls_plain: the view
-    // fbr_hull_pairs_kernel takes, its columns in col) and those with one (meshes).  meshes.npairs == 0: nothing attached.
-    struct HostHullSet {
-        std::vector<int32_t> link, vbeg, fbeg, pairs;
-        std::vector<double> verts, planes, diam;
-    } hull_host;
-    DevHulls hulls_plain = hulls;
-    DevMeshes meshes = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool has_meshes = false;
-    DevBuf mesh_tab;
-    // attachments of fbr_model_set_large_hull_meshes (csrc/fbr_mesh_bvh.h): meshes holds the triangles in tree order, mesh_bvh the trees;
-    // the pairs without a mesh are hulls_plain (two hulls of at most FBR_MAX_HULL_VERTICES vertices) and hulls_plain_big (the others)
-    bool mesh_large = false;
-    DevMeshBvh mesh_bvh = {nullptr, nullptr, nullptr};
-    DevHulls hulls_plain_big = hulls;
-    DevPairGrad hullg = {0, nullptr, nullptr};  // fbr_hull_distance_gradients: ancestor masks and per-pair steps / offset slots of the set above
-    DevBuf hullg_tab;
-    // fbr_mesh_distance_gradients (csrc/fbr_mesh_grad.h): the stencil points of the mesh pairs (built with the attachments) and the call's
-    // workspace, the recorded poses | the stencil distances -- buffers of its own: what fbr_candidate_hull_distances reads never moves
-    DevMeshGrad meshg = {0, 0, nullptr, nullptr, nullptr};
-    DevBuf meshg_tab, meshg_work;
+    // convex-hull collision set (fbr_model_set_hulls, fbr_model_set_large_hulls) and the triangle meshes attached to it, independent of
+    // the other two sets: one state (FbrHullSet above).  The frames of the robot hulls share the box call's workspace.
+    FbrHullSet hs;
     // suspended base (fbr_suspended_base_motion): the program that walks the attachment's path (kept while att_link stays the same) and its
     // steps on the device, the per-sample records, the results of a host-memory call
     FbrKinIdProgram susp_prog;
