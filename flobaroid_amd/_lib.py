@@ -142,6 +142,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_large_mesh_distance_gradients": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(fbr_states), _dp, ctypes.c_void_p, ctypes.c_int32]),
     "fbr_contact_torques": (
         ctypes.c_int,
@@ -680,7 +685,8 @@ class Engine:
         is ``fbr_model_set_hulls``, at most ``FBR_MAX_HULL_VERTICES`` (128) vertices a hull; True is ``fbr_model_set_large_hulls``, up to
         ``FBR_MAX_LARGE_HULL_VERTICES`` (1024): distances only -- no ``meshes`` (ValueError) unless ``large_meshes``, and the gradient
         calls refuse the set while one of its hulls has more than 128 vertices.  ``large_meshes``: attach ``meshes`` through
-        ``set_large_hull_meshes`` (up to ``FBR_MAX_LARGE_MESH_TRIANGLES`` triangles a mesh, on small or large hulls; distances only)."""
+        ``set_large_hull_meshes`` (up to ``FBR_MAX_LARGE_MESH_TRIANGLES`` triangles a mesh, on small or large hulls; the gradients of such a
+        set come from ``large_mesh_distance_gradients``)."""
         if large and meshes and not large_meshes:
             raise ValueError("set_hulls(large=True): triangle meshes on a set of large hulls are not built (meshes= needs large=False)")
         names = list(self.topo.link_names)
@@ -721,7 +727,8 @@ class Engine:
         without ``large=True`` (``fbr_model_set_large_hull_meshes``): KUKA LWR4's visual meshes, ``collisionMode: "full"`` on a robot
         without collision meshes.  The library builds a bounding-sphere tree per mesh and ``candidate_hull_distances`` walks the two
         trees of a pair for the 64 samples of a wave together; the values have the bits of the brute force over all triangle pairs.  No
-        cap on the triangle pairs of a pair.  Distances only: every gradient call refuses the set while such meshes are attached."""
+        cap on the triangle pairs of a pair.  ``large_mesh_distance_gradients`` serves the gradients of such a set; the three other hull
+        gradient calls refuse it while such meshes are attached."""
         self._set_meshes("fbr_model_set_large_hull_meshes", meshes)
 
     def set_hull_meshes(self, meshes) -> None:
@@ -857,6 +864,19 @@ class Engine:
         hulls; every other pair (every pair with option ``hull_large_all`` = 1) the same central differences with the facet pass of a
         touching stencil point shared by a wave.  A set installed without ``large=True`` is refused."""
         return self._distance_gradients("fbr_large_hull_distance_gradients", int(getattr(self, "num_hull_pairs", 0)), (float(epsilon),), st, ncand,
+                                        sample, scale, pose_sample, base_pos, device_out)
+
+    def large_mesh_distance_gradients(self, st: dict, ncand: int, sample, scale=None, pose_sample=None, base_pos=None, epsilon: float = 1e-7,
+                                      device_out: bool | None = None) -> dict:
+        """``mesh_distance_gradients`` for a hull set -- of ``set_hulls`` with or without ``large=True`` -- with meshes attached through
+        ``set_large_hull_meshes`` (``fbr_large_mesh_distance_gradients``): ``{"dist": (C, P_hull), "grad_q": (C, P_hull, n)}`` over ALL pairs of
+        the set, arguments and rules as there.  A pair of two small hulls without a mesh returns the bytes of ``hull_distance_gradients``,
+        a pair with a hull above ``FBR_MAX_HULL_VERTICES`` vertices and no mesh those of ``large_hull_distance_gradients``, each from the set
+        without meshes; a pair with a mesh the mesh distance through the trees and its central differences over ``epsilon``, with the
+        bytes ``mesh_distance_gradients`` gives where the meshes fit both attachments.  Option ``mesh_grad_order`` (1: candidate-major, 2:
+        slot-major, 0: the default) orders the entries of a wave of the tree stage and never changes a value; option ``hull_large_all`` has
+        no effect.  A set without such an attachment is refused by the name of the call that serves it."""
+        return self._distance_gradients("fbr_large_mesh_distance_gradients", int(getattr(self, "num_hull_pairs", 0)), (float(epsilon),), st, ncand,
                                         sample, scale, pose_sample, base_pos, device_out)
 
     def _distance_gradients(self, entry: str, P: int, extra: tuple, st: dict, ncand: int, sample, scale, pose_sample, base_pos, device_out) -> dict:

@@ -1,10 +1,12 @@
 // fbr_collision_api.hip -- the collision entry points of the C-ABI (include/fbr.h): the capsule, box and convex-hull sets, the triangle
 // meshes attached to hulls, their candidate distances and their distance gradients.  The kernels are those of fbr_capsule.h, fbr_box.h,
-// fbr_hull.h, fbr_mesh.h and their *_grad.h siblings (section FBR_KERNELS_COLLISION); the tables every set shares are built by
+// fbr_hull.h, fbr_mesh.h, fbr_mesh_bvh.h and their *_grad.h siblings (section FBR_KERNELS_COLLISION); the tables every set shares are built by
 // fbr_collision_tables.h.  DESIGN.md, "collision layout".
 #define FBR_KERNELS_COLLISION
 #include "fbr_internal.h"
 #include "fbr_hull_large_grad.h"
+#include "fbr_mesh_bvh_grad.h"
+#include <functional>
 #include <limits>
 
 // ---- what the three sets share -------------------------------------------------------------------------------------------------------
@@ -205,13 +207,15 @@ static int build_hull_views(const fbr_model *m, const DevHulls &set, const FbrHu
 {
     const int npairs = set.npairs;
     const FbrPairClasses pc = fbr_hull_pair_classes(set.nhulls, hh.vbeg.data(), mtab, npairs, hh.pairs.data());
-    // the stencil tables and the columns they cover: the MESH view (small meshes: the others have distances only), the BIG view and every
-    // pair (fbr_large_hull_distance_gradients: a set of fbr_model_set_large_hulls without meshes)
+    // the stencil tables and the columns they cover: the MESH view (fbr_mesh_distance_gradients: small meshes, fbr_large_mesh_distance_gradients:
+    // a tree attachment), the BIG view (a set of fbr_model_set_large_hulls without meshes or with a tree attachment) and every pair
+    // (fbr_large_hull_distance_gradients with option hull_large_all: a set of fbr_model_set_large_hulls without meshes)
     std::vector<int> every((size_t)npairs);
     std::iota(every.begin(), every.end(), 0);
     const bool lgrad = large_set && meshes == FBR_MESHES_NONE && npairs > 0;
-    const std::vector<int> *cols[3] = {meshes == FBR_MESHES_SMALL ? &pc.col[FBR_PAIR_MESH] : nullptr,
-                                       lgrad && !pc.col[FBR_PAIR_BIG].empty() ? &pc.col[FBR_PAIR_BIG] : nullptr, lgrad ? &every : nullptr};
+    const bool bgrad = large_set && meshes != FBR_MESHES_SMALL && npairs > 0;
+    const std::vector<int> *cols[3] = {meshes != FBR_MESHES_NONE ? &pc.col[FBR_PAIR_MESH] : nullptr,
+                                       bgrad && !pc.col[FBR_PAIR_BIG].empty() ? &pc.col[FBR_PAIR_BIG] : nullptr, lgrad ? &every : nullptr};
     FbrStencilTable st[3];
     if (cols[0] || cols[1] || cols[2]) {
         FbrKinIdProgram prog;
@@ -440,7 +444,8 @@ extern "C" int fbr_model_set_large_hull_meshes(fbr_model *m, int32_t nmesh, cons
     return attach_meshes(m, true, nmesh, hull, tbeg, tris);
 }
 
-// attachments of fbr_model_set_large_hull_meshes are in place: distances only, `who` has no gradients of them
+// attachments of fbr_model_set_large_hull_meshes are in place: `who` has no gradients of them (fbr_large_mesh_distance_gradients has; the
+// message is the one from before that call existed: callers match it)
 static bool refuse_large_meshes(const fbr_model *m, const char *who)
 {
     if (m->hs.meshes != FBR_MESHES_TREE) return false;
@@ -788,15 +793,24 @@ extern "C" int fbr_hull_distance_gradients(fbr_model *m, const fbr_states *st, c
                               });
 }
 
-// The two staged gradient calls: the pairs of `small` through fbr_hull_grad_kernel, into their columns; the pl pairs of the staged view (sg
-// its stencil table) through three stages (csrc/fbr_mesh_grad.h) -- launch_A(grid, C, T, q, rpy, bpos, sample, scale, pose, se, omc, rel) records the
-// relative pose of every stencil point, launch_B(C, tiles, rel, dv) measures them, launch_C(grid, C, T, sample, pose, dv, dist, grad) forms
-// the quotients.  The stages' kernels are each call's own: as one kernel for both they missed the register and timing rule.
-template <class LaunchA, class LaunchB, class LaunchC>
+// The staged gradient calls: the pairs of `small` through fbr_hull_grad_kernel, into their columns; every class of `staged` -- pl pairs of a
+// view, sg its stencil table -- through three stages (csrc/fbr_mesh_grad.h): A(grid, C, T, q, rpy, bpos, sample, scale, pose, se, omc, rel)
+// records the relative pose of every stencil point, B(C, tiles, rel, dv) measures them, Q(grid, C, T, sample, pose, dv, dist, grad) forms
+// the quotients.  The stages' kernels are each class's own: as one kernel for two they missed the register and timing rule.
+// The classes write disjoint columns, so their order does not matter to a value.
+struct StagedClass {
+    long pl;
+    const FbrStencil *sg;
+    std::function<void(unsigned, long, long, const double *, const double *, const double *, const long *, const double *, const long *, double, double,
+                       double *)>
+        A;
+    std::function<void(long, long, const double *, double *)> B;
+    std::function<void(unsigned, long, long, const long *, const long *, const double *, double *, double *)> Q;
+};
+
 static int staged_distance_gradients(fbr_model *m, const char *name, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                      const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
-                                     int32_t out_mem, const DevHulls &small, long pl, const FbrStencil &sg, LaunchA launch_A, LaunchB launch_B,
-                                     LaunchC launch_C)
+                                     int32_t out_mem, const DevHulls &small, const std::vector<StagedClass> &staged)
 {
     double se, omc;
     fbr_boxgrad_trig(epsilon, &se, &omc);
@@ -805,27 +819,84 @@ static int staged_distance_gradients(fbr_model *m, const char *name, const fbr_s
         m, name, st, base_pos, ncand, sample, scale, pose_sample, dist_out, grad_q_out, out_mem, H.set.npairs, H.set.fr.nslots,
         [&](int grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
             double *ddist, double *dgrad) -> int {
-            const long tiles = (C + 63) / 64, ps = small.npairs, ni = sg.dev.nitems;
+            const long tiles = (C + 63) / 64, ps = small.npairs;
             if (ps > 0)
                 hipLaunchKernelGGL(fbr_hull_grad_kernel, dim3((unsigned)std::min<long>(ps * tiles, grid)), dim3(64), 0, m->stream, m->dm, small, H.grad, C, T,
                                    dq, drpy, dbp, dsmp, dscale, dpose, epsilon, se, omc, ddist, dgrad, m->cap_scratch.as<double>(),
                                    m->capg_flag.as<int>());
-            if (pl == 0) return FBR_OK;
-            if ((long)sg.sbeg.size() != pl + 1) {
-                set_err(std::string(name) + ": the stencil tables do not match the set");
-                return FBR_E_INVALID;
+            // per class the recorded poses [ni][13][C] | the stencil distances [ni][C], one class after the other
+            size_t total = 0;
+            for (const StagedClass &sc : staged) {
+                if (sc.pl == 0) continue;
+                if ((long)sc.sg->sbeg.size() != sc.pl + 1) {
+                    set_err(std::string(name) + ": the stencil tables do not match the set");
+                    return FBR_E_INVALID;
+                }
+                total += (size_t)sc.sg->dev.nitems * (FBR_MESHGRAD_REL + 1) * (size_t)C;
             }
-            // the recorded poses [ni][13][C] | the stencil distances [ni][C]
-            if (int rc = m->hs.work.ensure((size_t)ni * (FBR_MESHGRAD_REL + 1) * (size_t)C * sizeof(double))) return rc;
-            double *rel = m->hs.work.as<double>(), *dv = rel + (size_t)ni * FBR_MESHGRAD_REL * (size_t)C;
-            launch_A((unsigned)std::min<long>(pl * tiles, grid), C, T, dq, drpy, dbp, dsmp, dscale, dpose, se, omc, rel);
-            {
-                ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
-                launch_B(C, tiles, (const double *)rel, dv);
+            if (total == 0) return FBR_OK;
+            if (int rc = m->hs.work.ensure(total * sizeof(double))) return rc;
+            double *rel = m->hs.work.as<double>();
+            for (const StagedClass &sc : staged) {
+                if (sc.pl == 0) continue;
+                const size_t ni = (size_t)sc.sg->dev.nitems;
+                double *dv = rel + ni * FBR_MESHGRAD_REL * (size_t)C;
+                sc.A((unsigned)std::min<long>(sc.pl * tiles, grid), C, T, dq, drpy, dbp, dsmp, dscale, dpose, se, omc, rel);
+                {
+                    ProfScope pb(m, FBR_PROF_REDUCE);  // (stage B by itself, inside the call's FBR_PROF_KIN)
+                    sc.B(C, tiles, (const double *)rel, dv);
+                }
+                sc.Q((unsigned)((C * sc.pl + 255) / 256), C, T, dsmp, dpose, (const double *)dv, ddist, dgrad);
+                rel = dv + ni * (size_t)C;
             }
-            launch_C((unsigned)((C * pl + 255) / 256), C, T, dsmp, dpose, (const double *)dv, ddist, dgrad);
             return FBR_OK;
         });
+}
+
+// the three launches of the BIG class (csrc/fbr_hull_large_grad.h) on the view `staged` with the stencil table sg; wopt: option hull_grad_tile
+static StagedClass large_hull_class(fbr_model *m, const DevHulls &staged, const FbrStencil &sg, double epsilon, double wopt)
+{
+    const FbrHullSet &H = m->hs;
+    const FbrStencil *psg = &sg;
+    return StagedClass{
+        staged.npairs, psg,
+        [=, &H](unsigned grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
+                const long *dpose, double se, double omc, double *rel) {
+            hipLaunchKernelGGL(fbr_hull_large_grad_frames_kernel, dim3(grid), dim3(64), 0, m->stream, m->dm, staged, H.grad, psg->dev, C, T, dq, drpy, dbp, dsmp,
+                               dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+        },
+        [=](long C, long, const double *rel, double *dv) {
+            const long pl = staged.npairs;
+            const int width =
+                wopt != 0 ? (int)wopt : fbr_hull_large_grad_width(psg->sbeg.data(), (int)pl, C, (long)FBR_HULL_LARGE_GRAD_WAVES_PER_CU * m->num_cus);
+            const long tpp = ((long)psg->dev.smax * C + width - 1) / width;
+            hipLaunchKernelGGL(fbr_hull_large_grad_dist_kernel, dim3((unsigned)std::min<long>(pl * tpp, (long)m->num_cus * 32)), dim3(64), 0, m->stream, staged,
+                               psg->dev, C, width, tpp, rel, dv);
+        },
+        [=](unsigned grid, long C, long T, const long *dsmp, const long *dpose, const double *dv, double *ddist, double *dgrad) {
+            hipLaunchKernelGGL(fbr_hull_large_grad_quot_kernel, dim3(grid), dim3(256), 0, m->stream, staged, psg->dev, (int)m->hm.n, C, T, dsmp, dpose, epsilon,
+                               dv, ddist, dgrad);
+        }};
+}
+
+// the three launches of the MESH class: stages A and C of csrc/fbr_mesh_grad.h; stage B launch_B(ms, mg, C, tiles, rel, dv) the attachment's own
+template <class LaunchB> static StagedClass mesh_class(fbr_model *m, double epsilon, LaunchB launch_B)
+{
+    const FbrHullSet &H = m->hs;
+    const DevMeshes ms = H.mesh_pairs();
+    const DevMeshGrad mg = H.views.mesh.dev;
+    return StagedClass{
+        ms.npairs, &H.views.mesh,
+        [=, &H](unsigned grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale,
+                const long *dpose, double se, double omc, double *rel) {
+            hipLaunchKernelGGL(fbr_mesh_grad_frames_kernel, dim3(grid), dim3(64), 0, m->stream, m->dm, H.set, H.grad, ms, mg, C, T, dq, drpy, dbp, dsmp, dscale,
+                               dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
+        },
+        [=](long C, long tiles, const double *rel, double *dv) { launch_B(ms, mg, C, tiles, rel, dv); },
+        [=, &H](unsigned grid, long C, long T, const long *dsmp, const long *dpose, const double *dv, double *ddist, double *dgrad) {
+            hipLaunchKernelGGL(fbr_mesh_grad_quot_kernel, dim3(grid), dim3(256), 0, m->stream, H.set, ms, mg, (int)m->hm.n, C, T, dsmp, dpose, epsilon, dv,
+                               ddist, dgrad);
+        }};
 }
 
 // A hull set with triangle meshes attached (fbr_model_set_hull_meshes): the SMALL pairs directly, the MESH pairs staged.
@@ -850,24 +921,12 @@ extern "C" int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, c
         return FBR_E_INVALID;
     }
     const FbrHullSet &H = m->hs;
-    const DevMeshes ms = H.mesh_pairs();
-    const DevMeshGrad mg = H.views.mesh.dev;
     return staged_distance_gradients(
         m, "fbr_mesh_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, epsilon, dist_out, grad_q_out, out_mem, H.of(FBR_PAIR_SMALL),
-        ms.npairs, H.views.mesh,
-        [&](unsigned grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
-            double se, double omc, double *rel) {
-            hipLaunchKernelGGL(fbr_mesh_grad_frames_kernel, dim3(grid), dim3(64), 0, m->stream, m->dm, H.set, H.grad, ms, mg, C, T, dq, drpy, dbp, dsmp, dscale,
-                               dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
-        },
-        [&](long C, long tiles, const double *rel, double *dv) {
+        {mesh_class(m, epsilon, [m, &H](const DevMeshes &ms, const DevMeshGrad &mg, long C, long tiles, const double *rel, double *dv) {
             hipLaunchKernelGGL(fbr_mesh_grad_dist_kernel, dim3((unsigned)std::min<long>(mg.nitems * tiles, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
                                H.set, ms, mg, C, rel, dv);
-        },
-        [&](unsigned grid, long C, long T, const long *dsmp, const long *dpose, const double *dv, double *ddist, double *dgrad) {
-            hipLaunchKernelGGL(fbr_mesh_grad_quot_kernel, dim3(grid), dim3(256), 0, m->stream, H.set, ms, mg, (int)m->hm.n, C, T, dsmp, dpose, epsilon, dv,
-                               ddist, dgrad);
-        });
+        })});
 }
 
 // A hull set installed by fbr_model_set_large_hulls: the SMALL pairs directly, the BIG pairs -- every pair with option hull_large_all --
@@ -905,24 +964,50 @@ extern "C" int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states 
     const bool all = m->opt.hull_large_all != 0;
     const DevHulls small = all ? kNoHulls : H.of(FBR_PAIR_SMALL), staged = all ? H.set : H.of(FBR_PAIR_BIG);
     const FbrStencil &sg = all ? H.views.all : H.views.big;
+    return staged_distance_gradients(m, "fbr_large_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, epsilon, dist_out, grad_q_out,
+                                     out_mem, small, {large_hull_class(m, staged, sg, epsilon, wopt)});
+}
+
+// A hull set of either setter with a tree attachment (fbr_model_set_large_hull_meshes): the SMALL pairs directly, the BIG pairs through the
+// stages of csrc/fbr_hull_large_grad.h, the MESH pairs through stages A and C of csrc/fbr_mesh_grad.h around the tree stage of
+// csrc/fbr_mesh_bvh_grad.h.  Option hull_large_all has no effect here.
+extern "C" int fbr_large_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                                 const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out,
+                                                 double *grad_q_out, int32_t out_mem)
+{
+    if (!distance_gradient_args(m, st, sample, dist_out, grad_q_out, out_mem)) return FBR_E_INVALID;
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0)) {
+        set_err("fbr_large_mesh_distance_gradients: epsilon must be finite and positive");
+        return FBR_E_INVALID;
+    }
+    if (m->hs.set.nhulls == 0 || m->hs.set.npairs == 0) {
+        set_err("fbr_large_mesh_distance_gradients: no hull set with at least one pair (fbr_model_set_hulls, fbr_model_set_large_hulls)");
+        return FBR_E_INVALID;
+    }
+    if (m->hs.meshes != FBR_MESHES_TREE) {
+        set_err("fbr_large_mesh_distance_gradients: the hull set has no triangle meshes attached by fbr_model_set_large_hull_meshes; "
+                "fbr_mesh_distance_gradients serves small meshes (fbr_model_set_hull_meshes), fbr_large_hull_distance_gradients large hulls without "
+                "meshes (fbr_model_set_large_hulls), fbr_hull_distance_gradients small hulls without meshes (fbr_model_set_hulls)");
+        return FBR_E_INVALID;
+    }
+    const double oopt = m->opt.mesh_grad_order;
+    if (!(oopt == 0 || oopt == FBR_MESH_GRAD_CANDIDATE_MAJOR || oopt == FBR_MESH_GRAD_SLOT_MAJOR)) {
+        set_err("fbr_large_mesh_distance_gradients: option mesh_grad_order must be 0 (the default order), 1 (candidate-major) or 2 (slot-major)");
+        return FBR_E_INVALID;
+    }
+    const double wopt = m->opt.hull_grad_tile;  // (of the BIG class: not looked at by a set without such a pair)
+    if (m->hs.of(FBR_PAIR_BIG).npairs > 0 && !(wopt == 0 || wopt == 1 || wopt == 2 || wopt == 4 || wopt == 8 || wopt == 16 || wopt == 32 || wopt == 64)) {
+        set_err("fbr_large_mesh_distance_gradients: option hull_grad_tile must be 0 or a power of two from 1 to 64");
+        return FBR_E_INVALID;
+    }
+    const int order = oopt == 0 ? FBR_MESH_GRAD_ORDER_DEFAULT : (int)oopt;
+    const FbrHullSet &H = m->hs;
     return staged_distance_gradients(
-        m, "fbr_large_hull_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, epsilon, dist_out, grad_q_out, out_mem, small, staged.npairs,
-        sg,
-        [&](unsigned grid, long C, long T, const double *dq, const double *drpy, const double *dbp, const long *dsmp, const double *dscale, const long *dpose,
-            double se, double omc, double *rel) {
-            hipLaunchKernelGGL(fbr_hull_large_grad_frames_kernel, dim3(grid), dim3(64), 0, m->stream, m->dm, staged, H.grad, sg.dev, C, T, dq, drpy, dbp, dsmp,
-                               dscale, dpose, epsilon, se, omc, rel, m->cap_scratch.as<double>(), m->capg_flag.as<int>());
-        },
-        [&](long C, long, const double *rel, double *dv) {
-            const long pl = staged.npairs;
-            const int width =
-                wopt != 0 ? (int)wopt : fbr_hull_large_grad_width(sg.sbeg.data(), (int)pl, C, (long)FBR_HULL_LARGE_GRAD_WAVES_PER_CU * m->num_cus);
-            const long tpp = ((long)sg.dev.smax * C + width - 1) / width;
-            hipLaunchKernelGGL(fbr_hull_large_grad_dist_kernel, dim3((unsigned)std::min<long>(pl * tpp, (long)m->num_cus * 32)), dim3(64), 0, m->stream, staged,
-                               sg.dev, C, width, tpp, rel, dv);
-        },
-        [&](unsigned grid, long C, long T, const long *dsmp, const long *dpose, const double *dv, double *ddist, double *dgrad) {
-            hipLaunchKernelGGL(fbr_hull_large_grad_quot_kernel, dim3(grid), dim3(256), 0, m->stream, staged, sg.dev, (int)m->hm.n, C, T, dsmp, dpose, epsilon, dv,
-                               ddist, dgrad);
-        });
+        m, "fbr_large_mesh_distance_gradients", st, base_pos, ncand, sample, scale, pose_sample, epsilon, dist_out, grad_q_out, out_mem, H.of(FBR_PAIR_SMALL),
+        {large_hull_class(m, H.of(FBR_PAIR_BIG), H.views.big, epsilon, wopt),
+         mesh_class(m, epsilon, [m, &H, order](const DevMeshes &ms, const DevMeshGrad &mg, long C, long, const double *rel, double *dv) {
+             const long tpp = ((long)mg.smax * C + 63) / 64;
+             hipLaunchKernelGGL(fbr_mesh_bvh_grad_dist_kernel, dim3((unsigned)std::min<long>(ms.npairs * tpp, (long)m->num_cus * 32)), dim3(64), 0, m->stream,
+                                H.set, ms, H.bvh, mg, C, order, tpp, rel, dv);
+         })});
 }

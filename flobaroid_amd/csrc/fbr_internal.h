@@ -123,7 +123,7 @@ struct FbrHullViews {
         const int2 *pairs = nullptr;
         const int *col = nullptr;  // null: the class is the whole set (a set without meshes), a pair's column is its number
     } view[FBR_PAIR_CLASSES];
-    FbrStencil mesh, big, all;  // of the MESH view (small meshes), of the BIG view (a set with a big hull), of every pair (hull_large_all)
+    FbrStencil mesh, big, all;  // of the MESH view (either attachment), of the BIG view (a set with a big hull), of every pair (hull_large_all)
     DevBuf tab;
 };
 

@@ -19,6 +19,7 @@ struct FbrOptions {
     // ---- collision
     double hull_large_all = 0;              // fbr_candidate_hull_distances on a set of fbr_model_set_large_hulls: 1: every pair through fbr_hull_large_pairs_kernel
     double hull_grad_tile = 0;              // fbr_large_hull_distance_gradients: live lanes of an item of its distance stage, a power of two 1 .. 64 (0: by the entry count, fbr_hull_large_grad_width)
+    double mesh_grad_order = 0;             // fbr_large_mesh_distance_gradients: the entries of a wave of its distance stage, 1: candidate-major, 2: slot-major (0: FBR_MESH_GRAD_ORDER_DEFAULT, csrc/fbr_mesh_bvh_grad.h)
     // ---- fused Gram program
     double gram_lane_waves = 8;             // gram_lane, models of the one-workgroup-per-CU shape: 8 waves of 18 accumulators (16: 16 waves of 10; measured slower)
     double gram_force_tiles = 1;            // gram_lane: the force rows of the base wrench run on tiles of the columns that have a force (fbr_gram64.h)
@@ -67,6 +68,7 @@ static inline const FbrOptionKey *fbr_option_keys(int *count)
         {"fused_id", &FbrOptions::fused_id, false},
         {"hull_large_all", &FbrOptions::hull_large_all, false},  // (read at every call: both pair lists are built with the set)
         {"hull_grad_tile", &FbrOptions::hull_grad_tile, false},  // (read, and checked, by every call)
+        {"mesh_grad_order", &FbrOptions::mesh_grad_order, false},  // (read, and checked, by every call)
         {"gram_lane", &FbrOptions::gram_lane, false},
         {"gram_force_tiles", &FbrOptions::gram_force_tiles, true},   // (these three shape the program of the sample-contiguous pass, get_gram64)
         {"gram_lane_waves", &FbrOptions::gram_lane_waves, true},

@@ -410,9 +410,10 @@ def _has_meshes(collision) -> bool:
 
 
 def _refuse_large_mesh_gradient(collision) -> None:
-    """a set built with ``collision_set(..., large_meshes=True)`` is served for distances only (``Engine.set_large_hull_meshes``): every
-    gradient entry point refuses it, whatever its ``*_gradient`` keywords say, by the names and triangle counts of its meshes above
-    ``FBR_MAX_MESH_TRIANGLES`` triangles or on hulls above ``FBR_MAX_HULL_VERTICES`` vertices"""
+    """without ``large_mesh_gradient=True`` a set built with ``collision_set(..., large_meshes=True)`` is refused by every gradient entry
+    point, whatever its other ``*_gradient`` keywords say, by the names and triangle counts of its meshes above ``FBR_MAX_MESH_TRIANGLES``
+    triangles or on hulls above ``FBR_MAX_HULL_VERTICES`` vertices (the message is the one from before that gradient was built: callers
+    match it)"""
     from .collision import FBR_MAX_HULL_VERTICES, FBR_MAX_MESH_TRIANGLES
 
     if not (_has_meshes(collision) and collision.get("large_meshes")):
@@ -426,6 +427,33 @@ def _refuse_large_mesh_gradient(collision) -> None:
     raise ValueError("gradients on the device do not cover triangle meshes of more than 256 triangles or on hulls of more than 128 vertices: "
                      "the collision set was built with large_meshes=True and has " + (", ".join(why) if why else "no such mesh")
                      + "; the constraint values are served (Engine.set_large_hull_meshes), their gradients are not built")
+
+
+def _wants_large_mesh_gradient(config, collision, large_mesh_gradient) -> bool:
+    """True when ``large_mesh_gradient=True`` selects the rows of ``Engine.large_mesh_distance_gradients``: a set built with
+    ``large_meshes``, hull pairs only, and a configuration that uses the meshes (``collisionMode: "full"``, or ``fullMeshLinks`` in
+    ``"convex"``).  False without the keyword: every refusal of before then holds.  The keyword with anything else raises and says which
+    condition fails."""
+    if not large_mesh_gradient:
+        return False
+    mode = config.get("collisionMode", "capsule")
+    if mode in ("capsule", "box"):
+        raise ValueError(f"large_mesh_gradient=True: collisionMode '{mode}' has no triangle meshes (they belong to collisionMode 'full' and to "
+                         "fullMeshLinks in collisionMode 'convex')")
+    if not (_has_meshes(collision) and collision.get("large_meshes")):
+        serves = ("mesh_gradient=True serves a set with triangle meshes attached without it" if _has_meshes(collision) else
+                  "large_hull_gradient=True serves a set of hulls above 128 vertices without meshes" if _large_hulls(collision) else
+                  "hull_gradient=True serves a set of hulls only")
+        raise ValueError("large_mesh_gradient=True: the collision set was not built with large_meshes=True "
+                         "(flobaroid_amd.collision.collision_set(..., hulls=, meshes=, large_meshes=True)); " + serves)
+    if mode != "full" and not config.get("fullMeshLinks"):
+        raise ValueError(f"large_mesh_gradient=True: collisionMode '{mode}' without fullMeshLinks does not use the meshes of the collision set")
+    if "hulls" not in collision or not _has_hull_pairs(collision) or "columns" not in collision:
+        raise ValueError("large_mesh_gradient=True: the collision set needs hull pairs "
+                         "(flobaroid_amd.collision.collision_set(..., hulls=, meshes=, large_meshes=True))")
+    if (np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)[:, 0] != 2).any():
+        raise ValueError("large_mesh_gradient=True: the collision set has capsule or box pairs")
+    return True
 
 
 def _refuse_mesh_gradient(collision) -> None:
@@ -816,7 +844,8 @@ def _chain_positions(engine, candidates, freq, sample, scale, grad_q, max_bytes)
 
 def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: list, freq: float, config: dict, collision: dict,
                                  constraints: dict | None = None, max_bytes: int = 2**31, box_gradient: bool = False, epsilon=None,
-                                 hull_gradient: bool = False, mesh_gradient: bool = False, large_hull_gradient: bool = False) -> dict:
+                                 hull_gradient: bool = False, mesh_gradient: bool = False, large_hull_gradient: bool = False,
+                                 large_mesh_gradient: bool = False) -> dict:
     """The collision block ``g = distance - margin`` (C, P) of ``ncand`` equal candidates stacked in ``states`` and its derivative with
     respect to the entries of the candidates' ``fourier_coefficients`` dicts, from which ``states`` were generated at ``freq`` Hz
     (``candidate_states``).  ``collision``: capsules, pairs and optionally margins (``flobaroid_amd.collision.collision_set``);
@@ -855,17 +884,27 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     vertex counts of those hulls, whatever the keywords above.  ``True`` serves it: ``collisionMode: "convex"``, a set of hull pairs only
     with at least one such hull and no triangle meshes; the hull set is installed with ``large=True`` and the rows of ALL its pairs come
     from ``Engine.large_hull_distance_gradients`` exactly as ``hull_gradient=True`` takes them from the hull call (``hull_gradient`` may
-    then be either value).  The keyword with anything else raises ``ValueError`` and says which condition fails."""
+    then be either value).  The keyword with anything else raises ``ValueError`` and says which condition fails.
+
+    ``large_mesh_gradient=False``: a set built with ``collision_set(..., large_meshes=True)`` (KUKA LWR4 in ``collisionMode: "full"``) is
+    refused by the names and triangle counts of its meshes, whatever the keywords above.  ``True`` serves it: a set with ``large_meshes``,
+    hull pairs only, ``collisionMode: "full"`` or ``fullMeshLinks`` in ``"convex"``; the hull set is installed with ``large_meshes=True``
+    (and ``large=True`` where a hull exceeds 128 vertices) and the rows of ALL its pairs come from
+    ``Engine.large_mesh_distance_gradients`` (the other three keywords may then be either value): the mesh pairs through the trees, the
+    plain pairs as the hull and the large-hull call return them.  The keyword with anything else raises ``ValueError``, says which
+    condition fails and, where one exists, names the keyword that serves the set."""
     _check_config(config)
-    _refuse_large_mesh_gradient(collision)
-    large_rows = _wants_large_hull_gradient(config, collision, large_hull_gradient)
-    if not large_rows:
+    tree_rows = _wants_large_mesh_gradient(config, collision, large_mesh_gradient)
+    if not tree_rows:
+        _refuse_large_mesh_gradient(collision)
+    large_rows = not tree_rows and _wants_large_hull_gradient(config, collision, large_hull_gradient)
+    if not (large_rows or tree_rows):
         _refuse_large_hull_gradient(collision)
-    mesh_rows = not large_rows and _wants_mesh_gradient(config, collision, mesh_gradient)
-    if not mesh_rows:
+    mesh_rows = not (large_rows or tree_rows) and _wants_mesh_gradient(config, collision, mesh_gradient)
+    if not (mesh_rows or tree_rows):
         _refuse_mesh_gradient(collision)
     mode = config.get("collisionMode", "capsule")
-    if large_rows or mesh_rows or _wants_hull_gradient(config, collision, hull_gradient):
+    if tree_rows or large_rows or mesh_rows or _wants_hull_gradient(config, collision, hull_gradient):
         C, n = int(ncand), engine.n
         bpos = states.get("base_position") if engine.floating else None
         cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision)
@@ -874,8 +913,10 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
         sel = np.argsort(cols[:, 1], kind="stable")  # (the set's own pair order)
         smp, sc, pose = (np.ascontiguousarray(np.asarray(cons[k])[:, sel]) for k in ("eval_sample", "eval_scale", "eval_pose"))
         kw = {"meshes": collision["meshes"]} if mesh_rows else ({"large": True} if large_rows else {})
+        if tree_rows:
+            kw = dict({"large": True} if _large_hulls(collision) else {}, meshes=collision["meshes"], large_meshes=True)
         engine.set_hulls(collision["hulls"], collision["hull_pairs"], offset_in_link_axes=bool(collision.get("offset_in_link_axes", False)), **kw)
-        gradients = (engine.large_hull_distance_gradients if large_rows else
+        gradients = (engine.large_mesh_distance_gradients if tree_rows else engine.large_hull_distance_gradients if large_rows else
                      engine.mesh_distance_gradients if mesh_rows else engine.hull_distance_gradients)
         dg = gradients(states, C, smp, scale=sc, pose_sample=pose, base_pos=bpos, epsilon=eps)
         part, nh = _chain_positions(engine, candidates, freq, smp, sc, dg["grad_q"], max_bytes)
@@ -932,14 +973,15 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
 
 def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
                                                    max_bytes: int = 2**31, box_gradient: bool = False, hull_gradient: bool = False,
-                                                   mesh_gradient: bool = False, large_hull_gradient: bool = False) -> dict:
+                                                   mesh_gradient: bool = False, large_hull_gradient: bool = False,
+                                                   large_mesh_gradient: bool = False) -> dict:
     """``candidate_collision_gradient`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
     (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``, ``hull_gradient``, ``mesh_gradient``,
-    ``large_hull_gradient``: as there."""
+    ``large_hull_gradient``, ``large_mesh_gradient``: as there."""
     st = candidate_states(engine, candidates, int(T), float(freq), device=True)
     return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes,
                                         box_gradient=box_gradient, hull_gradient=hull_gradient, mesh_gradient=mesh_gradient,
-                                        large_hull_gradient=large_hull_gradient)
+                                        large_hull_gradient=large_hull_gradient, large_mesh_gradient=large_mesh_gradient)
 
 
 def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
@@ -1076,7 +1118,7 @@ def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_a
 def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict, joint_names,
                                           config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1,
                                           box_gradient: bool = False, hull_gradient: bool = False, mesh_gradient: bool = False,
-                                          large_hull_gradient: bool = False) -> dict:
+                                          large_hull_gradient: bool = False, large_mesh_gradient: bool = False) -> dict:
     """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
     and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
     one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
@@ -1103,19 +1145,26 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     "full"``) is refused by the names of the meshed links; ``True`` with such a set and configuration: the rows of all its pairs come from
     ``Engine.mesh_distance_gradients`` (``candidate_collision_gradient``).  ``large_hull_gradient=False``: a ``collision`` set with a hull
     above 128 vertices is refused by the names and vertex counts of those hulls; ``True`` with ``collisionMode: "convex"``, hull pairs only
-    and no meshes: the rows of all its pairs come from ``Engine.large_hull_distance_gradients`` (``candidate_collision_gradient``)."""
+    and no meshes: the rows of all its pairs come from ``Engine.large_hull_distance_gradients`` (``candidate_collision_gradient``).
+    ``large_mesh_gradient=False``: a ``collision`` set built with ``large_meshes=True`` is refused by the names and triangle counts of its
+    meshes; ``True`` with such a set of hull pairs only, in ``collisionMode: "full"`` or with ``fullMeshLinks`` in ``"convex"``: the rows
+    of all its pairs come from ``Engine.large_mesh_distance_gradients`` (``candidate_collision_gradient``)."""
     _check_config(config)
-    _refuse_large_mesh_gradient(collision)
-    large_rows = collision is not None and _wants_large_hull_gradient(config, collision, large_hull_gradient)
+    if large_mesh_gradient and collision is None:
+        raise ValueError("large_mesh_gradient=True: no collision set (collision=)")
+    tree_rows = collision is not None and _wants_large_mesh_gradient(config, collision, large_mesh_gradient)
+    if not tree_rows:
+        _refuse_large_mesh_gradient(collision)
+    large_rows = not tree_rows and collision is not None and _wants_large_hull_gradient(config, collision, large_hull_gradient)
     if large_hull_gradient and collision is None:
         raise ValueError("large_hull_gradient=True: no collision set (collision=)")
-    if not large_rows:
+    if not (large_rows or tree_rows):
         _refuse_large_hull_gradient(collision)
-    mesh_rows = not large_rows and collision is not None and _wants_mesh_gradient(config, collision, mesh_gradient)
-    if not mesh_rows:
+    mesh_rows = not (large_rows or tree_rows) and collision is not None and _wants_mesh_gradient(config, collision, mesh_gradient)
+    if not (mesh_rows or tree_rows):
         _refuse_mesh_gradient(collision)
-    hull_rows = not (mesh_rows or large_rows) and collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
-    if _has_hull_pairs(collision) and not (hull_rows or mesh_rows or large_rows):
+    hull_rows = not (mesh_rows or large_rows or tree_rows) and collision is not None and _wants_hull_gradient(config, collision, hull_gradient)
+    if _has_hull_pairs(collision) and not (hull_rows or mesh_rows or large_rows or tree_rows):
         raise ValueError(_NO_HULL_GRADIENT)
     if _has_box_pairs(collision) and not box_gradient:
         raise ValueError("gradients on the device cover capsule pairs only: the collision set has box pairs (the reference differentiates those "
@@ -1147,7 +1196,8 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     con_grad = _gradient_dict(con, n, nh)
     if coll is not None:
         cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll, box_gradient=box_gradient,
-                                          epsilon=eps, hull_gradient=hull_rows, mesh_gradient=mesh_rows, large_hull_gradient=large_rows)["grad"]
+                                          epsilon=eps, hull_gradient=hull_rows, mesh_gradient=mesh_rows, large_hull_gradient=large_rows,
+                                          large_mesh_gradient=tree_rows)["grad"]
         con_grad = {k: np.concatenate([v, cg[k]], axis=1) for k, v in con_grad.items()}
     return {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
             "layout": lay, "ag_cache": ag, "objectives": obj}

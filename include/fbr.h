@@ -90,7 +90,7 @@ typedef struct {
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
  * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes;
  * fbr_mesh_distance_gradients; fbr_model_set_large_hulls, option "hull_large_all"; fbr_large_hull_distance_gradients, option
- * "hull_grad_tile"; fbr_model_set_large_hull_meshes. */
+ * "hull_grad_tile"; fbr_model_set_large_hull_meshes; fbr_large_mesh_distance_gradients, option "mesh_grad_order". */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -357,8 +357,9 @@ int fbr_model_set_hull_meshes(fbr_model *m, int32_t nmesh, const int32_t *hull, 
  * meshed hull to a kernel that walks the two trees for the 64 samples of a wave together (csrc/fbr_mesh_bvh.h).  The value is the one
  * fbr_model_set_hull_meshes defines -- the minimum over triangles (triangle pairs), exactly 0.0 on contact, never negative -- with the
  * bits the brute force gives on the same poses: the tree only skips what could not have won.  Pairs without a mesh go to the kernels
- * they go to without any mesh attached and return the same bytes.  Distances only: fbr_hull_distance_gradients,
- * fbr_mesh_distance_gradients and fbr_large_hull_distance_gradients return FBR_E_UNSUPPORTED while such attachments are in place.
+ * they go to without any mesh attached and return the same bytes.  The gradients of such a set have an entry point of their own,
+ * fbr_large_mesh_distance_gradients below: fbr_hull_distance_gradients, fbr_mesh_distance_gradients and fbr_large_hull_distance_gradients
+ * return FBR_E_UNSUPPORTED while such attachments are in place.
  * FBR_E_INVALID in addition: a tree deeper than the traversal's stack holds (median splits of 8192 triangles cannot produce one).
  */
 #define FBR_MAX_LARGE_MESH_TRIANGLES 8192
@@ -463,6 +464,36 @@ int fbr_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double
  * fbr_mesh_distance_gradients keep refusing a set with a hull above FBR_MAX_HULL_VERTICES vertices.
  */
 int fbr_large_hull_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
+                                      const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
+                                      int32_t out_mem);
+
+/*
+ * The same for a hull set of fbr_model_set_hulls OR fbr_model_set_large_hulls while meshes attached by fbr_model_set_large_hull_meshes are in
+ * place: the gradient half of collisionMode "full" on KUKA LWR4 (and of fullMeshLinks there).  Arguments, layouts, memory spaces, the
+ * zeroing of grad_q_out, the exact zeros and the rule -- central differences over epsilon on the stencil of the other gradient calls -- are
+ * those of fbr_mesh_distance_gradients; npairs is the hull set's, ALL its pairs, each through the route of its class:
+ *   two hulls of at most FBR_MAX_HULL_VERTICES vertices, no mesh   the bytes fbr_hull_distance_gradients returns for the pair from a set
+ *                                                                  without meshes
+ *   a hull above FBR_MAX_HULL_VERTICES vertices, no mesh           the bytes fbr_large_hull_distance_gradients returns for the pair from the
+ *                                                                  set without meshes (its three stages, option "hull_grad_tile")
+ *   a mesh on either side                                          the stencil's relative poses are recorded and the quotients formed as by
+ *                                                                  fbr_mesh_distance_gradients; in between one mesh distance per recorded
+ *                                                                  pose is evaluated through the trees (csrc/fbr_mesh_bvh_grad.h)
+ * A stencil value of a mesh pair has the bits the brute force over all triangle pairs gives for its pose (the traversal of
+ * fbr_candidate_hull_distances, unchanged), so a set whose meshes fit both attachments returns the bytes of fbr_mesh_distance_gradients.  A
+ * wave of the tree stage holds 64 consecutive entries (stencil point, candidate) of ONE mesh pair; option "mesh_grad_order" chooses their
+ * order, and a value never depends on it.  Option "hull_large_all" has no effect on this call.  A mesh distance is never negative and exactly
+ * 0.0 on contact: a pair in intersection has an exactly zero row.  A NaN pose gives NaN in dist_out and in the evaluated joints' entries
+ * only.  No atomics: the same bits on every run.  Workspace: ncand x (stencil points of all mesh pairs and of all pairs of the second class)
+ * x 14 doubles.
+ * FBR_E_INVALID, by name, the set left in place: no hull set or a set with no pair; no attachment of fbr_model_set_large_hull_meshes (the
+ * message names the call that serves the set: fbr_mesh_distance_gradients for small meshes, fbr_large_hull_distance_gradients for large
+ * hulls without meshes, fbr_hull_distance_gradients for small hulls without meshes); epsilon not finite or not positive; option
+ * "mesh_grad_order" not 0, 1 or 2; option "hull_grad_tile" as for fbr_large_hull_distance_gradients where the set has a pair of the second
+ * class (it is not looked at otherwise); and the argument checks of
+ * fbr_hull_distance_gradients.
+ */
+int fbr_large_mesh_distance_gradients(fbr_model *m, const fbr_states *st, const double *base_pos, int32_t ncand, const int64_t *sample,
                                       const double *scale, const int64_t *pose_sample, double epsilon, double *dist_out, double *grad_q_out,
                                       int32_t out_mem);
 
@@ -784,6 +815,11 @@ int fbr_suspended_records(fbr_model *m, const fbr_states *st, const double *x_st
  *   "hull_grad_tile"             0     fbr_large_hull_distance_gradients: the live lanes of a work item of its distance stage, a power of two from
  *                                      1 to 64 (anything else: the call returns FBR_E_INVALID); 0: the widest that leaves 12 items a CU, the waves a CU holds.  The
  *                                      touching entries of an item run their facet passes one after the other.  Read by every call
+ *   "mesh_grad_order"            0     fbr_large_mesh_distance_gradients: the order of the (stencil point, candidate) entries of a mesh pair, 64
+ *                                      consecutive ones a wave of its distance stage -- 1: candidate-major (a wave holds all stencil points of
+ *                                      its candidates), 2: slot-major (a wave holds one stencil point of 64 candidates), 0: the default order,
+ *                                      candidate-major (measured: DESIGN.md); anything else: the call returns FBR_E_INVALID.  A value never depends on it.  Read
+ *                                      by every call
  *   "gram_serial", "gram_timing", "tsqr_timing"  0   diagnostics (producer on the main stream; cycle counters printed to stderr)
  * fbr_model_option_name enumerates the keys (index 0 .. until it fails).
  */
