@@ -833,7 +833,9 @@ class Engine:
         """Signed box distance and its central-difference derivative with respect to the joint positions at one chosen configuration per
         candidate and box pair (``fbr_box_distance_gradients``): ``{"dist": (C, P_box), "grad_q": (C, P_box, n)}``, arguments and rules as
         for ``capsule_distance_gradients``.  ``epsilon``: the step of the difference (the reference's ``analyticalGradientEpsilon``).  Joints
-        off the tree path between a pair's links, joints above both links and fixed joints are exact zeros."""
+        off the tree path between a pair's links, joints above both links and fixed joints are exact zeros.  A pair of two robot boxes
+        with ``center_in_link_axes`` does not depend on the base pose and returns the bits of a stationary base (so do the hull and mesh
+        calls below with ``offset_in_link_axes``)."""
         return self._distance_gradients("fbr_box_distance_gradients", int(getattr(self, "num_box_pairs", 0)), (float(epsilon),), st, ncand, sample,
                                         scale, pose_sample, base_pos, device_out)
 

@@ -77,13 +77,25 @@ FBR_HD void fbr_boxgrad_turn(double sn, double omc, const double *z, const doubl
 // world member's R | centre (12).  distf(X, Y): the signed distance of the two bodies at the frames X, Y [12] (R | centre) -- the boxes'
 // fbr_box_distance, the hulls' fbr_hull_distance (fbr_hull_grad.h); it has ONE call site.  Returns the distance and, through grad(d, v), the
 // central difference over +- eps of every evaluated joint d.  A NaN pose gives NaN in the distance and in the evaluated joints' entries.
-// mask(k) must leave the bit of a world member clear.
+// mask(k) must leave the bit of a world member clear.  base_of_pose(e3, b3): the caller's base pose (rpy, position); it is asked only
+// where the pair depends on it (below).
 template <class MaskFn, class QFn, class BaseFn, class SlotSave, class SlotLoad, class ConstFn, class GradFn, class DistFn>
 FBR_HD double fbr_rigidgrad_item(int ka, int kb, int cmode, const double *xa, const double *xb, double eps, double se, double omc, const int *steps,
-                                 int floating, MaskFn mask, QFn qf, BaseFn basef, SlotSave save, SlotLoad load, ConstFn consts, GradFn grad,
-                                 DistFn distf)
+                                 int floating, MaskFn mask, QFn qf, BaseFn base_of_pose, SlotSave save, SlotLoad load, ConstFn consts,
+                                 GradFn grad, DistFn distf)
 {
     const int kend = (ka > kb ? ka : kb) + 1;
+    // Two robot members whose offsets turn with their links: the base moves the pair rigidly, so its distance and its row do not depend on
+    // the base pose.  Such a pair is walked from an identity base (wave-uniform), and returns the bits of a stationary base whatever the
+    // base does.  With the offsets in world axes, or against a world member, the base pose counts and is the caller's.
+    const bool rel = ka >= 0 && kb >= 0 && cmode != 0;
+    auto basef = [&](double *e3, double *b3) {
+        if (rel) {
+            for (int i = 0; i < 3; i++) e3[i] = b3[i] = 0.0;
+        } else {
+            base_of_pose(e3, b3);
+        }
+    };
     double A[12], pA[3] = {0, 0, 0}, B[12], pB[3] = {0, 0, 0};  // the boxes R | centre (a robot box has its link's R) and the link origins
     for (int i = 0; i < 12; i++) {
         A[i] = ka < 0 ? xa[i] : 0.0;

@@ -95,14 +95,18 @@ def fourier_coefficients(a, b, q, nf, wf: float = 1.0, joint_limits=None, use_de
     return {"wf": float(wf), "a": A, "b": B, "q_offset": qc, "q_range": np.minimum(qc - lo, hi - qc) * 0.95}
 
 
+def _suspended_keys(suspended: dict) -> None:
+    unknown = set(suspended) - {"attachment_frame", "att_link", "damping", "x_std"}
+    if unknown:
+        raise ValueError(f"suspended: unknown keys {sorted(unknown)}")
+
+
 def suspended_spec(engine, suspended: dict) -> tuple:
     """``(att_link, damping, x_std)`` of a ``suspended=`` argument: a dict with ``x_std`` (the standard parameters whose inertial part
     swings) and optionally ``attachment_frame`` (a link name of the topology; default ``crane_ft``) or ``att_link`` (a link index) and
     ``damping`` (default 2000.0) -- the defaults are what ``simulateTrajectory`` passes (trajectoryGenerator.py:171-187:
     ``floatingBaseAttachmentFrame``, ``suspendedDamping``)."""
-    unknown = set(suspended) - {"attachment_frame", "att_link", "damping", "x_std"}
-    if unknown:
-        raise ValueError(f"suspended: unknown keys {sorted(unknown)}")
+    _suspended_keys(suspended)
     if "x_std" not in suspended:
         raise ValueError("suspended: x_std (the standard parameters) is required")
     if "att_link" in suspended and "attachment_frame" in suspended:
@@ -120,7 +124,7 @@ def suspended_spec(engine, suspended: dict) -> tuple:
 
 
 def candidate_states(engine, candidates: list, T: int, freq: float, device: bool = True, use_deg_vectorised_quirk: bool = False,
-                     suspended: dict | None = None) -> dict:
+                     suspended: dict | None = None, with_info: bool = False) -> dict:
     """States of ``len(candidates)`` candidate trajectories (dicts of ``fourier_coefficients``), T samples each at ``freq`` Hz, as ONE
     stacked batch ready for ``Engine.gram_grouped`` / ``candidate_dopt`` -- what ``computeTrajectoryDynamics`` builds per candidate on the
     host (trajectoryGenerator.py:83-155): joint states from the Fourier series, a stationary base (zero twist / acceleration / rpy).
@@ -128,6 +132,8 @@ def candidate_states(engine, candidates: list, T: int, freq: float, device: bool
     ``suspended`` (``suspended_spec``; floating base only): the base swings from a ball joint at the attachment frame instead --
     ``rpy``, ``base_vel``, ``base_acc`` and ``base_position`` come from one ``Engine.suspended_base_motion`` with dt = 1 / freq
     (``simulate_suspended_base_motion`` per candidate, trajectoryGenerator.py:171-187).  None: the stationary base, nothing changed.
+    ``with_info`` (with ``suspended`` only): the entry ``suspended_info`` (C, 2) int64 joins the result -- the equilibrium iterations and
+    clamp events of ``Engine.suspended_base_motion(..., with_info=True)``; it is no per-sample array: pop it before the states go on.
 
     ``use_deg_vectorised_quirk``: with ``useDeg`` the reference's vectorised evaluation converts radians with ``deg2rad`` once more
     (lines 126-128 after a block that never produced degrees), i.e. its q, dq, ddq are pi / 180 of the per-sample generators' values;
@@ -159,8 +165,44 @@ def candidate_states(engine, candidates: list, T: int, freq: float, device: bool
         if not engine.floating:
             raise ValueError("suspended: the engine has no floating base")
         att, damping, x_std = suspended_spec(engine, suspended)
-        st.update(engine.suspended_base_motion(st, C, x_std, att, 1.0 / float(freq), damping))
+        base = engine.suspended_base_motion(st, C, x_std, att, 1.0 / float(freq), damping, with_info=bool(with_info))
+        if with_info:
+            base.pop("att_state")
+            base["suspended_info"] = base.pop("info")
+        st.update(base)
+    elif with_info:
+        raise ValueError("with_info: the info of the suspended base motion needs suspended=")
     return st
+
+
+def rest_base_states(states: dict) -> dict:
+    """The rest-base view of candidate states: ``q``, ``dq``, ``ddq``, ``sign`` (every other entry too) are the arrays of ``states``
+    themselves, ``rpy`` / ``base_rpy``, ``base_vel`` / ``base_velocity`` and ``base_acc`` / ``base_acceleration`` are zeros of their shape in
+    their memory space (NumPy or torch) -- the ``fb_identity``, ``fb_zero_twist`` and zero base acceleration the reference's gradient sweeps
+    evaluate at (analyticalGradient.py:80-81).  ``base_position`` stays: the sweeps do not read it."""
+    out = dict(states)
+    for k in ("rpy", "base_rpy", "base_vel", "base_velocity", "base_acc", "base_acceleration"):
+        if out.get(k) is not None:
+            v = out[k]
+            if hasattr(v, "cpu"):
+                import torch
+
+                out[k] = torch.zeros_like(v)
+            else:
+                out[k] = np.zeros_like(np.asarray(v))
+    return out
+
+
+SUSPENDED_BASE_RULES = ("identity", "held")
+
+
+def _suspended_rule(suspended, suspended_base) -> bool:
+    """True when the sweeps run at the rest base (the reference's rule, ``"identity"``, under ``suspended=``)"""
+    if suspended_base not in SUSPENDED_BASE_RULES:
+        raise ValueError(f"suspended_base: '{suspended_base}' is none of {SUSPENDED_BASE_RULES}")
+    if suspended is None and suspended_base != "identity":
+        raise ValueError(f"suspended_base='{suspended_base}' without suspended=: the rule applies to the simulated base motion only")
+    return suspended is not None and suspended_base == "identity"
 
 
 def candidate_dopt_from_coefficients(engine, candidates: list, T: int, freq: float, independent_cols, dopt_regularization: float = 1e-4,
@@ -658,8 +700,9 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
 # The D-optimality term of the optimiser's gradient per candidate (analyticalGradient.py compute_analytical_gradient, Phases 1, A and B,
 # lines 538-762): weight rows on the device (Engine.regressor_weights), the finite-difference sweep (Engine.fd_scores) and the chain with
 # the Jacobian of the Fourier series (Engine.fourier_gradient).  The collision rows of the constraint Jacobian: candidate_collision_gradient
-# below; Phase C and the whole gradient: candidate_gradients_from_coefficients at the end.  Not covered: the suspended base (the reference's
-# sweeps hold the simulated base pose fixed or evaluate at an identity base; the gradient entry points keep refusing that configuration).
+# below; Phase C and the whole gradient: candidate_gradients_from_coefficients at the end.  The suspended base (``suspended=``): the weights
+# come from the swung states; the sweeps run at the rest base (``suspended_base="identity"``, the reference's rule: rest_base_states) or at the
+# swung states held fixed (``"held"``).  Neither differentiates the base motion itself, as the reference does not.
 # ------------------------------------------------------------------------------------------------------------------------------------
 def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4, dopt_scale=1.0, YtY_prior=None, B=None):
     """The constant matrices of ``Engine.regressor_weights`` for C candidates from their Grams ``G`` (C, Pa, Pa) (``Engine.gram_grouped``):
@@ -699,7 +742,8 @@ def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4,
 
 def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, independent_cols, dopt_regularization: float = 1e-4,
                                               dopt_scale=None, YtY_prior=None, epsilon: float = 1e-7, subsample: int = 1,
-                                              friction_sign_threshold: float = 0.02, max_weight_bytes: int = 2**31):
+                                              friction_sign_threshold: float = 0.02, max_weight_bytes: int = 2**31, suspended=None,
+                                              suspended_base: str = "identity"):
     """D-optimality term and its gradient for every candidate (``fourier_coefficients`` dicts) without a sample leaving the device:
     coefficients -> states (``fbr_fourier_states``) -> one Gram per candidate (``fbr_gram_grouped``) -> ``dopt_weight_matrices`` on the host
     -> for chunks of whole candidates whose weight rows fit ``max_weight_bytes``: ``regressor_weights`` -> ``fd_scores`` -> forward
@@ -712,18 +756,25 @@ def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, 
 
     ``subsample`` = k sweeps the samples 0, k, 2 k, ... only and scales the result by k (``analyticalGradientSubsample``); the Gram, f and
     C always use every sample.  Friction engines: the viscous column is linear in dq and sits in W, so the sweep carries its derivative
-    (the reference adds it analytically, ``W_visc``); the Coulomb sign tanh(dq / threshold) is held at its baseline value, as there."""
-    st = _coefficient_states(engine, candidates, T, freq, friction_sign_threshold)
+    (the reference adds it analytically, ``W_visc``); the Coulomb sign tanh(dq / threshold) is held at its baseline value, as there.
+
+    ``suspended`` (``suspended_spec``; floating base only): the base motion of every candidate is simulated on the device
+    (``candidate_states(..., suspended=)``); the Gram, f, C and the weight rows take those swung states.  ``suspended_base``: where the
+    sweep runs -- ``"identity"`` (default, the reference's rule, analyticalGradient.py:80-81, 107-111): the same q, dq, ddq and sign with
+    rpy, base_vel and base_acc zero (``rest_base_states``); ``"held"``: the swung states, i.e. the partial derivative with the simulated
+    base trajectory frozen.  Neither differentiates the base motion.  Any other value, or ``"held"`` without ``suspended=``, raises."""
+    rest = _suspended_rule(suspended, suspended_base)
+    st = _coefficient_states(engine, candidates, T, freq, friction_sign_threshold, suspended)
     G = _host(engine.gram_grouped(st, len(candidates)))
     nld = est.d_optimality_batch(G, independent_cols, dopt_regularization, YtY_prior)
     scale = 1.0 if dopt_scale is None else float(dopt_scale)
     return nld * scale, _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale, YtY_prior, epsilon, subsample,
-                                       max_weight_bytes)
+                                       max_weight_bytes, rest_base=rest)
 
 
-def _coefficient_states(engine, candidates, T, freq, friction_sign_threshold, suspended=None):
+def _coefficient_states(engine, candidates, T, freq, friction_sign_threshold, suspended=None, with_info=False):
     """``candidate_states`` on the device with the Coulomb column tanh(dq / threshold) of a friction engine"""
-    st = candidate_states(engine, candidates, int(T), freq, device=True, suspended=suspended)
+    st = candidate_states(engine, candidates, int(T), freq, device=True, suspended=suspended, with_info=with_info)
     if engine.friction:
         import torch
 
@@ -738,8 +789,10 @@ def _gradient_dict(g, n: int, nh: int) -> dict:
             "a": g[..., 1 + 2 * n:1 + 2 * n + n * nh].reshape(lead + (n, nh)).copy(), "b": g[..., 1 + 2 * n + n * nh:].reshape(lead + (n, nh)).copy()}
 
 
-def _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale, YtY_prior, epsilon, subsample, max_weight_bytes):
-    """the gradient dict of ``candidate_dopt_gradient_from_coefficients`` from the candidates' device states and grouped Gram"""
+def _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale, YtY_prior, epsilon, subsample, max_weight_bytes,
+                   rest_base=False):
+    """the gradient dict of ``candidate_dopt_gradient_from_coefficients`` from the candidates' device states and grouped Gram;
+    ``rest_base``: the weights from ``st``, the scores from its rest-base view"""
     import torch
 
     C = len(candidates)
@@ -749,6 +802,7 @@ def _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_re
     Ts = (T + k - 1) // k
     if k > 1:
         st = {key: v.reshape(C, T, -1)[:, ::k].reshape(C * Ts, -1).contiguous() for key, v in st.items()}
+    at = rest_base_states(st) if rest_base else st
     per_cand = Ts * engine.rows * engine.cols * 8
     cc = max(1, min(C, int(max_weight_bytes) // max(per_cand, 1)))
     sens = torch.empty((3, C * Ts, n), dtype=torch.float64, device=st["q"].device)
@@ -758,7 +812,7 @@ def _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_re
         sub = {key: v[c0 * Ts:c1 * Ts] for key, v in st.items()}
         Wc = W[: (c1 - c0) * Ts * engine.rows]
         engine.regressor_weights(sub, c1 - c0, Cm[c0:c1], cols=cols, out=Wc)
-        sc = engine.fd_scores(sub, Wc, float(epsilon))
+        sc = engine.fd_scores({key: v[c0 * Ts:c1 * Ts] for key, v in at.items()} if rest_base else sub, Wc, float(epsilon))
         d = (sc[:, 1:] - sc[:, :1]) * (k / float(epsilon))
         sens[:, c0 * Ts:c1 * Ts] = d.reshape(-1, 3, n).permute(1, 0, 2)
     nh = max(c["a"].shape[1] for c in candidates)
@@ -845,7 +899,7 @@ def _chain_positions(engine, candidates, freq, sample, scale, grad_q, max_bytes)
 def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: list, freq: float, config: dict, collision: dict,
                                  constraints: dict | None = None, max_bytes: int = 2**31, box_gradient: bool = False, epsilon=None,
                                  hull_gradient: bool = False, mesh_gradient: bool = False, large_hull_gradient: bool = False,
-                                 large_mesh_gradient: bool = False) -> dict:
+                                 large_mesh_gradient: bool = False, suspended=None) -> dict:
     """The collision block ``g = distance - margin`` (C, P) of ``ncand`` equal candidates stacked in ``states`` and its derivative with
     respect to the entries of the candidates' ``fourier_coefficients`` dicts, from which ``states`` were generated at ``freq`` Hz
     (``candidate_states``).  ``collision``: capsules, pairs and optionally margins (``flobaroid_amd.collision.collision_set``);
@@ -892,8 +946,15 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     (and ``large=True`` where a hull exceeds 128 vertices) and the rows of ALL its pairs come from
     ``Engine.large_mesh_distance_gradients`` (the other three keywords may then be either value): the mesh pairs through the trees, the
     plain pairs as the hull and the large-hull call return them.  The keyword with anything else raises ``ValueError``, says which
-    condition fails and, where one exists, names the keyword that serves the set."""
-    _check_config(config)
+    condition fails and, where one exists, names the keyword that serves the set.
+
+    ``suspended``: not None says that ``states`` carry the simulated base motion (``candidate_states(..., suspended=)``: ``rpy`` and
+    ``base_position``); ``floatingBaseAttachment: "suspended"`` is then accepted, under every keyword above.  Every row is taken at the
+    base pose of sample ``eval_pose`` of the constraint block, held constant: the pose the winning evaluation was made at, for a
+    transition winner one of the seven representative poses.  That deviates from the reference on purpose: it differentiates a transition
+    winner at the pose of sample 0 (analyticalGradient.py:960-971), a different point from the one whose distance is the constraint
+    value.  The coupling through the base dynamics is neglected, as there."""
+    _check_config(config, suspended)
     tree_rows = _wants_large_mesh_gradient(config, collision, large_mesh_gradient)
     if not tree_rows:
         _refuse_large_mesh_gradient(collision)
@@ -907,7 +968,7 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
     if tree_rows or large_rows or mesh_rows or _wants_hull_gradient(config, collision, hull_gradient):
         C, n = int(ncand), engine.n
         bpos = states.get("base_position") if engine.floating else None
-        cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision)
+        cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision, suspended)
         eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)
         cols = np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)
         sel = np.argsort(cols[:, 1], kind="stable")  # (the set's own pair order)
@@ -940,11 +1001,12 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
         if mode != "capsule":
             raise ValueError("collisionMode 'box' needs a collision set with boxes (flobaroid_amd.collision.collision_set(..., boxes=))")
         engine.set_capsules(collision["capsules"], collision["pairs"])
-        cons = constraints if constraints is not None else candidate_collision_constraints(engine, states, C, config, margins=collision.get("margins"))
+        cons = constraints if constraints is not None else candidate_collision_constraints(engine, states, C, config, margins=collision.get("margins"),
+                                                                                           suspended=suspended)
         dg = engine.capsule_distance_gradients(states, C, cons["eval_sample"], scale=cons["eval_scale"], pose_sample=cons["eval_pose"], base_pos=bpos)
         out, nh = _chain_positions(engine, candidates, freq, cons["eval_sample"], cons["eval_scale"], dg["grad_q"], max_bytes)
         return {"g": np.asarray(cons["g"]), "grad": _gradient_dict(out, n, nh), "grad_q": np.asarray(_host(dg["grad_q"]))}
-    cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision)
+    cons = constraints if constraints is not None else _collision_block(engine, states, C, config, collision, suspended)
     eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)
     cols = np.asarray(collision["columns"], dtype=np.int64).reshape(-1, 2)
     P = cols.shape[0]
@@ -974,14 +1036,16 @@ def candidate_collision_gradient(engine, states: dict, ncand: int, candidates: l
 def candidate_collision_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, config: dict, collision: dict,
                                                    max_bytes: int = 2**31, box_gradient: bool = False, hull_gradient: bool = False,
                                                    mesh_gradient: bool = False, large_hull_gradient: bool = False,
-                                                   large_mesh_gradient: bool = False) -> dict:
+                                                   large_mesh_gradient: bool = False, suspended=None) -> dict:
     """``candidate_collision_gradient`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
     (``candidate_states``) and never leave it; only the per-pair rows come back.  ``box_gradient``, ``hull_gradient``, ``mesh_gradient``,
-    ``large_hull_gradient``, ``large_mesh_gradient``: as there."""
-    st = candidate_states(engine, candidates, int(T), float(freq), device=True)
+    ``large_hull_gradient``, ``large_mesh_gradient``: as there.  ``suspended`` (``suspended_spec``): the states carry the simulated base
+    motion (``candidate_states(..., suspended=)``) and every row is taken at the pose its winning evaluation was made at, as there."""
+    _check_config(config, suspended)
+    st = candidate_states(engine, candidates, int(T), float(freq), device=True, suspended=suspended)
     return candidate_collision_gradient(engine, st, len(candidates), candidates, freq, config, collision, max_bytes=max_bytes,
                                         box_gradient=box_gradient, hull_gradient=hull_gradient, mesh_gradient=mesh_gradient,
-                                        large_hull_gradient=large_hull_gradient, large_mesh_gradient=large_mesh_gradient)
+                                        large_hull_gradient=large_hull_gradient, large_mesh_gradient=large_mesh_gradient, suspended=suspended)
 
 
 def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, use_deg: bool = False, bounded: bool | None = None, exact: bool = False,
@@ -1023,17 +1087,31 @@ def constraint_gradient_to_optimizer_variables(grad: dict, candidate: dict, nf, 
 # from its velocity sweep, see dopt_sensitivities: no flag reproduces that here); candidates whose D-optimality term failed get the
 # soft-cost gradient only.
 # ------------------------------------------------------------------------------------------------------------------------------------
-def candidate_torque_jacobians(engine, states: dict, ncand: int, sample, x_std, epsilon: float = 1e-7, vel_sign=None) -> dict:
+def candidate_torque_jacobians(engine, states: dict, ncand: int, sample, x_std, epsilon: float = 1e-7, vel_sign=None, rest_base: bool = False) -> dict:
     """The ``torque_sens`` of the reference's gradient worker (``_dopt_gradient_worker_func``, the ``need_torque`` branches, analyticalGradient.py:114-183) for ``ncand`` equal candidates stacked in ``states``:
     joint n's torque at sample ``sample[c, n]`` of candidate c and its forward differences over the joint states, from one
     ``Engine.torque_row_sweep``.  Returns ``tau`` (C, n), the baseline values whose ``np.sign`` is the reference's ``sign_n``, and
     ``dtau_dq``, ``dtau_ddq_state``, ``dtau_dddq`` (C, n, n): row n holds the derivatives of tau_n with respect to q, dq and ddq (the
     reference's names), in the memory space of the states.  The Coulomb sign series, ``vel_sign`` and the base state are held at the
-    sample's values; the clean derivative, without the reference's carried-over dq_{n-1} + eps in the acceleration sweep."""
+    sample's values; the clean derivative, without the reference's carried-over dq_{n-1} + eps in the acceleration sweep.
+
+    ``rest_base=True`` (the suspended base under the reference's rule, analyticalGradient.py:107-125): the three derivative arrays come from
+    the sweep at ``rest_base_states(states)`` -- rpy, base_vel, base_acc zero, everything else the sample's own.  ``tau`` stays the torque at
+    the states passed in (the swung ones, whose sign is ``sign_n``): one ``Engine.inverse_dynamics`` over the C n gathered samples."""
     n = engine.n
-    sw = engine.torque_row_sweep(states, int(ncand), sample, x_std, float(epsilon), vel_sign=vel_sign)
+    sw = engine.torque_row_sweep(rest_base_states(states) if rest_base else states, int(ncand), sample, x_std, float(epsilon), vel_sign=vel_sign)
     d = (sw[..., 1:] - sw[..., :1]) / float(epsilon)
-    return {"tau": sw[..., 0], "dtau_dq": d[..., :n], "dtau_ddq_state": d[..., n:2 * n], "dtau_dddq": d[..., 2 * n:]}
+    tau = sw[..., 0]
+    if rest_base:
+        C, q = int(ncand), states["q"]
+        keys = [k for k in ("q", "dq", "ddq", "rpy", "base_rpy", "base_vel", "base_velocity", "base_acc", "base_acceleration", "sign")
+                if states.get(k) is not None]
+        flat = (_like(q, sample, np.int64).reshape(C, n) + _like(q, np.arange(C) * (int(q.shape[0]) // max(C, 1)), np.int64)[:, None]).reshape(-1)
+        take = lambda a: a[flat].contiguous() if hasattr(a, "cpu") else np.ascontiguousarray(np.asarray(a)[flat])  # noqa: E731
+        tau = engine.inverse_dynamics({k: take(states[k]) for k in keys}, x_std, vel_sign=None if vel_sign is None else take(vel_sign))
+        fb = engine.rows - n
+        tau = _like(sw, tau).reshape(C, n, engine.rows)[:, list(range(n)), list(range(fb, fb + n))]  # (row n of the sample gathered for joint n)
+    return {"tau": tau, "dtau_dq": d[..., :n], "dtau_ddq_state": d[..., n:2 * n], "dtau_dddq": d[..., 2 * n:]}
 
 
 def _like(ref, a, dtype=None):
@@ -1075,7 +1153,8 @@ def constraint_chain_rows(ag_cache: dict, torque_jacobians: dict, vel_at_peak):
     return sample, grad_q, grad_dq, grad_ddq
 
 
-def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_at_peak, chain, limits: dict, joint_names, config: dict) -> dict:
+def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_at_peak, chain, limits: dict, joint_names, config: dict,
+                                   suspended=None) -> dict:
     """The arithmetic of Phase C (analyticalGradient.py:764-953) for C candidates, arrays in and arrays out (NumPy or torch, the kind of
     ``torque_jacobians``), no engine.  ``ag_cache``: the entry ``ag_cache`` of ``objectives_from_extrema``; ``torque_jacobians``:
     ``candidate_torque_jacobians`` at ``ag_cache["torque_absmax_idx"]``; ``vel_at_peak`` (C, n): dq_n at ``vel_absmax_idx[n]``; ``limits``,
@@ -1087,8 +1166,14 @@ def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_a
     only where util_mean > 0 and util_std > 0, f3 only where f3 > 0, f4 only with ``trajectoryTargetVelocity`` > 0 and for joints with
     vel_absmax < the target -- its terms ``df1`` .. ``df4`` (C, E) before those factors (``df2`` of the x10 f2), and ``con_grad``
     (C, 5 n or 6 n, E) in ``constraint_layout`` order: -dq at the argmin, +dq at the argmax, sign d(dq), d|tau|, [-sign d(dq) with
-    ``minVelocityConstraint``,] -d|tau|."""
-    _check_config(config)
+    ``minVelocityConstraint``,] -d|tau|.
+
+    ``suspended``: not None says that ``ag_cache`` and ``torque_jacobians["tau"]`` come from states with the simulated base motion
+    (``candidate_torque_jacobians(..., rest_base=)`` chooses where the derivatives are taken); ``floatingBaseAttachment: "suspended"`` is
+    then accepted.  The arithmetic is the same."""
+    _check_config(config, suspended)
+    if suspended is not None:
+        _suspended_keys(suspended)
     tau = torque_jacobians["tau"]
     n = int(tau.shape[1])
     jn = list(joint_names)
@@ -1118,7 +1203,8 @@ def constraint_gradients_from_rows(ag_cache: dict, torque_jacobians: dict, vel_a
 def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict, joint_names,
                                           config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1,
                                           box_gradient: bool = False, hull_gradient: bool = False, mesh_gradient: bool = False,
-                                          large_hull_gradient: bool = False, large_mesh_gradient: bool = False) -> dict:
+                                          large_hull_gradient: bool = False, large_mesh_gradient: bool = False, suspended=None,
+                                          suspended_base: str = "identity") -> dict:
     """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
     and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
     one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
@@ -1140,7 +1226,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     capsule-less links, ``collisionMode: "box"``) raises ``ValueError``; ``True``: their rows are the reference's central differences of
     the box distance over the same ``epsilon`` (``candidate_collision_gradient``).  ``hull_gradient=False``: a ``collision`` set with hull
     pairs raises ``ValueError``; ``True`` with ``collisionMode: "convex"``: the rows of the hull pairs are the reference's central
-    differences of the hull distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered: the suspended base,
+    differences of the hull distance over the same ``epsilon`` (``candidate_collision_gradient``).  Not covered:
     gravity-only models (refused).  ``mesh_gradient=False``: a ``collision`` set with triangle meshes (``fullMeshLinks``, ``collisionMode:
     "full"``) is refused by the names of the meshed links; ``True`` with such a set and configuration: the rows of all its pairs come from
     ``Engine.mesh_distance_gradients`` (``candidate_collision_gradient``).  ``large_hull_gradient=False``: a ``collision`` set with a hull
@@ -1148,8 +1234,21 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     and no meshes: the rows of all its pairs come from ``Engine.large_hull_distance_gradients`` (``candidate_collision_gradient``).
     ``large_mesh_gradient=False``: a ``collision`` set built with ``large_meshes=True`` is refused by the names and triangle counts of its
     meshes; ``True`` with such a set of hull pairs only, in ``collisionMode: "full"`` or with ``fullMeshLinks`` in ``"convex"``: the rows
-    of all its pairs come from ``Engine.large_mesh_distance_gradients`` (``candidate_collision_gradient``)."""
-    _check_config(config)
+    of all its pairs come from ``Engine.large_mesh_distance_gradients`` (``candidate_collision_gradient``).
+
+    ``suspended`` (``suspended_spec``; floating base only): ``floatingBaseAttachment: "suspended"`` is accepted -- the one
+    ``candidate_states(..., suspended=)`` simulates the base motion of every candidate on the device, f and g are those of
+    ``candidate_objectives_from_coefficients(..., suspended=)``, every part is the stand-alone entry point's with the same arguments, and
+    the result carries ``suspended_info`` (C, 2) int64: the equilibrium iterations and clamp events of
+    ``Engine.suspended_base_motion(..., with_info=True)``, so a caller sees that a candidate's base hit the +-25 degree clamp.
+    ``suspended_base``: ``"identity"`` (default, the reference's rule) -- the D-optimality weights, the extrema, their indices and
+    ``sign_n`` come from the swung states, the D-optimality sweep and the torque sensitivities run at rpy = base_vel = base_acc = 0;
+    ``"held"`` -- both sweeps run at the swung states, the partial derivative with the simulated base trajectory frozen.  The collision
+    rows hold the base at the pose of the winning evaluation under both (``candidate_collision_gradient``).  Neither rule differentiates
+    the base motion (the coupling through the base dynamics is neglected, as in the reference), so a clamp event does not invalidate a
+    row: it only says that the frozen trajectory has a kink there.  None: the stationary base, and that configuration is refused."""
+    rest = _suspended_rule(suspended, suspended_base)
+    _check_config(config, suspended)
     if large_mesh_gradient and collision is None:
         raise ValueError("large_mesh_gradient=True: no collision set (collision=)")
     tree_rows = collision is not None and _wants_large_mesh_gradient(config, collision, large_mesh_gradient)
@@ -1172,16 +1271,18 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
     C, n, T = len(candidates), engine.n, int(T)
     eps = float(config.get("analyticalGradientEpsilon", 1e-7) if epsilon is None else epsilon)
-    st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02))
+    st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02), suspended, with_info=suspended is not None)
+    info = st.pop("suspended_info", None)
     vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
     obj, G, coll = _candidate_objective_parts(engine, st, C, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign,
-                                              collision)
+                                              collision, suspended)
     ag = obj["ag_cache"]
     dopt = _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, config.get("doptRegularization", 1e-4), obj["dopt_scale"], YtY_prior,
-                          eps, subsample, 2**31)
+                          eps, subsample, 2**31, rest_base=rest)
     ok = ~obj["failed"]
     dopt = {k: np.where(ok.reshape((C,) + (1,) * (v.ndim - 1)), v, 0.0) for k, v in dopt.items()}
-    jac = {k: _host(v) for k, v in candidate_torque_jacobians(engine, st, C, ag["torque_absmax_idx"], x_std, eps, vel_sign=vel_sign).items()}
+    jac = {k: _host(v) for k, v in candidate_torque_jacobians(engine, st, C, ag["torque_absmax_idx"], x_std, eps, vel_sign=vel_sign,
+                                                                rest_base=rest).items()}
     import torch
 
     vidx = torch.as_tensor(np.asarray(ag["vel_absmax_idx"], dtype=np.int64), device=st["dq"].device).reshape(C, 1, n)
@@ -1189,7 +1290,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     A, B, nh, qr = _padded_coefficients(candidates, n)
     wf = np.array([c["wf"] for c in candidates], dtype=np.float64)
     chain = lambda smp, gq, gdq, gddq: _host(engine.fourier_state_chain(wf, A, B, smp, float(freq), gq, gdq, gddq, q_range=qr))  # noqa: E731
-    pc = constraint_gradients_from_rows(ag, jac, vel_at_peak, chain, limits, joint_names, config)
+    pc = constraint_gradients_from_rows(ag, jac, vel_at_peak, chain, limits, joint_names, config, suspended=suspended)
     soft = _gradient_dict(pc["obj_grad"], n, nh)
     con = pc["con_grad"]
     lay = constraint_layout(n, bool(config.get("minVelocityConstraint", False)), None if coll is None else int(np.asarray(coll["g"]).shape[1]))
@@ -1197,7 +1298,10 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     if coll is not None:
         cg = candidate_collision_gradient(engine, st, C, candidates, freq, config, collision, constraints=coll, box_gradient=box_gradient,
                                           epsilon=eps, hull_gradient=hull_rows, mesh_gradient=mesh_rows, large_hull_gradient=large_rows,
-                                          large_mesh_gradient=tree_rows)["grad"]
+                                          large_mesh_gradient=tree_rows, suspended=suspended)["grad"]
         con_grad = {k: np.concatenate([v, cg[k]], axis=1) for k, v in con_grad.items()}
-    return {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
-            "layout": lay, "ag_cache": ag, "objectives": obj}
+    out = {"f": obj["f"], "g": obj["g"], "obj_grad": {k: dopt[k] + soft[k] for k in soft}, "dopt_grad": dopt, "soft_grad": soft, "con_grad": con_grad,
+           "layout": lay, "ag_cache": ag, "objectives": obj}
+    if suspended is not None:
+        out["suspended_info"] = _host(info)
+    return out
