@@ -181,6 +181,11 @@ _SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.POINTER(fbr_states), ctypes.c_int32, _ip, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_dopt_terms": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _ip, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double, _dp,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_fourier_gradient": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, ctypes.c_void_p,
@@ -240,6 +245,7 @@ FBR_VERSION = 104  # include/fbr.h FBR_VERSION: the C-ABI these ctypes signature
 FBR_MAX_HULL_VERTICES = 128  # include/fbr.h: a hull of Engine.set_hulls
 FBR_MAX_LARGE_HULL_VERTICES = 1024  # include/fbr.h: a hull of Engine.set_hulls(..., large=True)
 FBR_MAX_LARGE_MESH_TRIANGLES = 8192  # include/fbr.h: a mesh of Engine.set_large_hull_meshes / set_hulls(..., large_meshes=True)
+FBR_MAX_DOPT_COLUMNS = 512  # include/fbr.h: the selected columns of Engine.dopt_terms
 DEFAULT_OPTIONS: dict = {}
 
 
@@ -1149,6 +1155,67 @@ class Engine:
         _check(self._lib.fbr_regressor_weights(self._h, ctypes.byref(s), G, None if ca is None else ca.ctypes.data_as(_ip), nc, Cr.ptr, r.ptr, r.mem),
                "fbr_regressor_weights")
         return ret
+
+    def dopt_terms(self, G, cols, reg: float = 1e-4, prior=None, scale=None, eigenvalues: bool = False, weights: bool = False,
+                   device_out: bool | None = None) -> dict:
+        """The D-optimality arithmetic of C candidates from their Grams ``G`` (C, Pa, Pa) (``gram_grouped``) on the device
+        (``fbr_dopt_terms``): per candidate the eigenvalues of ``M = G[cols, cols] (+ prior)`` (lower triangle, as ``eigvalsh``) and
+        ``neg_log_det``, ``lambda_max``, ``delta = reg * max(lambda_max, 1e-30)``, ``n_observable`` (int64), ``status`` (int32; bit 1: a
+        non-finite entry, that candidate's numbers are NaN; bit 2: the factorisation met a pivot that is not positive).  ``eigenvalues``:
+        also ``eig`` (C, ncols) ascending.  ``weights``: also ``Cmat`` (C, ncols, ncols) = -2 scale (M + delta I)^-1, exactly symmetric,
+        what ``regressor_weights`` takes; a candidate with a non-zero status then raises ``np.linalg.LinAlgError``.  ``cols``: distinct,
+        any order; ``prior`` (ncols, ncols) is brought to the memory space of ``G``; ``scale``: a number or one per candidate.
+        The arrays are tensors when ``G`` is a CUDA tensor and NumPy arrays otherwise (``device_out`` overrides)."""
+        import torch
+
+        Gr = _Ref(G, name="G")
+        if len(Gr.obj.shape) != 3 or Gr.obj.shape[1] != Gr.obj.shape[2]:
+            raise ValueError(f"G: expected (C, Pa, Pa), got {tuple(Gr.obj.shape)}")
+        C, Pa = int(Gr.obj.shape[0]), int(Gr.obj.shape[1])
+        mem = Gr.mem
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        ca = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        n = int(ca.size)
+        pr = _Ref(None)
+        if prior is not None:
+            if _is_torch(prior):
+                prior = prior.reshape(n, n).cpu() if mem == FBR_HOST else prior.reshape(n, n).to(f"cuda:{self.device}")
+            else:
+                prior = np.ascontiguousarray(prior, dtype=np.float64).reshape(n, n)
+                if mem == FBR_DEVICE:
+                    prior = torch.from_numpy(prior).to(f"cuda:{self.device}")
+            pr = _Ref(prior, (n, n), "prior")
+        sc = None if scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (max(C, 1),)))
+        ok = C >= 1 and 1 <= n <= min(Pa, FBR_MAX_DOPT_COLUMNS)  # (else the call refuses before it touches an output: tiny stand-ins)
+        tr, terms = self._out(None, (max(C, 1), 4), mem)
+        er, eig = self._out(None, (C, n), mem) if eigenvalues and ok else (_Ref(None), None)
+        cr, Cm = self._out(None, (C, n, n), mem) if weights and ok else (_Ref(None), None)
+        if mem == FBR_DEVICE:
+            status = torch.empty((max(C, 1),), dtype=torch.int32, device=f"cuda:{self.device}")  # (the kernel writes every word)
+            sptr = status.data_ptr()
+        else:
+            status = np.zeros((max(C, 1),), dtype=np.int32)
+            sptr = status.ctypes.data
+        _check(self._lib.fbr_dopt_terms(self._h, Gr.ptr, C, Pa, ca.ctypes.data_as(_ip), n, pr.ptr, float(reg),
+                                        None if sc is None else sc.ctypes.data_as(_dp), tr.ptr, sptr, er.ptr, cr.ptr, mem), "fbr_dopt_terms")
+        out = {"neg_log_det": terms[:, 0], "lambda_max": terms[:, 1], "delta": terms[:, 2],
+               "n_observable": terms[:, 3].to(torch.int64) if mem == FBR_DEVICE else terms[:, 3].astype(np.int64), "status": status}
+        if eigenvalues:
+            out["eig"] = eig
+        if weights:
+            out["Cmat"] = Cm
+            st = status.cpu().numpy() if mem == FBR_DEVICE else status
+            if st.any():
+                err = np.linalg.LinAlgError(f"dopt_terms(weights=True): no weight matrix for candidates {np.nonzero(st)[0].tolist()} "
+                                            f"(status {st[st != 0].tolist()}: 1 = a non-finite Gram, 2 = M + delta I is not positive definite)")
+                err.status = st.copy()  # every candidate's status word
+                raise err
+        if device_out is not None and bool(device_out) != (mem == FBR_DEVICE):
+            out = {k: (torch.from_numpy(np.ascontiguousarray(v)).to(f"cuda:{self.device}") if device_out else v.cpu().numpy()) for k, v in out.items()}
+        elif mem == FBR_HOST:
+            out = {k: np.ascontiguousarray(v) for k, v in out.items()}
+        return out
 
     def fourier_gradient(self, wf, a, b, sens_q, sens_dq, sens_ddq, T: int, freq: float, q_range=None, tstride: int = 1, device_out: bool | None = None):
         """Chain of sensitivities (C * T, n) with the Jacobian of the series of ``fourier_states`` (``fbr_fourier_gradient``): a (C, 1 + 2 n +

@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 OUT = os.path.join(_HERE, "libfbr.so")
 OBJDIR = os.path.join(_HERE, "csrc", "_obj")
 STAMP = os.path.join(_HERE, "libfbr.build.json")
-SOURCES = ["fbr_api.hip", "fbr_collision_api.hip", "fbr_gram_api.hip", "fbr_tsqr_api.hip", "fbr_signal_api.hip"]
+SOURCES = ["fbr_api.hip", "fbr_collision_api.hip", "fbr_gram_api.hip", "fbr_tsqr_api.hip", "fbr_signal_api.hip", "fbr_dopt_api.hip"]
 # -Wno-inline-asm: the hand-written LDS-DMA of the TSQR kernels (csrc/fbr_tsqr.h fbr_dma16) writes M0 and says so in its clobber list;
 # clang warns about every instantiation that a reserved register is named there (it is still honoured)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-inline-asm"]

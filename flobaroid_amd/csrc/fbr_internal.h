@@ -254,6 +254,9 @@ struct fbr_model {
     int fd_tab_entries = -1;
     DevBuf wt_tab;            // fbr_regressor_weights: [selected columns | the others] of the call
     DevBuf fgrad_part;        // fbr_fourier_gradient: per-block partial sums [C][blocks][n][3 + 2 nharm]
+    // fbr_dopt_terms (fbr_dopt_api.hip): the matrices of a chunk of candidates [chunk][n][n]; [scale (ngroups) | cols (n)]; the results of a
+    // chunk of a host-memory call [terms | eig | Cmat | status]
+    DevBuf dopt_scratch, dopt_tab, dopt_out;
     FbrTsqrWork tsqr;
     std::vector<FbrTsqrWork> tsqr_groups;  // one factorisation per row group of the tree-structured TSQR (tsqr_group_plan)
     hipStream_t tsqr_streams[4] = {nullptr, nullptr, nullptr, nullptr};  // the groups' merge trees run beside the final factor's (created on first use)

@@ -307,6 +307,14 @@ def d_optimality_batch_terms(G_groups: np.ndarray, independent_cols, dopt_regula
     return _regularized_neg_log_det(ev, dopt_regularization), ev[..., -1].copy(), np.sum(ev > delta, axis=-1).astype(np.int64)
 
 
+def d_optimality_batch_terms_device(engine, G_groups, independent_cols, dopt_regularization: float = 1e-4,
+                                    YtY_prior=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``d_optimality_batch_terms`` with the eigenvalues computed on the device (``Engine.dopt_terms``): ``G_groups`` may stay a CUDA
+    tensor (``Engine.gram_grouped`` of device states); only the three numbers per candidate come to the host."""
+    t = engine.dopt_terms(G_groups, independent_cols, dopt_regularization, prior=YtY_prior, device_out=False)
+    return t["neg_log_det"], t["lambda_max"], t["n_observable"]
+
+
 def n_observable_base_params(G_aug: np.ndarray, independent_cols, dopt_regularization: float = 1e-4) -> int:
     """Eigenvalues of YBase^T YBase above the regularisation threshold (trajectoryOptimizer.py:275; the count
     trajectory.py:225-264 stores as ``n_observable_base_params``)."""

@@ -7,7 +7,7 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
 * ``candidate_dopt``      -- D-optimality of many candidate trajectories from ``Engine.gram_grouped``;
 * ``dopt_sensitivities``  -- the worker's ``sens_q, sens_dq, sens_ddq`` from ``Engine.fd_scores``;
 * ``candidate_objectives`` -- the whole ``objectiveFunc`` (f, g, soft costs) of many candidates from ``Engine.gram_grouped`` +
-  ``Engine.candidate_extrema``: only per-candidate numbers reach the host;
+  ``Engine.candidate_extrema``; with ``device_spectrum=True`` (``Engine.dopt_terms``) only per-candidate numbers reach the host;
 * ``candidate_collision_constraints`` -- its collision block from ``Engine.candidate_capsule_distances`` (``collisionMode: "capsule"``,
   pairs of links with capsules), ``Engine.candidate_box_distances`` (``collisionMode: "box"``, world links, capsule-less links) and
   ``Engine.candidate_hull_distances`` (``collisionMode: "convex"``, the reference's default: convex hulls of the links' meshes; with
@@ -31,11 +31,14 @@ from . import estimation as est
 
 
 def candidate_dopt(engine, states: dict, num_candidates: int, independent_cols, dopt_regularization: float = 1e-4, w=None,
-                   YtY_prior=None) -> np.ndarray:
+                   YtY_prior=None, device_spectrum: bool = False) -> np.ndarray:
     """Regularised D-optimality -sum(log(max(eig(YBase^T YBase [+ YtY_prior]) + delta, 1e-300))), delta = doptRegularization *
     lambda_max per candidate, of ``num_candidates`` trajectories stacked along the sample axis (equal length each), one fused
-    pass (trajectoryOptimizer.py:259-272 per candidate)."""
+    pass (trajectoryOptimizer.py:259-272 per candidate).  ``device_spectrum=True``: the eigenvalues are computed on the device as well
+    (``Engine.dopt_terms``) -- the Grams of device states never reach the host; False (default): ``eigvalsh`` on the host, as before."""
     G = engine.gram_grouped(states, int(num_candidates), w=w)
+    if device_spectrum:
+        return est.d_optimality_batch_terms_device(engine, G, independent_cols, dopt_regularization, YtY_prior)[0]
     G = G.cpu().numpy() if hasattr(G, "cpu") else G
     return est.d_optimality_batch(G, independent_cols, dopt_regularization, YtY_prior)
 
@@ -206,17 +209,18 @@ def _suspended_rule(suspended, suspended_base) -> bool:
 
 
 def candidate_dopt_from_coefficients(engine, candidates: list, T: int, freq: float, independent_cols, dopt_regularization: float = 1e-4,
-                                     YtY_prior=None, friction_sign_threshold: float = 0.02) -> np.ndarray:
+                                     YtY_prior=None, friction_sign_threshold: float = 0.02, device_spectrum: bool = False) -> np.ndarray:
     """D-optimality of every candidate without its samples ever leaving the device: Fourier coefficients -> states (``fbr_fourier_states``)
     -> one Gram per candidate (``fbr_gram_grouped``) -> eigenvalues on the host (trajectoryOptimizer.py:240-272 per candidate).
     ``friction_sign_threshold``: the Coulomb column is tanh(dq / threshold) -- callers with an option dict pass
-    ``opt.get('frictionSignThreshold', 0.02)`` (helpers.py getFrictionSignSeries, model.py:757), the value ``Model`` uses on the host path."""
+    ``opt.get('frictionSignThreshold', 0.02)`` (helpers.py getFrictionSignSeries, model.py:757), the value ``Model`` uses on the host path.
+    ``device_spectrum``: as for ``candidate_dopt``."""
     st = candidate_states(engine, candidates, T, freq, device=True)
     if engine.friction:
         import torch
 
         st["sign"] = torch.tanh(st["dq"] / float(friction_sign_threshold))
-    return candidate_dopt(engine, st, len(candidates), independent_cols, dopt_regularization, YtY_prior=YtY_prior)
+    return candidate_dopt(engine, st, len(candidates), independent_cols, dopt_regularization, YtY_prior=YtY_prior, device_spectrum=device_spectrum)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -657,43 +661,58 @@ def _collision_block(engine, states, ncand, config, collision, suspended=None):
 
 
 def candidate_objectives(engine, states: dict, ncand: int, independent_cols, x_std, limits: dict, joint_names, config: dict, dopt_scale=None,
-                         YtY_prior=None, vel_sign=None, collision=None, suspended=None) -> dict:
+                         YtY_prior=None, vel_sign=None, collision=None, suspended=None, device_spectrum: bool = False) -> dict:
     """``objectives_from_extrema`` of ``ncand`` equal candidates stacked in ``states``: one ``gram_grouped`` (D-optimality, lambda_max,
     n_observable per candidate with ``doptRegularization``, default 1e-4) and one ``candidate_extrema`` (the a-priori torques of ``x_std``
     reduced on the device) over the same states.  ``vel_sign``: Stribeck friction, as for ``Engine.inverse_dynamics``.  ``collision``
     (``flobaroid_amd.collision.collision_set``: capsules, pairs, margins): the collision block of capsule mode is appended to ``g``
     (``candidate_collision_constraints``); None: no collision block, every array as without the argument.  ``suspended``: not None says
     that ``states`` carry the simulated base motion (``candidate_states(..., suspended=)``: ``rpy``, ``base_vel``, ``base_acc``, and
-    ``base_position`` for the collision block); ``floatingBaseAttachment: "suspended"`` is then accepted."""
+    ``base_position`` for the collision block); ``floatingBaseAttachment: "suspended"`` is then accepted.  ``device_spectrum=True``: the
+    D-optimality terms come from one ``Engine.dopt_terms`` call on the grouped Gram where ``gram_grouped`` left it -- with device states
+    only per-candidate numbers reach the host; False (default): the Gram is brought to the host for ``eigvalsh``, every array as before.
+    The keyword with ``useBasisProjection`` in ``config`` raises: the host route serves that case."""
     return _candidate_objective_parts(engine, states, ncand, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign,
-                                      collision, suspended)[0]
+                                      collision, suspended, device_spectrum)[0]
 
 
 def _candidate_objective_parts(engine, states, ncand, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign, collision,
-                               suspended=None):
-    """``candidate_objectives`` together with what the gradients reuse: (result, the grouped Gram on the host, the collision block or None)"""
+                               suspended=None, device_spectrum=False, with_weights=False):
+    """``candidate_objectives`` together with what the gradients reuse: (result, the grouped Gram on the host -- under ``device_spectrum``
+    where ``gram_grouped`` left it, a tensor for device states --, the collision block or None, the weight matrices or None).
+    ``with_weights`` (under ``device_spectrum``): the one ``Engine.dopt_terms`` call also forms -2 (M + delta I)^-1, in the memory space of
+    the Gram, for the caller to scale by ``dopt_scale``, which is known only after the terms."""
     _check_config(config, suspended)
-    G = _host(engine.gram_grouped(states, int(ncand)))
-    nld, _, nobs = est.d_optimality_batch_terms(G, independent_cols, config.get("doptRegularization", 1e-4), YtY_prior)
+    Cm = None
+    if device_spectrum:
+        _refuse_basis_projection(config)
+        G = engine.gram_grouped(states, int(ncand))
+        t = engine.dopt_terms(G, independent_cols, config.get("doptRegularization", 1e-4), prior=YtY_prior, weights=bool(with_weights))
+        nld, nobs, Cm = _host(t["neg_log_det"]), _host(t["n_observable"]), t.get("Cmat")
+    else:
+        G = _host(engine.gram_grouped(states, int(ncand)))
+        nld, _, nobs = est.d_optimality_batch_terms(G, independent_cols, config.get("doptRegularization", 1e-4), YtY_prior)
     ext = engine.candidate_extrema(states, int(ncand), x_std, vel_sign=vel_sign)
     coll = _collision_block(engine, states, ncand, config, collision, suspended)
-    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale, collision=coll, suspended=suspended), G, coll
+    return objectives_from_extrema(nld, nobs, ext, limits, joint_names, config, dopt_scale, collision=coll, suspended=suspended), G, coll, Cm
 
 
 def candidate_objectives_from_coefficients(engine, candidates: list, T: int, freq: float, model_or_x_std, independent_cols, limits: dict,
-                                           joint_names, config: dict, dopt_scale=None, YtY_prior=None, collision=None, suspended=None) -> dict:
+                                           joint_names, config: dict, dopt_scale=None, YtY_prior=None, collision=None, suspended=None,
+                                           device_spectrum: bool = False) -> dict:
     """``candidate_objectives`` from Fourier coefficients (``fourier_coefficients`` dicts): states generated on the device
     (``candidate_states``), the Coulomb column tanh(dq / ``frictionSignThreshold``) as ``candidate_dopt_from_coefficients`` sets it and
     ``vel_sign`` = dq under Stribeck friction -- only per-candidate arrays come back to the host.  ``model_or_x_std``: the a-priori standard
     parameters, or an object with ``xStdModel`` (``Model``).  ``suspended`` (``suspended_spec``): the base motion of every candidate is
     simulated on the device (``candidate_states(..., suspended=)``) and ``floatingBaseAttachment: "suspended"`` accepted; None: the
-    stationary base, and that configuration is refused."""
+    stationary base, and that configuration is refused.  ``device_spectrum``: as for ``candidate_objectives`` -- True keeps the Grams in
+    HBM, so that only per-candidate numbers reach the host."""
     _check_config(config, suspended)
     x_std = getattr(model_or_x_std, "xStdModel", model_or_x_std)
     st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02), suspended)
     vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
     return candidate_objectives(engine, st, len(candidates), independent_cols, x_std, limits, joint_names, config, dopt_scale=dopt_scale,
-                                YtY_prior=YtY_prior, vel_sign=vel_sign, collision=collision, suspended=suspended)
+                                YtY_prior=YtY_prior, vel_sign=vel_sign, collision=collision, suspended=suspended, device_spectrum=device_spectrum)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -704,6 +723,14 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
 # come from the swung states; the sweeps run at the rest base (``suspended_base="identity"``, the reference's rule: rest_base_states) or at the
 # swung states held fixed (``"held"``).  Neither differentiates the base motion itself, as the reference does not.
 # ------------------------------------------------------------------------------------------------------------------------------------
+def _refuse_basis_projection(config) -> None:
+    """``device_spectrum=True`` covers YBase = Y[:, independent_cols] only: a configuration that switches ``useBasisProjection`` on (a
+    truthy value; ``Model`` itself sets the key to 0) is refused"""
+    if config.get("useBasisProjection"):
+        raise ValueError("device_spectrum=True does not cover useBasisProjection (a basis-projection matrix B: YBase = Y B): the host route "
+                         "(device_spectrum=False, dopt_weight_matrices(..., B=B)) serves that case")
+
+
 def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4, dopt_scale=1.0, YtY_prior=None, B=None):
     """The constant matrices of ``Engine.regressor_weights`` for C candidates from their Grams ``G`` (C, Pa, Pa) (``Engine.gram_grouped``):
     returns ``(Cmat, cols)``, ``Cmat`` (C, ncols, ncols), such that ``W_c = Y_c[:, cols] @ Cmat[c]`` are the reference's weight rows
@@ -743,7 +770,7 @@ def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4,
 def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, freq: float, independent_cols, dopt_regularization: float = 1e-4,
                                               dopt_scale=None, YtY_prior=None, epsilon: float = 1e-7, subsample: int = 1,
                                               friction_sign_threshold: float = 0.02, max_weight_bytes: int = 2**31, suspended=None,
-                                              suspended_base: str = "identity"):
+                                              suspended_base: str = "identity", device_spectrum: bool = False):
     """D-optimality term and its gradient for every candidate (``fourier_coefficients`` dicts) without a sample leaving the device:
     coefficients -> states (``fbr_fourier_states``) -> one Gram per candidate (``fbr_gram_grouped``) -> ``dopt_weight_matrices`` on the host
     -> for chunks of whole candidates whose weight rows fit ``max_weight_bytes``: ``regressor_weights`` -> ``fd_scores`` -> forward
@@ -762,12 +789,22 @@ def candidate_dopt_gradient_from_coefficients(engine, candidates: list, T: int, 
     (``candidate_states(..., suspended=)``); the Gram, f, C and the weight rows take those swung states.  ``suspended_base``: where the
     sweep runs -- ``"identity"`` (default, the reference's rule, analyticalGradient.py:80-81, 107-111): the same q, dq, ddq and sign with
     rpy, base_vel and base_acc zero (``rest_base_states``); ``"held"``: the swung states, i.e. the partial derivative with the simulated
-    base trajectory frozen.  Neither differentiates the base motion.  Any other value, or ``"held"`` without ``suspended=``, raises."""
+    base trajectory frozen.  Neither differentiates the base motion.  Any other value, or ``"held"`` without ``suspended=``, raises.
+
+    ``device_spectrum=True``: f and the matrices C come from one ``Engine.dopt_terms(..., weights=True)`` on the Grams in HBM and C goes to
+    ``regressor_weights`` as a tensor -- only per-candidate numbers cross PCIe; False (default): the host route above, every array as
+    before."""
     rest = _suspended_rule(suspended, suspended_base)
     st = _coefficient_states(engine, candidates, T, freq, friction_sign_threshold, suspended)
+    scale = 1.0 if dopt_scale is None else float(dopt_scale)
+    if device_spectrum:
+        G = engine.gram_grouped(st, len(candidates))
+        terms = engine.dopt_terms(G, independent_cols, dopt_regularization, prior=YtY_prior, scale=scale, weights=True)
+        Cm = terms["Cmat"]
+        return _host(terms["neg_log_det"]) * scale, _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale,
+                                                                  YtY_prior, epsilon, subsample, max_weight_bytes, rest_base=rest, weights=Cm)
     G = _host(engine.gram_grouped(st, len(candidates)))
     nld = est.d_optimality_batch(G, independent_cols, dopt_regularization, YtY_prior)
-    scale = 1.0 if dopt_scale is None else float(dopt_scale)
     return nld * scale, _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale, YtY_prior, epsilon, subsample,
                                        max_weight_bytes, rest_base=rest)
 
@@ -790,15 +827,19 @@ def _gradient_dict(g, n: int, nh: int) -> dict:
 
 
 def _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, dopt_regularization, scale, YtY_prior, epsilon, subsample, max_weight_bytes,
-                   rest_base=False):
+                   rest_base=False, weights=None):
     """the gradient dict of ``candidate_dopt_gradient_from_coefficients`` from the candidates' device states and grouped Gram;
-    ``rest_base``: the weights from ``st``, the scores from its rest-base view"""
+    ``rest_base``: the weights from ``st``, the scores from its rest-base view; ``weights``: the matrices C when the caller has them
+    (``Engine.dopt_terms``: ``G`` is then not read), else ``dopt_weight_matrices`` forms them on the host"""
     import torch
 
     C = len(candidates)
     n = engine.n
     T, k = int(T), max(int(subsample), 1)
-    Cm, cols = dopt_weight_matrices(G, independent_cols, dopt_regularization, scale, YtY_prior)
+    if weights is not None:
+        Cm, cols = weights, np.asarray(independent_cols, dtype=np.int32)
+    else:
+        Cm, cols = dopt_weight_matrices(G, independent_cols, dopt_regularization, scale, YtY_prior)
     Ts = (T + k - 1) // k
     if k > 1:
         st = {key: v.reshape(C, T, -1)[:, ::k].reshape(C * Ts, -1).contiguous() for key, v in st.items()}
@@ -1204,7 +1245,7 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
                                           config: dict, dopt_scale=None, YtY_prior=None, collision=None, epsilon=None, subsample: int = 1,
                                           box_gradient: bool = False, hull_gradient: bool = False, mesh_gradient: bool = False,
                                           large_hull_gradient: bool = False, large_mesh_gradient: bool = False, suspended=None,
-                                          suspended_base: str = "identity") -> dict:
+                                          suspended_base: str = "identity", device_spectrum: bool = False) -> dict:
     """Objective, constraints and both their gradients for every candidate (``fourier_coefficients`` dicts) -- what ``IpoptProblem.gradient``
     and ``.jacobian`` (optimizer.py:386-416) need, ``compute_analytical_gradient`` for a whole batch -- without a sample leaving the device:
     one ``candidate_states``; ``candidate_objectives`` (f, g, the extrema's indices); the D-optimality gradient
@@ -1246,9 +1287,16 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     ``"held"`` -- both sweeps run at the swung states, the partial derivative with the simulated base trajectory frozen.  The collision
     rows hold the base at the pose of the winning evaluation under both (``candidate_collision_gradient``).  Neither rule differentiates
     the base motion (the coupling through the base dynamics is neglected, as in the reference), so a clamp event does not invalidate a
-    row: it only says that the frozen trajectory has a kink there.  None: the stationary base, and that configuration is refused."""
+    row: it only says that the frozen trajectory has a kink there.  None: the stationary base, and that configuration is refused.
+
+    ``device_spectrum=True``: the D-optimality terms and the matrices C of the weight rows come from ONE ``Engine.dopt_terms(...,
+    weights=True)`` on the Grams in HBM, C scaled by ``dopt_scale`` where it lies: neither the Grams nor C cross PCIe; a candidate whose
+    Gram is not finite then raises ``np.linalg.LinAlgError`` (``Engine.dopt_terms``).  False (default):
+    the host route, every array as before.  The keyword with ``useBasisProjection`` in ``config`` raises."""
     rest = _suspended_rule(suspended, suspended_base)
     _check_config(config, suspended)
+    if device_spectrum:
+        _refuse_basis_projection(config)
     if large_mesh_gradient and collision is None:
         raise ValueError("large_mesh_gradient=True: no collision set (collision=)")
     tree_rows = collision is not None and _wants_large_mesh_gradient(config, collision, large_mesh_gradient)
@@ -1274,11 +1322,11 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02), suspended, with_info=suspended is not None)
     info = st.pop("suspended_info", None)
     vel_sign = st["dq"] if getattr(engine, "stribeck", 0.0) > 0 else None
-    obj, G, coll = _candidate_objective_parts(engine, st, C, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign,
-                                              collision, suspended)
+    obj, G, coll, Cm = _candidate_objective_parts(engine, st, C, independent_cols, x_std, limits, joint_names, config, dopt_scale, YtY_prior, vel_sign,
+                                                  collision, suspended, device_spectrum, with_weights=device_spectrum)
     ag = obj["ag_cache"]
     dopt = _dopt_gradient(engine, st, G, candidates, T, freq, independent_cols, config.get("doptRegularization", 1e-4), obj["dopt_scale"], YtY_prior,
-                          eps, subsample, 2**31, rest_base=rest)
+                          eps, subsample, 2**31, rest_base=rest, weights=None if Cm is None else Cm * obj["dopt_scale"])
     ok = ~obj["failed"]
     dopt = {k: np.where(ok.reshape((C,) + (1,) * (v.ndim - 1)), v, 0.0) for k, v in dopt.items()}
     jac = {k: _host(v) for k, v in candidate_torque_jacobians(engine, st, C, ag["torque_absmax_idx"], x_std, eps, vel_sign=vel_sign,

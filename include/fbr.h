@@ -90,7 +90,7 @@ typedef struct {
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
  * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes;
  * fbr_mesh_distance_gradients; fbr_model_set_large_hulls, option "hull_large_all"; fbr_large_hull_distance_gradients, option
- * "hull_grad_tile"; fbr_model_set_large_hull_meshes; fbr_large_mesh_distance_gradients, option "mesh_grad_order". */
+ * "hull_grad_tile"; fbr_model_set_large_hull_meshes; fbr_large_mesh_distance_gradients, option "mesh_grad_order"; fbr_dopt_terms (with FBR_MAX_DOPT_COLUMNS). */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -573,6 +573,26 @@ int fbr_fd_scores(fbr_model *m, const fbr_states *st, const double *W, double ep
  */
 int fbr_regressor_weights(fbr_model *m, const fbr_states *st, int32_t ngroups, const int32_t *cols, int32_t ncols, const double *C, double *W,
                           int32_t mem);
+
+/*
+ * The D-optimality arithmetic of ngroups candidates from their Grams G [ngroups][Pa][Pa] (fbr_gram_grouped), on the device: per candidate c
+ *   M_c = G_c[cols, cols] (+ prior),  only its LOWER triangle is read (what numpy.linalg.eigvalsh reads),
+ *   eig_c: the eigenvalues of M_c, ascending (Householder tridiagonalisation, bisection on Sturm counts: absolute error of order
+ *          eps |M_c|, LAPACK's error model; M_c is first scaled by a power of two, so the spectrum of 2^k G is exactly 2^k times that of G),
+ *   terms[c] = { neg_log_det = -sum_i log(max(eig_i + delta, 1e-300)),  lambda_max = eig_{n-1},  delta = reg max(lambda_max, 1e-30),
+ *                n_observable = #(eig_i > delta) }       (excitation/trajectoryOptimizer.py:263-277),
+ *   Cmat[c] = -2 scale[c] (M_c + delta I)^-1, exactly symmetric (Cholesky; analyticalGradient.py:538-565): the C of fbr_regressor_weights.
+ * cols [ncols]: host, distinct, any order, 0 <= col < Pa;  prior [ncols][ncols] in `mem` space like G, or NULL;  scale [ngroups]: host, or
+ * NULL (= 1);  terms [ngroups][4], status [ngroups] or NULL, eig [ngroups][ncols] or NULL, Cmat [ngroups][ncols][ncols] or NULL: `mem` space.
+ * status[c]: 0, or bit 1 (value 1): M_c has a non-finite entry -- the candidate's terms, eig and Cmat are NaN, n_observable 0 --, bit 2
+ * (value 2): a pivot of the factorisation was not positive (reg = 0 on a singular matrix): Cmat[c] is NaN, its terms stand.  One
+ * candidate's outputs depend on nothing but that candidate: no atomics, fixed summation orders, the same bits on every run, in both
+ * memory spaces and with or without eig / Cmat.  One workgroup per candidate, chunks of at most 65535 candidates (csrc/fbr_dopt.h).
+ * FBR_E_INVALID: ngroups < 1, ncols outside 1 .. min(Pa, FBR_MAX_DOPT_COLUMNS), an index out of range or twice, reg negative or not finite.
+ */
+#define FBR_MAX_DOPT_COLUMNS 512
+int fbr_dopt_terms(fbr_model *m, const double *G, int32_t ngroups, int32_t Pa, const int32_t *cols, int32_t ncols, const double *prior, double reg,
+                   const double *scale, double *terms, int32_t *status, double *eig, double *Cmat, int32_t mem);
 
 /*
  * Joint states of ncand candidate trajectories, T samples each, generated ON THE DEVICE from their Fourier coefficients -- the
