@@ -186,6 +186,11 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _ip, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double, _dp,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
     ),
+    "fbr_dopt_observability": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _ip, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32],
+    ),
     "fbr_fourier_gradient": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp, _dp, _dp, _dp, ctypes.c_void_p,
@@ -1211,6 +1216,63 @@ class Engine:
                                             f"(status {st[st != 0].tolist()}: 1 = a non-finite Gram, 2 = M + delta I is not positive definite)")
                 err.status = st.copy()  # every candidate's status word
                 raise err
+        if device_out is not None and bool(device_out) != (mem == FBR_DEVICE):
+            out = {k: (torch.from_numpy(np.ascontiguousarray(v)).to(f"cuda:{self.device}") if device_out else v.cpu().numpy()) for k, v in out.items()}
+        elif mem == FBR_HOST:
+            out = {k: np.ascontiguousarray(v) for k, v in out.items()}
+        return out
+
+    def dopt_observability(self, G, cols, threshold: float = 1e-6, prior=None, eigenvalues: bool = False, vectors: bool = False,
+                           device_out: bool | None = None) -> dict:
+        """The observability analysis of C candidates from their Grams ``G`` (C, Pa, Pa) on the device (``fbr_dopt_observability``): what
+        the reference runs on ``YBase`` by SVD (trajectory.py:225-264), from the eigenpairs of ``M = G[cols, cols] (+ prior)``.  Per
+        candidate ``n_observable`` (int64; the eigenvalues not below ``threshold**2 * lambda_max``), ``energy`` (C, ncols) (the squared
+        components of the unobservable eigenvectors per column), ``margin`` (the relative distance of the nearest eigenvalue from that
+        cut) and ``status`` (int32; bit 1: a non-finite entry, the candidate's numbers are NaN; bit 4: an eigenvalue lies within the
+        error band of the cut, its classification is not decided by the fp64 Gram; bit 8: the QL iteration did not converge, ``energy``
+        and ``vec`` of that candidate are NaN).  ``eigenvalues``: also ``eig`` (C, ncols), bit for bit that of ``dopt_terms``;
+        ``vectors``: also ``vec`` (C, ncols, ncols), ``vec[c, :, i]`` the eigenvector of ``eig[c, i]``, its largest component positive.
+        A ``threshold`` outside (0, 1) or with ``threshold**2 < 8 max(128, ncols) 2**-52`` is refused.  Memory spaces: as ``dopt_terms``."""
+        import torch
+
+        Gr = _Ref(G, name="G")
+        if len(Gr.obj.shape) != 3 or Gr.obj.shape[1] != Gr.obj.shape[2]:
+            raise ValueError(f"G: expected (C, Pa, Pa), got {tuple(Gr.obj.shape)}")
+        C, Pa = int(Gr.obj.shape[0]), int(Gr.obj.shape[1])
+        mem = Gr.mem
+        if mem == FBR_DEVICE:
+            self._sync_torch()
+        ca = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        n = int(ca.size)
+        pr = _Ref(None)
+        if prior is not None:
+            if _is_torch(prior):
+                prior = prior.reshape(n, n).cpu() if mem == FBR_HOST else prior.reshape(n, n).to(f"cuda:{self.device}")
+            else:
+                prior = np.ascontiguousarray(prior, dtype=np.float64).reshape(n, n)
+                if mem == FBR_DEVICE:
+                    prior = torch.from_numpy(prior).to(f"cuda:{self.device}")
+            pr = _Ref(prior, (n, n), "prior")
+        ok = C >= 1 and 1 <= n <= min(Pa, FBR_MAX_DOPT_COLUMNS)  # (else the call refuses before it touches an output: tiny stand-ins)
+        Cs, ns = max(C, 1), (n if ok else 1)
+        gr, energy = self._out(None, (Cs, ns), mem)
+        mr, margin = self._out(None, (Cs,), mem)
+        er, eig = self._out(None, (C, n), mem) if eigenvalues and ok else (_Ref(None), None)
+        vr, vec = self._out(None, (C, n, n), mem) if vectors and ok else (_Ref(None), None)
+        if mem == FBR_DEVICE:
+            words = torch.empty((2, Cs), dtype=torch.int32, device=f"cuda:{self.device}")  # (the kernel writes every word)
+            nptr, sptr = words[0].data_ptr(), words[1].data_ptr()
+        else:
+            words = np.zeros((2, Cs), dtype=np.int32)
+            nptr, sptr = words[0].ctypes.data, words[1].ctypes.data
+        _check(self._lib.fbr_dopt_observability(self._h, Gr.ptr, C, Pa, ca.ctypes.data_as(_ip), n, pr.ptr, float(threshold), nptr, gr.ptr, mr.ptr,
+                                                er.ptr, vr.ptr, sptr, mem), "fbr_dopt_observability")
+        out = {"n_observable": words[0].to(torch.int64) if mem == FBR_DEVICE else words[0].astype(np.int64), "energy": energy, "margin": margin,
+               "status": words[1]}
+        if eigenvalues:
+            out["eig"] = eig
+        if vectors:
+            out["vec"] = vec
         if device_out is not None and bool(device_out) != (mem == FBR_DEVICE):
             out = {k: (torch.from_numpy(np.ascontiguousarray(v)).to(f"cuda:{self.device}") if device_out else v.cpu().numpy()) for k, v in out.items()}
         elif mem == FBR_HOST:

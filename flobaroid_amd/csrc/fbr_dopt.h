@@ -86,8 +86,11 @@ FBR_HD void fbr_dopt_gather(const FbrDoptLanes &L, const FbrDoptIn &in, int k, d
     FBR_DOPT_SYNC();
 }
 
-// Stage 1 (second half): A -> tridiagonal d [n], e [n - 1].  xs, vs, ps, ws: [n] of shared memory each.
-FBR_HD void fbr_dopt_tridiagonal(const FbrDoptLanes &L, int n, double *A, double *d, double *e, double *xs, double *vs, double *ps, double *ws)
+// Stage 1 (second half): A -> tridiagonal d [n], e [n - 1].  xs, vs, ps, ws: [n] of shared memory each.  taus ([n] of shared memory, or
+// null): the reflectors are kept for fbr_dopt_form_qt -- tau_k in taus[k] (0: H_k = I) and v_k[k + 2 .. n) in row k of A beyond column
+// k + 1, which nothing reads after step k (v_k[k + 1] = 1 is implicit).  d and e are the same bits with and without.
+FBR_HD void fbr_dopt_tridiagonal(const FbrDoptLanes &L, int n, double *A, double *d, double *e, double *xs, double *vs, double *ps, double *ws,
+                                 double *taus = nullptr)
 {
 #pragma clang fp contract(off)
     for (int k = 0; k + 2 < n; k++) {
@@ -99,7 +102,10 @@ FBR_HD void fbr_dopt_tridiagonal(const FbrDoptLanes &L, int n, double *A, double
         for (int j = k + 2; j < n; j++) sigma += xs[j] * xs[j];
         if (!(sigma > 0.0)) {  // the column is already tridiagonal: H = I
             FBR_DOPT_LANES(t)
-            if (t == 0) d[k] = A[(long)k * n + k], e[k] = alpha;
+            if (t == 0) {
+                d[k] = A[(long)k * n + k], e[k] = alpha;
+                if (taus) taus[k] = 0.0;
+            }
             FBR_DOPT_SYNC();
             continue;
         }
@@ -108,7 +114,10 @@ FBR_HD void fbr_dopt_tridiagonal(const FbrDoptLanes &L, int n, double *A, double
         FBR_DOPT_LANES(t)
         {
             for (int j = k + 1 + t; j < n; j += L.nt) vs[j] = j == k + 1 ? 1.0 : xs[j] * sc;
-            if (t == 0) d[k] = A[(long)k * n + k], e[k] = beta;
+            if (t == 0) {
+                d[k] = A[(long)k * n + k], e[k] = beta;
+                if (taus) taus[k] = tau;
+            }
         }
         FBR_DOPT_SYNC();
         FBR_DOPT_LANES(t)
@@ -128,6 +137,7 @@ FBR_HD void fbr_dopt_tridiagonal(const FbrDoptLanes &L, int n, double *A, double
         for (int c = k + 1 + t; c < n; c += L.nt) {
             const double wc = ws[c], vc = vs[c];
             for (int r = k + 1; r < n; r++) A[(long)r * n + c] -= vs[r] * wc + ws[r] * vc;  // (a + b == b + a: A stays symmetric)
+            if (taus && c >= k + 2) A[(long)k * n + c] = vc;
         }
         FBR_DOPT_SYNC();
     }
@@ -353,7 +363,285 @@ FBR_HD void fbr_dopt_candidate(const FbrDoptLanes &L, const FbrDoptIn &in, doubl
     if (t == 0 && status) *status = st;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Eigenvectors and the observability analysis (fbr_dopt_observability, fbr.h; the reference's trajectory.py:225-264 on the Gram).
+//   4. W = Q^T = H_{n-3} .. H_0 from the kept reflectors, one lane per column of W (fbr_dopt_form_qt): T = Q^T A Q, so the eigenvectors of
+//      A are the ROWS of Z^T Q^T with Z those of T.  W is stored that way round -- the transpose of LAPACK's Z -- so that a plane rotation
+//      of two eigenvectors touches two rows and consecutive lanes sit on consecutive addresses.
+//   5. implicit QL with Wilkinson shifts on (d, e) (EISPACK tql2's recurrence, the block found again before every sweep as dsteqr does):
+//      lane 0 runs the scalar recurrence of a sweep and stages its rotations in cs, sn; after a barrier lane r applies them to column r of
+//      W.  An off-diagonal counts as zero below eps (|d_l| + |e_l|)_max: absolute accuracy eps |A|, which is what the residual is held to;
+//      orthogonality is that of a product of rotations, of order n eps also inside clusters.  At most 30 n sweeps in all, a bound fixed
+//      before the loop; past it FBR_DOPT_NO_CONVERGENCE and NaN vectors and energy (nothing spins).
+//   6. the eigenvalues REPORTED stay those of the bisection, bit for bit what fbr_dopt_terms gives; the pairs of the QL run are ranked
+//      ascending (ties by index) and paired with them by index.  Every vector's component of largest magnitude, the first at a tie, is
+//      positive.
+//   7. lm = max(eig_max, 0), cut = thr^2 lm; index i is unobservable iff max(eig_i, 0) < cut (S_i < thr S_0 with S^2 = max(eig, 0): the
+//      zero matrix has nothing unobservable); energy[j] = sum over unobservable i, ascending, of V[j][i]^2; n_observable = n - their
+//      number; margin = min_i |eig_i - cut| / cut (+inf when cut = 0).
+// The limit of the Gram route: an eigenvalue of M is known to about band(n) eig_max, band(n) = max(128, n) 2^-52 (no smaller than the bar
+// the eigenvalues are held to, tests/dopt_reference.py bar_lambda, for every n <= 512), i.e. a singular value of YBase only down to
+// sqrt(band) S_0, about 2e-7 S_0.  An eigenvalue within band(n) lm of the cut sets FBR_DOPT_AMBIGUOUS: fp64 Gram arithmetic does not decide
+// that index (the numbers are returned all the same), and the entry point refuses thr^2 < 8 band(n).  Agreement with an SVD of YBase for
+// singular values between 1e-8 S_0 and the threshold is a property of the Gram, not of this kernel.
+// ------------------------------------------------------------------------------------------------------------------------------------
+#define FBR_DOPT_AMBIGUOUS 4
+#define FBR_DOPT_NO_CONVERGENCE 8
+#define FBR_DOPT_OBS_SHARED (9 * FBR_MAX_DOPT_COLUMNS)  // doubles of LDS a workgroup of the observability kernel needs
+
+FBR_HD double fbr_dopt_band(int n) { return (n > 128 ? n : 128) * DBL_EPSILON; }
+
+// sqrt(a^2 + b^2) without overflow, from +, *, /, sqrt alone (the same bits on the host and the device)
+FBR_HD double fbr_dopt_pythag(double a, double b)
+{
+#pragma clang fp contract(off)
+    const double x = fabs(a), y = fabs(b), hi = x > y ? x : y, lo = x > y ? y : x;
+    if (hi == 0.0) return 0.0;
+    const double q = lo / hi;
+    return hi * sqrt(1.0 + q * q);
+}
+
+// Stage 4: W [n][n] = H_{n-3} .. H_0 from the reflectors fbr_dopt_tridiagonal kept in A and taus.  Lane c owns column c: no barrier inside.
+FBR_HD void fbr_dopt_form_qt(const FbrDoptLanes &L, int n, const double *A, const double *taus, double *W)
+{
+#pragma clang fp contract(off)
+    FBR_DOPT_LANES(t)
+    for (int c = t; c < n; c += L.nt) {
+        for (int r = 0; r < n; r++) W[(long)r * n + c] = r == c ? 1.0 : 0.0;
+        for (int k = 0; k + 2 < n; k++) {
+            const double tau = taus[k];
+            if (tau == 0.0) continue;
+            const double *v = A + (long)k * n;
+            double s = W[(long)(k + 1) * n + c];
+            for (int j = k + 2; j < n; j++) s += v[j] * W[(long)j * n + c];
+            s *= tau;
+            W[(long)(k + 1) * n + c] -= s;
+            for (int j = k + 2; j < n; j++) W[(long)j * n + c] -= v[j] * s;
+        }
+    }
+    FBR_DOPT_SYNC();
+}
+
+// Stage 5: implicit QL on (d, e [n], e[n - 1] unused on entry); the rows of W are rotated along: on return row i of W is the eigenvector
+// of d[i] (unsorted).  cs, sn, ctl: [n] of shared memory each.  Returns 0 or FBR_DOPT_NO_CONVERGENCE.
+FBR_HD int fbr_dopt_ql(const FbrDoptLanes &L, int n, double *d, double *e, double *cs, double *sn, double *ctl, double *W)
+{
+#pragma clang fp contract(off)
+    const int maxit = 30 * n;  // sweeps in all
+    int l = 0;                 // (lane 0's: the row being worked on, the sum of the shifts, the running magnitude)
+    double f = 0.0, tst1 = 0.0;
+    bool fresh = true;
+    int fail = 0;
+    for (int it = 0; it <= maxit; it++) {
+        FBR_DOPT_LANES(t)
+        if (t == 0) {
+            if (it == 0) e[n - 1] = 0.0;
+            int m = l;
+            while (l < n) {
+                if (fresh) tst1 = fmax(tst1, fabs(d[l]) + fabs(e[l])), fresh = false;
+                for (m = l; m < n - 1; m++)
+                    if (fabs(e[m]) <= DBL_EPSILON * tst1) break;
+                if (m > l) break;
+                d[l] += f;
+                l++, fresh = true;
+            }
+            if (l >= n) {
+                ctl[0] = -1.0;
+            } else if (it == maxit) {
+                ctl[0] = -2.0;
+            } else {
+                // the shift
+                double g = d[l], p = (d[l + 1] - g) / (2.0 * e[l]);
+                double r = fbr_dopt_pythag(p, 1.0);
+                if (p < 0.0) r = -r;
+                d[l] = e[l] / (p + r);
+                d[l + 1] = e[l] * (p + r);
+                const double dl1 = d[l + 1];
+                double h = g - d[l];
+                for (int i = l + 2; i < n; i++) d[i] -= h;
+                f += h;
+                // the sweep, from the bottom of the block up
+                p = d[m];
+                double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
+                const double el1 = e[l + 1];
+                for (int i = m - 1; i >= l; i--) {
+                    c3 = c2, c2 = c, s2 = s;
+                    g = c * e[i];
+                    h = c * p;
+                    r = fbr_dopt_pythag(p, e[i]);
+                    e[i + 1] = s * r;
+                    s = e[i] / r;
+                    c = p / r;
+                    p = c * d[i] - s * g;
+                    d[i + 1] = h + s * (c * g + s * d[i]);
+                    cs[i] = c, sn[i] = s;
+                }
+                p = -s * s2 * c3 * el1 * e[l] / dl1;
+                e[l] = s * p;
+                d[l] = c * p;
+                ctl[0] = (double)l, ctl[1] = (double)m;
+            }
+        }
+        FBR_DOPT_SYNC();
+        const double c0 = ctl[0];
+        if (c0 < 0.0) {
+            fail = c0 < -1.5 ? FBR_DOPT_NO_CONVERGENCE : 0;
+            break;
+        }
+        const int lo = (int)c0, hi = (int)ctl[1];
+        FBR_DOPT_LANES(t)
+        for (int r = t; r < n; r += L.nt) {
+            double up = W[(long)hi * n + r];  // row i + 1, as the rotations above it left it
+            for (int i = hi - 1; i >= lo; i--) {
+                const double c = cs[i], s = sn[i], w = W[(long)i * n + r];
+                W[(long)(i + 1) * n + r] = s * w + c * up;
+                up = c * w - s * up;
+            }
+            W[(long)lo * n + r] = up;
+        }
+        FBR_DOPT_SYNC();
+    }
+    FBR_DOPT_SYNC();  // (ctl is written again by the caller)
+    return fail;
+}
+
+struct FbrDoptObsOut {
+    int *n_observable;  // [1]
+    double *energy;     // [n]
+    double *margin;     // [1] or null
+    double *eig;        // [n] or null
+    double *vec;        // [n][n] or null: vec[j][i] = component j of the eigenvector of eig[i]
+    int *status;        // [1] or null
+};
+
+// One candidate of fbr_dopt_observability.  A, W: [n][n] scratch each; sh: FBR_DOPT_OBS_SHARED doubles of shared memory.
+FBR_HD void fbr_dopt_obs_candidate(const FbrDoptLanes &L, const FbrDoptIn &in, double thr, double *A, double *W, double *sh, const FbrDoptObsOut &o)
+{
+#pragma clang fp contract(off)
+    const int n = in.n;
+    double *d = sh, *e = sh + FBR_MAX_DOPT_COLUMNS, *xs = e + FBR_MAX_DOPT_COLUMNS, *vs = xs + FBR_MAX_DOPT_COLUMNS, *ps = vs + FBR_MAX_DOPT_COLUMNS,
+           *ws = ps + FBR_MAX_DOPT_COLUMNS, *taus = ws + FBR_MAX_DOPT_COLUMNS, *cs = taus + FBR_MAX_DOPT_COLUMNS, *sn = cs + FBR_MAX_DOPT_COLUMNS;
+    // (the scan and the scaling are those of fbr_dopt_candidate, so that eig is bit for bit what fbr_dopt_terms reports)
+    FBR_DOPT_LANES(t)
+    {
+        double am = 0.0, bad = 0.0;
+        for (int r = t; r < n; r += L.nt)
+            for (int c = 0; c <= r; c++) {
+                const double v = fbr_dopt_entry(in, r, c);
+                if (!fbr_dopt_finite(v)) bad = 1.0;
+                am = fmax(am, fabs(v));
+            }
+        ps[t] = am;
+        ws[t] = bad;
+    }
+    FBR_DOPT_SYNC();
+    double amax = 0.0;
+    bool bad = false;
+    for (int t = 0; t < L.nt; t++) {
+        amax = fmax(amax, ps[t]);
+        bad = bad || ws[t] != 0.0;
+    }
+    FBR_DOPT_SYNC();
+    if (bad) {
+        FBR_DOPT_LANES(t)
+        {
+            if (t == 0) {
+                *o.n_observable = 0;
+                if (o.margin) *o.margin = NAN;
+                if (o.status) *o.status = FBR_DOPT_NONFINITE;
+            }
+            for (int j = t; j < n; j += L.nt) {
+                o.energy[j] = NAN;
+                if (o.eig) o.eig[j] = NAN;
+                if (o.vec)
+                    for (int r = 0; r < n; r++) o.vec[(long)r * n + j] = NAN;
+            }
+        }
+        return;
+    }
+    int k2 = 0;
+    if (amax > 0.0) {
+        int ex;
+        (void)frexp(amax, &ex);
+        k2 = 1 - ex;
+        if (k2 > 1022) k2 = 1022;
+    }
+    fbr_dopt_gather(L, in, k2, 0.0, A);
+    fbr_dopt_tridiagonal(L, n, A, d, e, xs, vs, ps, ws, taus);
+    fbr_dopt_bisect(L, n, d, e, ws, xs);  // xs: the eigenvalues of A, kept to the end
+    fbr_dopt_form_qt(L, n, A, taus, W);
+    const int fail = fbr_dopt_ql(L, n, d, e, cs, sn, ps, W);
+    // rank of every QL eigenvalue (ties by index) -> vs[rank] = its row of W; ws[row] = the sign that makes its largest component positive
+    FBR_DOPT_LANES(t)
+    for (int i = t; i < n; i += L.nt) {
+        const double di = d[i];
+        int rank = 0;
+        for (int j = 0; j < n; j++) rank += d[j] < di || (d[j] == di && j < i);
+        vs[rank] = (double)i;
+        const double *w = W + (long)i * n;
+        double big = 0.0, sg = 1.0;
+        for (int j = 0; j < n; j++)
+            if (fabs(w[j]) > big) big = fabs(w[j]), sg = w[j] < 0.0 ? -1.0 : 1.0;
+        ws[i] = sg;
+    }
+    FBR_DOPT_SYNC();
+    const double lmax = ldexp(xs[n - 1], -k2), lm = fmax(lmax, 0.0), cut = thr * thr * lm, band = fbr_dopt_band(n) * lm;
+    int nun = 0, amb = 0;
+    double mg = INFINITY;
+    for (int i = 0; i < n; i++) {
+        const double ev = ldexp(xs[i], -k2), dist = fabs(ev - cut);
+        nun += fmax(ev, 0.0) < cut;
+        if (cut > 0.0) mg = fmin(mg, dist / cut);
+        if (dist < band) amb = FBR_DOPT_AMBIGUOUS;
+    }
+    FBR_DOPT_LANES(t)
+    {
+        if (t == 0) {
+            *o.n_observable = n - nun;
+            if (o.margin) *o.margin = mg;
+            if (o.status) *o.status = amb | fail;
+        }
+        for (int j = t; j < n; j += L.nt) {
+            double s = 0.0;
+            for (int i = 0; i < nun; i++) {
+                const double v = W[(long)vs[i] * n + j];
+                s += v * v;
+            }
+            o.energy[j] = fail ? NAN : s;
+            if (o.eig) o.eig[j] = ldexp(xs[j], -k2);
+            if (o.vec)
+                for (int i = 0; i < n; i++) {
+                    const int row = (int)vs[i];
+                    o.vec[(long)j * n + i] = fail ? NAN : ws[row] * W[(long)row * n + j];
+                }
+        }
+    }
+}
+
 #if defined(__HIPCC__)
+struct DevDoptObs {
+    const double *G;      // [ngroups of the launch][Pa][Pa]
+    const double *prior;  // [n][n] or null
+    const int *cols;      // [n]
+    double *A;            // scratch [ngroups of the launch][2][n][n]
+    double *energy, *margin, *eig, *vec;
+    int *n_observable, *status;
+    int Pa, n;
+    double thr;
+};
+
+// (a kernel of its own: the terms-only launch below keeps its registers and its 24 KB of LDS)
+__global__ __launch_bounds__(256) void fbr_dopt_obs_kernel(DevDoptObs p)
+{
+    __shared__ double sh[FBR_DOPT_OBS_SHARED];
+    const long c = blockIdx.x, n = p.n;
+    const FbrDoptLanes L = {(int)threadIdx.x, (int)threadIdx.x + 1, (int)blockDim.x};
+    const FbrDoptIn in = {p.G + c * p.Pa * p.Pa, p.Pa, p.n, p.cols, p.prior, 0.0, 1.0};
+    const FbrDoptObsOut o = {p.n_observable + c, p.energy + c * n, p.margin ? p.margin + c : nullptr, p.eig ? p.eig + c * n : nullptr,
+                             p.vec ? p.vec + c * n * n : nullptr, p.status ? p.status + c : nullptr};
+    fbr_dopt_obs_candidate(L, in, p.thr, p.A + 2 * c * n * n, p.A + (2 * c + 1) * n * n, sh, o);
+}
+
 struct DevDopt {
     const double *G;      // [ngroups of the launch][Pa][Pa]
     const double *prior;  // [n][n] or null

@@ -392,3 +392,18 @@ def post_identify_friction(tau_residual_2d: np.ndarray, velocities: np.ndarray, 
         p = la.lstsq(A, b, rcond=None)[0]
         Fc[j], Fv[j], off[j] = p[0], max(p[1], 0.0), p[2]
     return {"Fc": Fc, "Fv": Fv, "off": off, "deadzone_kept": kept, "lambda_fv": lam, "fv_energy": fv_energy}
+
+
+def merge_unobservable_params(opt: dict, fields) -> list:
+    """The merge of identifier.py:1536-1562: the ``unobservable_params`` of a trajectory / measurement file (``fields``: an ``np.load``
+    result or a dict, e.g. ``excitation.observability_fields``) are added to ``opt['dontChangeParams']``, which pins them to their
+    a-priori values -- existing entries first, in their order, no index twice.  ``opt`` is changed only when something is added, as in
+    the reference; a file without the key changes nothing.  Returns the indices that were added."""
+    if "unobservable_params" not in fields:
+        return []
+    unobs = [int(p) for p in np.asarray(fields["unobservable_params"]).reshape(-1).tolist()]
+    existing = list(dict.fromkeys(int(p) for p in opt.get("dontChangeParams", [])))
+    new = [p for p in dict.fromkeys(unobs) if p not in set(existing)]
+    if new:
+        opt["dontChangeParams"] = existing + new
+    return new

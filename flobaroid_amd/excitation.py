@@ -21,7 +21,9 @@ and, for the analytical gradient, 1 + 3 n regressors per sample in a Python/iDyn
   (``Engine.box_distance_gradients``, ``Engine.hull_distance_gradients``, ``Engine.mesh_distance_gradients``);
 * ``candidate_gradients_from_coefficients`` -- everything ``IpoptProblem.gradient`` / ``.jacobian`` need of many candidates: the above plus
   the soft-cost gradients and the position, velocity and torque rows of the constraint Jacobian (analyticalGradient.py:764-953) from
-  ``Engine.torque_row_sweep`` + ``Engine.fourier_state_chain``.
+  ``Engine.torque_row_sweep`` + ``Engine.fourier_state_chain``;
+* ``candidate_observability`` -- the observability analysis the reference runs on the chosen trajectory (trajectory.py:225-264), per
+  candidate from ``Engine.gram_grouped`` + ``Engine.dopt_observability``; ``observability_fields``: its three keys of the trajectory file.
 """
 from __future__ import annotations
 
@@ -723,12 +725,12 @@ def candidate_objectives_from_coefficients(engine, candidates: list, T: int, fre
 # come from the swung states; the sweeps run at the rest base (``suspended_base="identity"``, the reference's rule: rest_base_states) or at the
 # swung states held fixed (``"held"``).  Neither differentiates the base motion itself, as the reference does not.
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _refuse_basis_projection(config) -> None:
+def _refuse_basis_projection(config, what: str = "device_spectrum=True", host: str = "device_spectrum=False, dopt_weight_matrices(..., B=B)") -> None:
     """``device_spectrum=True`` covers YBase = Y[:, independent_cols] only: a configuration that switches ``useBasisProjection`` on (a
-    truthy value; ``Model`` itself sets the key to 0) is refused"""
+    truthy value; ``Model`` itself sets the key to 0) is refused.  ``what`` / ``host``: the route that refuses and the one that serves."""
     if config.get("useBasisProjection"):
-        raise ValueError("device_spectrum=True does not cover useBasisProjection (a basis-projection matrix B: YBase = Y B): the host route "
-                         "(device_spectrum=False, dopt_weight_matrices(..., B=B)) serves that case")
+        raise ValueError(f"{what} does not cover useBasisProjection (a basis-projection matrix B: YBase = Y B): the host route "
+                         f"({host}) serves that case")
 
 
 def dopt_weight_matrices(G, independent_cols, dopt_regularization: float = 1e-4, dopt_scale=1.0, YtY_prior=None, B=None):
@@ -1353,3 +1355,55 @@ def candidate_gradients_from_coefficients(engine, candidates: list, T: int, freq
     if suspended is not None:
         out["suspended_info"] = _host(info)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The observability analysis of the trajectory file (trajectory.py:225-264) per candidate: which base parameters a candidate does not
+# excite and which identified parameters that pins (identifier.py:1536-1562: estimation.merge_unobservable_params).
+# ------------------------------------------------------------------------------------------------------------------------------------
+def candidate_observability(engine, states: dict, ncand: int, independent_cols, config: dict, w=None, YtY_prior=None) -> dict:
+    """The reference's observability analysis of ``ncand`` equal candidates stacked in ``states``: one ``gram_grouped`` and one
+    ``Engine.dopt_observability`` on the Gram where it lies -- with device states only per-candidate numbers and one (C, nb) array reach
+    the host.  The reference takes an SVD of ``YBase = Y[:, independent_cols]``, counts the singular values below
+    ``observabilityThreshold`` (default 1e-6) times the largest, sums the squared components of those right singular vectors per base
+    parameter and maps that energy through ``Pb``; here the same numbers come from the eigenpairs of ``YBase^T YBase`` (eigenvalues S^2,
+    the same vectors).  Per candidate:
+
+    ``n_observable_base_params`` (C,) int64; ``unobservable_energy`` (C, nb); ``unobservable_params``: a list of C sorted int64 arrays,
+    the identified-parameter indices with a score above 0.5 -- ``Pb`` carries the energy of base parameter j to ``independent_cols[j]``
+    --; ``observability_threshold``; ``margin`` (C,): the relative distance of the nearest eigenvalue from the cut ``threshold^2
+    lambda_max``; ``ambiguous`` (C,) bool: an eigenvalue lies so close to the cut that the fp64 Gram does not decide its side (status
+    bit 4); ``status`` (C,).
+
+    The Gram squares the condition number: singular values below about 2e-7 of the largest are not resolved, and a threshold below
+    that is refused by the engine.  ``YtY_prior``: the analysis is that of the summed information ``YBase^T YBase + YtY_prior`` (a
+    sequential design); the reference has no prior in this step.  A truthy ``useBasisProjection`` in ``config`` raises: the host route
+    (an SVD of ``YBase = Y B``) serves that case."""
+    _refuse_basis_projection(config, "candidate_observability", "numpy.linalg.svd of YBase = Y B, as trajectory.py does")
+    thr = config.get("observabilityThreshold", 1e-6)
+    G = engine.gram_grouped(states, int(ncand), w=w)
+    o = engine.dopt_observability(G, independent_cols, thr, prior=YtY_prior, device_out=False)
+    cols = np.asarray(independent_cols, dtype=np.int64).reshape(-1)
+    energy, status = o["energy"], o["status"]
+    return {"n_observable_base_params": o["n_observable"], "unobservable_energy": energy,
+            "unobservable_params": [np.sort(cols[energy[c] > 0.5]).astype(np.int64) for c in range(energy.shape[0])],
+            "observability_threshold": thr, "margin": o["margin"], "ambiguous": (status & 4) != 0, "status": status}
+
+
+def candidate_observability_from_coefficients(engine, candidates: list, T: int, freq: float, independent_cols, config: dict,
+                                              YtY_prior=None) -> dict:
+    """``candidate_observability`` from Fourier coefficients (``fourier_coefficients`` dicts): the states are generated on the device
+    (``candidate_states``), the Coulomb column of a friction engine is tanh(dq / ``frictionSignThreshold``); neither the samples nor the
+    Grams cross PCIe."""
+    _refuse_basis_projection(config, "candidate_observability", "numpy.linalg.svd of YBase = Y B, as trajectory.py does")
+    st = _coefficient_states(engine, candidates, T, freq, config.get("frictionSignThreshold", 0.02))
+    return candidate_observability(engine, st, len(candidates), independent_cols, config, YtY_prior=YtY_prior)
+
+
+def observability_fields(result: dict, c: int) -> dict:
+    """The three keys the reference stores in the trajectory file for candidate ``c`` of a ``candidate_observability`` result, as
+    trajectory.py:262-264 writes them: ``unobservable_params`` (an int64 array), ``observability_threshold``,
+    ``n_observable_base_params`` (an int) -- ready for ``np.savez(file, **save_dict, **fields)``."""
+    return {"unobservable_params": np.array([int(i) for i in result["unobservable_params"][c]], dtype=np.int64),
+            "observability_threshold": result["observability_threshold"],
+            "n_observable_base_params": int(result["n_observable_base_params"][c])}

@@ -90,7 +90,8 @@ typedef struct {
  * fbr_fourier_state_chain; fbr_suspended_base_motion, fbr_suspended_records; fbr_model_set_boxes, fbr_candidate_box_distances;
  * fbr_box_distance_gradients; fbr_model_set_hulls, fbr_candidate_hull_distances; fbr_hull_distance_gradients; fbr_model_set_hull_meshes;
  * fbr_mesh_distance_gradients; fbr_model_set_large_hulls, option "hull_large_all"; fbr_large_hull_distance_gradients, option
- * "hull_grad_tile"; fbr_model_set_large_hull_meshes; fbr_large_mesh_distance_gradients, option "mesh_grad_order"; fbr_dopt_terms (with FBR_MAX_DOPT_COLUMNS). */
+ * "hull_grad_tile"; fbr_model_set_large_hull_meshes; fbr_large_mesh_distance_gradients, option "mesh_grad_order"; fbr_dopt_terms (with FBR_MAX_DOPT_COLUMNS);
+ * fbr_dopt_observability. */
 #define FBR_VERSION 104
 int fbr_version(void);
 int fbr_device_count(void);        /* number of visible HIP devices (0 if none / no runtime) */
@@ -593,6 +594,32 @@ int fbr_regressor_weights(fbr_model *m, const fbr_states *st, int32_t ngroups, c
 #define FBR_MAX_DOPT_COLUMNS 512
 int fbr_dopt_terms(fbr_model *m, const double *G, int32_t ngroups, int32_t Pa, const int32_t *cols, int32_t ncols, const double *prior, double reg,
                    const double *scale, double *terms, int32_t *status, double *eig, double *Cmat, int32_t mem);
+
+/*
+ * The observability analysis of ngroups candidates from their Grams, on the device: what the reference runs on YBase of the chosen
+ * trajectory by SVD (trajectory.py:225-264), here per candidate on M_c = G_c[cols, cols] (+ prior) of fbr_dopt_terms, whose eigenvalues
+ * are S^2 and whose eigenvectors are the right singular vectors of YBase:
+ *   eig_c: bit for bit the eigenvalues fbr_dopt_terms reports;  vec[c][j][i]: component j of the eigenvector of eig[c][i] (the kept
+ *          Householder reflectors, implicit QL with Wilkinson shifts; residual and orthogonality of order n eps |M_c|, also inside
+ *          clusters such as the null space of unexcited joints); its component of largest magnitude, the first at a tie, is positive;
+ *   lm = max(eig_max, 0), cut = threshold^2 lm;  index i is unobservable iff max(eig_i, 0) < cut (S_i < threshold S_0: for the zero matrix
+ *          nothing is);  n_observable[c] = ncols - their number;  energy[c][j] = sum over the unobservable i, ascending, of vec[c][j][i]^2;
+ *   margin[c] = min_i |eig_i - cut| / cut (+inf when cut = 0).
+ * The limit of the Gram route: fp64 knows an eigenvalue of M_c to about band lm, band(ncols) = max(128, ncols) 2^-52, hence a singular
+ * value of YBase only down to about 2e-7 S_0.  FBR_E_INVALID for a threshold outside (0, 1) or with threshold^2 < 8 band (1e-6, the
+ * reference's default, passes up to ncols = 512); status bit 4 (value 4) where some eig_i lies within band lm of the cut: the
+ * classification of that index is not decided by this arithmetic, the numbers are returned all the same.  Agreement with an SVD of YBase
+ * for singular values between 1e-8 S_0 and the threshold is a property of the Gram, not of the kernel.
+ * cols, prior: as for fbr_dopt_terms.  n_observable [ngroups], energy [ngroups][ncols], margin [ngroups] or NULL, eig [ngroups][ncols] or
+ * NULL, vec [ngroups][ncols][ncols] or NULL, status [ngroups] or NULL: `mem` space.  status[c]: bit 1 (value 1): a non-finite entry -- the
+ * candidate's outputs are NaN, n_observable 0 --; bit 4: above; bit 8 (value 8): the QL iteration used up its 30 ncols sweeps -- vec and
+ * energy of that candidate are NaN, the rest stands.  One candidate's outputs depend on nothing but that candidate; the same bits on every
+ * run, in both memory spaces and with or without margin / eig / vec.  One workgroup per candidate, 2 ncols^2 doubles of scratch each.
+ * FBR_E_INVALID also for what fbr_dopt_terms refuses.
+ */
+int fbr_dopt_observability(fbr_model *m, const double *G, int32_t ngroups, int32_t Pa, const int32_t *cols, int32_t ncols, const double *prior,
+                           double threshold, int32_t *n_observable, double *energy, double *margin, double *eig, double *vec, int32_t *status,
+                           int32_t mem);
 
 /*
  * Joint states of ncand candidate trajectories, T samples each, generated ON THE DEVICE from their Fourier coefficients -- the
